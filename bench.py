@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: restored frames/s of FLAIR's sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): gaussian-demo, one clip of 16 frames at 256x256 per
 GPU, 250-step generalised-DDIM chain (space_timesteps(1000,"250"), rho=0.25), bf16 UNet
@@ -9,8 +9,17 @@ GPU, 250-step generalised-DDIM chain (space_timesteps(1000,"250"), rho=0.25), bf
 operator on the GPU, identity aux prior with aligned=True.  A "step" is one denoising step
 of the clip = one UNet forward + restore_fn + fused sampler update.  W warm-up steps, then
 exactly K steps are timed between barrier + synchronize; frames/s for the whole 250-step
-job is  n_gpus * frames / (250 * mean step time)  (with the default K = 248 the timed region
-is the whole chain but the warm-up steps).  Inputs are resident in HBM before timing.
+job is  n_gpus * frames / (250 * mean step time)  (with the default K = 250 - W - 2 the timed
+region is the whole chain but the warm-up steps and the two steps of the instrumented pass).
+When W + K + 2 exceeds the chain, the chain starts over from the same x_T, as the next job on
+the clip would (its first step recomputes the SPyNet flows and re-captures the UNet's graph).
+Inputs are resident in HBM before timing; every input is seeded, so runs with the same
+arguments see the same inputs.
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step (rank 0)
+as DIR/<name>.npy: the sample x_{t-1} and pred_xstart (float32, the sampler's (B*T, 3, S, S)
+layout) and the timestep t (float64).  Above DUMP_BUDGET_BYTES in all, every array is replaced by
+the same fixed, seeded sample of its flattened elements (see dump_outputs).
 
 The JSON line also carries
   roofline     -- the dominant kernel (implicit-GEMM conv on MFMA): algorithmic FLOPs of its
@@ -33,6 +42,7 @@ if ROOT not in sys.path:
 TOTAL_STEPS = 250
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.3}   # dense, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
+DUMP_BUDGET_BYTES = 60 * 10 ** 6                     # --dump-outputs: array data written in all (< 64 MB with headers)
 # rocprofv3 kernel names of the conv variants (keys of profiles/*_hbm_traffic_pmc.json)
 CONV_ROCPROF = {0: "conv_igemm_kernel<{E}, 128, 128, 2, 2>", 1: "conv_igemm_kernel<{E}, 64, 128, 1, 4>",
                 2: "conv_igemm_kernel<{E}, 64, 64, 2, 2>", 3: "conv3x3_halo_kernel<{E}, 8, 1, 1>",
@@ -81,10 +91,35 @@ def cpu_baseline_prior():
             "sample": "oracle/codeformer.py, one 512x512 face, fp32"}
 
 
+def dump_outputs(out, path):
+    """--dump-outputs: write the tensors of one sampler step's result `out` as <path>/<name>.npy (floating point as
+    float32, integers as float64).  When they exceed DUMP_BUDGET_BYTES together, each array is cut to the same share of
+    its flattened elements, at sorted indices drawn by numpy's default_rng(0): a fixed sample for a fixed shape, so two
+    runs with the same arguments stay comparable element for element.  Returns {name: [shape written, full shape]}."""
+    import numpy as np
+    arrays = {}
+    for name, v in out.items():
+        if torch.is_tensor(v):
+            dt = torch.float32 if v.is_floating_point() else torch.float64
+            arrays[name] = v.detach().to("cpu", dt).numpy()
+    total = sum(x.nbytes for x in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, x in arrays.items():
+        full = list(x.shape)
+        if total > DUMP_BUDGET_BYTES:
+            n = max(1, x.size * DUMP_BUDGET_BYTES // total)
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, size=n, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
+        written[name] = [list(x.shape), full]
+    return written
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the whole chain minus warm-up)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps, exactly (default: the whole chain minus the warm-up and the two instrumented steps)")
     ap.add_argument("--total-steps", type=int, default=None,
                     help="length of the sampling chain (default 250; 1000 for x16_bicubic = BASELINE config 5)")
     ap.add_argument("--warmup", type=int, default=2)
@@ -108,6 +143,8 @@ def parse():
                          "as fast on one GPU (the step is GPU-bound), but the host spends ~5 ms instead of ~60 ms per "
                          "step, which keeps 8 rank processes on one node from competing for CPU time")
     ap.add_argument("--no-graph", dest="graph", action="store_false", help="launch every kernel eagerly")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's sample / pred_xstart / t as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -321,8 +358,12 @@ def main():
     S, T = a.size, a.frames
     global TOTAL_STEPS
     TOTAL_STEPS = a.total_steps or (1000 if a.task == "x16_bicubic" else 250)
+    W = max(0, a.warmup)
     if a.steps is None:
-        a.steps = TOTAL_STEPS - 2
+        a.steps = max(1, TOTAL_STEPS - W - 2)
+    if a.steps < 1:
+        raise SystemExit(f"--steps {a.steps}: at least one step must be timed")
+    K = a.steps
     hp = wl.TASKS[a.task]
     bicubic = "bicubic" in a.task
     torch.manual_seed(0)
@@ -396,12 +437,14 @@ def main():
             gan.convert_to_bf16()
         aux_model = wl.codeformer_aux(gan)
 
-    W = max(0, a.warmup)
-    K = max(1, min(a.steps, TOTAL_STEPS - W - 2))      # keep two steps for the instrumented pass (eager warm + measured)
-    gen = diffusion.p_sample_loop_progressive(
-        model, x_T.shape, noise=x_T, clip_denoised=True, model_kwargs=kwargs, device=dev,
-        restore_fn=restore_fn, aux_model=aux_model, w=hp["w"], tau=5, aligned=True, rho=hp["rho"],
-        noise_level=hp["noise_level"], zeta=hp["zeta"])
+    def chains():
+        """The timed path: the denoising steps of the clip's chain, and of the same chain again when a run outlasts it."""
+        while True:
+            yield from diffusion.p_sample_loop_progressive(
+                model, x_T.shape, noise=x_T, clip_denoised=True, model_kwargs=kwargs, device=dev,
+                restore_fn=restore_fn, aux_model=aux_model, w=hp["w"], tau=5, aligned=True, rho=hp["rho"],
+                noise_level=hp["noise_level"], zeta=hp["zeta"])
+    gen = chains()
 
     def sync():
         torch.cuda.synchronize()
@@ -422,6 +465,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     finite = bool(torch.isfinite(out["sample"]).all().item())
+    dumped = dump_outputs(out, a.dump_outputs) if a.dump_outputs and rank == 0 else None
+    # the instrumented pass below wants steady-state steps (not a chain's first: SPyNet, graph re-capture) within one
+    # chain; a run that ended at a chain boundary steps on, untimed (never with the default K: W + K + 2 <= the chain)
+    for _ in range({0: 1, TOTAL_STEPS - 1: 2}.get((W + K) % TOTAL_STEPS, 0)):
+        next(gen)
 
     # ---- roofline leg.  One more (eagerly launched, steady-state) step records every conv / GroupNorm / alignment / warp /
     # attention call together with a closure that re-issues the identical library call (same tensors, same arguments).
@@ -679,7 +727,7 @@ def main():
                                   f"{'/'.join(str((S // v) ** 2) for v in attn_res)} tokens), blur x4 restore_fn on GPU")
                                + ", one clip per GPU",
                    "steps_per_clip": TOTAL_STEPS, "value_definition": f"n_gpus*frames/({TOTAL_STEPS}*mean timed step)",
-                   "finite_output": finite, "weight_broadcast_s": max(b["s"] for b in bcast_per_rank),
+                   "finite_output": finite, "dumped_outputs": dumped, "weight_broadcast_s": max(b["s"] for b in bcast_per_rank),
                    "weight_broadcast_bytes": bcast_bytes, "weight_broadcast_per_rank": bcast_per_rank,
                    "hip_graph": use_graph, "params_M": n_params / 1e6,
                    "attention_resolutions": None if bicubic else list(attn_res),

@@ -7,6 +7,9 @@ import pytest
 import torch
 
 from tests.golden.weights import name_seeded_weights
+from tests.util import fixture_threads  # noqa: F401
+
+pytestmark = pytest.mark.usefixtures("fixture_threads")
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 

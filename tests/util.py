@@ -1,4 +1,5 @@
 """Helpers shared by the parity tests."""
+import pytest
 import torch
 
 
@@ -49,3 +50,18 @@ def parity_log(line):
     except OSError:
         pass
     print(line)
+
+
+# The fp32 fixtures under tests/golden/ were written by tests/golden/make_golden.py with torch on 8 intra-op CPU threads.
+# How torch splits a CPU reduction over threads sets its summation order, and the networks amplify that last-bit
+# difference about a thousandfold (a whole-network output moves by ~1e-3 relative at 1, 3 or 16 threads), so the CPU
+# oracle is compared with a fixture on the fixture's own thread count.
+FIXTURE_THREADS = 8
+
+
+@pytest.fixture
+def fixture_threads():
+    n = torch.get_num_threads()
+    torch.set_num_threads(FIXTURE_THREADS)
+    yield
+    torch.set_num_threads(n)
