@@ -1,19 +1,22 @@
 // Attention kernels of the FLAIR UNet.
 //
 // (1) Spatial QKV attention per (frame, head) over the H*W tokens of a frame, head
-//     width 64 -- replaces QKVAttentionLegacy / QKVAttention (guided_diffusion/
-//     unet_new.py:540-605: einsum QK^T, f32 softmax, einsum AV).
+//     width D in {32, 64, 128} -- replaces QKVAttentionLegacy / QKVAttention (guided_diffusion/
+//     unet_new.py:540-605: einsum QK^T, f32 softmax, einsum AV).  Other widths (multiples of 8)
+//     go to flair_attention_wide (prior.hip) while its LDS tile holds them (d + L <= 2048).
 //       * bf16: flash-style MFMA kernel.  S^T = K.Q^T is computed with keys on the
 //         accumulator rows and queries on the lanes, so the softmax row statistics are
 //         lane-local (+1 exchange with lane^32) and the probability tile is reused in
 //         place as the B operand of O^T += V^T.P^T (cdna_hip_programming.md section 3,
 //         "An accumulator tile as the next MFMA's operand").
-//       * f32: one wavefront per query (head width 64 = one channel per lane), exact
-//         f32 arithmetic; this is the tight-tolerance parity path, not a speed path.
+//       * f32: one wavefront per query at D = 64 (one channel per lane), two queries per
+//         wavefront at D = 32, two channels per lane at D = 128; exact f32 arithmetic; this
+//         is the tight-tolerance parity path, not a speed path.
 // (2) Temporal window attention per pixel -- replaces TemporalAttention's
 //     unfold + flash_attn_func (unet_new.py:473-515, nn.py:370-386): one query (own
 //     frame) against the F-1 neighbouring frames (replicate padding at clip ends).
-//     VALU / bandwidth bound: 8 lanes per (frame, pixel, head), 8 channels per lane.
+//     VALU / bandwidth bound: G lanes per (frame, pixel, head), 8 channels per lane; G = d/8
+//     rounded up to a power of two (8 at d = 64), d any multiple of 8 in [8, 256].
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
@@ -25,7 +28,7 @@ namespace {
 
 struct AttnArgs {
     const void* qkv;  // [frames][L][ld]
-    void* out;        // [frames][L][outLd], channel = head*64 + d
+    void* out;        // [frames][L][outLd], channel = head*D + d
     int ld, outLd;
     int L, heads;
     int qOff, kOff, vOff, headStride;  // channel offsets: x_off + head*headStride
@@ -33,30 +36,42 @@ struct AttnArgs {
 };
 
 // ------------------------------------------------------------------ f32 / generic path
-template <typename E>
+template <typename E, int D>
 __global__ void attn_rowwise_kernel(AttnArgs a) {
+    // LPQ lanes per query (QPW queries per wavefront), CPL channels per lane: D = 32: 32 x 2 x 1, D = 64: 64 x 1 x 1,
+    // D = 128: 64 x 1 x 2 (channels lane and lane + 64)
+    constexpr int LPQ = D < 64 ? D : 64, QPW = 64 / LPQ, CPL = D / LPQ;
     const int lane = threadIdx.x & 63;
-    const int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int q = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * QPW + lane / LPQ;
+    const int cl = lane % LPQ;
     const int fh = blockIdx.y;
     const int f = fh / a.heads, hd = fh % a.heads;
-    if (q >= a.L) return;
+    if (q >= a.L) return;  // D = 32: the two queries of a wavefront reduce within their own 32 lanes
     const E* base = reinterpret_cast<const E*>(a.qkv) + (long)f * a.L * a.ld + hd * a.headStride;
-    const float qv = ET<E>::ld(base + (long)q * a.ld + a.qOff + lane);
-    float m = -INFINITY, l = 0.f, acc = 0.f;
-    for (int s = 0; s < a.L; ++s) {
-        float d = qv * ET<E>::ld(base + (long)s * a.ld + a.kOff + lane);
+    float qv[CPL];
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off);
+    for (int j = 0; j < CPL; ++j) qv[j] = ET<E>::ld(base + (long)q * a.ld + a.qOff + cl + LPQ * j);
+    float m = -INFINITY, l = 0.f, acc[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
+    for (int s = 0; s < a.L; ++s) {
+        float d = qv[0] * ET<E>::ld(base + (long)s * a.ld + a.kOff + cl);
+#pragma unroll
+        for (int j = 1; j < CPL; ++j) d = fmaf(qv[j], ET<E>::ld(base + (long)s * a.ld + a.kOff + cl + LPQ * j), d);
+#pragma unroll
+        for (int off = LPQ / 2; off > 0; off >>= 1) d += __shfl_xor(d, off);
         d *= a.scale;
         const float mn = fmaxf(m, d);
         const float alpha = __expf(m - mn);
         const float p = __expf(d - mn);
         l = l * alpha + p;
-        acc = acc * alpha + p * ET<E>::ld(base + (long)s * a.ld + a.vOff + lane);
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) acc[j] = acc[j] * alpha + p * ET<E>::ld(base + (long)s * a.ld + a.vOff + cl + LPQ * j);
         m = mn;
     }
-    E* o = reinterpret_cast<E*>(a.out) + ((long)f * a.L + q) * a.outLd + hd * 64 + lane;
-    ET<E>::st(o, acc / l);
+    E* o = reinterpret_cast<E*>(a.out) + ((long)f * a.L + q) * a.outLd + hd * D + cl;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) ET<E>::st(o + LPQ * j, acc[j] / l);
 }
 
 // ------------------------------------------------------------------------- bf16 MFMA
@@ -179,16 +194,35 @@ __global__ __launch_bounds__(256) void attn_mfma_bf16_kernel(AttnArgs a) {
 
 // -------------------------------------------------------------- bf16 MFMA, pipelined
 // Same mathematics and operand roles as attn_mfma_bf16_kernel above, restructured around the latency that
-// kernel exposes once per 32-token tile (load K/V -> LDS -> barrier -> compute -> barrier):
-//   * KV tiles of 64 tokens, two LDS stages, ONE barrier per tile; the next tile's K and V are requested into
+// kernel exposes once per 32-token tile (load K/V -> LDS -> barrier -> compute -> barrier), for head widths
+// D = 32, 64 and 128:
+//   * KV tiles of KV tokens, two LDS stages, ONE barrier per tile; the next tile's K and V are requested into
 //     registers before the current tile's MFMAs and written to the other stage afterwards;
-//   * V stays row-major in LDS ([token][64 d], written with 16-byte stores) and its transposed MFMA fragments
+//   * V stays row-major in LDS ([token][D], written with 16-byte stores) and its transposed MFMA fragments
 //     come from ds_read_b64_tr_b16 (the hardware transpose read) instead of eight 2-byte scatter stores per
-//     thread and tile; row pitch 192 B = 48 dwords, so the four rows of a transposed block hit four disjoint
-//     16-bank quarters (conflict-free per 32-lane half);
+//     thread and tile.  Each 32-lane half of that read takes 16 dwords from each of 4 consecutive rows, so
+//     the row pitch VPITCH is the smallest >= 2D bytes that is an ODD multiple of 64 B (16 banks): the four
+//     rows then start 16 banks apart (mod 64) and hit four disjoint 16-bank quarters, conflict-free.
+//     D = 32: 64 B (16 dwords, no padding); D = 64: 192 B (48 dwords; 128 B would put rows 0 and 2 on the
+//     same banks); D = 128: 320 B (80 dwords; 256 B would put all four rows on the same banks);
+//   * KV = 64 tokens at D = 32 and 64, KV = 32 at D = 128.  Two stages of 64-token K+V tiles at D = 128
+//     would be 2 x 36 KB = 72 KB per workgroup: past the 64 KB of static LDS, and two workgroups per CU.
+//     32-token tiles keep it at 36 KB (D = 64: 40 KB) and a tile still carries 16 MFMAs as at D = 64 (8
+//     k-steps of S^T, 2 x 4 of O^T) against half the softmax work per MFMA.  D = 128 runs two workgroups
+//     per CU all the same: its Q fragments (32 VGPRs) and O^T accumulators (64) do not fit the 168-register
+//     budget of three (the NW = 4 build spilled 68 bytes to scratch), and 2 x 4 waves fill 256 registers;
 //   * NW = 2 wavefronts (64 queries) per workgroup when 128-query workgroups would leave CUs idle (L = 256:
 //     256 instead of 128 workgroups), else 4.
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
+
+// K tile of width D: rows of D/8 16-byte chunks, swizzled so that the ds_read_b128 fragment reads (row = lane&31,
+// one chunk per 32-lane half) spread each 16-lane group over the 64 banks
+template <int D>
+__device__ __forceinline__ int k_off_d(int row, int chunk) {
+    if constexpr (D == 32) return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4);
+    else if constexpr (D == 64) return k_off(row, chunk);
+    else return row * 256 + ((chunk ^ (row & 15)) << 4);
+}
 
 // (lo, hi) -> packed bf16 pair; inline asm so that the vectoriser cannot pair the conversions by register
 // neighbourhood and re-interleave afterwards (measured in the ISA: 32 cvt + 32 fix-ups instead of 16 cvt)
@@ -198,12 +232,14 @@ __device__ __forceinline__ unsigned cvt_pk_bf16_asm(float lo, float hi) {
     return r;
 }
 
-template <int NW>
-__global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs a) {
-    constexpr int NT = 64 * NW, KV = 64;
-    constexpr int KPITCH = 128, VPITCH = 192;
-    constexpr int STAGE = KV * KPITCH + KV * VPITCH;                  // 20 KB per stage
-    constexpr int PIECES = KV * 8;                                   // 16-byte pieces of one K (or V) tile
+template <int NW, int D>
+__global__ __launch_bounds__(64 * NW, D == 128 ? 2 : 3) void attn_mfma_bf16_v2_kernel(AttnArgs a) {
+    static_assert(D == 32 || D == 64 || D == 128, "head width");
+    constexpr int NT = 64 * NW, KV = D == 128 ? 32 : 64, H2 = KV / 32;
+    constexpr int CH = D / 8, LOG2CH = D == 32 ? 2 : D == 64 ? 3 : 4;  // 16-byte chunks per row
+    constexpr int KPITCH = 2 * D, VPITCH = D == 32 ? 64 : D == 64 ? 192 : 320;
+    constexpr int STAGE = KV * KPITCH + KV * VPITCH;                 // 8 / 20 / 18 KB per stage
+    constexpr int PIECES = KV * CH;                                  // 16-byte pieces of one K (or V) tile
     constexpr int LI = (PIECES + NT - 1) / NT;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -214,15 +250,15 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
     const int q = blockIdx.x * (32 * NW) + wave * 32 + lr;
     const bool qok = q < a.L;
 
-    uint4 qf[4];
+    uint4 qf[D / 16];
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
+    for (int s = 0; s < D / 16; ++s)
         qf[s] = qok ? *reinterpret_cast<const uint4*>(base + (long)q * a.ld + a.qOff + 16 * s + 8 * lh)
                     : make_uint4(0, 0, 0, 0);
 
-    f32x16 o[2];
+    f32x16 o[D / 32];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < D / 32; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
     float m = -1e30f, l = 0.f;
@@ -233,7 +269,7 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
 #pragma unroll
         for (int i = 0; i < LI; ++i) {
             const int id = i * NT + tid;
-            const int kv = id >> 3, ch = id & 7;
+            const int kv = id >> LOG2CH, ch = id & (CH - 1);
             const int tok = t * KV + kv;
             const bool ok = id < PIECES && tok < a.L;
             kreg[i] = ok ? *reinterpret_cast<const uint4*>(base + (long)tok * a.ld + a.kOff + ch * 8) : make_uint4(0, 0, 0, 0);
@@ -247,8 +283,8 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
         for (int i = 0; i < LI; ++i) {
             const int id = i * NT + tid;
             if (id < PIECES) {
-                const int kv = id >> 3, ch = id & 7;
-                *reinterpret_cast<uint4*>(sk + k_off(kv, ch)) = kreg[i];
+                const int kv = id >> LOG2CH, ch = id & (CH - 1);
+                *reinterpret_cast<uint4*>(sk + k_off_d<D>(kv, ch)) = kreg[i];
                 *reinterpret_cast<uint4*>(sv + kv * VPITCH + ch * 16) = vreg[i];
             }
         }
@@ -270,27 +306,28 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
         const char* sv = sk + KV * KPITCH;
         if (t + 1 < ntile) issue(t + 1);
 
-        // ---- S^T[kv][q] = K . Q^T for the two 32-token halves of the tile
-        f32x16 s[2];
+        // ---- S^T[kv][q] = K . Q^T for the 32-token parts of the tile
+        f32x16 s[H2];
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
+        for (int h2 = 0; h2 < H2; ++h2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[h2][r] = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const uint4 kf = *reinterpret_cast<const uint4*>(sk + k_off(32 * h2 + lr, 2 * ks + lh));
+            for (int ks = 0; ks < D / 16; ++ks) {
+                const uint4 kf = *reinterpret_cast<const uint4*>(sk + k_off_d<D>(32 * h2 + lr, 2 * ks + lh));
                 s[h2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf),
                                                             __builtin_bit_cast(bf16x8, qf[ks]), s[h2], 0, 0, 0);
             }
         }
         // rows of this lane: kv = 32*h2 + (r&3) + 8*(r>>2) + 4*lh.  The softmax is the VALU bottleneck of this
-        // kernel (32 scores per lane and tile against 16 MFMAs), so: tokens beyond L are masked only in the last tile
-        // (wave-uniform branch), the scale rides in the exponent's FMA (p = 2^(s*sc - m), the running maximum is
-        // kept in scaled units), v_exp_f32 directly, and the accumulators are rescaled only when some row's maximum grew
+        // kernel (32 scores per lane and tile against 16 MFMAs at D = 64), so: tokens beyond L are masked only in the
+        // last tile (wave-uniform branch), the scale rides in the exponent's FMA (p = 2^(s*sc - m), the running
+        // maximum is kept in scaled units), v_exp_f32 directly, and the accumulators are rescaled only when some
+        // row's maximum grew
         if ((t + 1) * KV > a.L) {
             asm volatile("; partly masked last tile" ::: "memory");   // keeps this a branch (if-converted it is 64 VALU per tile)
 #pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
+            for (int h2 = 0; h2 < H2; ++h2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int kv = t * KV + 32 * h2 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -299,14 +336,14 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
         }
         float tmax = -1e30f;
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
+        for (int h2 = 0; h2 < H2; ++h2)
 #pragma unroll
             for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[h2][r]);
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32)) * sc;
         const float mn = fmaxf(m, tmax);
         float ps[4] = {0.f, 0.f, 0.f, 0.f};                     // four short add chains instead of one of 32
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
+        for (int h2 = 0; h2 < H2; ++h2)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 s[h2][r] = __builtin_amdgcn_exp2f(fmaf(s[h2][r], sc, -mn));
@@ -318,7 +355,7 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
             const float alpha = __builtin_amdgcn_exp2f(m - mn);
             l *= alpha;
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < D / 32; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
             m = mn;
@@ -328,7 +365,7 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
         // ---- O^T[d][q] += V^T[d][kv] . P^T[kv][q]: k-step (h2, ks2) covers tokens 32*h2 + 16*ks2 .. +15 in the
         // order (r&3) + 8*(r>>2) + 4*lh of the accumulator registers 8*ks2 .. 8*ks2+7 (any order, used on both sides)
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
+        for (int h2 = 0; h2 < H2; ++h2)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 uint4 pf;
@@ -337,7 +374,7 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
                 pf.z = cvt_pk_bf16_asm(s[h2][8 * ks + 4], s[h2][8 * ks + 5]);
                 pf.w = cvt_pk_bf16_asm(s[h2][8 * ks + 6], s[h2][8 * ks + 7]);
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
+                for (int i = 0; i < D / 32; ++i) {
                     // elements 0..3: tokens row0 + 4*lh + {0..3}; elements 4..7: the same rows + 8
                     const char* vb = sv + (32 * h2 + 16 * ks) * VPITCH + 64 * i + trOff;
                     const s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
@@ -360,9 +397,9 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_mfma_bf16_v2_kernel(AttnArgs 
     }
     if (!qok) return;
     const float inv = 1.f / l;
-    bf16_t* op = reinterpret_cast<bf16_t*>(a.out) + ((long)f * a.L + q) * a.outLd + hd * 64;
+    bf16_t* op = reinterpret_cast<bf16_t*>(a.out) + ((long)f * a.L + q) * a.outLd + hd * D;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < D / 32; ++i)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             uint2 pk;
@@ -389,28 +426,35 @@ template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const floa
 __device__ __forceinline__ float rh(float v) { return __half2float(__float2half(v)); }
 
 struct TAttnArgs {
-    const void* qkv;  // [T][HW][ld]: q | k | v, each C wide, channel = head*64 + d
+    const void* qkv;  // [T][HW][ld]: q | k | v, each C wide, channel = head*d + c
     const float* kpos;  // [window-1][C]: W_k . pe_j, added to k of window slot j
     void* out;          // [T][HW][outLd]
     int ld, outLd, T, C, window;
     long HW;
     int roundFp16;
     float scale;
+    int headDim;        // d, a multiple of 8 in [8, 256]
 };
 
-template <typename E>
+// G lanes per item, 8 channels each.  MASKED = false: d = 8*G (a compile-time width); MASKED = true: d/8 < G, the
+// lanes sub >= d/8 read the head's first 8 channels (in bounds), add 0 to the dot product and store nothing.
+template <typename E, int G, bool MASKED>
 __global__ void temporal_attn_kernel(TAttnArgs a) {
-    const int heads = a.C / 64;
-    const long items = (long)a.T * a.HW * heads;  // one item = (t, pixel, head), 8 lanes each
+    constexpr int LOG2G = G == 1 ? 0 : G == 2 ? 1 : G == 4 ? 2 : G == 8 ? 3 : G == 16 ? 4 : 5;
+    static_assert((1 << LOG2G) == G && G <= 32, "lane group");
+    const int D = MASKED ? a.headDim : 8 * G;
+    const int heads = a.C / D;
+    const long items = (long)a.T * a.HW * heads;  // one item = (t, pixel, head), G lanes each
     const long gid = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const long item = gid >> 3;
-    const int sub = (int)(gid & 7);
-    if (item >= items) return;  // whole 8-lane groups leave together
+    const long item = gid >> LOG2G;
+    const int sub = (int)(gid & (G - 1));
+    if (item >= items) return;  // whole G-lane groups leave together
+    const bool on = !MASKED || sub * 8 < D;
     const int hd = (int)(item % heads);
     const long tp = item / heads;
     const long pix = tp % a.HW;
     const int t = (int)(tp / a.HW);
-    const int c = hd * 64 + sub * 8;
+    const int c = hd * D + (on ? sub * 8 : 0);
     const E* base = reinterpret_cast<const E*>(a.qkv);
     float q[8];
     load8<E>(base + ((long)t * a.HW + pix) * a.ld + c, q);
@@ -440,9 +484,9 @@ __global__ void temporal_attn_kernel(TAttnArgs a) {
             }
             d = fmaf(q[i], kk, d);
         }
-        d += __shfl_xor(d, 1);
-        d += __shfl_xor(d, 2);
-        d += __shfl_xor(d, 4);
+        if (!on) d = 0.f;
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) d += __shfl_xor(d, off);
         d *= a.scale;
         const float mn = fmaxf(m, d);
         const float alpha = __expf(m - mn), p = __expf(d - mn);
@@ -458,37 +502,92 @@ __global__ void temporal_attn_kernel(TAttnArgs a) {
         acc[i] *= inv;
         if (a.roundFp16) acc[i] = rh(acc[i]);
     }
-    store8<E>(reinterpret_cast<E*>(a.out) + ((long)t * a.HW + pix) * a.outLd + c, acc);
+    if (on) store8<E>(reinterpret_cast<E*>(a.out) + ((long)t * a.HW + pix) * a.outLd + c, acc);
+}
+
+template <typename E, int G>
+void launch_temporal(const TAttnArgs& a, hipStream_t stream) {
+    const long threads = (long)a.T * a.HW * (a.C / a.headDim) * G;
+    const int grid = (int)((threads + 255) / 256);
+    if (a.headDim == 8 * G)
+        hipLaunchKernelGGL((temporal_attn_kernel<E, G, false>), dim3(grid), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((temporal_attn_kernel<E, G, true>), dim3(grid), dim3(256), 0, stream, a);
+}
+
+template <typename E>
+void launch_temporal(const TAttnArgs& a, hipStream_t stream) {
+    const int n = a.headDim / 8;   // lanes that carry channels; the group is n rounded up to a power of two
+    if (n <= 1) launch_temporal<E, 1>(a, stream);
+    else if (n <= 2) launch_temporal<E, 2>(a, stream);
+    else if (n <= 4) launch_temporal<E, 4>(a, stream);
+    else if (n <= 8) launch_temporal<E, 8>(a, stream);
+    else if (n <= 16) launch_temporal<E, 16>(a, stream);
+    else launch_temporal<E, 32>(a, stream);
+}
+
+template <int D>
+void launch_qkv_bf16(const flair_attn_params* p, const AttnArgs& a, hipStream_t stream) {
+    const long wg128 = (long)((p->L + 127) / 128) * p->frames * p->heads;
+    if (wg128 >= 256)
+        hipLaunchKernelGGL((attn_mfma_bf16_v2_kernel<4, D>), dim3((p->L + 127) / 128, p->frames * p->heads), dim3(256),
+                           0, stream, a);
+    else
+        hipLaunchKernelGGL((attn_mfma_bf16_v2_kernel<2, D>), dim3((p->L + 63) / 64, p->frames * p->heads), dim3(128), 0,
+                           stream, a);
+}
+
+template <int D>
+void launch_qkv_f32(const flair_attn_params* p, const AttnArgs& a, hipStream_t stream) {
+    constexpr int QPB = 4 * (D < 64 ? 64 / D : 1);   // queries per 256-thread workgroup
+    hipLaunchKernelGGL((attn_rowwise_kernel<float, D>), dim3((p->L + QPB - 1) / QPB, p->frames * p->heads), dim3(256), 0,
+                       stream, a);
 }
 
 }  // namespace
 
+// flair_attention_wide (prior.hip) holds 16 rows of d + L floats in 128 KiB of LDS
+constexpr int kWideAttnMaxDL = 2048;
+
 extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, void* out, hipStream_t stream) {
     FLAIR_CHECK(p && qkv && out, "flair_qkv_attention: null argument");
-    FLAIR_CHECK(p->head_dim == 64, "flair_qkv_attention: head width %d unsupported (64 only)", p->head_dim);
     FLAIR_CHECK(p->frames > 0 && p->L > 0 && p->heads > 0, "flair_qkv_attention: empty shape");
+    const int d = p->head_dim;
+    const bool native = d == 32 || d == 64 || d == 128;
+    FLAIR_CHECK(native || (d > 0 && d % 8 == 0 && d + p->L <= kWideAttnMaxDL),
+                "flair_qkv_attention: head width %d unsupported at L = %d (32, 64 and 128 at any L; other multiples of 8 "
+                "while head width + L <= %d)", d, p->L, kWideAttnMaxDL);
     FLAIR_CHECK(p->ld % 8 == 0 && p->out_ld % 8 == 0 && p->q_off % 8 == 0 && p->k_off % 8 == 0 &&
                     p->v_off % 8 == 0 && p->head_stride % 8 == 0,
                 "flair_qkv_attention: offsets/strides must be multiples of 8 elements");
+    const int hi_off = p->q_off > p->k_off ? (p->q_off > p->v_off ? p->q_off : p->v_off)
+                                           : (p->k_off > p->v_off ? p->k_off : p->v_off);
+    FLAIR_CHECK(hi_off + (long)(p->heads - 1) * p->head_stride + d <= p->ld && (long)p->heads * d <= p->out_ld,
+                "flair_qkv_attention: %d heads of width %d exceed ld %d / out_ld %d", p->heads, d, p->ld, p->out_ld);
+    if (!native) return flair_attention_wide(p, qkv, out, stream);
     AttnArgs a;
     a.qkv = qkv; a.out = out; a.ld = p->ld; a.outLd = p->out_ld; a.L = p->L; a.heads = p->heads;
     a.qOff = p->q_off; a.kOff = p->k_off; a.vOff = p->v_off; a.headStride = p->head_stride;
     a.scale = p->scale;
     if (p->dtype == FLAIR_BF16) {
+        // FLAIR_ATTN_V2=0 selects the round-1 kernel, which exists for head width 64 only
         static const int v2 = getenv("FLAIR_ATTN_V2") ? atoi(getenv("FLAIR_ATTN_V2")) : 1;
-        const long wg128 = (long)((p->L + 127) / 128) * p->frames * p->heads;
-        if (!v2)
+        if (d == 32)
+            launch_qkv_bf16<32>(p, a, stream);
+        else if (d == 128)
+            launch_qkv_bf16<128>(p, a, stream);
+        else if (!v2)
             hipLaunchKernelGGL(attn_mfma_bf16_kernel, dim3((p->L + 127) / 128, p->frames * p->heads), dim3(256), 0,
                                stream, a);
-        else if (wg128 >= 256)
-            hipLaunchKernelGGL(attn_mfma_bf16_v2_kernel<4>, dim3((p->L + 127) / 128, p->frames * p->heads), dim3(256),
-                               0, stream, a);
         else
-            hipLaunchKernelGGL(attn_mfma_bf16_v2_kernel<2>, dim3((p->L + 63) / 64, p->frames * p->heads), dim3(128), 0,
-                               stream, a);
+            launch_qkv_bf16<64>(p, a, stream);
     } else if (p->dtype == FLAIR_F32) {
-        hipLaunchKernelGGL(attn_rowwise_kernel<float>, dim3((p->L + 3) / 4, p->frames * p->heads), dim3(256), 0,
-                           stream, a);
+        if (d == 32)
+            launch_qkv_f32<32>(p, a, stream);
+        else if (d == 128)
+            launch_qkv_f32<128>(p, a, stream);
+        else
+            launch_qkv_f32<64>(p, a, stream);
     } else {
         FLAIR_CHECK(false, "flair_qkv_attention: bad dtype");
     }
@@ -499,18 +598,20 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
 extern "C" int flair_temporal_attention(const flair_tattn_params* p, const void* qkv, const float* kpos, void* out,
                                         hipStream_t stream) {
     FLAIR_CHECK(p && qkv && kpos && out, "flair_temporal_attention: null argument");
-    FLAIR_CHECK(p->C % 64 == 0 && p->window % 2 == 1 && p->window >= 3, "flair_temporal_attention: C=%d window=%d",
-                p->C, p->window);
+    const int d = p->head_dim ? p->head_dim : 64;   // 0: the width-64 default of ABI version <= 6
+    FLAIR_CHECK(d % 8 == 0 && d >= 8 && d <= 256,
+                "flair_temporal_attention: head width %d unsupported (multiples of 8 from 8 to 256)", d);
+    FLAIR_CHECK(p->C > 0 && p->C % d == 0 && p->window % 2 == 1 && p->window >= 3,
+                "flair_temporal_attention: C=%d head width=%d window=%d", p->C, d, p->window);
     FLAIR_CHECK(p->ld >= 3 * p->C && p->ld % 8 == 0 && p->out_ld % 8 == 0, "flair_temporal_attention: strides");
     TAttnArgs a;
     a.qkv = qkv; a.kpos = kpos; a.out = out; a.ld = p->ld; a.outLd = p->out_ld; a.T = p->T; a.C = p->C;
     a.window = p->window; a.HW = (long)p->H * p->W; a.roundFp16 = p->round_fp16; a.scale = p->scale;
-    const long threads = (long)p->T * a.HW * (p->C / 64) * 8;
-    const int grid = (int)((threads + 255) / 256);
+    a.headDim = d;
     if (p->dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(temporal_attn_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, a);
+        launch_temporal<bf16_t>(a, stream);
     else if (p->dtype == FLAIR_F32)
-        hipLaunchKernelGGL(temporal_attn_kernel<float>, dim3(grid), dim3(256), 0, stream, a);
+        launch_temporal<float>(a, stream);
     else
         FLAIR_CHECK(false, "flair_temporal_attention: bad dtype");
     FLAIR_LAUNCH_CHECK();

@@ -139,6 +139,28 @@ class ResBlock(nn.Module):
 
 
 # -------------------------------------------------------------------------- attention
+QKV_ATTN_WIDTHS = (32, 64, 128)   # flair_qkv_attention's MFMA (bf16) / row (f32) kernels, at any token count
+
+
+def qkv_head_width(channels, num_heads):
+    """Head width of a spatial attention block, refused at construction unless flair_qkv_attention can run it:
+    32, 64, 128 at any size; other multiples of 8 on flair_attention_wide while width + tokens <= 2048."""
+    d = channels // num_heads if num_heads > 0 and channels % num_heads == 0 else 0
+    if d <= 0 or d % 8:
+        raise NotImplementedError(f"flair_amd: attention head width {channels}/{num_heads} unsupported "
+                                  f"({QKV_ATTN_WIDTHS} at any size, other multiples of 8 while width + H*W <= 2048)")
+    return d
+
+
+def temporal_head_width(channels, num_heads):
+    """Head width of a temporal attention block: flair_temporal_attention runs multiples of 8 from 8 to 256."""
+    d = channels // num_heads if num_heads > 0 and channels % num_heads == 0 else 0
+    if d < 8 or d > 256 or d % 8:
+        raise NotImplementedError(f"flair_amd: temporal attention head width {channels}/{num_heads} unsupported "
+                                  "(multiples of 8 from 8 to 256)")
+    return d
+
+
 class QKVAttentionLegacy(nn.Module):
     """unet_new.py:540-570 -- layout marker; executed by ops.qkv_attention."""
 
@@ -165,6 +187,7 @@ class AttentionBlock(nn.Module):
         else:
             assert channels % num_head_channels == 0
             self.num_heads = channels // num_head_channels
+        qkv_head_width(channels, self.num_heads)
         if self.bottleneck:
             self.emb_layers = nn.Sequential(nn.SiLU(), linear(512, 512))
         self.norm = PlaceHolder(normalization(channels))
@@ -215,8 +238,7 @@ class TemporalAttention(nn.Module):
             assert channels % num_head_channels == 0
             self.num_heads = channels // num_head_channels
         assert num_frames % 2 == 1, "num_frames must be odd"
-        if channels // self.num_heads != 64:
-            raise NotImplementedError("flair_amd: temporal attention head width must be 64")
+        self.head_dim = temporal_head_width(channels, self.num_heads)
         self.num_frames = num_frames
         self.q_linear = linear(channels, channels)
         self.k_linear = linear(channels, channels)
@@ -256,7 +278,7 @@ class TemporalAttention(nn.Module):
         n = ops.group_norm(h, pk["g"], pk["be"], eps=self.norm.wrapped_module.eps)
         qkv = ops.conv(n, pk["wqkv"], pk["bqkv"], 3 * c, (1, 1, 1))
         a = ops.temporal_attention(qkv, pk["kpos"], self.num_frames,
-                                   round_fp16=(ctx.dtype == torch.float32))
+                                   round_fp16=(ctx.dtype == torch.float32), head_dim=self.head_dim)
         return ops.conv(a, pk["wp"], pk["bp"], c, (1, 1, 1), res0=h)
 
 

@@ -51,7 +51,7 @@ class TAttnParams(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int),
                 ("W", ctypes.c_int), ("C", ctypes.c_int), ("window", ctypes.c_int),
                 ("ld", ctypes.c_int), ("out_ld", ctypes.c_int), ("round_fp16", ctypes.c_int),
-                ("scale", ctypes.c_float)]
+                ("scale", ctypes.c_float), ("head_dim", ctypes.c_int)]
 
 
 class DcnParams(ctypes.Structure):
@@ -421,7 +421,9 @@ def qkv_attention(qkv, heads, *, new_order=False, out=None):
     return out
 
 
-def temporal_attention(qkv, kpos, window, *, round_fp16, out=None):
+def temporal_attention(qkv, kpos, window, *, round_fp16, head_dim=64, out=None):
+    """qkv: (T, H, W, 3C) clip tensor of q | k | v, C = heads * head_dim -> (T, H, W, C); softmax scale
+    1/sqrt(head_dim) (flash_attn_func's default)."""
     T, H, W, C3 = qkv.shape
     C = C3 // 3
     p = TAttnParams()
@@ -432,7 +434,8 @@ def temporal_attention(qkv, kpos, window, *, round_fp16, out=None):
         out = torch.empty((T, H, W, C), dtype=qkv.dtype, device=qkv.device)
     p.out_ld = _ld(out)
     p.round_fp16 = int(round_fp16)
-    p.scale = 1.0 / (64 ** 0.5)
+    p.head_dim = head_dim
+    p.scale = 1.0 / (head_dim ** 0.5)
     assert kpos.shape == (window - 1, C)
     check(lib().flair_temporal_attention(ctypes.byref(p), ptr(qkv), ptr(_f32(kpos)), ptr(out), stream()),
           "flair_temporal_attention")

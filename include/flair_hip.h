@@ -59,7 +59,8 @@ typedef enum {
 /* Last error message of the calling thread ("" if none). */
 const char* flair_last_error(void);
 /* ABI version of this header: bumped whenever entry points are added or a struct changes
- * (3: round 2; 4: + face crop / paste entries, flair_bcast_weights; 5: round 4 entries; 6: + calibration launches).
+ * (3: round 2; 4: + face crop / paste entries, flair_bcast_weights; 5: round 4 entries; 6: + calibration launches;
+ * 7: flair_tattn_params.head_dim).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -266,10 +267,12 @@ int flair_scale_pixels(void* x, int dtype, int ld, int C, long P, const float* w
                        hipStream_t stream);
 
 /* ---------------------------------------------------------------------- attention
- * Spatial attention over the L tokens of each frame, per head of width 64
+ * Spatial attention over the L tokens of each frame, per head of width d = head_dim
  * (unet_new.py:540-605).  qkv: [frames][L][ld]; q/k/v of head h start at channel
- * {q,k,v}_off + h*head_stride (legacy order: 0/64/128 + h*192; new order: 0/C/2C + h*64);
- * out: [frames][L][out_ld], channel h*64 + d.  scale multiplies q.k (1/sqrt(64)). */
+ * {q,k,v}_off + h*head_stride (legacy order: 0/d/2d + h*3d; new order: 0/C/2C + h*d);
+ * out: [frames][L][out_ld], channel h*d + j.  scale multiplies q.k (1/sqrt(d)).
+ * d = 32, 64, 128: MFMA kernels (bf16) / exact row kernels (f32) at any L; any other
+ * multiple of 8 runs on flair_attention_wide while d + L <= 2048; else -1. */
 typedef struct {
     int dtype;
     int frames, L, heads, head_dim;
@@ -281,15 +284,18 @@ int flair_qkv_attention(const flair_attn_params* p, const void* qkv, void* out, 
 
 /* Temporal window attention per pixel (unet_new.py:473-515 + nn.py:370-386): query = own
  * frame, keys/values = the window-1 neighbouring frames (replicate padded), softmax scale
- * `scale`.  qkv: [T][H*W][ld] holding q|k|v (C each); kpos: [window-1][C] f32 added to the
+ * `scale` (flash_attn_func's default is 1/sqrt(head_dim)).  qkv: [T][H*W][ld] holding q|k|v
+ * (C each, C/head_dim heads of head_dim channels); kpos: [window-1][C] f32 added to the
  * keys of each window slot (W_k applied to the positional code of that offset);
- * round_fp16 reproduces the reference's fp16 cast of q/k/v and of the result. */
+ * round_fp16 reproduces the reference's fp16 cast of q/k/v and of the result.
+ * head_dim: a multiple of 8 from 8 to 256; 0 means 64 (ABI version <= 6 callers). */
 typedef struct {
     int dtype;
     int T, H, W, C, window;
     int ld, out_ld;
     int round_fp16;
     float scale;
+    int head_dim;
 } flair_tattn_params;
 int flair_temporal_attention(const flair_tattn_params* p, const void* qkv, const float* kpos,
                              void* out, hipStream_t stream);
