@@ -8,7 +8,11 @@ torchvision's ResNet-50 behind ``IntermediateLayerGetter`` (``retinaface.py:99-1
 outputs of layer2, layer3, layer4) -- torchvision is not importable here, so its v1.5 Bottleneck layout (stride on the 3x3
 convolution) is restated and that part is PARITY UNPINNED; the state-dict names are the reference's
 (``detection_Resnet50_Final.pth`` with its ``module.`` prefixes stripped as ``facelib/detection/__init__.py:39-43`` does
-loads unchanged).
+loads unchanged).  ``network_name="mobile0.25"`` builds the other body of ``retinaface.py:95-98`` (``cfg_mnet``):
+``MobileNetV1`` of ``retinaface_net.py:100-135`` behind the same getter (stage1 / stage2 / stage3), whose ``conv_dw`` blocks
+are a depthwise ``flair_dwconv_nhwc`` launch and a 1x1 ``flair_conv_nhwc`` launch each; it imports torch only, so that body
+is pinned against the reference like the rest (``tests/golden/g12_retinaface_mobile.npz``), and
+``detection_mobilenet0.25_Final.pth`` loads the same way.
 
 The ``nn.Module`` classes are parameter containers.  Every Conv2d + eval BatchNorm (+ LeakyReLU / ReLU) is ONE
 ``flair_conv_nhwc`` launch with the BatchNorm folded into the packed weights; the Bottleneck's ``relu(out + identity)`` and
@@ -20,6 +24,7 @@ once, too).  float32 throughout, like the reference (``half=False``).
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _lib, ops
 from .. import ops as A
@@ -32,8 +37,9 @@ def generate_config(network_name):
         return {"name": "Resnet50", "min_sizes": [[16, 32], [64, 128], [256, 512]], "steps": [8, 16, 32], "variance": [0.1, 0.2],
                 "clip": False, "return_layers": {"layer2": 1, "layer3": 2, "layer4": 3}, "in_channel": 256, "out_channel": 256}
     if network_name == "mobile0.25":
-        raise NotImplementedError("flair_amd: the MobileNet-0.25 body (depthwise convolutions) is not built; FLAIR uses "
-                                  "det_model='retinaface_resnet50' (face_restoration_helper.py:69)")
+        return {"name": "mobilenet0.25", "min_sizes": [[16, 32], [64, 128], [256, 512]], "steps": [8, 16, 32],
+                "variance": [0.1, 0.2], "clip": False, "return_layers": {"stage1": 1, "stage2": 2, "stage3": 3}, "in_channel": 32,
+                "out_channel": 64}
     raise NotImplementedError(f"network_name={network_name}")
 
 
@@ -47,8 +53,8 @@ class _ConvBN(nn.Sequential):
         super().__init__(*layers)
         self.leaky = leaky
 
-    def pack(self, dtype, device, relu_after=False):
-        self._p = _fold(self[0], self[1], dtype, device)
+    def pack(self, dtype, device, relu_after=False, cout_pad=None):
+        self._p = _fold(self[0], self[1], dtype, device, cout_pad)
         lk = self.leaky
         self._act = (A.ACT_RELU if lk == 0 else A.ACT_LRELU01) if lk is not None else (A.ACT_RELU if relu_after else A.ACT_NONE)
         assert lk in (None, 0, 0.1)
@@ -57,16 +63,23 @@ class _ConvBN(nn.Sequential):
         return _conv(x, self._p, self[0], self._act, out=out)
 
 
-def _fold(conv, bn, dtype, device):
-    """Packed weights / bias of conv followed by an eval-mode BatchNorm (bn may be None)."""
+def _fold_bn(conv, bn):
+    """conv's weight / bias (f32) with an eval-mode BatchNorm after it folded in (bn may be None)."""
     w = conv.weight.detach().float()
     b = conv.bias.detach().float() if conv.bias is not None else w.new_zeros(w.shape[0])
     if bn is not None:
         g = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
         w = w * g.view(-1, 1, 1, 1)
         b = (b - bn.running_mean.detach().float()) * g + bn.bias.detach().float()
+    return w, b
+
+
+def _fold(conv, bn, dtype, device, cout_pad=None):
+    """Packed weights / bias of conv followed by an eval-mode BatchNorm (bn may be None); cout_pad: zero output channels
+    appended up to that width (default: the next multiple of 4)."""
+    w, b = _fold_bn(conv, bn)
     cout, cin = w.shape[0], w.shape[1]
-    cpad = (cout + 3) // 4 * 4
+    cpad = cout_pad if cout_pad is not None else (cout + 3) // 4 * 4
     wp = ops.pack_conv_weight(w.to(device), [(cin, ops.pad_channels(cin, dtype))], dtype, cpad)
     b = b.to(device)
     return wp, torch.cat([b, b.new_zeros(cpad - cout)]).contiguous(), cpad
@@ -138,6 +151,65 @@ class _ResNet50Body(nn.Module):
                 h = blk.run(h)
             if i >= 2:
                 outs.append(h)
+        return outs
+
+
+class _ConvDW(nn.Sequential):
+    """conv_dw of retinaface_net.py:25-33: Sequential(depthwise Conv2d(3, stride, groups=inp), BatchNorm2d, LeakyReLU(0.1),
+    Conv2d(inp, oup, 1), BatchNorm2d, LeakyReLU(0.1)), both BatchNorms folded: the depthwise-only flair_dwconv_nhwc launch, then
+    the 1x1 as flair_conv_nhwc.  That pair measured faster than the fused depthwise + 1x1 launch at 512^2 (512 vs 852 us for
+    the 13 blocks of a 10-frame window, profiles/retinaface_mobile_detect.txt).  Channels are padded to
+    ops.pad_channels with zero weights and biases, so the padding stays zero from block to block."""
+
+    def __init__(self, inp, oup, stride, leaky=0.1):
+        super().__init__(nn.Conv2d(inp, inp, 3, stride, 1, groups=inp, bias=False), nn.BatchNorm2d(inp),
+                         nn.LeakyReLU(negative_slope=leaky, inplace=True), nn.Conv2d(inp, oup, 1, 1, 0, bias=False),
+                         nn.BatchNorm2d(oup), nn.LeakyReLU(negative_slope=leaky, inplace=True))
+        assert leaky == 0.1
+        self.stride = stride
+
+    def pack(self, dtype, device):
+        assert dtype == torch.float32
+        inp, oup = self[0].out_channels, self[3].out_channels
+        cp, op = ops.pad_channels(inp, dtype), ops.pad_channels(oup, dtype)
+        wd, bd = _fold_bn(self[0], self[1])                                   # (inp, 1, 3, 3)
+        wp, bp = _fold_bn(self[3], self[4])                                   # (oup, inp, 1, 1)
+        w_dw = torch.zeros(9, cp)
+        w_dw[:, :inp] = wd.reshape(inp, 9).t()
+        w_pw = ops.pack_conv_weight(wp.to(device), [(inp, cp)], dtype, op)
+        self._p = (w_dw.to(device), F.pad(bd, (0, cp - inp)).to(device), w_pw, F.pad(bp, (0, op - oup)).to(device), op)
+
+    def run(self, x):
+        w_dw, b_dw, w_pw, b_pw, op = self._p
+        d = ops.dwconv(x, w_dw, b_dw, stride=self.stride, act=A.ACT_LRELU01)
+        return ops.conv(d, w_pw, b_pw, op, (1, 1, 1), act=A.ACT_LRELU01)
+
+
+class _MobileNetV1Body(nn.Module):
+    """What IntermediateLayerGetter(MobileNetV1(), {'stage1': 1, 'stage2': 2, 'stage3': 3}) keeps of retinaface_net.py:100-135
+    (avg / fc are dropped, so the state dict has neither): stage1 = conv_bn(3, 8, 2, leaky=0.1) + five conv_dw, stage2 = six
+    conv_dw, stage3 = two conv_dw; run() returns the outputs of the three stages (strides 8 / 16 / 32; 64 / 128 / 256 channels)."""
+
+    def __init__(self):
+        super().__init__()
+        self.stage1 = nn.Sequential(_ConvBN(3, 8, 3, 2, leaky=0.1), _ConvDW(8, 16, 1), _ConvDW(16, 32, 2), _ConvDW(32, 32, 1),
+                                    _ConvDW(32, 64, 2), _ConvDW(64, 64, 1))
+        self.stage2 = nn.Sequential(_ConvDW(64, 128, 2), *[_ConvDW(128, 128, 1) for _ in range(5)])
+        self.stage3 = nn.Sequential(_ConvDW(128, 256, 2), _ConvDW(256, 256, 1))
+
+    def pack(self, dtype, device):
+        self.stage1[0].pack(dtype, device, cout_pad=ops.pad_channels(8, dtype))     # zero channels 8..15 feed the first conv_dw
+        for m in self.modules():
+            if isinstance(m, _ConvDW):
+                m.pack(dtype, device)
+
+    def run(self, x):
+        h = self.stage1[0].run(x)
+        outs = []
+        for stage in (self.stage1[1:], self.stage2, self.stage3):
+            for blk in stage:
+                h = blk.run(h)
+            outs.append(h)
         return outs
 
 
@@ -258,7 +330,7 @@ class RetinaFace(nn.Module):
         self.target_size, self.max_size = 1600, 2150
         self.resize, self.scale, self.scale1 = 1.0, None, None
         self.mean = (104.0, 117.0, 123.0)
-        self.body = _ResNet50Body()
+        self.body = _MobileNetV1Body() if cfg["name"] == "mobilenet0.25" else _ResNet50Body()
         c2 = cfg["in_channel"]
         oc = cfg["out_channel"]
         self.fpn = FPN([c2 * 2, c2 * 4, c2 * 8], oc)
@@ -299,7 +371,8 @@ class RetinaFace(nn.Module):
         return self._neck_heads(self.body.run(x))
 
     def _neck_heads(self, body_feats):
-        """FPN -> SSH -> heads on the three body outputs (clip tensors of 512 / 1024 / 2048 channels)."""
+        """FPN -> SSH -> heads on the three body outputs (clip tensors of 512 / 1024 / 2048 channels for ResNet-50, 64 / 128 /
+        256 for MobileNet-0.25)."""
         fpn = self.fpn.run(body_feats)
         feats = [self.ssh1.run(fpn[0]), self.ssh2.run(fpn[1]), self.ssh3.run(fpn[2])]
         bbox = torch.cat([self.BboxHead[i].run(f) for i, f in enumerate(feats)], dim=1)

@@ -704,6 +704,24 @@ def add_act(x0, x1=None, act=ACT_NONE, out=None):
     return out
 
 
+def dwconv(x, w_dw, b_dw, *, stride, pw=None, act=ACT_LRELU01, out=None):
+    """MobileNet ``conv_dw`` block on an f32 clip tensor (flair_dwconv_nhwc): act(depthwise 3x3(x) + b_dw), then, when
+    pw = (w_pw [Cout][C], b_pw [Cout]) is given, act(1x1 of that + b_pw) in the same launch.  w_dw: [9][C] f32 (BatchNorm folded);
+    x has C = w_dw.shape[1] channels (padded to a multiple of 4); out: optional (T, ceil(H/s), ceil(W/s), >= Cout) view."""
+    T, H, W, C = x.shape
+    assert x.dtype == torch.float32 and tuple(w_dw.shape) == (9, C)
+    w_pw, b_pw = pw if pw is not None else (None, None)
+    cout = w_pw.shape[0] if w_pw is not None else C
+    assert w_pw is None or tuple(w_pw.shape) == (cout, C)
+    Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
+    if out is None:
+        out = torch.empty((T, Ho, Wo, cout), dtype=torch.float32, device=x.device)
+    assert tuple(out.shape[:3]) == (T, Ho, Wo) and out.shape[3] >= cout and out.dtype == torch.float32
+    check(lib().flair_dwconv_nhwc(ptr(x), _ld(x), T, H, W, C, stride, ptr(_f32(w_dw)), ptr(_f32(b_dw)), ptr(_f32(w_pw)),
+                                  ptr(_f32(b_pw)), cout, act, ptr(out), _ld(out), stream()), "flair_dwconv_nhwc")
+    return out
+
+
 def maxpool3x3s2(x, out=None):
     """nn.MaxPool2d(3, 2, 1) on a clip tensor."""
     T, H, W, C = x.shape

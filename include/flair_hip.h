@@ -60,7 +60,7 @@ typedef enum {
 const char* flair_last_error(void);
 /* ABI version of this header: bumped whenever entry points are added or a struct changes
  * (3: round 2; 4: + face crop / paste entries, flair_bcast_weights; 5: round 4 entries; 6: + calibration launches;
- * 7: flair_tattn_params.head_dim).
+ * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -255,6 +255,16 @@ int flair_add_act_nhwc(const void* x0, int x0_ld, const void* x1, int x1_ld, int
 /* nn.MaxPool2d(3, stride 2, padding 1) on [F][H][W][C] -> [F][(H+1)/2][(W+1)/2][C] (the stem of that ResNet-50). */
 int flair_maxpool3x3s2_nhwc(const void* x, int x_ld, int dtype, int F, int H, int W, int C, void* y,
                             int y_ld, hipStream_t stream);
+/* `conv_dw` of the detector's MobileNet-0.25 body (retinaface_net.py:25-33, built by MobileNetV1 at :100-135 for
+ * retinaface.py:95-98, cfg_mnet at :31-49) on f32 [T][H][W][x_ld] clip tensors:
+ *   d = act(depthwise3x3(x, w_dw) + b_dw)   groups = C, stride 1 or 2, zero padding 1, out ceil(H/s) x ceil(W/s)
+ *   y = act(d @ w_pw^T + b_pw)              1x1 C -> Cout, in the same launch (d stays on chip)
+ * w_dw: [9][C] (tap-major, BatchNorm scale folded in); w_pw: [Cout][C]; biases f32 [C] / [Cout] (NULL = 0).  w_pw == NULL:
+ * y = d alone (Cout ignored).  act applies to both stages (ACT_LRELU01 for conv_dw).  C and Cout multiples of 4, C <= 512
+ * with the 1x1 stage; y_ld >= the channels written; all pointers 16-byte aligned. */
+int flair_dwconv_nhwc(const float* x, int x_ld, int T, int H, int W, int C, int stride, const float* w_dw,
+                      const float* b_dw, const float* w_pw, const float* b_pw, int Cout, int act, float* y,
+                      int y_ld, hipStream_t stream);
 /* x[f][p][c] += bias[f][c]  (AttentionbottleBlock h + emb_out, unet_new.py:426-428). */
 int flair_add_frame_bias(void* x, int dtype, int ld, int C, int F, long HW, const float* bias,
                          int bias_ld, hipStream_t stream);
