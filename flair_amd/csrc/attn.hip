@@ -1,17 +1,21 @@
 // Attention kernels of the FLAIR UNet.
 //
 // (1) Spatial QKV attention per (frame, head) over the H*W tokens of a frame, head
-//     width D in {32, 64, 128} -- replaces QKVAttentionLegacy / QKVAttention (guided_diffusion/
-//     unet_new.py:540-605: einsum QK^T, f32 softmax, einsum AV).  Other widths (multiples of 8)
-//     go to flair_attention_wide (prior.hip) while its LDS tile holds them (d + L <= 2048).
+//     width D in {32, 64, 128} or a multiple of 64 from 192 to 1024 (one head per layer at
+//     the modules' defaults) -- replaces QKVAttentionLegacy / QKVAttention (guided_diffusion/
+//     unet_new.py:540-605: einsum QK^T, f32 softmax, einsum AV), at any L.  Other widths
+//     (multiples of 8) go to flair_attention_wide (prior.hip) while its LDS tile holds them
+//     (d + L <= 2048).
 //       * bf16: flash-style MFMA kernel.  S^T = K.Q^T is computed with keys on the
 //         accumulator rows and queries on the lanes, so the softmax row statistics are
 //         lane-local (+1 exchange with lane^32) and the probability tile is reused in
 //         place as the B operand of O^T += V^T.P^T (cdna_hip_programming.md section 3,
 //         "An accumulator tile as the next MFMA's operand").
+//         From D = 192 the channels of one head are split across the waves of a workgroup,
+//         which sum their partial scores through LDS (attn_mfma_bf16_wide_kernel).
 //       * f32: one wavefront per query at D = 64 (one channel per lane), two queries per
-//         wavefront at D = 32, two channels per lane at D = 128; exact f32 arithmetic; this
-//         is the tight-tolerance parity path, not a speed path.
+//         wavefront at D = 32, two / D/64 channels per lane at D = 128 / from 192; exact f32
+//         arithmetic; this is the tight-tolerance parity path, not a speed path.
 // (2) Temporal window attention per pixel -- replaces TemporalAttention's
 //     unfold + flash_attn_func (unet_new.py:473-515, nn.py:370-386): one query (own
 //     frame) against the F-1 neighbouring frames (replicate padding at clip ends).
@@ -409,6 +413,244 @@ __global__ __launch_bounds__(64 * NW, D == 128 ? 2 : 3) void attn_mfma_bf16_v2_k
         }
 }
 
+// -------------------------------------------------------- bf16 MFMA, wide heads (d = 192 ... 1024)
+// One head of d = 64 * nc channels (nc = 3 ... 16) for 32 queries per workgroup of NW waves, KV tiles of 32 tokens.
+// A 32 x d f32 O^T tile is 4 KiB per 32 channels, too much for one wave, so the CHANNELS are split across the waves:
+// 64-channel chunk c belongs to wave c % NW, which owns up to CPW chunks (template parameters; the run-time nc masks
+// the last one): NW = 4, CPW = 1 up to d = 256, NW = 4, CPW = 2 up to 512, NW = 8, CPW = 2 beyond (4 waves with 3 or 4
+// chunks each need 416 / > 512 registers: the 4-chunk build spilled).  Per tile, every wave
+//   * computes its partial S^T = K_c . Q_c^T over its own chunks (the K fragments come straight from global memory:
+//     no other wave reads them, and the 16-byte loads of one chunk consume whole 128-byte lines);
+//   * writes the partial (16 floats per lane) to LDS; ONE workgroup barrier; reads the NW partials and adds them in
+//     wave order, so all waves hold the same S^T bit for bit;
+//   * runs the online softmax of v2 on it (redundantly in each wave: the same cost per wave as one wave doing it,
+//     and no second barrier to hand P around) and keeps P^T in registers as the B operand;
+//   * does O^T_c += V_c^T . P^T for its own chunks, V_c read transposed (ds_read_b64_tr_b16) from a tile that only
+//     this wave writes: [32 tokens][64 * CPW] bf16 rows at pitch 64 * (2 * CPW + 1) bytes, an odd multiple of 64 B
+//     (conflict-free transposed reads, see v2).  The wave writes V(t) there after its S MFMAs and reads it after the
+//     barrier; LDS operations of one wave are executed in order, so no barrier guards this tile.
+// K(t+1) is requested into registers right after tile t's S MFMAs, V(t+1) right after tile t's softmax (so it is not
+// live across the exchange, where the NW partials are); both land during the remaining work of tile t.  The
+// partials are double-buffered by tile parity, so the one barrier per tile also orders tile t+2's writes after tile
+// t's reads.  LDS: 2 x NW x 4 KiB of partials + NW x 32 x pitch = 56 / 72 / 144 KiB (two / two / one per CU).
+template <int NW, int CPW>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_mfma_bf16_wide_kernel(AttnArgs a, int nc) {
+    constexpr int VP = 64 * (2 * CPW + 1);
+    extern __shared__ __attribute__((aligned(16))) char wsmem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 31, lh = lane >> 5;
+    const int fh = blockIdx.y;
+    const int f = fh / a.heads, hd = fh % a.heads;
+    const bf16_t* base = reinterpret_cast<const bf16_t*>(a.qkv) + (long)f * a.L * a.ld + hd * a.headStride;
+    const int q = blockIdx.x * 32 + lr;
+    const bool qok = q < a.L;
+    float4* sS = reinterpret_cast<float4*>(wsmem);                    // [parity][wave][4][64 lanes] float4
+    char* sv = wsmem + 2 * NW * 4 * 64 * 16 + wave * 32 * VP;         // this wave's V tile
+    // chunk j of this wave: channels 64 * (wave + NW*j) ..; only the last j can be beyond nc (wave-uniform)
+    auto own = [&](int j) { return wave + NW * j < nc; };
+    auto chan = [&](int j) { return own(j) ? 64 * (wave + NW * j) : 0; };
+
+    // rows beyond L (queries of the last block, tokens of the last tile) are read from row L-1 instead of masked
+    // loads: those queries are not stored, those tokens' scores are set to -1e30 after the exchange (P = 0 against
+    // finite V); a chunk the wave does not own reads chunk 0 (in bounds) and is skipped by wave-uniform branches
+    const int qc = qok ? q : a.L - 1;
+    uint4 qf[CPW][4];
+#pragma unroll
+    for (int j = 0; j < CPW; ++j)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            qf[j][s] = *reinterpret_cast<const uint4*>(base + (long)qc * a.ld + a.qOff + chan(j) + 16 * s + 8 * lh);
+    f32x16 o[CPW][2];
+#pragma unroll
+    for (int j = 0; j < CPW; ++j)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[j][b][r] = 0.f;
+    float m = -1e30f, l = 0.f;
+    const float sc = a.scale * 1.4426950408889634f;
+
+    // K fragments (A operand of S^T: row kv = lane&31, channels 16s + 8*lh ..) and V (token lane>>1, channels
+    // 32*(lane&1) + 8i .. of the chunk: one address per lane and chunk) of tile t
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // a register value: uint4 copies into LDS went
+    uint4 kf[CPW][4];                                                // through a scratch temporary (memcpy)
+    u32x4 vr[CPW][4];
+    auto issueK = [&](int t) {
+        const int tk = min(t * 32 + lr, a.L - 1);
+#pragma unroll
+        for (int j = 0; j < CPW; ++j)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                kf[j][s] = *reinterpret_cast<const uint4*>(base + (long)tk * a.ld + a.kOff + chan(j) + 16 * s + 8 * lh);
+    };
+    auto issueV = [&](int t) {
+        const int tv = min(t * 32 + (lane >> 1), a.L - 1);
+#pragma unroll
+        for (int j = 0; j < CPW; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                vr[j][i] = *reinterpret_cast<const u32x4*>(base + (long)tv * a.ld + a.vOff + chan(j) + 32 * (lane & 1) + 8 * i);
+    };
+    const int gl = lane & 15;
+    const int trOff = ((gl >> 2) + 4 * lh) * VP + (16 * ((lane >> 4) & 1) + 4 * (gl & 3)) * 2;
+
+    const int ntile = (a.L + 31) / 32;
+    issueK(0);
+    issueV(0);
+    for (int t = 0; t < ntile; ++t) {
+        // ---- partial S^T[kv][q] over this wave's chunks
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int j = 0; j < CPW; ++j)
+            if (own(j))
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+                    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[j][ks]),
+                                                                __builtin_bit_cast(bf16x8, qf[j][ks]), s, 0, 0, 0);
+        if (t + 1 < ntile) issueK(t + 1);
+        // ---- V(t) into this wave's tile (after tile t-1's transposed reads: same wave, in order)
+#pragma unroll
+        for (int j = 0; j < CPW; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                *reinterpret_cast<u32x4*>(sv + (lane >> 1) * VP + 128 * j + 64 * (lane & 1) + 16 * i) = vr[j][i];
+        asm volatile("" ::: "memory");   // and this tile's transposed reads behind these stores
+        // ---- sum the NW partials through LDS (same order in every wave)
+        float4* slot = sS + (t & 1) * NW * 256;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            slot[wave * 256 + g * 64 + lane] = make_float4(s[4 * g], s[4 * g + 1], s[4 * g + 2], s[4 * g + 3]);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 v = slot[w * 256 + g * 64 + lane];
+                s[4 * g] += v.x; s[4 * g + 1] += v.y; s[4 * g + 2] += v.z; s[4 * g + 3] += v.w;
+            }
+        // ---- online softmax (as v2): rows of this lane are kv = (r&3) + 8*(r>>2) + 4*lh
+        if ((t + 1) * 32 > a.L) {
+            asm volatile("; partly masked last tile" ::: "memory");
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh >= a.L) s[r] = -1e30f;
+        }
+        float tmax = -1e30f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32)) * sc;
+        const float mn = fmaxf(m, tmax);
+        float ps[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = __builtin_amdgcn_exp2f(fmaf(s[r], sc, -mn));
+            ps[r & 3] += s[r];
+        }
+        float psum = (ps[0] + ps[1]) + (ps[2] + ps[3]);
+        psum += __shfl_xor(psum, 32);
+        if (__builtin_amdgcn_ballot_w64(mn > m) != 0) {
+            const float alpha = __builtin_amdgcn_exp2f(m - mn);
+            l *= alpha;
+#pragma unroll
+            for (int j = 0; j < CPW; ++j)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[j][b][r] *= alpha;
+            m = mn;
+        }
+        l += psum;
+        if (t + 1 < ntile) issueV(t + 1);   // lands during this P.V and the next S (not live across the exchange)
+        // ---- O^T[d][q] += V^T[d][kv] . P^T[kv][q] for this wave's chunks
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            uint4 pf;
+            pf.x = cvt_pk_bf16_asm(s[8 * ks + 0], s[8 * ks + 1]);
+            pf.y = cvt_pk_bf16_asm(s[8 * ks + 2], s[8 * ks + 3]);
+            pf.z = cvt_pk_bf16_asm(s[8 * ks + 4], s[8 * ks + 5]);
+            pf.w = cvt_pk_bf16_asm(s[8 * ks + 6], s[8 * ks + 7]);
+#pragma unroll
+            for (int j = 0; j < CPW; ++j)
+                if (own(j))
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const char* vb = sv + 16 * ks * VP + 128 * j + 64 * b + trOff;
+                        const s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                            (__attribute__((address_space(3))) s16x4_t*)(vb));
+                        const s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                            (__attribute__((address_space(3))) s16x4_t*)(vb + 8 * VP));
+                        uint4 vf;
+                        vf.x = ((const unsigned*)&v0)[0]; vf.y = ((const unsigned*)&v0)[1];
+                        vf.z = ((const unsigned*)&v1)[0]; vf.w = ((const unsigned*)&v1)[1];
+                        o[j][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf),
+                                                                          __builtin_bit_cast(bf16x8, pf), o[j][b], 0, 0, 0);
+                    }
+        }
+        asm volatile("" ::: "memory");   // the next tile's V stores stay behind these reads
+    }
+    if (!qok) return;
+    const float inv = 1.f / l;
+    bf16_t* op = reinterpret_cast<bf16_t*>(a.out) + ((long)f * a.L + q) * a.outLd + hd * 64 * nc;
+#pragma unroll
+    for (int j = 0; j < CPW; ++j)
+        if (own(j))
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    uint2 pk;
+                    pk.x = pack2bf(o[j][b][4 * g + 0] * inv, o[j][b][4 * g + 1] * inv);
+                    pk.y = pack2bf(o[j][b][4 * g + 2] * inv, o[j][b][4 * g + 3] * inv);
+                    *reinterpret_cast<uint2*>(op + 64 * (wave + NW * j) + 32 * b + 8 * g + 4 * lh) = pk;
+                }
+}
+
+// f32 at the wide widths: attn_rowwise_kernel's one wavefront per query with nc = d / 64 channels per lane (lane + 64j)
+__global__ void attn_rowwise_wide_kernel(AttnArgs a, int nc) {
+    constexpr int MAXC = 16;
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int fh = blockIdx.y;
+    const int f = fh / a.heads, hd = fh % a.heads;
+    if (q >= a.L) return;
+    const float* base = reinterpret_cast<const float*>(a.qkv) + (long)f * a.L * a.ld + hd * a.headStride + lane;
+    float qv[MAXC], acc[MAXC];
+#pragma unroll
+    for (int j = 0; j < MAXC; ++j) {
+        qv[j] = j < nc ? base[(long)q * a.ld + a.qOff + 64 * j] : 0.f;
+        acc[j] = 0.f;
+    }
+    float m = -INFINITY, l = 0.f;
+    for (int s = 0; s < a.L; ++s) {
+        const float* kr = base + (long)s * a.ld + a.kOff;
+        float d = qv[0] * kr[0];
+#pragma unroll
+        for (int j = 1; j < MAXC; ++j)
+            if (j < nc) d = fmaf(qv[j], kr[64 * j], d);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off);
+        d *= a.scale;
+        const float mn = fmaxf(m, d);
+        const float alpha = __expf(m - mn);
+        const float p = __expf(d - mn);
+        l = l * alpha + p;
+        const float* vr = base + (long)s * a.ld + a.vOff;
+#pragma unroll
+        for (int j = 0; j < MAXC; ++j)
+            if (j < nc) acc[j] = acc[j] * alpha + p * vr[64 * j];
+        m = mn;
+    }
+    float* o = reinterpret_cast<float*>(a.out) + ((long)f * a.L + q) * a.outLd + hd * 64 * nc + lane;
+#pragma unroll
+    for (int j = 0; j < MAXC; ++j)
+        if (j < nc) o[64 * j] = acc[j] / l;
+}
+
 // ---------------------------------------------------------------- temporal window
 template <typename E> __device__ __forceinline__ void load8(const E* p, float* v);
 template <> __device__ __forceinline__ void load8<float>(const float* p, float* v) {
@@ -544,19 +786,43 @@ void launch_qkv_f32(const flair_attn_params* p, const AttnArgs& a, hipStream_t s
                        stream, a);
 }
 
+// d = 64 * nc, nc = 3 ... 16: 4 waves with 1 or 2 chunks each up to nc = 8, else 8 waves with up to 2 chunks
+template <int NW, int CPW>
+int launch_qkv_bf16_wide_cfg(const flair_attn_params* p, const AttnArgs& a, int nc, hipStream_t stream) {
+    constexpr int lds = 2 * NW * 4 * 64 * 16 + NW * 32 * 64 * (2 * CPW + 1);
+    static LdsAttrOnce attr;
+    FLAIR_CHECK(flair_max_lds_once(attr, reinterpret_cast<const void*>(&attn_mfma_bf16_wide_kernel<NW, CPW>), lds) ==
+                    hipSuccess,
+                "flair_qkv_attention: hipFuncSetAttribute failed");
+    hipLaunchKernelGGL((attn_mfma_bf16_wide_kernel<NW, CPW>), dim3((p->L + 31) / 32, p->frames * p->heads), dim3(64 * NW),
+                       lds, stream, a, nc);
+    return FLAIR_OK;
+}
+
+int launch_qkv_bf16_wide(const flair_attn_params* p, const AttnArgs& a, hipStream_t stream) {
+    const int nc = p->head_dim / 64;
+    if (nc <= 4) return launch_qkv_bf16_wide_cfg<4, 1>(p, a, nc, stream);
+    if (nc <= 8) return launch_qkv_bf16_wide_cfg<4, 2>(p, a, nc, stream);
+    return launch_qkv_bf16_wide_cfg<8, 2>(p, a, nc, stream);
+}
+
 }  // namespace
 
 // flair_attention_wide (prior.hip) holds 16 rows of d + L floats in 128 KiB of LDS
 constexpr int kWideAttnMaxDL = 2048;
+// flair_qkv_attention's wide-head kernels: multiples of 64 in [192, 1024] at any L
+constexpr int kWideHeadMin = 192, kWideHeadMax = 1024;
 
 extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, void* out, hipStream_t stream) {
     FLAIR_CHECK(p && qkv && out, "flair_qkv_attention: null argument");
     FLAIR_CHECK(p->frames > 0 && p->L > 0 && p->heads > 0, "flair_qkv_attention: empty shape");
     const int d = p->head_dim;
     const bool native = d == 32 || d == 64 || d == 128;
-    FLAIR_CHECK(native || (d > 0 && d % 8 == 0 && d + p->L <= kWideAttnMaxDL),
-                "flair_qkv_attention: head width %d unsupported at L = %d (32, 64 and 128 at any L; other multiples of 8 "
-                "while head width + L <= %d)", d, p->L, kWideAttnMaxDL);
+    const bool wide = d % 64 == 0 && d >= kWideHeadMin && d <= kWideHeadMax;
+    FLAIR_CHECK(native || wide || (d > 0 && d % 8 == 0 && d + p->L <= kWideAttnMaxDL),
+                "flair_qkv_attention: head width %d unsupported at L = %d (32, 64 and 128 and multiples of 64 from %d to "
+                "%d at any L; other multiples of 8 while head width + L <= %d)", d, p->L, kWideHeadMin, kWideHeadMax,
+                kWideAttnMaxDL);
     FLAIR_CHECK(p->ld % 8 == 0 && p->out_ld % 8 == 0 && p->q_off % 8 == 0 && p->k_off % 8 == 0 &&
                     p->v_off % 8 == 0 && p->head_stride % 8 == 0,
                 "flair_qkv_attention: offsets/strides must be multiples of 8 elements");
@@ -564,7 +830,7 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
                                            : (p->k_off > p->v_off ? p->k_off : p->v_off);
     FLAIR_CHECK(hi_off + (long)(p->heads - 1) * p->head_stride + d <= p->ld && (long)p->heads * d <= p->out_ld,
                 "flair_qkv_attention: %d heads of width %d exceed ld %d / out_ld %d", p->heads, d, p->ld, p->out_ld);
-    if (!native) return flair_attention_wide(p, qkv, out, stream);
+    if (!native && !wide) return flair_attention_wide(p, qkv, out, stream);
     AttnArgs a;
     a.qkv = qkv; a.out = out; a.ld = p->ld; a.outLd = p->out_ld; a.L = p->L; a.heads = p->heads;
     a.qOff = p->q_off; a.kOff = p->k_off; a.vOff = p->v_off; a.headStride = p->head_stride;
@@ -572,7 +838,10 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
     if (p->dtype == FLAIR_BF16) {
         // FLAIR_ATTN_V2=0 selects the round-1 kernel, which exists for head width 64 only
         static const int v2 = getenv("FLAIR_ATTN_V2") ? atoi(getenv("FLAIR_ATTN_V2")) : 1;
-        if (d == 32)
+        if (wide) {
+            const int rc = launch_qkv_bf16_wide(p, a, stream);
+            if (rc != FLAIR_OK) return rc;
+        } else if (d == 32)
             launch_qkv_bf16<32>(p, a, stream);
         else if (d == 128)
             launch_qkv_bf16<128>(p, a, stream);
@@ -582,7 +851,10 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
         else
             launch_qkv_bf16<64>(p, a, stream);
     } else if (p->dtype == FLAIR_F32) {
-        if (d == 32)
+        if (wide)
+            hipLaunchKernelGGL(attn_rowwise_wide_kernel, dim3((p->L + 3) / 4, p->frames * p->heads), dim3(256), 0, stream,
+                               a, d / 64);
+        else if (d == 32)
             launch_qkv_f32<32>(p, a, stream);
         else if (d == 128)
             launch_qkv_f32<128>(p, a, stream);

@@ -144,11 +144,13 @@ QKV_ATTN_WIDTHS = (32, 64, 128)   # flair_qkv_attention's MFMA (bf16) / row (f32
 
 def qkv_head_width(channels, num_heads):
     """Head width of a spatial attention block, refused at construction unless flair_qkv_attention can run it:
-    32, 64, 128 at any size; other multiples of 8 on flair_attention_wide while width + tokens <= 2048."""
+    32, 64, 128 and the multiples of 64 from 192 to 1024 at any size; other multiples of 8 on flair_attention_wide
+    while width + tokens <= 2048 (checked by the kernel entry at run time)."""
     d = channels // num_heads if num_heads > 0 and channels % num_heads == 0 else 0
     if d <= 0 or d % 8:
         raise NotImplementedError(f"flair_amd: attention head width {channels}/{num_heads} unsupported "
-                                  f"({QKV_ATTN_WIDTHS} at any size, other multiples of 8 while width + H*W <= 2048)")
+                                  f"({QKV_ATTN_WIDTHS} and multiples of 64 from 192 to 1024 at any size, other "
+                                  "multiples of 8 while width + H*W <= 2048)")
     return d
 
 

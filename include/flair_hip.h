@@ -281,8 +281,9 @@ int flair_scale_pixels(void* x, int dtype, int ld, int C, long P, const float* w
  * (unet_new.py:540-605).  qkv: [frames][L][ld]; q/k/v of head h start at channel
  * {q,k,v}_off + h*head_stride (legacy order: 0/d/2d + h*3d; new order: 0/C/2C + h*d);
  * out: [frames][L][out_ld], channel h*d + j.  scale multiplies q.k (1/sqrt(d)).
- * d = 32, 64, 128: MFMA kernels (bf16) / exact row kernels (f32) at any L; any other
- * multiple of 8 runs on flair_attention_wide while d + L <= 2048; else -1. */
+ * d = 32, 64, 128 and the multiples of 64 from 192 to 1024: MFMA kernels (bf16; from 192 the
+ * head's channels are split across the waves of a workgroup) / exact row kernels (f32) at any
+ * L; any other multiple of 8 runs on flair_attention_wide while d + L <= 2048; else -1. */
 typedef struct {
     int dtype;
     int frames, L, heads, head_dim;
@@ -411,7 +412,8 @@ int flair_layernorm_nhwc(const void* x, int dtype, int x_ld, long rows, int C, c
                          void* y2, int y2_ld, hipStream_t stream);
 /* Attention with heads of any width (AttnBlock.forward, codeformer.py:217-241: one head of C = 512 over the 256
  * pixels of the 16x16 level).  Same layout contract as flair_qkv_attention; head_dim a multiple of 8 (bf16) / 4
- * (f32), 64 * (head_dim + L) bytes of LDS <= 128 KiB. */
+ * (f32), 64 * (head_dim + L) bytes of LDS <= 128 KiB.  A 16-row VALU kernel: flair_qkv_attention calls it only for
+ * widths it has no MFMA kernel for (multiples of 8 other than 32, 64, 128 and 192 ... 1024 in steps of 64). */
 int flair_attention_wide(const flair_attn_params* p, const void* qkv, void* out, hipStream_t stream);
 /* idx[row] = argmax_n logits[row][n] (softmax + topk(1) of codeformer.py:727-728; first index on ties) and
  * y[row][0..D) = codebook[idx[row]] (VectorQuantizer.get_codebook_feat, :82-94).  codebook: [N][D] f32.
