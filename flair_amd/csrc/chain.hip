@@ -1220,8 +1220,10 @@ extern "C" int flair_conv_chain(const flair_chain_params* p, const void* const* 
     FLAIR_CHECK(((uintptr_t)wB) % 16 == 0 && (!wA || ((uintptr_t)wA) % 16 == 0), "flair_conv_chain: weight alignment");
     FLAIR_CHECK(p->y_ld >= p->CoutB && (p->y_ld * esz) % 16 == 0 && ((uintptr_t)y) % 16 == 0,
                 "flair_conv_chain: output stride/alignment");
-    FLAIR_CHECK(!res0 || ((p->res_ld[0] * esz) % 16 == 0 && ((uintptr_t)res0) % 16 == 0), "flair_conv_chain: res0 alignment");
-    FLAIR_CHECK(!res1 || ((p->res_ld[1] * esz) % 16 == 0 && ((uintptr_t)res1) % 16 == 0), "flair_conv_chain: res1 alignment");
+    FLAIR_CHECK(!res0 || (p->res_ld[0] >= p->CoutB && (p->res_ld[0] * esz) % 16 == 0 && ((uintptr_t)res0) % 16 == 0),
+                "flair_conv_chain: res0 stride/alignment");
+    FLAIR_CHECK(!res1 || (p->res_ld[1] >= p->CoutB && (p->res_ld[1] * esz) % 16 == 0 && ((uintptr_t)res1) % 16 == 0),
+                "flair_conv_chain: res1 stride/alignment");
     a.res0 = res0; a.res1 = res1; a.res0Ld = p->res_ld[0]; a.res1Ld = p->res_ld[1];
     a.outScale = p->out_scale;
     a.actParam = p->act_param; a.actPeriod = p->act_period;

@@ -2318,8 +2318,19 @@ extern "C" int flair_conv_nhwc(const flair_conv_params* p, const void* const* x,
         FLAIR_CHECK(wb < 0x80000000ull, "flair_conv_nhwc: weights span %llu bytes (limit 2 GiB)", wb);
         a.wBytes = (unsigned)wb;
     }
-    FLAIR_CHECK(p->y_ld >= p->Cout && (p->y_ld * esz) % 8 == 0 && ((uintptr_t)y) % 16 == 0,
-                "flair_conv_nhwc: output stride/alignment");
+    // The epilogues move 8 couts of a pixel as 16-byte pieces of y / res0 / res1 whenever Cout % 8 == 0 (halo, K-split and
+    // LDS-DMA kernels unconditionally), and f32 quads as 16 bytes in store_quad; only bf16 outputs with Cout % 8 == 4 are
+    // written and read in 8-byte quads everywhere.  So strides and residual pointers are 16-byte granular, except there.
+    const int gran = (p->dtype == FLAIR_BF16 && p->Cout % 8 != 0) ? 8 : 16;
+    FLAIR_CHECK(p->y_ld >= p->Cout && (p->y_ld * esz) % gran == 0 && ((uintptr_t)y) % 16 == 0,
+                "flair_conv_nhwc: output stride/alignment (y_ld = %d: >= Cout = %d, a multiple of %d bytes; y 16-byte aligned)",
+                p->y_ld, p->Cout, gran);
+    FLAIR_CHECK(!res0 || (p->res_ld[0] >= p->Cout && (p->res_ld[0] * esz) % gran == 0 && ((uintptr_t)res0) % gran == 0),
+                "flair_conv_nhwc: res0 stride/alignment (res_ld = %d: >= Cout = %d; stride and pointer multiples of %d bytes)",
+                p->res_ld[0], p->Cout, gran);
+    FLAIR_CHECK(!res1 || (p->res_ld[1] >= p->Cout && (p->res_ld[1] * esz) % gran == 0 && ((uintptr_t)res1) % gran == 0),
+                "flair_conv_nhwc: res1 stride/alignment (res_ld = %d: >= Cout = %d; stride and pointer multiples of %d bytes)",
+                p->res_ld[1], p->Cout, gran);
     FLAIR_CHECK(((uintptr_t)w) % 16 == 0, "flair_conv_nhwc: weight alignment");
     FLAIR_CHECK(!bias || ((uintptr_t)bias) % 16 == 0, "flair_conv_nhwc: bias alignment");
     a.nseg = p->nseg;

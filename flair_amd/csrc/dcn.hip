@@ -595,6 +595,11 @@ extern "C" int flair_dcn_align(const flair_dcn_params* p, const void* x0, const 
                 "flair_dcn_align: Cin=%d G=%d not supported", p->Cin, p->G);
     FLAIR_CHECK(p->Cout % 4 == 0 && p->Cout <= 128 && p->raw_ld >= 27 * p->G && (p->raw_ld * esz) % 16 == 0,
                 "flair_dcn_align: Cout (<=128) / raw_ld");
+    FLAIR_CHECK(p->x_ld[0] >= p->Cin / 2 && p->x_ld[1] >= p->Cin / 2 && (p->x_ld[0] * esz) % 16 == 0 &&
+                    (p->x_ld[1] * esz) % 16 == 0 && ((uintptr_t)x0) % 16 == 0 && ((uintptr_t)x1) % 16 == 0 &&
+                    ((uintptr_t)raw) % 16 == 0 && p->y_ld >= p->Cout,
+                "flair_dcn_align: strides/alignment (x_ld = %d, %d: >= Cin / 2 = %d, 16-byte granular; x0, x1, raw 16-byte "
+                "aligned; y_ld = %d >= Cout = %d)", p->x_ld[0], p->x_ld[1], p->Cin / 2, p->y_ld, p->Cout);
     DcnArgs a;
     a.x[0] = x0; a.x[1] = x1; a.xLd[0] = p->x_ld[0]; a.xLd[1] = p->x_ld[1];
     a.Cin = p->Cin; a.raw = raw; a.rawLd = p->raw_ld; a.flow1 = flow1; a.flow2 = flow2;

@@ -382,6 +382,8 @@ extern "C" int flair_axpby_f32(const float* x, const float* y, float a, float b,
 
 extern "C" int flair_scale_pixels(void* x, int dtype, int ld, int C, long P, const float* wmap, hipStream_t stream) {
     FLAIR_CHECK(x && wmap && P > 0 && C > 0, "flair_scale_pixels: bad argument");
+    FLAIR_CHECK(ld >= C && ld % (dtype == FLAIR_BF16 ? 8 : 4) == 0 && ((uintptr_t)x) % 16 == 0,
+                "flair_scale_pixels: ld = %d (>= C = %d, 16-byte granular) / x alignment", ld, C);
     if (dtype == FLAIR_BF16) {
         FLAIR_CHECK(C % 8 == 0, "flair_scale_pixels: C %% 8");
         hipLaunchKernelGGL(scale_pixels_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(256), 0, stream,

@@ -513,6 +513,13 @@ extern "C" int flair_groupnorm_nhwc(const flair_gn_params* p, const void* x0, co
     FLAIR_CHECK(C > 0 && C % vec == 0 && C % p->groups == 0, "flair_groupnorm_nhwc: C=%d groups=%d", C, p->groups);
     FLAIR_CHECK(p->c0 > 0 && p->c0 <= C && p->c0 % vec == 0 && (p->c0 == C || x1),
                 "flair_groupnorm_nhwc: bad segment split c0=%d", p->c0);
+    {   // every access moves 16-byte channel pieces: strides and pointers at that granularity
+        auto ok = [&](const void* t, int ld, int c) { return ld >= c && ld % vec == 0 && ((uintptr_t)t) % 16 == 0; };
+        FLAIR_CHECK(ok(x0, p->ld0, p->c0) && (p->c0 == C || ok(x1, p->ld1, C - p->c0)) && ok(y, p->y_ld, C) &&
+                        (!raw || ok(raw, p->raw_ld, C)),
+                    "flair_groupnorm_nhwc: strides/alignment (ld0 = %d, ld1 = %d, y_ld = %d, raw_ld = %d: at least the channels "
+                    "they hold, multiples of %d elements; pointers 16-byte aligned)", p->ld0, p->ld1, p->y_ld, p->raw_ld, vec);
+    }
     FLAIR_CHECK(p->F > 0 && p->frames_per_stat > 0 && p->F % p->frames_per_stat == 0,
                 "flair_groupnorm_nhwc: frames %d / frames_per_stat %d", p->F, p->frames_per_stat);
     FLAIR_CHECK(p->resample >= 0 && p->resample <= 2, "flair_groupnorm_nhwc: resample mode");

@@ -363,6 +363,7 @@ extern "C" int flair_resize_nhwc(const void* x, int dtype, int x_ld, int F, int 
     FLAIR_CHECK(x && y && F > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && mode >= 0 && mode <= 4,
                 "flair_resize_nhwc: bad argument");
     FLAIR_CHECK(mode != 3 || (Hi == 2 * Ho && Wi == 2 * Wo), "flair_resize_nhwc: avg-pool needs exact 2x");
+    FLAIR_CHECK(x_ld >= C && y_ld >= C, "flair_resize_nhwc: x_ld = %d / y_ld = %d below C = %d", x_ld, y_ld, C);
     const long n = (long)F * Ho * Wo * C;
     {
         const int vec = dtype == FLAIR_BF16 ? 8 : 4;

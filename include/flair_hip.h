@@ -77,10 +77,13 @@ int flair_abi_version(void);
  *            the segments are the channel-wise concatenation the reference builds with
  *            th.cat (seg_c[i] must be a multiple of 32 (bf16) / 16 (f32); pad with zeros)
  *   w      : [Cout][KT*KH*KW][sum seg_c] in the activation dtype
- *   bias   : [Cout] f32 or NULL;  res0/res1: [T][H][W][Cout-slice] or NULL
+ *   bias   : [Cout] f32 or NULL;  res0/res1: [T][H][W][Cout-slice] or NULL, pixel stride res_ld[i] >= Cout
  *   frame_bias : [T][frame_bias_ld] f32 or NULL, added before the activation (the per-frame
  *            embedding terms `h + emb_out` of unet.py:246 and sr3.py:82)
- *   y      : [T][H][W] pixels, y_ld elements apart, Cout (multiple of 4) written per pixel
+ *   y      : [T][H][W] pixels, y_ld elements apart, Cout (multiple of 4) written per pixel, 16-byte aligned
+ *   strides: segments, y_ld and res_ld are multiples of 16 bytes and res0 / res1 16-byte aligned (the epilogues move
+ *            16-byte pieces), except for bf16 with Cout % 8 == 4, whose outputs and residuals move as 8-byte quads:
+ *            there y_ld, res_ld and the residual pointers need 8 bytes only
  *   workspace : optional device scratch of flair_conv_workspace_bytes(p) bytes; when given,
  *            deep-K convolutions on few pixels (the 16x16..4x4 levels) are split over K
  *            (f32 partial sums + a reduce/epilogue launch) */
@@ -134,7 +137,8 @@ int flair_conv_variant(const flair_conv_params* p);
  * :731-739) -- same rounding points as the two launches (the intermediate is rounded to the element type).
  *   x[i], seg_c, seg_ld : input segments as in flair_conv_nhwc (T frames of H x W, W % 8 == 0)
  *   wA : [C][9][sum seg_c] or NULL;  wB : [CoutB][9][C];  biases f32 or NULL
- *   res0 / res1 : [T][H][W][CoutB-slice] or NULL, added after actB;  y : pixel stride y_ld */
+ *   res0 / res1 : [T][H][W][CoutB-slice] or NULL, added after actB;  y : pixel stride y_ld
+ *   y_ld, res_ld >= CoutB; segment, output and residual strides and pointers at 16-byte granularity */
 typedef struct {
     int dtype;
     int T, H, W;
@@ -169,7 +173,9 @@ int flair_conv_chain(const flair_chain_params* p, const void* const* x, const vo
  *   gamma, beta : [C] f32;  film : [F][film_ld] f32 rows of (scale[C] | shift[C]) or NULL
  *   workspace   : flair_groupnorm_workspace_bytes(p) bytes of device scratch
  *   limits      : C <= 2048 (f32) / 4096 (bf16): one 16-byte channel piece per thread of a <= 512-thread row group
- *                 (FLAIR_ERR_ARG "too wide" beyond that); C a multiple of 4 (f32) / 8 (bf16). */
+ *                 (FLAIR_ERR_ARG "too wide" beyond that); C a multiple of 4 (f32) / 8 (bf16).
+ *   strides     : ld0 / ld1 / y_ld / raw_ld at least the channels they hold and multiples of 16 bytes; x0, x1, y, raw
+ *                 16-byte aligned (film rows may have any stride >= 2C and any 4-byte alignment). */
 typedef struct {
     int dtype;
     int C, c0;   /* channels in total / in segment 0 */
@@ -272,7 +278,7 @@ int flair_add_frame_bias(void* x, int dtype, int ld, int C, int F, long HW, cons
  * unet_new.py:875). */
 int flair_cast_channels(const float* src, int src_ld, int C, long P, void* dst, int dtype,
                         int dst_ld, int dst_coff, hipStream_t stream);
-/* x[p][:] *= wmap[p]  (BasicVSR++ per-pixel vsrpp_weights, unet_new.py:739). */
+/* x[p][:] *= wmap[p]  (BasicVSR++ per-pixel vsrpp_weights, unet_new.py:739); ld >= C, 16-byte granular, x 16-byte aligned. */
 int flair_scale_pixels(void* x, int dtype, int ld, int C, long P, const float* wmap,
                        hipStream_t stream);
 
@@ -336,7 +342,7 @@ int flair_vsrpp_prep(const void* prop, int prop_ld, const void* feat2, int feat2
                      void* cond1, int cond1_ld, void* cond2, int cond2_ld, float* flow2_out,
                      void* flowpad, int pad_ld, hipStream_t stream);
 /* mode 0/1: bilinear (align_corners False/True), 2: bicubic (A=-0.75), 3: 2x2 avg-pool,
- * 4: nearest;
+ * 4: nearest;  x_ld, y_ld >= C;
  * channel 0 / 1 of the result are multiplied by scale_c0 / scale_c1 (flow rescaling). */
 int flair_resize_nhwc(const void* x, int dtype, int x_ld, int F, int Hi, int Wi, int C, int mode,
                       int Ho, int Wo, void* y, int y_ld, float scale_c0, float scale_c1,
@@ -353,7 +359,8 @@ int flair_resize_nhwc(const void* x, int dtype, int x_ld, int F, int Hi, int Wi,
  *           (the reference's o1|o2|mask order is 2*(g*9+k)+{0,1} and 18*G + g*9 + k; the
  *           caller permutes the output channels of the last conv_offset convolution once,
  *           when it packs that layer's weights).  G in {8, 16}; Cin/G a power of two.
- *   flow1, flow2 : [F][H][W][2] f32 or NULL (zero);  w : [Cout][9][Cin];  bias f32 */
+ *   flow1, flow2 : [F][H][W][2] f32 or NULL (zero);  w : [Cout][9][Cin];  bias f32
+ *   x_ld[i] >= Cin/2 and raw_ld multiples of 16 bytes; x0, x1, raw 16-byte aligned; y_ld >= Cout */
 typedef struct {
     int dtype;
     int F, H, W;

@@ -1,0 +1,298 @@
+"""CPU: the guarded-view helper of tests/util.py catches every kind of stray write, and the stride-taking entries refuse
+strides below their channel count or granularity and misaligned pointers with their message, before any launch.
+(Only parameters that must be refused reach an entry here: an accepted shape would launch.)"""
+import ctypes
+
+import pytest
+import torch
+
+from tests.util import IN_FILL, OUT_FILL, assert_untouched, guarded
+
+# ------------------------------------------------------------------------------------------------ the helper itself
+
+
+def _buf(dtype=torch.bfloat16, fill=OUT_FILL):
+    buf, view = guarded(2, 3, 5, 8, dtype, "cpu", coff=8, ld=24, fill=fill)
+    view.copy_(torch.arange(view.numel(), dtype=torch.float32).view(view.shape).to(dtype))
+    return buf, view, buf.clone()
+
+
+def test_guarded_layout():
+    buf, view = guarded(2, 3, 5, 8, torch.float32, "cpu", coff=8, ld=24)
+    assert tuple(buf.shape) == (4, 3, 5, 24) and tuple(view.shape) == (2, 3, 5, 8)
+    assert view.stride() == (3 * 5 * 24, 5 * 24, 24, 1) and view.data_ptr() == buf[1, 0, 0, 8].data_ptr()
+    assert torch.all(buf == OUT_FILL)
+    assert torch.isnan(guarded(1, 2, 2, 4, torch.bfloat16, "cpu", fill=IN_FILL)[0]).all()
+    assert OUT_FILL == float(torch.tensor(OUT_FILL, dtype=torch.bfloat16))      # exact in bf16
+
+
+def test_view_writes_pass():
+    buf, view, before = _buf()
+    view.mul_(2)
+    assert_untouched(buf, before, view)
+
+
+@pytest.mark.parametrize("where", ["pad channel", "channel before", "guard frame before", "guard frame after"])
+def test_flags_a_changed_guard(where):
+    buf, view, before = _buf()
+    idx = {"pad channel": (1, 2, 4, 16), "channel before": (2, 0, 0, 7), "guard frame before": (0, 1, 1, 9),
+           "guard frame after": (3, 2, 4, 23)}[where]
+    buf[idx] = 0.0
+    with pytest.raises(AssertionError, match="outside the view"):
+        assert_untouched(buf, before, view)
+
+
+def test_flags_a_nan_sentinel_replaced_by_another_nan():
+    buf, view, before = _buf(fill=IN_FILL)
+    flat = buf.view(torch.int16)
+    flat[0, 0, 0, 0] = 0x7FC1                                   # still NaN, another pattern
+    assert torch.isnan(buf[0, 0, 0, 0])
+    with pytest.raises(AssertionError, match="outside the view"):
+        assert_untouched(buf, before, view)
+
+
+def test_flags_a_changed_read_only_view():
+    buf, view, before = _buf(fill=IN_FILL)
+    assert_untouched(buf, before)
+    view[1, 2, 3, 4] += 1
+    with pytest.raises(AssertionError, match="read-only"):
+        assert_untouched(buf, before)
+
+
+# ------------------------------------------------------------------------------------------------ entry refusals
+P16, P8, P2 = ctypes.c_void_p(4096), ctypes.c_void_p(4096 + 8), ctypes.c_void_p(4096 + 2)   # fake device pointers
+
+
+def _lib():
+    from flair_amd import _lib
+    return _lib.lib()
+
+
+def _refused(rc, *needles):
+    assert rc == -1
+    msg = _lib().flair_last_error()
+    for n in needles:
+        assert n.encode() in msg, msg
+    return msg
+
+
+def _conv_params(dtype=1, cout=64, segs=(64,), seg_ld=None, y_ld=None):
+    from flair_amd import ops
+    p = ops.ConvParams()
+    p.dtype = dtype
+    p.T, p.H, p.W = 1, 8, 8
+    p.KT, p.KH, p.KW = 1, 3, 3
+    p.Cout = cout
+    p.nseg = len(segs)
+    for i, c in enumerate(segs):
+        p.seg_c[i] = c
+        p.seg_ld[i] = seg_ld if seg_ld is not None else c
+    p.y_ld = y_ld if y_ld is not None else cout
+    p.stride = 1
+    p.out_scale = 1.0
+    return p
+
+
+def _conv(p, x=P16, res0=None, res1=None, y=P16):
+    arr = (ctypes.c_void_p * 4)(*([x] * p.nseg + [None] * (4 - p.nseg)))
+    return _lib().flair_conv_nhwc(ctypes.byref(p), arr, P16, None, None, res0, res1, y, None, ctypes.c_size_t(0), None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_conv_refuses_segment_strides(dtype):
+    c = 64
+    _refused(_conv(_conv_params(dtype, segs=(c,), seg_ld=c - (8 if dtype else 4))), "segment 0 stride/alignment")
+    _refused(_conv(_conv_params(dtype, segs=(c,), seg_ld=c + (4 if dtype else 2))), "segment 0 stride/alignment")
+    _refused(_conv(_conv_params(dtype, segs=(c,)), x=P8), "segment 0 stride/alignment")
+
+
+@pytest.mark.parametrize("dtype,cout,y_ld", [
+    (1, 64, 60),        # below Cout
+    (1, 64, 68),        # 8-byte granular: Cout % 8 == 0 stores 16-byte pieces
+    (0, 64, 66),        # f32: 8-byte granular
+    (0, 36, 38),        # f32 Cout % 8 == 4: store_quad writes float4
+    (1, 36, 38),        # bf16 Cout % 8 == 4: 4-byte granular
+])
+def test_conv_refuses_output_strides(dtype, cout, y_ld):
+    _refused(_conv(_conv_params(dtype, cout=cout, y_ld=y_ld)), "output stride/alignment", f"y_ld = {y_ld}")
+
+
+def test_conv_refuses_a_misaligned_output():
+    _refused(_conv(_conv_params(1, cout=36, y_ld=36), y=P8), "output stride/alignment")
+
+
+@pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("dtype,cout,res_ld,ptr", [
+    (1, 64, 56, P16),   # below Cout
+    (1, 64, 68, P16),   # 8-byte granular stride under 16-byte residual loads
+    (1, 64, 64, P8),    # 8-byte aligned pointer under 16-byte residual loads
+    (0, 64, 66, P16),
+    (0, 64, 64, P8),
+    (1, 36, 38, P16),   # bf16 Cout % 8 == 4: 8 bytes are enough, 4 are not
+    (1, 36, 36, P2),
+    (1, 36, 32, P16),
+])
+def test_conv_refuses_residual_strides(which, dtype, cout, res_ld, ptr):
+    p = _conv_params(dtype, cout=cout)
+    p.res_ld[which] = res_ld
+    p.res_ld[1 - which] = cout
+    res = [P16, P16]
+    res[which] = ptr
+    _refused(_conv(p, res0=res[0], res1=res[1]), f"res{which} stride/alignment", f"res_ld = {res_ld}")
+
+
+def _chain_params(dtype=1, y_ld=64, res_ld=(0, 0), seg_ld=64):
+    from flair_amd import ops
+    p = ops.ChainParams()
+    p.dtype = dtype
+    p.T, p.H, p.W = 1, 8, 32
+    p.C, p.CoutB = 64, 64
+    p.nseg = 1
+    p.seg_c[0], p.seg_ld[0] = 64, seg_ld
+    p.y_ld = y_ld
+    p.res_ld[0], p.res_ld[1] = res_ld
+    p.out_scale = 1.0
+    return p
+
+
+def _chain(p, res0=None, res1=None, y=P16, x=P16):
+    arr = (ctypes.c_void_p * 4)(x, None, None, None)
+    return _lib().flair_conv_chain(ctypes.byref(p), arr, P16, None, P16, None, res0, res1, y, None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_chain_refuses_strides(dtype):
+    _refused(_chain(_chain_params(dtype, seg_ld=56)), "segment 0 stride/alignment")
+    _refused(_chain(_chain_params(dtype, y_ld=56)), "output stride/alignment")
+    _refused(_chain(_chain_params(dtype, y_ld=66)), "output stride/alignment")
+    _refused(_chain(_chain_params(dtype), y=P8), "output stride/alignment")
+    _refused(_chain(_chain_params(dtype, res_ld=(56, 0)), res0=P16), "res0 stride/alignment")
+    _refused(_chain(_chain_params(dtype, res_ld=(64, 66)), res0=P16, res1=P16), "res1 stride/alignment")
+    _refused(_chain(_chain_params(dtype, res_ld=(64, 0)), res0=P8), "res0 stride/alignment")
+
+
+def _gn(dtype=1, C=64, c0=64, ld0=64, ld1=0, y_ld=64, raw_ld=0, x0=P16, x1=None, y=P16, raw=None):
+    from flair_amd import ops
+    p = ops.GnParams()
+    p.dtype, p.C, p.c0, p.ld0, p.ld1, p.groups = dtype, C, c0, ld0, ld1, 32
+    p.F, p.H, p.W, p.frames_per_stat, p.eps = 1, 4, 4, 1, 1e-5
+    p.y_ld, p.raw_ld = y_ld, raw_ld
+    return _lib().flair_groupnorm_nhwc(ctypes.byref(p), x0, x1, P16, P16, None, y, raw, P16, None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_group_norm_refuses_strides(dtype):
+    g = 8 if dtype else 4
+    _refused(_gn(dtype, ld0=56), "strides/alignment")
+    _refused(_gn(dtype, ld0=64 + g // 2), "strides/alignment")
+    _refused(_gn(dtype, x0=P8), "strides/alignment")
+    _refused(_gn(dtype, C=128, c0=64, ld1=56, x1=P16), "strides/alignment")
+    _refused(_gn(dtype, C=128, c0=64, ld1=64, x1=P8), "strides/alignment")
+    _refused(_gn(dtype, y_ld=56), "strides/alignment")
+    _refused(_gn(dtype, y_ld=64 + g // 2), "strides/alignment")
+    _refused(_gn(dtype, y=P8), "strides/alignment")
+    _refused(_gn(dtype, raw_ld=56, raw=P16), "strides/alignment")
+    _refused(_gn(dtype, raw_ld=64, raw=P8), "strides/alignment")
+
+
+def _attn(ld, out_ld, d=64, q_off=0):
+    from flair_amd import ops
+    p = ops.AttnParams()
+    p.dtype, p.frames, p.L, p.heads, p.head_dim = 1, 1, 64, 1, d
+    p.ld, p.out_ld = ld, out_ld
+    p.q_off, p.k_off, p.v_off, p.head_stride = q_off, q_off + d, q_off + 2 * d, 3 * d
+    p.scale = 0.125
+    return _lib().flair_qkv_attention(ctypes.byref(p), P16, P16, None)
+
+
+@pytest.mark.parametrize("d", [32, 64, 128])
+def test_qkv_attention_refuses_strides(d):
+    _refused(_attn(3 * d - 8, d, d), "exceed ld")
+    _refused(_attn(3 * d, d - 8, d), "exceed ld")
+    _refused(_attn(3 * d + 4, d, d), "multiples of 8")
+    _refused(_attn(3 * d + 8, d + 4, d), "multiples of 8")
+    _refused(_attn(3 * d + 8, d, d, q_off=4), "multiples of 8")
+
+
+def _tattn(ld, out_ld, C=64):
+    from flair_amd import ops
+    p = ops.TAttnParams()
+    p.dtype, p.T, p.H, p.W, p.C, p.window = 1, 4, 2, 2, C, 5
+    p.ld, p.out_ld, p.scale, p.head_dim = ld, out_ld, 0.125, 64
+    return _lib().flair_temporal_attention(ctypes.byref(p), P16, P16, P16, None)
+
+
+def test_temporal_attention_refuses_strides():
+    _refused(_tattn(3 * 64 - 8, 64), "strides")
+    _refused(_tattn(3 * 64 + 4, 64), "strides")
+    _refused(_tattn(3 * 64, 68), "strides")
+
+
+def _dcn(dtype=1, c=64, x_ld=(64, 64), raw_ld=432, y_ld=64, x0=P16, x1=P16, raw=P16):
+    from flair_amd import ops
+    p = ops.DcnParams()
+    p.dtype, p.F, p.H, p.W, p.Cin, p.Cout, p.G = dtype, 1, 8, 8, 2 * c, c, 16
+    p.x_ld[0], p.x_ld[1] = x_ld
+    p.raw_ld, p.y_ld, p.max_residue_magnitude = raw_ld, y_ld, 10.0
+    return _lib().flair_dcn_align(ctypes.byref(p), x0, x1, raw, None, None, P16, P16, P16, None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_dcn_refuses_strides(dtype):
+    g = 8 if dtype else 4
+    _refused(_dcn(dtype, x_ld=(56, 64)), "strides/alignment")
+    _refused(_dcn(dtype, x_ld=(64, 56)), "strides/alignment")
+    _refused(_dcn(dtype, x_ld=(64 + g // 2, 64)), "strides/alignment")
+    _refused(_dcn(dtype, x0=P8), "strides/alignment")
+    _refused(_dcn(dtype, x1=P8), "strides/alignment")
+    _refused(_dcn(dtype, raw=P8), "strides/alignment")
+    _refused(_dcn(dtype, y_ld=60), "strides/alignment")
+    _refused(_dcn(dtype, raw_ld=420), "raw_ld")
+    _refused(_dcn(dtype, raw_ld=432 + g // 2), "raw_ld")
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_elementwise_entries_refuse_strides(dtype):
+    lib = _lib()
+    g = 8 if dtype else 4
+    P = ctypes.c_long(16)
+    # add_act: ld below C, off-granule ld, misaligned pointer
+    _refused(lib.flair_add_act_nhwc(P16, 56, None, 0, dtype, 64, P, 0, P16, 64, None), "bad argument")
+    _refused(lib.flair_add_act_nhwc(P16, 64, P16, 64 + g // 2, dtype, 64, P, 0, P16, 64, None))
+    _refused(lib.flair_add_act_nhwc(P16, 64, None, 0, dtype, 64, P, 0, P8, 64, None))
+    # maxpool
+    _refused(lib.flair_maxpool3x3s2_nhwc(P16, 56, dtype, 1, 4, 4, 64, P16, 64, None), "bad argument")
+    _refused(lib.flair_maxpool3x3s2_nhwc(P16, 64, dtype, 1, 4, 4, 64, P16, 64 + g // 2, None))
+    _refused(lib.flair_maxpool3x3s2_nhwc(P8, 64, dtype, 1, 4, 4, 64, P16, 64, None))
+    # scale_pixels
+    _refused(lib.flair_scale_pixels(P16, dtype, 56, 64, P, P16, None), "flair_scale_pixels: ld = 56")
+    _refused(lib.flair_scale_pixels(P16, dtype, 64 + g // 2, 64, P, P16, None), "flair_scale_pixels: ld")
+    _refused(lib.flair_scale_pixels(P8, dtype, 64, 64, P, P16, None), "flair_scale_pixels: ld")
+    # flow_warp: flow_ld < 2 / odd, x / y strides off the vector granule
+    _refused(lib.flair_flow_warp(P16, dtype, 64, P16, 1, 1, 4, 4, 64, 0, P16, 64, None), "flair_flow_warp")
+    _refused(lib.flair_flow_warp(P16, dtype, 64, P16, 3, 1, 4, 4, 64, 0, P16, 64, None), "flair_flow_warp")
+    _refused(lib.flair_flow_warp(P16, dtype, 64 + g // 2, P16, 2, 1, 4, 4, 64, 0, P16, 64, None), "flair_flow_warp")
+    _refused(lib.flair_flow_warp(P16, dtype, 64, P16, 2, 1, 4, 4, 64, 0, P16, 64 + g // 2, None), "flair_flow_warp")
+    # resize: strides below C
+    f = ctypes.c_float(1.0)
+    _refused(lib.flair_resize_nhwc(P16, dtype, 2, 1, 4, 4, 3, 0, 8, 8, P16, 4, f, f, None), "x_ld = 2")
+    _refused(lib.flair_resize_nhwc(P16, dtype, 4, 1, 4, 4, 3, 0, 8, 8, P16, 2, f, f, None), "y_ld = 2")
+    # layout / cast / affine / frame bias: the channel window must fit the stride
+    _refused(lib.flair_nchw_f32_to_nhwc(P16, 1, 8, 2, 2, P16, dtype, 16, 12, None))
+    _refused(lib.flair_nhwc_to_nchw_f32(P16, dtype, 16, 12, 1, 8, 2, 2, P16, None))
+    _refused(lib.flair_cast_channels(P16, 4, 8, P, P16, dtype, 16, 12, None))
+    _refused(lib.flair_cast_channels(P16, 4, 8, P, P16, dtype, 16, 0, None))        # src_ld < C
+    _refused(lib.flair_add_frame_bias(P16, dtype, 56, 64, 1, P, P16, 64, None), "flair_add_frame_bias")
+    _refused(lib.flair_add_frame_bias(P16, dtype, 64, 64, 1, P, P16, 56, None), "flair_add_frame_bias")
+
+
+def test_affine_and_dwconv_refuse_strides():
+    lib = _lib()
+    P = ctypes.c_long(16)
+    f = ctypes.c_float(0.0)
+    _refused(lib.flair_affine_channels_f32(P16, 2, 3, P, f, f, f, f, P16, P16, P16, 4, None), "flair_affine_channels_f32")
+    _refused(lib.flair_affine_channels_f32(P16, 4, 3, P, f, f, f, f, P16, P16, P16, 2, None), "flair_affine_channels_f32")
+    _refused(lib.flair_dwconv_nhwc(P16, 4, 1, 4, 4, 8, 1, P16, P16, None, None, 8, 2, P16, 8, None), "x_ld = 4")
+    _refused(lib.flair_dwconv_nhwc(P16, 10, 1, 4, 4, 8, 1, P16, P16, None, None, 8, 2, P16, 8, None), "x_ld = 10")
+    _refused(lib.flair_dwconv_nhwc(P16, 8, 1, 4, 4, 8, 1, P16, P16, None, None, 8, 2, P16, 6, None), "y_ld = 6")
+    _refused(lib.flair_dwconv_nhwc(P8, 8, 1, 4, 4, 8, 1, P16, P16, None, None, 8, 2, P16, 8, None), "flair_dwconv_nhwc")

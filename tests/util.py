@@ -65,3 +65,49 @@ def fixture_threads():
     torch.set_num_threads(FIXTURE_THREADS)
     yield
     torch.set_num_threads(n)
+
+
+# Guarded views: a clip tensor placed as a channel slice [coff, coff + C) of a wider buffer, with one guard frame before
+# and one after it.  Everything outside the view holds a sentinel: NaN around inputs (a kernel that reads outside its
+# input turns its result into NaN), a finite, bf16-exact value around outputs (a kernel that writes outside its output
+# changes it).  The guards also keep stray accesses inside the test's own allocation.
+IN_FILL = float("nan")
+OUT_FILL = -1232.0          # exact in bf16 and f32
+
+
+def guarded(T, H, W, C, dtype, dev, *, coff=0, ld=None, fill=OUT_FILL):
+    """-> (buf, view): buf (T + 2, H, W, ld) filled with `fill`; view = buf[1:T + 1, :, :, coff:coff + C]."""
+    ld = coff + C if ld is None else ld
+    assert coff >= 0 and coff + C <= ld, (coff, C, ld)
+    buf = torch.full((T + 2, H, W, ld), fill, dtype=dtype, device=dev)
+    return buf, buf[1:T + 1, :, :, coff:coff + C]
+
+
+def bits(t):
+    """Integer view of a tensor's bits (NaN patterns compare as numbers)."""
+    return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def view_mask(buf, view):
+    """Boolean mask over buf of the elements of `view` (a [f0:f0 + T, :, :, c0:c0 + C] slice of buf)."""
+    assert view.untyped_storage().data_ptr() == buf.untyped_storage().data_ptr()
+    off = view.storage_offset() - buf.storage_offset()
+    frame = buf.shape[1] * buf.shape[2] * buf.shape[3]
+    f0, c0 = off // frame, off % frame
+    assert c0 < buf.shape[3] and tuple(view.shape[1:3]) == tuple(buf.shape[1:3])
+    m = torch.zeros(buf.shape, dtype=torch.bool, device=buf.device)
+    m[f0:f0 + view.shape[0], :, :, c0:c0 + view.shape[3]] = True
+    return m
+
+
+def assert_untouched(buf, before, view=None, what=""):
+    """buf is bitwise equal to `before` (its copy taken before the launch) outside `view`; everywhere when view is None."""
+    changed = bits(buf) != bits(before)
+    if view is not None:
+        changed &= ~view_mask(buf, view)
+    n = int(changed.sum().item())
+    if n:
+        idx = changed.nonzero()[0].tolist()
+        where = "outside the view" if view is not None else "in a read-only buffer"
+        raise AssertionError(f"{what}: {n} element(s) changed {where}, first at {idx}: "
+                             f"{before[tuple(idx)].item()!r} -> {buf[tuple(idx)].item()!r}")
