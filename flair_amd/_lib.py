@@ -43,7 +43,7 @@ def lib():
     global _lib
     if _lib is None:
         global LIB_PATH
-        if os.environ.get("FLAIR_HIP_LIB"):        # diagnostic builds (make timing / make probe) only
+        if os.environ.get("FLAIR_HIP_LIB"):        # another build of the library, for same-box comparisons (tools/ab_libs.sh)
             LIB_PATH = os.environ["FLAIR_HIP_LIB"]
         if not os.path.exists(LIB_PATH):
             raise FlairHipUnavailable(

@@ -22,7 +22,6 @@
 //     VALU / bandwidth bound: G lanes per (frame, pixel, head), 8 channels per lane; G = d/8
 //     rounded up to a power of two (8 at d = 64), d any multiple of 8 in [8, 256].
 #include <hip/hip_fp16.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -78,128 +77,10 @@ __global__ void attn_rowwise_kernel(AttnArgs a) {
     for (int j = 0; j < CPL; ++j) ET<E>::st(o + LPQ * j, acc[j] / l);
 }
 
-// ------------------------------------------------------------------------- bf16 MFMA
-// 4 waves x 32 queries per workgroup; KV tiles of 32 tokens shared through LDS.
-__device__ __forceinline__ int k_off(int row, int chunk) {  // K tile: 128-byte rows, 8 chunks
-    return row * 128 + ((chunk ^ (row & 7)) << 4);
-}
-
-__global__ __launch_bounds__(256) void attn_mfma_bf16_kernel(AttnArgs a) {
-    __shared__ __attribute__((aligned(16))) char sK[32 * 128];       // [kv][d]
-    __shared__ __attribute__((aligned(16))) bf16_t sVt[64 * 40];     // [d][kv], row padded to 40
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int fh = blockIdx.y;
-    const int f = fh / a.heads, hd = fh % a.heads;
-    const bf16_t* base = reinterpret_cast<const bf16_t*>(a.qkv) + (long)f * a.L * a.ld + hd * a.headStride;
-    const int q = blockIdx.x * 128 + wave * 32 + lr;
-    const bool qok = q < a.L;
-
-    // Q^T fragments (B operand): element j of k-step s = Q[q][16s + 8h + j]
-    uint4 qf[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-        qf[s] = qok ? *reinterpret_cast<const uint4*>(base + (long)q * a.ld + a.qOff + 16 * s + 8 * lh)
-                    : make_uint4(0, 0, 0, 0);
-
-    f32x16 o[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-    float m = -1e30f, l = 0.f;
-
-    const int ntile = (a.L + 31) / 32;
-    for (int t = 0; t < ntile; ++t) {
-        // ---- stage K (row-major, swizzled) and V (transposed) for tokens 32t..32t+31
-        {
-            const int kv = tid >> 3, ch = tid & 7;
-            const int tok = t * 32 + kv;
-            uint4 kq = make_uint4(0, 0, 0, 0), vq = make_uint4(0, 0, 0, 0);
-            if (tok < a.L) {
-                kq = *reinterpret_cast<const uint4*>(base + (long)tok * a.ld + a.kOff + ch * 8);
-                vq = *reinterpret_cast<const uint4*>(base + (long)tok * a.ld + a.vOff + ch * 8);
-            }
-            *reinterpret_cast<uint4*>(sK + k_off(kv, ch)) = kq;
-            const bf16_t* ve = reinterpret_cast<const bf16_t*>(&vq);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sVt[(ch * 8 + e) * 40 + kv] = ve[e];
-        }
-        __syncthreads();
-
-        // ---- S^T[kv][q] = K . Q^T
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const uint4 kf = *reinterpret_cast<const uint4*>(sK + k_off(lr, 2 * ks + lh));
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf),
-                                                        __builtin_bit_cast(bf16x8, qf[ks]), s, 0, 0, 0);
-        }
-        // rows of this lane: kv = (r&3) + 8*(r>>2) + 4*lh
-        float tmax = -1e30f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int kv = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            s[r] = kv < a.L ? s[r] * a.scale : -1e30f;
-            tmax = fmaxf(tmax, s[r]);
-        }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-        const float mn = fmaxf(m, tmax);
-        const float alpha = __expf(m - mn);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = __expf(s[r] - mn);
-            psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32);
-        l = l * alpha + psum;
-        m = mn;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-
-        // ---- O^T[d][q] += V^T[d][kv] . P^T[kv][q]; P^T registers 8s..8s+7 are k-step s
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            uint4 pf;
-            pf.x = pack2bf(s[8 * ks + 0], s[8 * ks + 1]);
-            pf.y = pack2bf(s[8 * ks + 2], s[8 * ks + 3]);
-            pf.z = pack2bf(s[8 * ks + 4], s[8 * ks + 5]);
-            pf.w = pack2bf(s[8 * ks + 6], s[8 * ks + 7]);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const bf16_t* vr = sVt + (32 * i + lr) * 40 + 16 * ks + 4 * lh;
-                const uint2 v0 = *reinterpret_cast<const uint2*>(vr);
-                const uint2 v1 = *reinterpret_cast<const uint2*>(vr + 8);
-                const uint4 vf = make_uint4(v0.x, v0.y, v1.x, v1.y);
-                o[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf),
-                                                               __builtin_bit_cast(bf16x8, pf), o[i], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-    if (!qok) return;
-    const float inv = 1.f / l;
-    bf16_t* op = reinterpret_cast<bf16_t*>(a.out) + ((long)f * a.L + q) * a.outLd + hd * 64;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            uint2 pk;
-            pk.x = pack2bf(o[i][4 * g + 0] * inv, o[i][4 * g + 1] * inv);
-            pk.y = pack2bf(o[i][4 * g + 2] * inv, o[i][4 * g + 3] * inv);
-            *reinterpret_cast<uint2*>(op + 32 * i + 8 * g + 4 * lh) = pk;
-        }
-}
-
 // -------------------------------------------------------------- bf16 MFMA, pipelined
-// Same mathematics and operand roles as attn_mfma_bf16_kernel above, restructured around the latency that
-// kernel exposes once per 32-token tile (load K/V -> LDS -> barrier -> compute -> barrier), for head widths
-// D = 32, 64 and 128:
+// 32 queries per wave, the S^T and O^T products on the matrix cores, structured around the latency that the plain
+// tiled kernel of round 1 exposed once per 32-token tile (load K/V -> LDS -> barrier -> compute -> barrier), for head
+// widths D = 32, 64 and 128:
 //   * KV tiles of KV tokens, two LDS stages, ONE barrier per tile; the next tile's K and V are requested into
 //     registers before the current tile's MFMAs and written to the other stage afterwards;
 //   * V stays row-major in LDS ([token][D], written with 16-byte stores) and its transposed MFMA fragments
@@ -224,7 +105,7 @@ typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 template <int D>
 __device__ __forceinline__ int k_off_d(int row, int chunk) {
     if constexpr (D == 32) return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4);
-    else if constexpr (D == 64) return k_off(row, chunk);
+    else if constexpr (D == 64) return row * 128 + ((chunk ^ (row & 7)) << 4);
     else return row * 256 + ((chunk ^ (row & 15)) << 4);
 }
 
@@ -836,8 +717,6 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
     a.qOff = p->q_off; a.kOff = p->k_off; a.vOff = p->v_off; a.headStride = p->head_stride;
     a.scale = p->scale;
     if (p->dtype == FLAIR_BF16) {
-        // FLAIR_ATTN_V2=0 selects the round-1 kernel, which exists for head width 64 only
-        static const int v2 = getenv("FLAIR_ATTN_V2") ? atoi(getenv("FLAIR_ATTN_V2")) : 1;
         if (wide) {
             const int rc = launch_qkv_bf16_wide(p, a, stream);
             if (rc != FLAIR_OK) return rc;
@@ -845,9 +724,6 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
             launch_qkv_bf16<32>(p, a, stream);
         else if (d == 128)
             launch_qkv_bf16<128>(p, a, stream);
-        else if (!v2)
-            hipLaunchKernelGGL(attn_mfma_bf16_kernel, dim3((p->L + 127) / 128, p->frames * p->heads), dim3(256), 0,
-                               stream, a);
         else
             launch_qkv_bf16<64>(p, a, stream);
     } else if (p->dtype == FLAIR_F32) {

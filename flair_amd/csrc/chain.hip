@@ -25,8 +25,6 @@
 //   * stage B reads its B operands straight from that LDS tile.
 // MFMA operand roles, the 80-byte LDS pitch (conflict-free ds_read_b128) and the tap loop are those of
 // conv3x3_halo_kernel (conv.hip); a work item is 32 pixels x 64 output channels on one wavefront.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -44,20 +42,7 @@ struct ChainArgs {
     float actParam; int actPeriod;   // FLAIR_ACT_DCN_OFFSETS on stage B
     void* y; int yLd;
     int T, H, W;
-    unsigned long long* dbg;   // probe build only (-DFLAIR_CHAIN_STAMPS): per-workgroup s_memtime stamps
 };
-
-// In-kernel phase stamps of the diagnostic build (tools/probes/chain_probe.py); the product build
-// compiles them out (no stamp executes, no argument is read).
-#ifdef FLAIR_CHAIN_STAMPS
-#include <stdlib.h>
-#define STAMP(k)                                                                           \
-    do {                                                                                   \
-        if (a.dbg && threadIdx.x == 0) a.dbg[blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
 
 template <typename E> struct MmaC;
 template <> struct MmaC<bf16_t> {
@@ -135,7 +120,6 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
     const int tile = bid % perFrame;
     const int h0 = (tile / tilesW) * TH, w0 = (tile % tilesW) * TW;
     const long frameOff = (long)t * a.H * a.W;
-    STAMP(0);
     // biases -> LDS once (a per-element global load in the epilogues would serialise on its latency)
     for (int i = C + tid; i < C + CHAIN_MAX_COUTB; i += NT)
         sbias[i] = (a.biasB && i - C < a.CoutB) ? a.biasB[i - C] : 0.f;
@@ -278,7 +262,6 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
         write_in(sin, 0);
         write_w(0);
         __syncthreads();
-        STAMP(1);
         auto step = [&](int k, auto setTag) {
             constexpr int SET = decltype(setTag)::value;
             issue_step(k + 2, SET);                                // set SET went to LDS before this chunk's barrier: free again
@@ -295,7 +278,6 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
             step(k, std::integral_constant<int, 0>{});
             if (k + 1 < nkA) step(k + 1, std::integral_constant<int, 1>{});
         }
-        STAMP(2);
         // ---- intermediate -> LDS (bias, activation, zero outside the image, element type rounding)
 #pragma unroll
         for (int ii = 0; ii < MAXIA; ++ii) {
@@ -335,7 +317,6 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
         write_w(0);
         __syncthreads();
     }
-    STAMP(3);
 
     // ================================ stage B ================================
     int pbB[MAXIB], wbB[MAXIB];
@@ -377,7 +358,6 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
                 __syncthreads();
             }
         }
-        if (batch == 0) STAMP(4);
         // ---- epilogue of this batch, straight from the accumulators (no LDS round trip, no barrier).  A lane of
         // the 32x32 MFMA result holds 4 consecutive couts of its pixel per register quad (quad g: couts 8g + 4*lh ..);
         // v_permlane32_swap between the two half-waves turns quads 2j, 2j+1 into 8 consecutive couts per lane
@@ -458,13 +438,11 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
                 }
             }
         }
-        if (batch == 0) STAMP(5);
         if (batch + 1 < nBatch) {
             write_w(0);
             __syncthreads();
         }
     }
-    STAMP(6);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -492,23 +470,14 @@ struct ResArgs {
     float outScale;
     void* y; int yLd;
     int T, H, W;
-    unsigned long long* stamps;   // diagnostic build, debug == 20: per-workgroup sums of s_memtime deltas (wait, barrier, compute, total)
-    int debug;            // phase switches of the diagnostic build (-DFLAIR_TIMING_SWITCHES): 1 no MFMA phase, 2 no weight DMA after
-                          // the prologue, 3 no epilogue, 4 return after the prologue
 };
-#ifdef FLAIR_TIMING_SWITCHES
-#define RES_DBG(a) ((a).debug)
-#else
-#define RES_DBG(a) 0
-#endif
 
-// NW wavefronts per workgroup, each owning RPW = 8 / NW image rows (32 pixels each) x the 64 couts of the current block:
-//   <8 waves x 1 row>: 6 fragment reads per 4 MFMAs (1.5 ds_read_b128 per MFMA: three quarters of the LDS read rate at the full
-//                      matrix rate), two waves per SIMD;
-//   <4 waves x 2 rows>: the (RPW + 2) halo rows of a column tap are read once for its three row taps and a weight fragment
-//                      serves both rows: 20 reads per 24 MFMAs (0.83), one wave per SIMD with up to 512 registers.
+// NW = 8 wavefronts per workgroup, each owning RPW = 8 / NW = 1 image row (32 pixels) x the 64 couts of the current block: 6 fragment
+// reads per 4 MFMAs (1.5 ds_read_b128 per MFMA: three quarters of the LDS read rate at the full matrix rate), two waves per SIMD.
+// (Four waves of two rows, 20 reads per 24 MFMAs and one wave per SIMD, measured a same-box step of 82.1 against 81.7 ms.)
 template <int ACT, int NW>      // ACT 0: max(v, slope v) (none / ReLU / LeakyReLU)   1: DCN offsets / masks   2: SiLU
 __global__ __launch_bounds__(64 * NW, NW / 4) void conv_resident_kernel(ResArgs a) {
+    static_assert(NW == 8, "eight waves of one row");
     prefetch_kernargs<sizeof(ResArgs)>();
     using E = bf16_t;
     constexpr int RPW = 8 / NW;
@@ -704,10 +673,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void conv_resident_kernel(ResArgs 
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWS + NST) : "memory");
     };
 
-#ifdef FLAIR_TIMING_SWITCHES
-    unsigned long long stW = 0, stB = 0, stC = 0, stT0 = 0;
-    const unsigned long long stStart = __builtin_amdgcn_s_memtime();
-#endif
     f32x16 acc0[RPW][2], acc1[RPW][2];
     // one block = two stages; `accP` accumulates block blk, the epilogue of `accQ` (block blk - 1) runs beside it
     auto block = [&](int blk, f32x16 (&accP)[RPW][2], f32x16 (&accQ)[RPW][2]) {
@@ -715,78 +680,33 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void conv_resident_kernel(ResArgs 
 #pragma unroll
         for (int ch = 0; ch < 2; ++ch) {
             const int s_ = 2 * blk + ch;
-#ifdef FLAIR_TIMING_SWITCHES
-            unsigned long long tA = 0, tB = 0, tC = 0;
-            if (a.debug == 20) tA = __builtin_amdgcn_s_memtime();
-#endif
             wait_stage(s_);
-#ifdef FLAIR_TIMING_SWITCHES
-            if (a.debug == 20) tB = __builtin_amdgcn_s_memtime();
-#endif
             __builtin_amdgcn_s_barrier();            // stage s_ is in LDS for everybody; everybody is done with stage s_ - 1
-#ifdef FLAIR_TIMING_SWITCHES
-            if (a.debug == 20) {
-                tC = __builtin_amdgcn_s_memtime();
-                stW += tB - tA;
-                stB += tC - tB;
-                stT0 = tC;
-            }
-#endif
-            const bool dma = s_ + 2 < nS && RES_DBG(a) != 2;          // ring slot (s_ + 2) % 3 = (s_ - 1) % 3 is free from here on
-            if (RES_DBG(a) == 4) return;
+            const bool dma = s_ + 2 < nS;            // ring slot (s_ + 2) % 3 = (s_ - 1) % 3 is free from here on
             if (ch == 0) init_acc(accP, blk);        // (the biases landed with the first stage)
-            if (RES_DBG(a) == 1) continue;
-            // the DMA instructions of stage s_ + 2 go out one per step, the last one BEHIND the stage's output stores (wait_stage
-            // counts on that order); issued in one batch ahead of the MFMAs they cost ~100 cycles each with nothing beside them
+            // the DMA instructions of stage s_ + 2 go out one per step (NWS == 5), the last one BEHIND the stage's output stores
+            // (wait_stage counts on that order); issued in one batch ahead of the MFMAs they cost ~100 cycles each with nothing beside them
             auto dma_step = [&](int step) {
-                if constexpr (RPW == 1) {
-                    constexpr int at[9] = {-1, -1, 0, 1, 2, -1, 3, 4, -1};
-                    if (dma && at[step] >= 0) issue_w_one(s_ + 2, at[step]);
-                } else {
-                    if (dma) issue_w_one(s_ + 2, step);              // NWS == 9
-                }
+                constexpr int at[9] = {-1, -1, 0, 1, 2, -1, 3, 4, -1};
+                if (dma && at[step] >= 0) issue_w_one(s_ + 2, at[step]);
             };
-            if (prev && RES_DBG(a) != 3) {
+            if (prev) {
                 compute(s_ % NRING, ch, accP, [&](int step) {
-                    // 4 RPW pieces per block, 2 RPW per stage, spread over the nine steps
-                    if constexpr (RPW == 1) {
-                        if (step == 1) epi_piece(accQ, blk - 1, 2 * ch);
-                        if (step == 5) epi_piece(accQ, blk - 1, 2 * ch + 1);
-                    } else {
-                        if (step == 0 || step == 2 || step == 4 || step == 6) epi_piece(accQ, blk - 1, 4 * ch + step / 2);
-                    }
+                    // 4 pieces per block, 2 per stage, spread over the nine steps
+                    if (step == 1) epi_piece(accQ, blk - 1, 2 * ch);
+                    if (step == 5) epi_piece(accQ, blk - 1, 2 * ch + 1);
                     dma_step(step);
                 });
             } else {
                 compute(s_ % NRING, ch, accP, [&](int step) { dma_step(step); });
             }
-#ifdef FLAIR_TIMING_SWITCHES
-            if (a.debug == 20) {
-                __builtin_amdgcn_sched_barrier(0);
-                stC += __builtin_amdgcn_s_memtime() - stT0;
-            }
-#endif
         }
     };
     for (int blk = 0; blk < nBlk; blk += 2) {
         block(blk, acc0, acc1);
         if (blk + 1 < nBlk) block(blk + 1, acc1, acc0);
     }
-#ifdef FLAIR_TIMING_SWITCHES
-    if (a.debug == 20 && a.stamps && lane == 0) {
-        const unsigned long long tE = __builtin_amdgcn_s_memtime();
-        unsigned long long* d = a.stamps + ((size_t)blockIdx.x * NW + wave) * 4;
-        d[0] = stW; d[1] = stB; d[2] = stC; d[3] = tE - stStart;
-    }
-#endif
     // the last block's epilogue is exposed
-    if (RES_DBG(a) == 3) {
-#pragma unroll
-        for (int j = 0; j < RPW; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(acc0[j][0][r]), "v"(acc0[j][1][r]), "v"(acc1[j][0][r]), "v"(acc1[j][1][r]));
-        return;
-    }
     if (nBlk & 1) {
 #pragma unroll
         for (int g = 0; g < 4 * RPW; ++g) epi_piece(acc0, nBlk - 1, g);
@@ -802,38 +722,28 @@ int launch_resident(const ChainArgs& c, hipStream_t s) {
     a.w = c.wB; a.wBytes = c.wBBytes; a.bias = c.biasB; a.Cout = c.CoutB; a.act = c.actB;
     a.actParam = c.actParam; a.actPeriod = c.actPeriod; a.outScale = c.outScale;
     a.y = c.y; a.yLd = c.yLd; a.T = c.T; a.H = c.H; a.W = c.W;
-    a.debug = 0;
-    a.stamps = nullptr;
-#ifdef FLAIR_TIMING_SWITCHES
-    a.debug = getenv("FLAIR_RES_DEBUG") ? atoi(getenv("FLAIR_RES_DEBUG")) : 0;
-    if (const char* e = getenv("FLAIR_RES_STAMPS")) a.stamps = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16));
-#endif
     constexpr size_t lds = 2 * 22 * 1024 + 3 * 36 * 1024 + 2048;
     const int grid = a.T * (a.H / 8) * (a.W / 32);
-    // FLAIR_CONV_RESIDENT_WAVES = 4: four waves of two rows (default: eight waves of one row; same-box step 81.7 vs 82.1 ms)
-    static const int nw = getenv("FLAIR_CONV_RESIDENT_WAVES") ? atoi(getenv("FLAIR_CONV_RESIDENT_WAVES")) : 8;
-    auto go = [&](auto tag, auto nwTag) -> int {
-        constexpr int ACT = decltype(tag)::value, NW = decltype(nwTag)::value;
+    auto go = [&](auto tag) -> int {
+        constexpr int ACT = decltype(tag)::value;
         static LdsAttrOnce attr;
-        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv_resident_kernel<ACT, NW>));
+        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv_resident_kernel<ACT, 8>));
         FLAIR_CHECK(e == hipSuccess, "flair_conv_chain: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL((conv_resident_kernel<ACT, NW>), dim3(grid), dim3(64 * NW), lds, s, a);
+        hipLaunchKernelGGL((conv_resident_kernel<ACT, 8>), dim3(grid), dim3(64 * 8), lds, s, a);
         FLAIR_LAUNCH_CHECK();
         return FLAIR_OK;
     };
-    auto pick = [&](auto tag) -> int {
-        return nw == 8 ? go(tag, std::integral_constant<int, 8>{}) : go(tag, std::integral_constant<int, 4>{});
-    };
-    if (a.act == FLAIR_ACT_DCN_OFFSETS) return pick(std::integral_constant<int, 1>{});
-    if (a.act == FLAIR_ACT_SILU) return pick(std::integral_constant<int, 2>{});
-    return pick(std::integral_constant<int, 0>{});
+    if (a.act == FLAIR_ACT_DCN_OFFSETS) return go(std::integral_constant<int, 1>{});
+    if (a.act == FLAIR_ACT_SILU) return go(std::integral_constant<int, 2>{});
+    return go(std::integral_constant<int, 0>{});
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Pair of 3x3 convolutions c = 64 -> 64 -> 64 on LDS-DMA staging (round 4; FLAIR_CONV_PAIR=0 selects the older form): the HASA form of
+// Pair of 3x3 convolutions c = 64 -> 64 -> 64 on LDS-DMA staging (round 4): the HASA form of
 // conv_chain_kernel above spends 7.8 k cycles of its 32.5 k on the first fetch (load -> register -> ds_write -> barrier), 11.0 k on
 // a stage-A K loop whose MFMA floor is 6.9 k (two barriers per chunk), 4.1 k on moving the intermediate to LDS in 8-byte pieces and
-// 7.2 k on stage B (floor 4.6 k) -- tools/probes/chain_probe.py.  Here, as in conv_resident_kernel:
+// 7.2 k on stage B (floor 4.6 k) (in-kernel s_memtime stamps).  Here, as in conv_resident_kernel:
+
 //   * the (8+4) x 36 input halo of both 32-channel chunks arrives ONCE by LDS-DMA (2 x 27 KB, 64-byte rows, 16-byte pieces
 //     XOR-swizzled by the pixel column on the source address);
 //   * the four weight stages (A chunk 0 / 1, B chunk 0 / 1; 36 KB each) go through two ring slots, the next stage in flight while one is
@@ -1238,24 +1148,17 @@ extern "C" int flair_conv_chain(const flair_chain_params* p, const void* const* 
     }
     a.y = y; a.yLd = p->y_ld;
     a.T = p->T; a.H = p->H; a.W = p->W;
-    a.dbg = nullptr;
-#ifdef FLAIR_CHAIN_STAMPS
-    if (const char* e = getenv("FLAIR_CHAIN_DBG_PTR")) a.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16));
-#endif
     // round 4: the input-resident LDS-DMA form for the wide-output convolution without stage A (the c -> 27*G offset convolution)
-    {
-        static const bool useRes = !(getenv("FLAIR_CONV_RESIDENT") && atoi(getenv("FLAIR_CONV_RESIDENT")) == 0);
-        if (useRes && !hasA && p->dtype == FLAIR_BF16 && p->C == 64 && p->W % 32 == 0 && p->H % 8 == 0 && !res0 && !res1 &&
-            (p->y_ld * 2) % 16 == 0 && p->CoutB % 8 == 0 &&
-            (unsigned long long)p->H * p->W * p->y_ld * 2 < 0x40000000ull)
-            return launch_resident(a, stream);
-    }
-    // round 4: the c = 64 pair on LDS-DMA staging (conv_pair_kernel; FLAIR_CONV_PAIR=0: the register-staged form above).
+    if (!hasA && p->dtype == FLAIR_BF16 && p->C == 64 && p->W % 32 == 0 && p->H % 8 == 0 && !res0 && !res1 &&
+        (p->y_ld * 2) % 16 == 0 && p->CoutB % 8 == 0 &&
+        (unsigned long long)p->H * p->W * p->y_ld * 2 < 0x40000000ull)
+        return launch_resident(a, stream);
+    // round 4: the c = 64 pair on LDS-DMA staging (conv_pair_kernel) instead of the register-staged form above.
     // Same box: fused-chain family 11.57 / 11.56 -> 10.59 / 10.55 ms per step (310 launches, 18.7 -> 15.5 us), step 72.84 / 72.76 -> 71.58 / 71.60 ms.
     {
-        static const bool usePair = !(getenv("FLAIR_CONV_PAIR") && atoi(getenv("FLAIR_CONV_PAIR")) == 0);
         auto lin = [](int c) { return c == FLAIR_ACT_NONE || c == FLAIR_ACT_RELU || c == FLAIR_ACT_LRELU01; };
-        if (usePair && hasA && p->dtype == FLAIR_BF16 && p->C == 64 && p->nseg == 1 && cin == 64 && p->CoutB == 64 && p->W % 32 == 0 &&
+        if (hasA && p->dtype
+ == FLAIR_BF16 && p->C == 64 && p->nseg == 1 && cin == 64 && p->CoutB == 64 && p->W % 32 == 0 &&
             p->H % 8 == 0 && lin(p->actA) && lin(p->actB) && (unsigned long long)p->H * p->W * p->y_ld * 2 < 0x40000000ull &&
             (!res0 || (unsigned long long)p->H * p->W * p->res_ld[0] * 2 < 0x40000000ull) &&
             (!res1 || (unsigned long long)p->H * p->W * p->res_ld[1] * 2 < 0x40000000ull))

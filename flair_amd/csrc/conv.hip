@@ -20,8 +20,6 @@
 // (chunk ^= (row>>2)&3) that makes every ds_read_b128 fragment read conflict-free.
 // Global loads for step k+1 are issued before the MFMAs of step k and written to the
 // other LDS buffer afterwards (one barrier per step).
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -48,33 +46,20 @@ struct ConvArgs {
     long P;  // T*H*W
     int nPixTiles, nCoTiles;
     int tFast;             // DMA kernel: frame index fastest in the tile order (launches with temporal taps)
-    int resPrefetch;       // DMA kernel: 0 no residual prefetch, 1 LDS-DMA touch of the residual lines one chunk ahead
     unsigned segBytes[4];  // addressable bytes of each input segment / of the weights
     unsigned wBytes;
     float* part;           // split-K: f32 partial sums [splitK][P][Cout] (null when splitK == 1)
     int splitK;
     const float* fbias;    // optional per-(frame, channel) bias [T][fbiasLd] (emb added to h)
     int fbiasLd;
-    int debug;             // phase-timing switches, compiled in only with -DFLAIR_TIMING_SWITCHES (see FLAIR_DBG)
     int stride;            // spatial stride (1 or 2; im2col path only)
     int tapShift;          // asym_pad: K/2 added to every spatial tap offset (taps start at stride*i)
     int reflect;           // reflect_pad: out-of-frame taps read the mirrored pixel (im2col path)
-    int ldsSwz;            // halo kernels: conflict-free lane -> staged-row order of the ds_write_b128 (staged_row)
     float actParam;        // FLAIR_ACT_DCN_OFFSETS: max residue magnitude
     int actPeriod;         // FLAIR_ACT_DCN_OFFSETS: 3 * deform groups
     int Hin, Win;          // input frame size (== H, W when stride == 1); H, W, P describe the OUTPUT
     int esz;               // element size in bytes (2: bf16, 4: f32)
 };
-
-// Phase-timing switches of the halo kernel (how profiles/README.md's dissection was measured):
-// 1 skip the MFMA phase, 2 skip the in-loop reloads, 3/4/5 return before the first fetch / after
-// the first staged chunk / before the epilogue.  A build without -DFLAIR_TIMING_SWITCHES (the
-// product build) compiles them out: FLAIR_DBG is the constant 0 and the environment is not read.
-#ifdef FLAIR_TIMING_SWITCHES
-#define FLAIR_DBG(a) ((a).debug)
-#else
-#define FLAIR_DBG(a) 0
-#endif
 
 template <typename E> struct Mma;
 
@@ -127,9 +112,8 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {
 // banked (address / 4) % 32 over groups of 8 consecutive lanes (MI355X_MICROARCH.md, LDS): two rows r, r+1 of one group
 // start 20 banks apart and collide on 4 banks (one extra LDS cycle per group: SQ_LDS_BANK_CONFLICT ~ 1 per LDS instruction
 // of the halo kernels, profiles/r02y_conv_pmc_sq.txt), rows r and r+4 start 16 banks apart and fill the 32 banks exactly.
-// So a lane group of 8 stages rows (8k + j, 8k + j + 4).  The switch keeps the linear order for A/B runs.
-__device__ __forceinline__ int staged_row(int id, bool swizzled) {
-    if (!swizzled) return id >> 2;
+// So a lane group of 8 stages rows (8k + j, 8k + j + 4).
+__device__ __forceinline__ int staged_row(int id) {
     const int g = id >> 3;
     return (g >> 2) * 8 + (g & 3) + 4 * ((id >> 2) & 1);
 }
@@ -348,7 +332,7 @@ void conv3x3_halo_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < HI; ++i) {
         const int id = i * NT + tid;
-        const int pix = staged_row(id, a.ldsSwz);
+        const int pix = staged_row(id);
         const int r = pix / HW_, c = pix % HW_;
         const int hh = h0 + r - 1, ww = w0 + c - 1;
         const bool ok = pix < HALO_ROWS && (unsigned)hh < (unsigned)a.H && (unsigned)ww < (unsigned)a.W;
@@ -359,7 +343,7 @@ void conv3x3_halo_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
         const int id = i * NT + tid;
-        const int row = staged_row(id, a.ldsSwz);
+        const int row = staged_row(id);
         const int co = row / 9, tap9 = row % 9;
         const bool ok = id < W_PIECES && co0 + co < a.Cout;
         woff[i] = ok ? (unsigned)(((co0 + co) * taps + tap9) * a.CinTot + (id & 3) * VEC) * ESZ : FLAIR_OOB;
@@ -397,13 +381,13 @@ void conv3x3_halo_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < HI; ++i) {
             const int id = i * NT + tid;
-            const int row = staged_row(id, a.ldsSwz);
+            const int row = staged_row(id);
             if (row < HALO_ROWS) *reinterpret_cast<uint4*>(sh + row * PITCH + (id & 3) * 16) = hr[i];
         }
 #pragma unroll
         for (int i = 0; i < WI; ++i) {
             const int id = i * NT + tid;
-            if (id < W_PIECES) *reinterpret_cast<uint4*>(sw + staged_row(id, a.ldsSwz) * PITCH + (id & 3) * 16) = wr[i];
+            if (id < W_PIECES) *reinterpret_cast<uint4*>(sw + staged_row(id) * PITCH + (id & 3) * 16) = wr[i];
         }
     };
     // number of K chunks this workgroup walks (temporal taps outside the clip are skipped)
@@ -459,7 +443,6 @@ void conv3x3_halo_kernel(ConvArgs a) {
     // software pipeline: chunk kk is multiplied out of LDS while chunks kk+1 .. kk+PF are in
     // flight in registers (set kk % PF holds chunk kk until it has been written to LDS)
     int issued = 0;
-    if (FLAIR_DBG(a) == 3) return;
 #pragma unroll
     for (int s_ = 0; s_ < PF; ++s_)
         if (issued < nch) {
@@ -469,18 +452,17 @@ void conv3x3_halo_kernel(ConvArgs a) {
         }
     write_lds(hreg[0], wreg[0]);
     __syncthreads();
-    if (FLAIR_DBG(a) == 4) return;
     for (int k = 0; k < nch; k += PF) {
 #pragma unroll
         for (int par = 0; par < PF; ++par) {
             const int kk = k + par;
             if (kk < nch) {
                 if (issued < nch) {       // set `par` went to LDS already: refill it
-                    if (FLAIR_DBG(a) != 2) issue(hreg[par], wreg[par]);
+                    issue(hreg[par], wreg[par]);
                     advance();
                     ++issued;
                 }
-                if (FLAIR_DBG(a) != 1) compute();
+                compute();
                 if (kk + 1 < nch) {
                     __syncthreads();      // everyone is done reading the staged chunk
                     write_lds(hreg[(par + 1) % PF], wreg[(par + 1) % PF]);
@@ -490,84 +472,12 @@ void conv3x3_halo_kernel(ConvArgs a) {
         }
     }
 
-    if (FLAIR_DBG(a) == 5) return;
-    // ---- epilogue, straight from the accumulators.  A lane of the 32x32 MFMA result holds 4 consecutive couts of its
-    // pixel per register quad (quad g: couts 8g + 4*lh ..); v_permlane32_swap between the two half-waves turns quads
-    // 2j, 2j+1 into 8 consecutive couts per lane (lower half 16j .. 16j+7, upper half 16j+8 .. 16j+15): one 16-byte bf16
-    // store and 16-byte residual loads per lane, 32 contiguous bytes per pixel and instruction (f32: a quad already is
-    // 16 bytes).  Measured against the LDS-transposed epilogue below on the clip-level shapes (tools/bench_conv.py, one
-    // box): 117.5 vs 121.6 us (64->64 2-D), 290 vs 268 us (3-D), equal elsewhere -- two workgroups per CU already hide
-    // either epilogue, so the LDS form stays the default and this one is selected with FLAIR_CONV_SWAP_EPILOGUE=1.
-    if ((a.Cout & 7) == 0 && a.debug == 7) {
-#pragma unroll
-        for (int j = 0; j < RPW; ++j) {
-            const int h = h0 + wave * RPW + j, w = w0 + lr;
-            const long p = ((long)t * a.H + h) * a.W + w;
-            const bool rowok = h < a.H;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if constexpr (sizeof(E) == 4) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int co = co0 + i * 32 + 8 * g + 4 * lh;
-                        if (rowok) store_quad<E>(a, p, co, acc[j][i][4 * g], acc[j][i][4 * g + 1], acc[j][i][4 * g + 2],
-                                                 acc[j][i][4 * g + 3]);
-                    }
-                } else {
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const int co = co0 + i * 32 + 16 * jj + 8 * lh;
-                        float v[8];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const auto sw2 = __builtin_amdgcn_permlane32_swap(
-                                __float_as_uint(acc[j][i][8 * jj + e]), __float_as_uint(acc[j][i][8 * jj + 4 + e]), false, false);
-                            v[e] = __uint_as_float(sw2[0]);
-                            v[4 + e] = __uint_as_float(sw2[1]);
-                        }
-                        if (!rowok || co >= a.Cout) continue;
-                        if (a.bias) {
-                            const float4 b0 = *reinterpret_cast<const float4*>(a.bias + co);
-                            const float4 b1 = *reinterpret_cast<const float4*>(a.bias + co + 4);
-                            v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-                            v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-                        }
-                        if (a.fbias) {
-                            const float* fb = a.fbias + (long)t * a.fbiasLd + co;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] += fb[e];
-                        }
-                        if (a.act == FLAIR_ACT_DCN_OFFSETS) {
-                            dcn_offset_act<8>(v, co, a.actParam, a.actPeriod);
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] = apply_act(v[e], a.act);
-                        }
-                        if (a.res0) {
-                            float r[8];
-                            Vec16<E>::load(reinterpret_cast<const E*>(a.res0) + p * a.res0Ld + co, r);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] += r[e];
-                        }
-                        if (a.res1) {
-                            float r[8];
-                            Vec16<E>::load(reinterpret_cast<const E*>(a.res1) + p * a.res1Ld + co, r);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] += r[e];
-                        }
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] *= a.outScale;
-                        Vec16<E>::store(reinterpret_cast<E*>(a.y) + p * a.yLd + co, v);
-                    }
-                }
-            }
-        }
-        return;
-    }
     // ---- epilogue.  The accumulator layout gives each lane 4 channels of one pixel (8-byte
     // pieces scattered over 32 pixels per store).  Transpose each wave's 32 x 64 tile through LDS
     // (staged as f32, so bias / activation / residuals stay exact) and let consecutive lanes
-    // write consecutive 16-byte pieces: whole 128-byte lines, vectorised residual loads.
+    // write consecutive 16-byte pieces: whole 128-byte lines, vectorised residual loads.  (A register-
+    // transposed epilogue by v_permlane32_swap measured 117.5 vs 121.6 us on 64->64 2-D, 290 vs 268 us
+    // on 3-D, equal elsewhere: two workgroups per CU already hide either epilogue.)
     if ((a.Cout & 7) == 0) {
         constexpr int VEC = ET<E>::VEC;
         constexpr int CHUNKS = 64 / VEC;                        // 16-byte output pieces per pixel
@@ -676,6 +586,7 @@ int launch_halo(const ConvArgs& a0, hipStream_t s) {
 // 256 VGPRs).  Needs Cout % 8 == 0.
 template <typename E, int TH, int RPW, int CF>
 __global__ __launch_bounds__(256 * TH / RPW / CF, (256 * TH / RPW / CF) / 256) void conv3x3_halo_ks_kernel(ConvArgs a) {
+    static_assert(RPW == 1 && CF == 2, "one image row and both 32-cout fragments per wave");
     prefetch_kernargs<sizeof(ConvArgs)>();
     constexpr int NRG = TH / RPW;                  // row groups
     constexpr int NCG = 2 / CF;                    // cout-fragment groups (CF fragments of 32 couts per wave)
@@ -725,7 +636,7 @@ __global__ __launch_bounds__(256 * TH / RPW / CF, (256 * TH / RPW / CF) / 256) v
 #pragma unroll
     for (int i = 0; i < HI; ++i) {
         const int id = i * NT + tid;
-        const int pix = staged_row(id, a.ldsSwz);
+        const int pix = staged_row(id);
         const int r = pix / HW_, c = pix % HW_;
         const int hh = h0 + r - 1, ww = w0 + c - 1;
         const bool ok = pix < HALO_ROWS && (unsigned)hh < (unsigned)a.H && (unsigned)ww < (unsigned)a.W;
@@ -736,7 +647,7 @@ __global__ __launch_bounds__(256 * TH / RPW / CF, (256 * TH / RPW / CF) / 256) v
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
         const int id = i * NT + tid;
-        const int row = staged_row(id, a.ldsSwz);
+        const int row = staged_row(id);
         const int co = row / 9, tap9 = row % 9;
         const bool ok = id < W_PIECES && co0 + co < a.Cout;
         woff[i] = ok ? (unsigned)(((co0 + co) * taps + tap9) * a.CinTot + (id & 3) * VEC) * ESZ : FLAIR_OOB;
@@ -771,13 +682,13 @@ __global__ __launch_bounds__(256 * TH / RPW / CF, (256 * TH / RPW / CF) / 256) v
 #pragma unroll
         for (int i = 0; i < HI; ++i) {
             const int id = i * NT + tid;
-            const int row = staged_row(id, a.ldsSwz);
+            const int row = staged_row(id);
             if (row < HALO_ROWS) *reinterpret_cast<uint4*>(sh + row * PITCH + (id & 3) * 16) = hreg[i];
         }
 #pragma unroll
         for (int i = 0; i < WI; ++i) {
             const int id = i * NT + tid;
-            if (id < W_PIECES) *reinterpret_cast<uint4*>(sw + staged_row(id, a.ldsSwz) * PITCH + (id & 3) * 16) = wreg[i];
+            if (id < W_PIECES) *reinterpret_cast<uint4*>(sw + staged_row(id) * PITCH + (id & 3) * 16) = wreg[i];
         }
     };
     int nValidDt = 0;
@@ -825,22 +736,18 @@ __global__ __launch_bounds__(256 * TH / RPW / CF, (256 * TH / RPW / CF) / 256) v
 
     // two-stage pipeline: chunk k is multiplied out of stage k&1 while chunk k+1 is written to the
     // other stage and chunk k+2 is in flight from L2 (one register set, one barrier per chunk)
-    // (timing switches of the diagnostic build: 21 no MFMA phase, 22 return before the epilogue, 23 no in-loop staging,
-    //  24 return at once)
-    if (FLAIR_DBG(a) == 24) return;
     issue();
     write_lds(0);
     if (nch > 1) issue();
     __syncthreads();
     for (int k = 0; k < nch; ++k) {
-        if (FLAIR_DBG(a) != 21) compute(k & 1);
+        compute(k & 1);
         if (k + 1 < nch) {
-            if (FLAIR_DBG(a) != 23) write_lds((k + 1) & 1);      // stage (k+1)&1 was last read before the previous barrier
-            if (k + 2 < nch && FLAIR_DBG(a) != 23) issue();
+            write_lds((k + 1) & 1);      // stage (k+1)&1 was last read before the previous barrier
+            if (k + 2 < nch) issue();
             __syncthreads();
         }
     }
-    if (FLAIR_DBG(a) == 22) return;
 
     // ---- epilogue: sum the two k-halves in the f32 staging tile, then transposed, coalesced stores.
     // Each lane finishes the SAME 16-byte channel piece (ch = lane % CHUNKS) of different pixels in every pass, so its VEC
@@ -984,25 +891,17 @@ struct DmaTile {
     int t, h0, w0, co0;
 };
 
-// NW wavefronts per workgroup, RPW image rows per wavefront (tile = NW * RPW rows x 32 pixels x 64 couts):
-//   <8, 2> clip-level launches (the shape described above);
-//   <8, 1> / <4, 1> single-round launches of 256 tiles of 8 / 4 rows = the per-frame convolutions of the BasicVSR++
-//   recurrence at 256^2 (c = 64) and 128^2 (c = 128): one tile per workgroup, where the gain is the short prologue (DMA instead
+// NW wavefronts per workgroup, RPW image rows per wavefront (tile = NW * RPW rows x 32 pixels x 64 couts), NSTAGE LDS stages:
+//   <8, 2, 2> clip-level launches (the shape described above);
+//   <8, 1, 2> single-round launches of 256 tiles of 8 rows = the per-frame convolutions of the BasicVSR++ recurrence at 256^2
+//   (c = 64) that conv_frame_kernel does not take: one tile per workgroup, where the gain is the short prologue (DMA instead
 //   of load -> ds_write -> barrier) and the register epilogue (no LDS transposition, no k-half reduction barriers).
-//   NSTAGE = 3 (one-tile launches only): three LDS stages, chunks n + 1 and n + 2 in flight while chunk n is multiplied (counted
-//   vmcnt): a per-frame launch at 128^2 multiplies a chunk in ~0.5 us but needs ~1.5 us to fetch one, so depth hides what
-//   a single chunk in flight cannot.
-//   KS = 2 (round 4, <8, 1, 3, 2>): K split -- waves w and w + NW / 2 share an image row, each multiplies ONE 16-channel k-step of every
-//   32-channel chunk (the decomposition of conv3x3_halo_ks_kernel on LDS-DMA staging with three stages): 4-row tiles with eight waves, for
-//   the per-frame convolutions of the 128^2 level, where four waves of one row each (one per SIMD) cannot hide their fragment reads.
-//   After the last chunk the pair exchanges one 32-cout accumulator through LDS and each wave finishes 32 couts of its row.
-template <int NW, int RPW, int NSTAGE, int KS>
+template <int NW, int RPW, int NSTAGE>
 __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, int tilesPerXcd) {
     using E = bf16_t;
-    static_assert(KS == 1 || (KS == 2 && RPW == 1 && NSTAGE == 3 && NW % 2 == 0), "K split: one-tile form with one row per wave");
-    constexpr int ROWW = NW / KS;                          // waves along the rows of the tile
-    constexpr int KSTEPS = 2 / KS;                         // 16-channel k-steps of a chunk this wave multiplies
-    constexpr int TH = ROWW * RPW, HWP = 34;               // tile rows, halo pitch in pixels
+    static_assert((RPW == 1 || RPW == 2) && NSTAGE == 2, "the clip-level and one-tile forms (two stages)");
+    constexpr int KSTEPS = 2;                              // 16-channel k-steps of a chunk
+    constexpr int TH = NW * RPW, HWP = 34;                 // tile rows, halo pitch in pixels
     constexpr int HALO_ROWS = (TH + 2) * HWP;              // staged pixels
     constexpr int HALO_INSTR = (HALO_ROWS + 15) / 16;      // DMA wave-instructions of 16 rows x 64 B
     constexpr int W_INSTR = 64 * 9 / 16;                   // 36
@@ -1014,7 +913,6 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = KS == 1 ? wave : wave % ROWW, kpart = KS == 1 ? 0 : wave / ROWW;      // row group / k-step of this wave
     const int lr = lane & 31, lh = lane >> 5;
     const int taps = a.KT * 9, pt = a.KT / 2;
     const int chunksPerTap = a.CinTot / 32;
@@ -1141,12 +1039,11 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     // B: halo row (2 wave + j + kh) * 34 + kw + lr, same chunk; XOR terms as written by the DMA.
     unsigned aoff[KSTEPS], boff[3][KSTEPS];
 #pragma unroll
-    for (int si = 0; si < KSTEPS; ++si) {
-        const int s_ = KS == 1 ? si : kpart;               // K split: the wave's own k-step
-        aoff[si] = (unsigned)(HALO_BYTES + lr * 64 + (((2 * s_ + lh) ^ ((lr >> 2) & 3)) << 4));
+    for (int s_ = 0; s_ < KSTEPS; ++s_) {
+        aoff[s_] = (unsigned)(HALO_BYTES + lr * 64 + (((2 * s_ + lh) ^ ((lr >> 2) & 3)) << 4));
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
-            boff[kw][si] = (unsigned)((RPW * wr * HWP + kw + lr) * 64 + (((2 * s_ + lh) ^ (((kw + lr) >> 2) & 3)) << 4));
+            boff[kw][s_] = (unsigned)((RPW * wave * HWP + kw + lr) * 64 + (((2 * s_ + lh) ^ (((kw + lr) >> 2) & 3)) << 4));
     }
 
     f32x16 acc[RPW][2];            // [row j][cout fragment]
@@ -1160,8 +1057,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     };
     // One chunk = 3 column taps x 3 row taps x 8 MFMAs.  Fragments of step n + 1 (A: 4 reads; B: 8 more reads when the
     // column tap changes) are requested before the 8 MFMAs of step n are issued (two fragment sets).
-    auto compute_as = [&](int stage, auto revTag) {
-        constexpr bool REV = decltype(revTag)::value;      // walk the column taps right to left (experiment: de-phase wave pairs)
+    auto compute = [&](int stage) {
         const char* sb = smem + stage * STAGE_BYTES;
         uint4 fb[2][RPW + 2][KSTEPS];   // [set][halo row RPW wave + h][k-step]
         uint4 fa[2][2][KSTEPS];         // [set][cout fragment][k-step]
@@ -1179,28 +1075,21 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                 for (int s_ = 0; s_ < KSTEPS; ++s_)
                     fa[set][cf][s_] = *reinterpret_cast<const uint4*>(sb + (kh * 3 + kw) * 4096 + cf * 2048 + aoff[s_]);
         };
-        auto mma = [&](const uint4 (&fa_)[KSTEPS], const uint4 (&fb_)[KSTEPS], f32x16& c) {
-            if constexpr (KS == 1) Mma<E>::run(fa_, fb_, c);
-            else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa_[0]), __builtin_bit_cast(bf16x8, fb_[0]), c, 0, 0, 0);
-        };
-        auto KW = [](int q) { return REV ? 2 - q : q; };
-        load_b(0, KW(0));
-        load_a(0, 0, KW(0));
+        load_b(0, 0);
+        load_a(0, 0, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, KSTEPS * (RPW + 2) + 2 * KSTEPS, 0);
 #pragma unroll
         for (int step = 0; step < 9; ++step) {
             const int kq = step / 3, kh = step % 3;
             const int nkq = (step + 1) / 3, nkh = (step + 1) % 3;
             if (step < 8) {
-                if (nkh == 0) load_b(nkq & 1, KW(nkq));
-                load_a((step + 1) & 1, nkh, KW(nkq));
+                if (nkh == 0) load_b(nkq & 1, nkq);
+                load_a((step + 1) & 1, nkh, nkq);
             }
-            if (FLAIR_DBG(a) == 17) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int j = 0; j < RPW; ++j)
 #pragma unroll
-                for (int cf = 0; cf < 2; ++cf) mma(fa[step & 1][cf], fb[kq & 1][j + kh], acc[j][cf]);
-            if (FLAIR_DBG(a) == 17) __builtin_amdgcn_s_setprio(0);
+                for (int cf = 0; cf < 2; ++cf) Mma<E>::run(fa[step & 1][cf], fb[kq & 1][j + kh], acc[j][cf]);
             if (step < 8) {
                 if (nkh == 0) __builtin_amdgcn_sched_group_barrier(0x100, KSTEPS * (RPW + 2) + 2 * KSTEPS, 0);
                 else __builtin_amdgcn_sched_group_barrier(0x100, 2 * KSTEPS, 0);
@@ -1208,17 +1097,8 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
             __builtin_amdgcn_sched_group_barrier(0x8, 2 * KSTEPS * RPW, 0);
         }
     };
-    auto compute = [&](int stage) {
-#ifdef FLAIR_TIMING_SWITCHES
-        if (FLAIR_DBG(a) == 18 && wave >= NW / 2) {
-            compute_as(stage, std::true_type{});
-            return;
-        }
-#endif
-        compute_as(stage, std::false_type{});
-    };
     // Epilogue, written for a low instruction count: it runs once per tile on all eight waves at once, so nothing hides its
-    // VALU issue time (timing switches, profiles/r03_dma_switches.txt: 74 us of a 156 us two-chunk convolution in the first
+    // VALU issue time (profiles/r03_dma_switches.txt: 74 us of a 156 us two-chunk convolution in the first
     // version -- 22 us stores, 12 us bias round trips, the rest instruction issue and instruction-cache misses of eight
     // inlined copies x six activation variants = 14 700 instructions).  Now: one unrolled pass per activation CLASS (chosen
     // by one wave-uniform branch outside), biases from LDS, one 64-bit address per tile and wave, pointer bumps after that.
@@ -1233,7 +1113,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
         // convolution with residual).  Now all residual pieces of the wave are requested in one batch up front
         // (the staging fragments are dead, the registers exist) and the waits are counted; the frame bias is part of the tile's
         // bias slot in LDS (bias_request).
-        const long p0w = ((long)tl.t * H + tl.h0 + RPW * wr) * W + tl.w0;                // first pixel of the wave's rows (wave-uniform)
+        const long p0w = ((long)tl.t * H + tl.h0 + RPW * wave) * W + tl.w0;              // first pixel of the wave's rows (wave-uniform)
         const int cl = 8 * lh;                                                           // this lane's cout offset inside a 16-cout half
         const unsigned yLdB = (unsigned)a.yLd * 2u, rLdB = (unsigned)a.res0Ld * 2u;
         const unsigned span = (unsigned)(RPW * W);                                       // pixels the wave's offsets stay below
@@ -1246,8 +1126,9 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
         const unsigned yLane = (unsigned)lr * yLdB + 2u * cl, rLane = (unsigned)lr * rLdB + 2u * cl;
         // Without a residual no load is issued at all: a load here is younger than the next chunk's DMA pieces, so waiting
         // for it also waits for those, which otherwise have the whole epilogue left to land (+9 us on a 105 us convolution).
-        constexpr bool ALLUP = RPW <= 2;           // four rows per wave: one batch per 32-cout fragment (the accumulators leave no room for all 16 pieces)
-        uint4 r0v[ALLUP ? 2 : 1][2][RPW];
+        // (An LDS-DMA touch of the residual lines one chunk ahead no longer paid in round 4: clip-level family 16.62 / 16.71 ms
+        // without, 16.73 / 16.74 ms with, the lines fetched a second time by these loads.)
+        uint4 r0v[2][2][RPW];
         auto res_request = [&](int i) {
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
@@ -1255,16 +1136,15 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                 const bool lane_ok = tl.co0 + cofs + cl < a.Cout;
 #pragma unroll
                 for (int j = 0; j < RPW; ++j)
-                    r0v[ALLUP ? i : 0][jj][j] = buf_load16(r0d, lane_ok ? rLane + (unsigned)(j * W) * rLdB + 2u * cofs : FLAIR_OOB);
+                    r0v[i][jj][j] = buf_load16(r0d, lane_ok ? rLane + (unsigned)(j * W) * rLdB + 2u * cofs : FLAIR_OOB);
             }
         };
-        if constexpr (HASRES && ALLUP) {
+        if constexpr (HASRES) {
             res_request(0);
             res_request(1);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if constexpr (HASRES && !ALLUP) res_request(i);
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
                 const int cofs = i * 32 + 16 * jj;                                       // cout offset of this group inside the tile
@@ -1300,7 +1180,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                     }                                      // ACT == 3: no activation and out_scale == 1 (the ResBlock convolutions)
                     if constexpr (HASRES) {
                         float r[8];
-                        Vec16<E>::load(reinterpret_cast<const E*>(&r0v[ALLUP ? i : 0][jj][j]), r);      // zeros without res0 / on padding lanes
+                        Vec16<E>::load(reinterpret_cast<const E*>(&r0v[i][jj][j]), r);      // zeros without res0 / on padding lanes
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] += r[e];
                         if (r1b && lane_ok) {
@@ -1317,9 +1197,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                     Vec16<E>::store(out, v);
                     const uint4 ov = *reinterpret_cast<const uint4*>(out);
                     const unsigned yo = lane_ok ? yLane + (unsigned)(j * W) * yLdB + 2u * cofs : FLAIR_OOB;
-                    if (FLAIR_DBG(a) != 16)
-                        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{ov.x, ov.y, ov.z, ov.w}, yd, (int)yo, 0, 0);
-                    else asm volatile("" ::"v"(ov.x), "v"(ov.y), "v"(ov.z), "v"(ov.w));
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{ov.x, ov.y, ov.z, ov.w}, yd, (int)yo, 0, 0);
                 }
             }
         }
@@ -1331,7 +1209,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     auto epilogue_plain_as = [&](const DmaTile& tl, int biasSlot, auto actTag) {
         constexpr int ACT = decltype(actTag)::value;       // 0: max(v, slope v)   1: DCN offsets / masks   2: SiLU
         const float slope = a.act == FLAIR_ACT_NONE ? 1.f : a.act == FLAIR_ACT_RELU ? 0.f : a.act == FLAIR_ACT_LRELU01 ? 0.1f : 0.2f;
-        const long p0 = ((long)tl.t * H + tl.h0 + RPW * wr) * W + tl.w0 + lr;            // this lane's pixel in row j = 0
+        const long p0 = ((long)tl.t * H + tl.h0 + RPW * wave) * W + tl.w0 + lr;          // this lane's pixel in row j = 0
         const int cl = 8 * lh;                                                           // this lane's cout offset inside a 16-cout half
         E* yb = reinterpret_cast<E*>(a.y) + p0 * a.yLd + tl.co0 + cl;
         const E* r0b = a.res0 ? reinterpret_cast<const E*>(a.res0) + p0 * a.res0Ld + tl.co0 + cl : nullptr;
@@ -1339,10 +1217,10 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
         const float* bl = reinterpret_cast<const float*>(smem + BIAS_OFF + (biasSlot & 1) * 256) + cl;
         const float scale = a.outScale;
 #pragma unroll
-        for (int i = 0; i < 2 / KS; ++i)                                                 // K split: the wave's sum sits in acc[.][0], its couts start at 32 * kpart
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const int cofs = (KS == 1 ? i : kpart) * 32 + 16 * jj;                   // cout offset of this group inside the tile
+                const int cofs = i * 32 + 16 * jj;                                       // cout offset of this group inside the tile
                 if (tl.co0 + cofs >= a.Cout) continue;                                   // wave-uniform: the whole 16-cout group is padding
                 // (Cout % 8 == 0) the upper 8 couts of the group may be padding: those lanes still take part in the
                 // v_permlane32_swap below (a swap under a divergent branch hands the active half garbage), only their
@@ -1389,8 +1267,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= scale;
                     if (!lane_ok) continue;
-                    if (FLAIR_DBG(a) != 16) Vec16<E>::store(yb + ro * a.yLd + cofs, v);
-                    else asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+                    Vec16<E>::store(yb + ro * a.yLd + cofs, v);
                 }
             }
     };
@@ -1408,24 +1285,6 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
         else if (a.act == FLAIR_ACT_SILU) go(std::integral_constant<int, 2>{});
         else if (RPW >= 2 && a.act == FLAIR_ACT_NONE && a.outScale == 1.f) go(std::integral_constant<int, 3>{});   // pack + store only
         else go(std::integral_constant<int, 0>{});      // NONE / RELU / LeakyReLU (GELU: refused on the host)
-    };
-    // Residual prefetch: one 4-byte LDS-DMA per output pixel of the wave (64 couts x 2 bytes = the pixel's 128-byte line),
-    // landing in the DMA scratch area, requested BEFORE the DMA pieces of the tile's last chunk: the epilogue's real loads
-    // then find their lines in the L2 instead of paying a trip to HBM with every wave of the CU waiting.  No register
-    // receives data, so nothing can be clobbered; the pieces are older than that chunk's DMA and retire with it.
-    auto prefetch_res = [&](const DmaTile& tl) {
-        const long p0w = ((long)tl.t * H + tl.h0 + RPW * wr) * W + tl.w0;
-        const u32x4_t rd = make_desc(reinterpret_cast<const char*>(a.res0) + (p0w * a.res0Ld + tl.co0) * 2, (unsigned)(RPW * W * a.res0Ld) * 2u);
-#pragma unroll
-        for (int jj = 0; jj < (RPW + 1) / 2; ++jj) {
-            const int j = 2 * jj + (lane >> 5);
-            const unsigned voff = j < RPW ? (unsigned)((j * W + lr) * a.res0Ld) * 2u : FLAIR_OOB;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(voff), "s"((unsigned)(NSTAGE * STAGE_BYTES + wave * 1024)), "s"(rd)
-                         : "memory");
-        }
     };
 
     // ---- the (tile, chunk) pipeline.  `cur` is the tile being multiplied, `nxt` the tile whose chunks are being issued.
@@ -1457,54 +1316,6 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     };
     bias_request(nxt);
     bias_commit(0);
-    if constexpr (NSTAGE == 3) {
-        // ---- one tile, three stages: wait(n) -> barrier -> issue(n + 2) -> multiply(n).  When chunk n is waited for, the only
-        // younger DMA in flight is chunk n + 1 (NSLOT instructions of this wave): vmcnt(NSLOT) retires chunk n and leaves it.
-        const int nch = chunks_of(cur.t);
-        issue(cur, wk, 0);
-        walk_next(cur.t, wk);
-        if (nch > 1) {
-            issue(cur, wk, 1);
-            walk_next(cur.t, wk);
-        }
-        zero_acc();
-        for (int n = 0; n < nch; ++n) {
-            if (n + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSLOT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();                    // chunk n is in LDS for everybody; stage (n + 2) % 3 = (n - 1) % 3 is free
-            if (n + 2 < nch) {
-                if (FLAIR_DBG(a) != 12) issue(cur, wk, (n + 2) % 3);
-                walk_next(cur.t, wk);
-            }
-            if (FLAIR_DBG(a) != 11) compute(n % 3);
-        }
-        if constexpr (KS == 2) {
-            // ---- sum the two k-steps of every row: the wave of k-step 0 finishes cout fragment 0, its partner fragment 1; each parks the
-            // fragment it gives away in LDS (stage 0: every wave is past its last fragment read after the barrier)
-            __syncthreads();
-            float* red = reinterpret_cast<float*>(smem);
-            float* mine = red + (wave * 64 + lane) * 16;
-            const float* theirs = red + ((wave ^ ROWW) * 64 + lane) * 16;                // partner: same row, other k-step (ROWW is a power of two)
-            static_assert((ROWW & (ROWW - 1)) == 0, "partner by xor");
-            if (kpart == 0) {
-#pragma unroll
-                for (int r = 0; r < 16; r += 4) *reinterpret_cast<float4*>(mine + r) = make_float4(acc[0][1][r], acc[0][1][r + 1], acc[0][1][r + 2], acc[0][1][r + 3]);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; r += 4) *reinterpret_cast<float4*>(mine + r) = make_float4(acc[0][0][r], acc[0][0][r + 1], acc[0][0][r + 2], acc[0][0][r + 3]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][0][r] = acc[0][1][r];                 // the kept fragment moves to slot 0 (the epilogue reads slot 0)
-            }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 16; r += 4) {
-                const float4 v = *reinterpret_cast<const float4*>(theirs + r);
-                acc[0][0][r] += v.x; acc[0][0][r + 1] += v.y; acc[0][0][r + 2] += v.z; acc[0][0][r + 3] += v.w;
-            }
-        }
-        if (FLAIR_DBG(a) != 13) epilogue(cur, 0);
-        return;
-    }
     const bool res0any = a.res0 || a.res1;
     int remIssue = chunks_of(nxt.t);           // chunks of `nxt` not yet issued
     int remCompute = remIssue;                 // chunks of `cur` not yet multiplied
@@ -1529,26 +1340,20 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                 bias_request(nxt);
             }
         }
-        if constexpr (RPW >= 2)
-            if (remCompute == 1 && a.res0 && FLAIR_DBG(a) != 19) {
-                if (a.resPrefetch == 1) prefetch_res(cur);
-            }
         if (more) {
-            if (FLAIR_DBG(a) != 12) issue(nxt, wk, stage ^ 1);     // (timing switches: 11 no MFMA phase, 12 no DMA, 13 no epilogue)
+            issue(nxt, wk, stage ^ 1);
             walk_next(nxt.t, wk);
             --remIssue;
         }
-        if (FLAIR_DBG(a) != 11) compute(stage);
+        compute(stage);
         if (biasPending) bias_commit(iNxt);
         bool storesInFlight = false;
         if (--remCompute == 0) {
-            if (FLAIR_DBG(a) != 13) {
-                epilogue(cur, iCur);
-                // every tile issues exactly 4 * RPW store instructions per wave as its youngest memory operations (a second
-                // residual is loaded under a branch, where hipcc places its own waits: not counted on)
-                // (RPW == 2: padding lanes' stores are issued too, out of range; RPW == 1: full tiles without a residual branch)
-                storesInFlight = (RPW >= 2 ? !a.res1 : cur.co0 + 64 <= a.Cout && !res0any) && FLAIR_DBG(a) != 14 && FLAIR_DBG(a) != 16;
-            }
+            epilogue(cur, iCur);
+            // every tile issues exactly 4 * RPW store instructions per wave as its youngest memory operations (a second
+            // residual is loaded under a branch, where hipcc places its own waits: not counted on)
+            // (RPW == 2: padding lanes' stores are issued too, out of range; RPW == 1: full tiles without a residual branch)
+            storesInFlight = RPW >= 2 ? !a.res1 : cur.co0 + 64 <= a.Cout && !res0any;
             ++iCur;
             if (!tile_at(iCur, cur)) break;
             remCompute = chunks_of(cur.t);
@@ -1570,25 +1375,15 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
 template <int NW, int RPW, int NSTAGE>
 __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void conv3x3_dma_kernel(ConvArgs a, int nTiles, int tilesPerXcd) {
     prefetch_kernargs<sizeof(ConvArgs) + 8>();
-    conv3x3_dma_body<NW, RPW, NSTAGE, 1>(a, nTiles, tilesPerXcd);
-}
-template <int NW, int RPW, int NSTAGE>          // the K-split form under its own name (rocprofv3 rows of the other forms keep theirs)
-__global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void conv3x3_dma_ks_kernel(ConvArgs a, int nTiles, int tilesPerXcd) {
-    prefetch_kernargs<sizeof(ConvArgs) + 8>();
-    conv3x3_dma_body<NW, RPW, NSTAGE, 2>(a, nTiles, tilesPerXcd);
+    conv3x3_dma_body<NW, RPW, NSTAGE>(a, nTiles, tilesPerXcd);
 }
 
-template <int NW, int RPW, int NSTAGE, int KS = 1>
+template <int NW, int RPW, int NSTAGE>
 int launch_dma(const ConvArgs& a0, hipStream_t s) {
-    constexpr int TH = NW / KS * RPW;
+    constexpr int TH = NW * RPW;
     ConvArgs a = a0;
     a.nCoTiles = cdiv(a.Cout, 64);
-    static const int tfast = getenv("FLAIR_DMA_TFAST") ? atoi(getenv("FLAIR_DMA_TFAST")) : 1;
-    a.tFast = tfast && a.KT == 3 && a.T > 1;
-    // round 4: the touch no longer pays (clip-level family 16.62 / 16.71 ms without, 16.73 / 16.74 with, same box) and the counters show
-    // the touched lines fetched a second time by the real loads (profiles/r04_dma_read_traffic_by_shape.txt): off by default
-    static const int resPf = getenv("FLAIR_DMA_RES_PREFETCH") ? atoi(getenv("FLAIR_DMA_RES_PREFETCH")) : 0;
-    a.resPrefetch = resPf;
+    a.tFast = a.KT == 3 && a.T > 1;
     const int nTiles = a.T * (a.H / TH) * (a.W / 32) * a.nCoTiles;
     const int nCu = flair_cu_count();                                  // of the CURRENT device
     int grid = nTiles < nCu ? (nTiles + 7) / 8 * 8 : nCu / 8 * 8;      // a multiple of 8: every XCD gets the same number of slots
@@ -1596,37 +1391,37 @@ int launch_dma(const ConvArgs& a0, hipStream_t s) {
     const int tilesPerXcd = (nTiles + 7) / 8;
     constexpr int HALO_INSTR = ((TH + 2) * 34 + 15) / 16;
     const size_t lds = NSTAGE * (size_t)(HALO_INSTR + 36) * 1024 + NW * 1024 + 512;  // stages + idle DMA slots' scratch + two bias slots
-    if (NSTAGE == 3) FLAIR_CHECK(nTiles <= grid, "flair_conv_nhwc: the three-stage form runs one tile per workgroup");
     static LdsAttrOnce attr;
     {
-        const void* fn;
-        if constexpr (KS == 1) fn = reinterpret_cast<const void*>(&conv3x3_dma_kernel<NW, RPW, NSTAGE>);
-        else fn = reinterpret_cast<const void*>(&conv3x3_dma_ks_kernel<NW, RPW, NSTAGE>);
-        const hipError_t e = flair_max_lds_once(attr, fn);
+        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv3x3_dma_kernel<NW, RPW, NSTAGE>));
         FLAIR_CHECK(e == hipSuccess, "flair_conv_nhwc: hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    if constexpr (KS == 1) hipLaunchKernelGGL((conv3x3_dma_kernel<NW, RPW, NSTAGE>), dim3(grid), dim3(64 * NW), lds, s, a, nTiles, tilesPerXcd);
-    else hipLaunchKernelGGL((conv3x3_dma_ks_kernel<NW, RPW, NSTAGE>), dim3(grid), dim3(64 * NW), lds, s, a, nTiles, tilesPerXcd);
+    hipLaunchKernelGGL((conv3x3_dma_kernel<NW, RPW, NSTAGE>), dim3(grid), dim3(64 * NW), lds, s, a, nTiles, tilesPerXcd);
+
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// One-tile 3x3 convolution with a THREE-deep weight ring (round 4): the per-frame convolutions of the 256^2 level (Cout <= 64, one
+// One-tile 3x3 convolution with a THREE-deep halo ring (round 4): the per-frame convolutions of the 256^2 level (Cout <= 64, one
 // 8 x 32 tile per workgroup, 4-7 K chunks).  conv3x3_dma_kernel<8, 1, 2> stages halo + weights of a chunk together in two 58 KB stages:
 // chunk n + 1 is requested when chunk n starts to be multiplied and must have landed 2 304 MFMA cycles later -- it has not (measured
-// ~2.2 us per chunk against 1.15 us of matrix work).  Three such stages do not fit the LDS; here the 36 KB weight images go through a
-// ring of three (requested TWO chunks ahead) and the 22 KB halo images through a ring of two, 152 KB together, every wave issuing
+// ~2.2 us per chunk against 1.15 us of matrix work).  Three such stages do not fit the LDS; here the 22 KB halo images go through a
+// ring of three (requested TWO chunks ahead) and the 36 KB weight images through a ring of two, 138 KB together, every wave issuing
 // the same number of DMA instructions per phase so that one immediate vmcnt serves all waves (the recipe of conv_resident_kernel /
-// conv_pair_kernel in chain.hip).  Epilogue from the accumulators; both residual inputs are requested at the head of the last chunk.
+// conv_pair_kernel in chain.hip).  (The transposed rings, weights three deep and halos two: per-frame family 19.03 / 18.95 against
+// 19.03 / 19.09 ms, step 70.63 / 70.65 against 70.54 / 70.57 ms, same box.)  Epilogue from the accumulators; both residual inputs
+// are requested at the head of the last chunk.
+
 // bf16, stride 1, KT = 1, W % 32 == 0, H % 8 == 0, segments multiples of 32 channels, activations none / ReLU / LeakyReLU(0.1 | 0.2).
-template <bool HALO3>       // false: halo ring of two + weight ring of three; true: halo ring of THREE + weight ring of two (138 KB)
+template <bool HALO3>       // true: the halo ring of three
 __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {
+    static_assert(HALO3, "halo ring of three, weight ring of two");
     prefetch_kernargs<sizeof(ConvArgs)>();
     using E = bf16_t;
     constexpr int NW = 8, HWP = 34;
     constexpr int HINSTR = 22, HIMG = HINSTR * 1024, WINSTR = 36, SLOT = WINSTR * 1024;
-    constexpr int HR = HALO3 ? 3 : 2, WR = HALO3 ? 2 : 3;
+    constexpr int HR = 3, WR = 2;
     constexpr int RING = HR * HIMG, BIAS = RING + WR * SLOT;
     constexpr int NH = (HINSTR + NW - 1) / NW, NWS = (WINSTR + NW - 1) / NW;   // 3, 5
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1691,7 +1486,7 @@ __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {
         issue_halo(1);
         issue_w(1);
     }
-    if (HALO3 && nS > 2) issue_halo(2);
+    if (nS > 2) issue_halo(2);
 
     unsigned aoff[2], boff[3][2];
 #pragma unroll
@@ -1746,18 +1541,12 @@ __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {
     for (int g = 0; g < 4; ++g) r0v[g] = r1v[g] = make_uint4(0u, 0u, 0u, 0u);
 
     for (int s_ = 0; s_ < nS; ++s_) {
-        // halo s_ and weights s_ have landed; younger in flight: at s_ = 0 halo 1 + weights 1 (+ halo 2), later the weights of s_ + 1
-        // (HALO3: the halo of s_ + 1, issued behind the weights of s_)
-        if constexpr (HALO3) {
-            if (s_ + 1 >= nS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (s_ == 0 && nS > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NH + NWS) : "memory");
-            else if (s_ == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH + NWS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH) : "memory");      // the halo of s_ + 1 (prologue / behind the weights of s_)
-        } else {
-            if (s_ + 1 >= nS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (s_ == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH + NWS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWS) : "memory");
-        }
+        // halo s_ and weights s_ have landed; younger in flight: at s_ = 0 halo 1 + weights 1 (+ halo 2), later the halo of s_ + 1
+        // (issued behind the weights of s_)
+        if (s_ + 1 >= nS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (s_ == 0 && nS > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NH + NWS) : "memory");
+        else if (s_ == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH + NWS) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH) : "memory");      // the halo of s_ + 1 (prologue / behind the weights of s_)
         __builtin_amdgcn_s_barrier();                    // ... for everybody; everybody is done with chunk s_ - 1
         if (s_ == 0) {
             const float* sb = reinterpret_cast<const float*>(smem + BIAS);
@@ -1769,13 +1558,8 @@ __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {
                     acc[cf][4 * g] = bq.x; acc[cf][4 * g + 1] = bq.y; acc[cf][4 * g + 2] = bq.z; acc[cf][4 * g + 3] = bq.w;
                 }
         }
-        if constexpr (HALO3) {
-            if (s_ >= 1 && s_ + 1 < nS) issue_w(s_ + 1);                   // weight slot of chunk s_ - 1
-            if (s_ >= 1 && s_ + 2 < nS) issue_halo((s_ + 2) % 3);          // halo slot of chunk s_ - 1
-        } else {
-            if (s_ >= 1 && s_ + 1 < nS) issue_halo((s_ + 1) & 1);          // halo slot of chunk s_ - 1
-            if (s_ + 2 < nS) issue_w(s_ + 2);                              // weight slot of chunk s_ - 1
-        }
+        if (s_ >= 1 && s_ + 1 < nS) issue_w(s_ + 1);                       // weight slot of chunk s_ - 1
+        if (s_ >= 1 && s_ + 2 < nS) issue_halo((s_ + 2) % 3);              // halo slot of chunk s_ - 1
         if (s_ + 1 == nS) {                                            // last chunk: the residual inputs, used in the epilogue
             if (a.res0) {
 #pragma unroll
@@ -1829,13 +1613,12 @@ static bool frame_kernel_ok(const ConvArgs& a) {
     return true;
 }
 
-template <bool HALO3>
 static int launch_frame(const ConvArgs& a, hipStream_t s) {
-    constexpr size_t lds = (HALO3 ? 3 * 22 + 2 * 36 : 2 * 22 + 3 * 36) * 1024 + 1024;
+    constexpr size_t lds = (3 * 22 + 2 * 36) * 1024 + 1024;
     static LdsAttrOnce attr;
-    const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv_frame_kernel<HALO3>));
+    const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv_frame_kernel<true>));
     FLAIR_CHECK(e == hipSuccess, "flair_conv_nhwc: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(conv_frame_kernel<HALO3>, dim3(a.T * (a.H / 8) * (a.W / 32)), dim3(512), lds, s, a);
+    hipLaunchKernelGGL(conv_frame_kernel<true>, dim3(a.T * (a.H / 8) * (a.W / 32)), dim3(512), lds, s, a);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -2007,7 +1790,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
             if (k >= nk) break;                     // block uniform
             const int cur = k & 1;
             if (k + PD < nk) {                      // set u went to LDS in the previous step: free for step k + PD
-                if (FLAIR_DBG(a) != 32) issue_loads(u);
+                issue_loads(u);
                 advance();
             }
             const char* wb = smem + cur * BUF;
@@ -2037,15 +1820,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
         }
     }
 
-    if (FLAIR_DBG(a) == 31) {                   // (timing switches of the diagnostic build: 31 no epilogue, 32 no loads past the first steps)
-#pragma unroll
-        for (int i = 0; i < FC; ++i)
-#pragma unroll
-            for (int j = 0; j < FP; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(acc[i][j][r]));     // keep the K loop alive
-        return;
-    }
     // ---- epilogue: lane = pixel column, register quad = 4 consecutive couts ----
     if (a.splitK > 1) {   // raw f32 partials; bias/act/residual happen in the reduce kernel
 #pragma unroll
@@ -2139,19 +1913,16 @@ int launch_pd(const ConvArgs& a0, hipStream_t s) {
     return FLAIR_OK;
 }
 
-// FLAIR_IGEMM_PD = 1 selects the one-step-ahead form of rounds 1-2 (A/B switch), default 4 steps in flight;
-// FLAIR_IGEMM_WIDE = 0 keeps 32-channel K steps everywhere (default: 64-channel steps, two in flight, for bf16 convolutions whose
-// input segments are all multiples of 64 channels -- the same bytes in flight as four 32-channel steps)
+// 4 K steps in flight; bf16 convolutions whose input segments are all multiples of 64 channels take 64-channel steps,
+// two in flight -- the same bytes in flight as four 32-channel steps
 template <typename E, int TC, int TP, int WC, int WP>
 int launch(const ConvArgs& a, hipStream_t s) {
-    static const int pd = getenv("FLAIR_IGEMM_PD") ? atoi(getenv("FLAIR_IGEMM_PD")) : 4;
-    static const int wide = getenv("FLAIR_IGEMM_WIDE") ? atoi(getenv("FLAIR_IGEMM_WIDE")) : 1;
     if constexpr (sizeof(E) == 2) {
-        bool ok = wide && pd > 1;
+        bool ok = true;
         for (int i = 0; i < a.nseg; ++i) ok = ok && a.segC[i] % 64 == 0;
         if (ok) return launch_pd<E, TC, TP, WC, WP, 2, 2>(a, s);
     }
-    return pd <= 1 ? launch_pd<E, TC, TP, WC, WP, 1, 1>(a, s) : launch_pd<E, TC, TP, WC, WP, 4, 1>(a, s);
+    return launch_pd<E, TC, TP, WC, WP, 4, 1>(a, s);
 }
 
 // Split-K factor for the im2col path: deep-K convolutions on few pixels (the 16x16 .. 4x4
@@ -2180,29 +1951,22 @@ int choose_variant(const ConvArgs& a) {
         // single-round launches (<= one workgroup per CU): K-split kernel, twice the wavefronts
         const bool ks = a.Cout % 8 == 0;
         // persistent LDS-DMA kernel (bf16): launches of more than one round of 8-row tiles whose 16-row tiles fill most CUs
-        static const bool useDma = !(getenv("FLAIR_CONV_DMA") && atoi(getenv("FLAIR_CONV_DMA")) == 0);
-        if (useDma && a.esz == 2 && ks && a.act != FLAIR_ACT_GELU && a.H % 16 == 0 && per * cdiv(a.H, 8) > 256 && per * (a.H / 16) >= 192) return 8;
-        // single-round launches (per-frame convolutions): the one-tile-per-workgroup forms of the LDS-DMA kernel (bf16)
-        // FLAIR_CONV_DMA_FRAME: 0 K-split kernels everywhere, 1 (default) <8 rows> form at the 256^2 level, 2 also the <4 rows>
-        // form at the 128^2 level.  Measured (profiles/r03_dma_switches.txt): a per-frame launch is launch (1.6 us) + cold first
-        // fetch (~4 us: every CU pulls its 58 KB at once after the boundary invalidated the L2s) + epilogue / drain (~3 us)
-        // whatever the staging mechanism: <8 rows> 12.6 vs 13.6 us on 64->64, equal on 224->64; <4 rows> 14.3 vs 11.9 us (one
-        // wave per SIMD does not hide the per-chunk DMA round trips that 8 K-split waves do), hence off by default.
-        // 3 (round 4): the <4 rows> form with EIGHT waves, K split like the K-split kernel (<8, 1, 3, KS = 2>): correct, +0.5 ms per step against
-        // the register-staged K-split kernel (77.5 / 77.7 -> 78.1 / 78.1, same box): LDS-DMA staging does not pay on one-tile launches of this size.
-        static const int dmaFrame = getenv("FLAIR_CONV_DMA_FRAME") ? atoi(getenv("FLAIR_CONV_DMA_FRAME")) : 1;
+        if (a.esz == 2 && ks && a.act != FLAIR_ACT_GELU && a.H % 16 == 0 && per * cdiv(a.H, 8) > 256 && per * (a.H / 16) >= 192) return 8;
+        // single-round launches (per-frame convolutions): the one-tile-per-workgroup LDS-DMA form (bf16) at the 256^2 level,
+        // the register-staged K-split kernel at the 128^2 level.  Measured (profiles/r03_dma_switches.txt): <8 rows> 12.6 vs
+        // 13.6 us on 64->64; <4 rows> LDS-DMA forms lost to the K-split kernel (one wave per SIMD: 14.3 vs 11.9 us; eight
+        // waves, K split: +0.5 ms per step).
         const bool dmaOk = a.esz == 2 && ks && a.act != FLAIR_ACT_GELU;
-        if (per * cdiv(a.H, 8) >= 256) return ks && per * cdiv(a.H, 8) <= 256 ? (dmaOk && dmaFrame >= 1 && a.H % 8 == 0 ? 9 : 6) : 3;
-        if (per * cdiv(a.H, 4) >= 256) return ks && per * cdiv(a.H, 4) <= 256 ? (dmaOk && dmaFrame >= 3 && a.H % 4 == 0 ? 11 : dmaOk && dmaFrame == 2 && a.H % 4 == 0 ? 10 : 7) : 4;
+        if (per * cdiv(a.H, 8) >= 256) return ks && per * cdiv(a.H, 8) <= 256 ? (dmaOk && a.H % 8 == 0 ? 9 : 6) : 3;
+        if (per * cdiv(a.H, 4) >= 256) return ks && per * cdiv(a.H, 4) <= 256 ? 7 : 4;
         return 5;
     }
     const long tiles128 = (long)cdiv(a.P, 128) * cdiv(a.Cout, 128);
     if (a.Cout > 64 && tiles128 >= 512) return 0;
     // deep-K convolutions on few pixels (16x16 / 8x8 levels, K = 2304 .. 13,824): 128x128 tiles with split-K move half
     // the L2->LDS bytes of 64x64 tiles per flop; hipGraph-timed 256->256 3x3x3 at 16x16^2: 57.7 -> 43.4 us,
-    // 512->512 at 16x8^2: 58.1 -> 45.2 us (4x4 stays on 64x64: 29.6 vs 34.0 us).  FLAIR_DEEPK_TILE128=0: round-1 choice.
-    static const bool deepk128 = !(getenv("FLAIR_DEEPK_TILE128") && atoi(getenv("FLAIR_DEEPK_TILE128")) == 0);
-    if (deepk128 && a.Cout >= 128 && a.P >= 1024 && tiles128 <= 64 && (long)a.KT * a.KH * a.KW * a.CinTot >= 2304) return 0;
+    // 512->512 at 16x8^2: 58.1 -> 45.2 us (4x4 stays on 64x64: 29.6 vs 34.0 us).
+    if (a.Cout >= 128 && a.P >= 1024 && tiles128 <= 64 && (long)a.KT * a.KH * a.KW * a.CinTot >= 2304) return 0;
     const long tiles64x128 = (long)cdiv(a.P, 128) * cdiv(a.Cout, 64);
     if (tiles64x128 >= 512) return 1;
     return 2;
@@ -2219,36 +1983,16 @@ int dispatch(const ConvArgs& a0, hipStream_t s) {
         case 2: return launch<E, 64, 64, 2, 2>(a, s);
         case 3: return launch_halo<E, 8, 1, 1>(a, s);
         case 4: return launch_halo<E, 4, 1, 1>(a, s);
-        case 6: {
-            // FLAIR_KS_RPW2=1: 8 waves of 2 rows x 64 couts (4 MFMAs per 4 LDS fragment reads) instead of 16 waves of 1 row
-            // (2 per 3).  Neutral end to end (90.95 vs 90.84 ms/step, three same-box pairs) and slower per call under
-            // rocprofv3 (26.1 vs 22.9 us): the one-row form stays the default.
-            static const int rpw2 = getenv("FLAIR_KS_RPW2") ? atoi(getenv("FLAIR_KS_RPW2")) : 0;
-            return rpw2 ? launch_halo_ks<E, 8, 2, 2>(a, s) : launch_halo_ks<E, 8, 1, 2>(a, s);
-        }
-        case 7: {
-            // (two rows per wave leave 4 waves per CU here: +3.5 ms/step)
-            // FLAIR_KS_CF1=1: one 32-cout fragment per wave, i.e. 16 waves per workgroup on the 4-row tiles of the 128^2 level
-            static const int cf1 = getenv("FLAIR_KS_CF1") ? atoi(getenv("FLAIR_KS_CF1")) : 0;
-            return cf1 ? launch_halo_ks<E, 4, 1, 1>(a, s) : launch_halo_ks<E, 4, 1, 2>(a, s);
-        }
-        case 8: {
-            // FLAIR_DMA_RPW4=1: four waves of FOUR rows x 32 pixels x 64 couts (eight accumulators per wave, one wave per SIMD):
-            // 72 fragment reads per 144 MFMAs instead of 60 per 72
-            static const int rpw4 = getenv("FLAIR_DMA_RPW4") ? atoi(getenv("FLAIR_DMA_RPW4")) : 0;
-            return rpw4 ? launch_dma<4, 4, 2>(a, s) : launch_dma<8, 2, 2>(a, s);
-        }
-        case 9: {
-            // conv_frame_kernel for the shapes it takes (FLAIR_CONV_FRAME: 2 (default) halo ring of three + weight ring of two, 1 halo ring of
-            // two + weight ring of three, 0 conv3x3_dma_kernel<8, 1, 2>).  Same box: per-frame family 19.59 / 19.55 -> 19.03 / 18.95 (1) ->
-            // 19.03 / 19.09 (2) ms per step, step 70.89 / 70.92 -> 70.63 / 70.65 -> 70.54 / 70.57 ms.
-            static const int frame = getenv("FLAIR_CONV_FRAME") ? atoi(getenv("FLAIR_CONV_FRAME")) : 2;
-            if (frame == 1 && frame_kernel_ok(a)) return launch_frame<false>(a, s);
-            if (frame == 2 && frame_kernel_ok(a)) return launch_frame<true>(a, s);
+        // one row per wave: two rows per wave were neutral end to end (90.95 vs 90.84 ms/step) and slower per call (26.1 vs 22.9 us)
+        case 6: return launch_halo_ks<E, 8, 1, 2>(a, s);
+        // two rows per wave leave 4 waves per CU here: +3.5 ms/step
+        case 7: return launch_halo_ks<E, 4, 1, 2>(a, s);
+        case 8: return launch_dma<8, 2, 2>(a, s);
+        case 9:
+            // conv_frame_kernel for the shapes it takes (same box: per-frame family 19.59 / 19.55 ms per step on
+            // conv3x3_dma_kernel<8, 1, 2>, 19.03 / 19.09 ms on conv_frame_kernel), conv3x3_dma_kernel<8, 1, 2> for the rest
+            if (frame_kernel_ok(a)) return launch_frame(a, s);
             return launch_dma<8, 1, 2>(a, s);
-        }
-        case 10: return launch_dma<4, 1, 3>(a, s);
-        case 11: return launch_dma<8, 1, 3, 2>(a, s);
         default: return launch_halo<E, 2, 1, 1>(a, s);
     }
 }
@@ -2370,22 +2114,9 @@ extern "C" int flair_conv_nhwc(const flair_conv_params* p, const void* const* x,
     FLAIR_CHECK(!p->reflect_pad || (!p->asym_pad && a.KT == 1 && p->H > a.KH / 2 && p->W > a.KW / 2),
                 "flair_conv_nhwc: reflect_pad needs a 2-D kernel smaller than the frame");
     a.reflect = p->reflect_pad ? 1 : 0;
-    {
-        static const int swz = getenv("FLAIR_CONV_LDS_SWZ") ? atoi(getenv("FLAIR_CONV_LDS_SWZ")) : 1;
-        a.ldsSwz = swz;
-    }
     a.part = nullptr;
     a.splitK = 1;
-    {   // A/B switch: 7 selects the register-transposed (v_permlane32_swap) epilogue of the throughput halo kernel
-        static const int swapEpilogue = getenv("FLAIR_CONV_SWAP_EPILOGUE") ? atoi(getenv("FLAIR_CONV_SWAP_EPILOGUE")) : 0;
-        a.debug = swapEpilogue ? 7 : 0;
-    }
-#ifdef FLAIR_TIMING_SWITCHES
-    {
-        static const int dbg = getenv("FLAIR_CONV_DEBUG") ? atoi(getenv("FLAIR_CONV_DEBUG")) : 0;
-        a.debug = dbg;
-    }
-#endif
+
     if (workspace && workspace_bytes >= flair_conv_workspace_bytes(p) && flair_conv_workspace_bytes(p) > 0) {
         FLAIR_CHECK(((uintptr_t)workspace) % 16 == 0, "flair_conv_nhwc: workspace alignment");
         a.part = reinterpret_cast<float*>(workspace);

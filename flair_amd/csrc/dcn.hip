@@ -23,7 +23,6 @@
 // XOR-swizzled LDS rows); the activation staging is replaced by a 4-corner NHWC gather of
 // 16-byte channel chunks (one deformable group = 8 or 16 contiguous channels).
 
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -116,14 +115,17 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // pair of bilinear weights rounded to bf16 (f32 accumulation): 38 vector instructions per 8 channels instead of 52 (32 bf16 -> f32
 // unpacks + 16 v_pk_fma_f32, which issue at 1.4x the cost of a plain instruction: tools/probes/valu_rate_probe.hip).  The weights lose
 // 16 mantissa bits: |error| <= 2^-9 * sum_k |w_k v_k| <= 2^-9 max|v| per blended value, the size of the bf16 rounding the value gets
-// anyway when it is staged for the MFMA; f32 tensors keep the exact path.
+// anyway when it is staged for the MFMA.  Used by the bf16 per-frame activated forms (ACTIVATED && ONEFRAME); the other bf16 forms
+// and f32 tensors keep the exact path.
 // PFD = gather register sets in flight (2: the loads of step k+1 fly while step k is blended; 3: also step k+2 --
 // for the c = 128 tiles, where only 8 wavefronts per CU exist to hide the gather round trip; 1 (round 4, the c = 64 per-frame form): the
 // loads of a step are waited for in the same step, at 64 VGPRs, and a SECOND workgroup on the CU hides them).
 template <typename E, int NCF, int NPF, int TPP, bool ACTIVATED, bool ONEFRAME, int PFD, bool DOT2>
 __global__ __launch_bounds__(32 * NPF * TPP, (PFD == 1 ? 8 : NCF >= 4 ? 32 * NPF * TPP / 256 : 4)) void dcn_kernel(DcnArgs a) {
+    static_assert(DOT2 == (sizeof(E) == 2 && ACTIVATED && ONEFRAME), "the dot2 blend exactly for the bf16 per-frame activated forms");
     prefetch_kernargs<sizeof(DcnArgs)>();
     constexpr int NT = 32 * NPF * TPP, NW = NT / 64;
+
     constexpr int TP = 32 * NPF, TC = 32 * NCF, CPR = TPP;
     constexpr int VEC = ET<E>::VEC;
     constexpr unsigned ESZ = sizeof(E);
@@ -554,22 +556,22 @@ static int launch_dcn_v2(const DcnArgs& a0, hipStream_t stream) {
     return FLAIR_OK;
 }
 
-// FLAIR_DCN_DOT2 = 0: the f32 blend for bf16 tensors too (A/B switch; the per-frame activated form of the recurrence only)
+// The dot2 blend for the bf16 per-frame activated forms of the recurrence; the f32 blend everywhere else
 template <typename E, int NCF, int NPF, int TPP, bool ACTIVATED, bool ONEFRAME>
 static int launch_dcn_v(const DcnArgs& a, hipStream_t stream) {
     if constexpr (sizeof(E) == 2 && ACTIVATED && ONEFRAME) {
-        static const bool dot2 = !(getenv("FLAIR_DCN_DOT2") && atoi(getenv("FLAIR_DCN_DOT2")) == 0);
         if constexpr (NCF == 2 && NPF == 4) {
             // ONE gather register set (64 VGPRs instead of 106) so that TWO 16-wave workgroups share a CU (2 x 78 KB of LDS, 8 waves per SIMD): at
             // 106 VGPRs a 256^2 frame's 512 workgroups ran as two rounds of one workgroup per CU, every barrier idling the CU for the skew of
             // its 16 waves; now the other workgroup's waves fill the barrier skew and the gather round trips that the second register set hid.
-            // Alignment family 7.86 / 7.98 -> 7.03 / 7.10 ms per step, step 78.07 / 77.61 -> 77.13 / 77.00 ms (same box).  FLAIR_DCN_PFD1=0: two sets.
-            static const bool pfd1 = !(getenv("FLAIR_DCN_PFD1") && atoi(getenv("FLAIR_DCN_PFD1")) == 0);
-            if (dot2 && pfd1) return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, true, 1>(a, stream);
+            // Alignment family 7.86 / 7.98 -> 7.03 / 7.10 ms per step, step 78.07 / 77.61 -> 77.13 / 77.00 ms (same box).
+            return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, true, 1>(a, stream);
+        } else {
+            return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, true>(a, stream);
         }
-        if (dot2) return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, true>(a, stream);
+    } else {
+        return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, false>(a, stream);
     }
-    return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, false>(a, stream);
 }
 
 template <typename E, int NCF, int NPF, int TPP>
@@ -624,20 +626,18 @@ extern "C" int flair_dcn_align(const flair_dcn_params* p, const void* x0, const 
         if (p->Cout > 64) {
             // c = 128: every workgroup streams the whole 590 KB weight matrix, so the pixel tile sets the weight traffic
             // (32-pixel tiles: 512 workgroups x 590 KB = 302 MB per 128x128 frame against 151 MB of gathers).
-            // FLAIR_DCN_TILE_C128 = 64: 64-pixel tiles (8 waves, one workgroup per CU on a 128x128 frame) halve it.
-            static const int tile128 = getenv("FLAIR_DCN_TILE_C128") ? atoi(getenv("FLAIR_DCN_TILE_C128")) : 1664;
-            // 1664 (default since round 4): 64-pixel tiles with SIXTEEN threads per pixel -- one K step = 128 channels = one input half
+            // 64-pixel tiles with SIXTEEN threads per pixel (round 4) -- one K step = 128 channels = one input half
             // of one tap (18 steps instead of 36), 16 waves per workgroup, one workgroup per CU on a 128x128 frame: twice the waves
             // in flight per CU, half the barriers, half the weight traffic of the 32-pixel tiles: 43.0 -> 32.7 us per launch
-            // (tools/bench_dcn.py, same box).  32 / 64: the round-2/3 forms.
-            if (tile128 == 1664 && a.P >= 64 * 256 && (p->Cin / 2) % 128 == 0) return launch_dcn<bf16_t, 4, 2, 16>(a, stream);
-            if (tile128 >= 64 && a.P >= 64 * 256) return launch_dcn<bf16_t, 4, 2, 8>(a, stream);
+            // (tools/bench_dcn.py, same box).  Other inputs: 64-pixel tiles with 8 threads per pixel (8 waves) halve the weight
+            // traffic as well, 32-pixel tiles for small frames.
+            if (a.P >= 64 * 256 && (p->Cin / 2) % 128 == 0) return launch_dcn<bf16_t, 4, 2, 16>(a, stream);
+            if (a.P >= 64 * 256) return launch_dcn<bf16_t, 4, 2, 8>(a, stream);
             return launch_dcn<bf16_t, 4, 1, 8>(a, stream);
         }
         // 64-pixel tiles need 47 KB of LDS: 3 workgroups per CU, so a 256x256 frame (1024 tiles) runs as 768 + 256
         // (a second, one-third-full round).  128-pixel tiles (78 KB, 2 per CU, 16 wavefronts each) make it one full round.
-        static const int wide = getenv("FLAIR_DCN_TILE") ? atoi(getenv("FLAIR_DCN_TILE")) : 128;
-        return (wide >= 128 && a.P >= 128 * 512) ? launch_dcn<bf16_t, 2, 4, 8>(a, stream) : launch_dcn<bf16_t, 2, 2, 8>(a, stream);
+        return a.P >= 128 * 512 ? launch_dcn<bf16_t, 2, 4, 8>(a, stream) : launch_dcn<bf16_t, 2, 2, 8>(a, stream);
     }
     return p->Cout <= 64 ? launch_dcn<float, 2, 2, 4>(a, stream) : launch_dcn<float, 4, 1, 8>(a, stream);
 }

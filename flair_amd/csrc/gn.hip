@@ -19,7 +19,6 @@
 //                 mean/rstd/gamma/beta/(scale,shift); optionally writes the 2x2
 //                 average-pooled or nearest-upsampled result and the resampled
 //                 raw input in the same pass.
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -483,13 +482,9 @@ static int gn_blocks_per_stat(const flair_gn_params* p) {
     const int rows = 256 / cv > 0 ? 256 / cv : 1;
     const long pix = (long)p->frames_per_stat * p->H * p->W;
     long bps = (pix + (long)rows * 16 - 1) / ((long)rows * 16);
-    // cap of statistics workgroups per statistic (FLAIR_GN_PARTIAL_BLOCKS; 1024 until round 3: 512 streams as fast with half the
-    // partials for gn_finalize: whole norm 75.6 -> 73.3 us on 16x256^2x64, 44.8 -> 41.8 us on 16x128^2x128; 256: equal, 128: slower)
-    static const int cap = [] {
-        const char* e = getenv("FLAIR_GN_PARTIAL_BLOCKS");
-        const int v = e ? atoi(e) : 512;
-        return v >= 1 && v <= 4096 ? v : 512;          // an unparsable or out-of-range value keeps the default
-    }();
+    // cap of statistics workgroups per statistic (1024 until round 3: 512 streams as fast with half the partials for
+    // gn_finalize: whole norm 75.6 -> 73.3 us on 16x256^2x64, 44.8 -> 41.8 us on 16x128^2x128; 256: equal, 128: slower)
+    constexpr int cap = 512;
     if (bps > cap) bps = cap;
     if (bps < 1) bps = 1;
     return (int)bps;
@@ -539,12 +534,11 @@ extern "C" int flair_groupnorm_nhwc(const flair_gn_params* p, const void* x0, co
     s.x[0] = x0; s.x[1] = x1;
     s.c[0] = p->c0; s.c[1] = C - p->c0;
     s.ld[0] = p->ld0; s.ld[1] = p->ld1;
-    {   // small tensors: one launch, one workgroup per (statistic, group)
-        static const long fusedMax = getenv("FLAIR_GN_FUSED_MAX") ? atol(getenv("FLAIR_GN_FUSED_MAX")) : (128l << 10);
+    {   // small tensors (one group's data fits the 128 KiB of LDS): one launch, one workgroup per (statistic, group)
         const int cpg = C / p->groups;
         const int esz = p->dtype == FLAIR_BF16 ? 2 : 4;
         const long groupBytes = pix * cpg * esz;                  // one group's data
-        if (p->resample == 0 && !raw && cpg % vec == 0 && 1024 % (cpg / vec) == 0 && p->c0 % cpg == 0 && groupBytes <= fusedMax && groupBytes <= (128l << 10) &&
+        if (p->resample == 0 && !raw && cpg % vec == 0 && 1024 % (cpg / vec) == 0 && p->c0 % cpg == 0 && groupBytes <= (128l << 10) &&
             (long)nstat * p->groups >= 16) {
             GnApply a;
             a.s = s;
@@ -597,7 +591,8 @@ extern "C" int flair_groupnorm_nhwc(const flair_gn_params* p, const void* x0, co
     int bpf = (int)((outPix + (long)rows * 4 - 1) / ((long)rows * 4));
     // ~4 workgroups per CU, each streaming a long pixel range: measured on the 16x256^2x64 / 16x128^2x128 clip
     // tensors 4096 blocks 105 / 101 us, 1024 blocks 91 / 63 us for the whole norm (tools/bench_gn.py, r02)
-    static const int totalBlocks = getenv("FLAIR_GN_BLOCKS") ? atoi(getenv("FLAIR_GN_BLOCKS")) : 1024;
+    constexpr int totalBlocks = 1024;
+
     const int maxBpf = totalBlocks / p->F > 0 ? totalBlocks / p->F : 1;
     if (bpf > maxBpf) bpf = maxBpf;
     if (bpf < 1) bpf = 1;

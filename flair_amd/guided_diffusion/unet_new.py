@@ -317,19 +317,13 @@ class ResidualBlocksWithInputConv(nn.Module):
 # pair) the residual block of every trunk and conv_offset[2]+[4], and the c -> 27*G offset convolution with its
 # input halo resident in LDS.  At c = 128 (128x128 frames: 64-pixel tiles, every workgroup streams all weights)
 # the fused pair measured 24.1 us against 22.5 us for the two launches, so that level keeps the two launches.
-import os as _os
-
-USE_CHAIN = _os.environ.get("FLAIR_CHAIN", "1") != "0"          # A/B switches for same-box comparisons
-ACT_IN_OFFSET_CONV = _os.environ.get("FLAIR_DCN_ACT", "1") != "0"
-CACHE_FLOW2 = _os.environ.get("FLAIR_FLOW2_CACHE", "1") != "0"
-CHAIN_WIDTHS = (64, 128) if _os.environ.get("FLAIR_CHAIN128", "0") == "1" else (64,)   # c = 128 pairs fused too (A/B switch)
 
 
 def run_trunk(pk, segs, c, *, extra_res=None, out=None, out_scale=1.0):
     """conv3x3+LeakyReLU -> x + conv(relu(conv(x))) [+ extra_res], scaled."""
     k = (1, 3, 3)
     t1 = ops.conv(segs, pk["w0"], pk["b0"], c, k, act=A.ACT_LRELU01)
-    if USE_CHAIN and c in CHAIN_WIDTHS and ops.chain_supported(t1, c):
+    if c == 64 and ops.chain_supported(t1, c):
         return ops.conv_chain(t1, pk["w1"], pk["b1"], A.ACT_RELU, pk["w2"], pk["b2"], A.ACT_NONE, c, c,
                               res0=t1, res1=extra_res, out=out, out_scale=out_scale)
     t2 = ops.conv(t1, pk["w1"], pk["b1"], c, k, act=A.ACT_RELU)
@@ -417,7 +411,7 @@ class BasicVSRPP(nn.Module):
         # The second-order flows flow_n1 + warp(flow_prev, flow_n1) (unet_new.py:716-718) and the 4-channel flow
         # segment of conv_offset[0]'s input depend on the optical flows alone: they are composed on the first
         # denoising step of a clip and kept with the cached flows (shared by every module of this resolution).
-        store = ctx.flows.get("_prop") if (CACHE_FLOW2 and isinstance(ctx.flows, dict)) else None
+        store = ctx.flows.get("_prop") if isinstance(ctx.flows, dict) else None
         key = (name, H, W, ctx.dtype, ka)
         cached = store.get(key) if store is not None else None
         fill = [] if (cached is None and store is not None) else None
@@ -442,7 +436,7 @@ class BasicVSRPP(nn.Module):
                     if fill is not None:
                         fill.append((flow_n2, flowpad))
                 o = ops.conv([cond_n1, cur, cond_n2, flowpad], pk_a["w0"], pk_a["b0"], c, k3, act=A.ACT_LRELU01)
-                if USE_CHAIN and c in CHAIN_WIDTHS and ops.chain_supported(o, c):
+                if c == 64 and ops.chain_supported(o, c):
                     o = ops.conv_chain(o, pk_a["w2"], pk_a["b2"], A.ACT_LRELU01, pk_a["w4"], pk_a["b4"],
                                        A.ACT_LRELU01, c, c)
                 else:
@@ -450,14 +444,15 @@ class BasicVSRPP(nn.Module):
                     o = ops.conv(o, pk_a["w4"], pk_a["b4"], c, k3, act=A.ACT_LRELU01)
                 # the offset convolution applies 10*tanh / sigmoid in its epilogue (once per value, where the VALU
                 # is idle) instead of the alignment kernel re-deriving them per gathered group (it is VALU-bound)
-                act6 = A.ACT_DCN_OFFSETS if ACT_IN_OFFSET_CONV else A.ACT_NONE
-                if USE_CHAIN and c == 64 and ops.chain_supported(o, c) and W % 32 == 0:
-                    raw = ops.conv_chain(o, None, None, A.ACT_NONE, pk_a["w6"], pk_a["b6"], act6, c, 27 * G,
+                if c == 64 and ops.chain_supported(o, c) and W % 32 == 0:
+                    raw = ops.conv_chain(o, None, None, A.ACT_NONE, pk_a["w6"], pk_a["b6"], A.ACT_DCN_OFFSETS, c, 27 * G,
                                          act_param=mag, act_period=3 * G)
                 else:
-                    raw = ops.conv(o, pk_a["w6"], pk_a["b6"], 27 * G, k3, act=act6, act_param=mag, act_period=3 * G)
+                    raw = ops.conv(o, pk_a["w6"], pk_a["b6"], 27 * G, k3, act=A.ACT_DCN_OFFSETS, act_param=mag,
+                                   act_period=3 * G)
                 aligned = ops.dcn_align(prop, feat_n2, raw, flow_n1, flow_n2, pk_a["wd"], pk_a["bd"], c,
-                                        groups=G, max_mag=mag, raw_activated=ACT_IN_OFFSET_CONV)
+                                        groups=G, max_mag=mag, raw_activated=True)
+
             else:
                 aligned = zero_c
             segs = [cur] + [o_[idx:idx + 1] for o_ in others] + [aligned]

@@ -60,3 +60,16 @@ def test_bcast_entry_validates_arguments():
     lib = _lib.lib()
     rc = lib.flair_bcast_weights(None, ctypes.c_size_t(0), 0, None, None)
     assert rc == -1 and b"flair_bcast_weights" in lib.flair_last_error()
+
+
+def test_dispatch_reads_no_environment():
+    """Kernel choice depends on the arguments alone: no HIP source reads an environment variable and no model module
+    reads os.environ (FLAIR_HIP_LIB, which picks the library file in flair_amd/_lib.py, is not a dispatch switch)."""
+    import glob
+    csrc = os.path.join(ROOT, "flair_amd", "csrc")
+    hip = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "common.h")]
+    py = sorted(glob.glob(os.path.join(ROOT, "flair_amd", "guided_diffusion", "*.py")))
+    assert len(hip) > 1 and py
+    bad = [os.path.relpath(f, ROOT) for f in hip if re.search(r"\bgetenv\b", open(f).read())]
+    bad += [os.path.relpath(f, ROOT) for f in py if re.search(r"\benviron\b", open(f).read())]
+    assert not bad, bad

@@ -45,7 +45,7 @@ def _ops():
     (4, 64, 64, [64], 128, (3, 3, 3), 0, 1),
     (1, 250, 256, [64], 64, (1, 3, 3), 3, 1),       # last row of tiles hangs over the image
     (1, 125, 128, [32], 128, (1, 3, 3), 0, 0),
-    # one-round launches of 4-row tiles (the 128^2 level, c = 128): the K-split kernel / conv_frame_ks_kernel
+    # one-round launches of 4-row tiles (the 128^2 level, c = 128): the K-split kernel conv3x3_halo_ks_kernel<E, 4, 1, 2>
     (1, 128, 128, [128], 128, (1, 3, 3), 2, 1),
     (1, 128, 128, [128, 128, 128, 32], 128, (1, 3, 3), 2, 0),
     (1, 128, 128, [64], 72, (1, 3, 3), 1, 2),
@@ -185,11 +185,7 @@ def test_conv_chain(dev, dtype, case):
 
 
 def test_conv_cases_cover_every_kernel_variant():
-    """The geometries above dispatch to the 10 conv kernel variants in use (flair_conv_variant; variants 10 / 11, the 4-row
-    one-tile LDS-DMA forms, are selected with FLAIR_CONV_DMA_FRAME=2 / 3 only: the default environment is assumed here)."""
-    import os
-    if os.environ.get("FLAIR_CONV_DMA_FRAME", "1") != "1":
-        pytest.skip("FLAIR_CONV_DMA_FRAME overrides the default dispatch")
+    """The geometries above dispatch to the 10 conv kernel variants (flair_conv_variant)."""
     ops = _ops()
     geo = [(2, 16, 16, [64], 64, (1, 3, 3)), (16, 64, 64, [64], 64, (1, 3, 3)), (2, 128, 128, [64, 64], 64, (1, 3, 3)),
            (1, 64, 32, [128], 432, (1, 3, 3)), (1, 30, 32, [64, 64, 64, 32], 64, (1, 3, 3)),

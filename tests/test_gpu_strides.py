@@ -122,10 +122,7 @@ def _conv_layout(dtype, segs, cout):
 
 
 def test_conv_cases_cover_every_variant_on_strided_views():
-    """Every variant 0-9 of flair_conv_variant (default environment) runs strided in bf16; f32 reaches 0-7."""
-    import os
-    if os.environ.get("FLAIR_CONV_DMA_FRAME", "1") != "1":
-        pytest.skip("FLAIR_CONV_DMA_FRAME overrides the default dispatch")
+    """Every variant 0-9 of flair_conv_variant runs strided in bf16; f32 reaches 0-7."""
     ops = _ops()
     for dtype, col in ((BF, 1), (FP, 2)):
         seen = set()
@@ -371,54 +368,52 @@ def test_temporal_attention_strided(dev, dtype, head_dim):
 # ------------------------------------------------------------------------------------------------ DCN
 DCN_CASES = [
     # dtype, F, H, W, half (= Cin / 2), Cout, G, activated   -> instantiation <NCF, NPF, TPP, ACTIVATED, ONEFRAME>
-    (BF, 2, 64, 128, 128, 128, 16, True),     # <4,2,16,A,1F>  dcn.hip:623 (P >= 16384, half % 128 == 0)
+    (BF, 2, 64, 128, 128, 128, 16, True),     # <4,2,16,A,1F>  (P >= 16384, half % 128 == 0)
     (BF, 2, 65, 127, 128, 128, 16, True),     # <4,2,16,A,->
     (BF, 2, 64, 128, 128, 128, 16, False),    # <4,2,16,-,->  the general kernel at large P
-    (BF, 2, 64, 128, 64, 128, 8, True),       # <4,2,8,A,1F>   dcn.hip:624 (P >= 16384, half 64 < Cout)
+    (BF, 2, 64, 128, 64, 128, 8, True),       # <4,2,8,A,1F>   (P >= 16384, half 64 < Cout)
     (BF, 2, 65, 127, 64, 128, 8, True),       # <4,2,8,A,->
     (BF, 2, 64, 128, 64, 128, 16, False),     # <4,2,8,-,->
-    (BF, 1, 12, 16, 128, 128, 16, True),      # <4,1,8,A,1F>   dcn.hip:625 (P < 16384)
+    (BF, 1, 12, 16, 128, 128, 16, True),      # <4,1,8,A,1F>   (P < 16384)
     (BF, 2, 9, 23, 64, 96, 8, True),          # <4,1,8,A,->
     (BF, 2, 9, 23, 128, 128, 16, False),      # <4,1,8,-,->
-    (BF, 4, 128, 128, 64, 64, 16, True),      # <2,4,8,A,1F>   dcn.hip:631 (Cout <= 64, P >= 65536)
+    (BF, 4, 128, 128, 64, 64, 16, True),      # <2,4,8,A,1F>   (Cout <= 64, P >= 65536)
     (BF, 5, 121, 109, 64, 64, 8, True),       # <2,4,8,A,->
     (BF, 4, 128, 128, 64, 64, 16, False),     # <2,4,8,-,->
-    (BF, 1, 16, 32, 64, 64, 16, True),        # <2,2,8,A,1F>   dcn.hip:631 (P < 65536)
+    (BF, 1, 16, 32, 64, 64, 16, True),        # <2,2,8,A,1F>   (P < 65536)
     (BF, 2, 11, 13, 64, 32, 8, True),         # <2,2,8,A,->
     (BF, 2, 11, 13, 64, 64, 16, False),       # <2,2,8,-,->
-    (FP, 1, 16, 32, 64, 64, 16, True),        # <2,2,4,A,1F>   dcn.hip:633 (f32, Cout <= 64)
+    (FP, 1, 16, 32, 64, 64, 16, True),        # <2,2,4,A,1F>   (f32, Cout <= 64)
     (FP, 2, 11, 13, 32, 48, 8, True),         # <2,2,4,A,->
     (FP, 2, 11, 13, 64, 64, 16, False),       # <2,2,4,-,->
-    (FP, 1, 8, 16, 128, 128, 16, True),       # <4,1,8,A,1F>   dcn.hip:633 (f32, Cout > 64)
+    (FP, 1, 8, 16, 128, 128, 16, True),       # <4,1,8,A,1F>   (f32, Cout > 64)
     (FP, 2, 9, 23, 64, 128, 8, True),         # <4,1,8,A,->
     (FP, 2, 9, 23, 128, 128, 16, False),      # <4,1,8,-,->
 ]
 __doc__ += """
-DCN (flair_dcn_align) cases and the instantiation each selects in the default environment.  launch_dcn (dcn.hip:574-580)
-picks ACTIVATED = raw_activated and ONEFRAME = activated and H*W a multiple of the pixel tile 32 * NPF:
-    case (dtype, F, H, W, Cin/2, Cout, G, act)   instantiation <E, NCF, NPF, TPP, ACTIVATED, ONEFRAME>   selected at
-    bf16 2 64x128  128 128 G16 act              <bf16, 4, 2, 16, 1, 1>   dcn.hip:623  (Cout > 64, P >= 16384, Cin/2 % 128 == 0)
-    bf16 2 65x127  128 128 G16 act              <bf16, 4, 2, 16, 1, 0>   dcn.hip:623
-    bf16 2 64x128  128 128 G16 pre              <bf16, 4, 2, 16, 0, 0>   dcn.hip:623
-    bf16 2 64x128   64 128 G8  act              <bf16, 4, 2, 8, 1, 1>    dcn.hip:624  (Cout > 64, P >= 16384, Cin/2 = 64)
-    bf16 2 65x127   64 128 G8  act              <bf16, 4, 2, 8, 1, 0>    dcn.hip:624
-    bf16 2 64x128   64 128 G16 pre              <bf16, 4, 2, 8, 0, 0>    dcn.hip:624
-    bf16 1 12x16   128 128 G16 act              <bf16, 4, 1, 8, 1, 1>    dcn.hip:625  (Cout > 64, P < 16384)
-    bf16 2 9x23     64  96 G8  act              <bf16, 4, 1, 8, 1, 0>    dcn.hip:625
-    bf16 2 9x23    128 128 G16 pre              <bf16, 4, 1, 8, 0, 0>    dcn.hip:625
-    bf16 4 128x128  64  64 G16 act              <bf16, 2, 4, 8, 1, 1>    dcn.hip:631  (Cout <= 64, P >= 65536)
-    bf16 5 121x109  64  64 G8  act              <bf16, 2, 4, 8, 1, 0>    dcn.hip:631
-    bf16 4 128x128  64  64 G16 pre              <bf16, 2, 4, 8, 0, 0>    dcn.hip:631
-    bf16 1 16x32    64  64 G16 act              <bf16, 2, 2, 8, 1, 1>    dcn.hip:631  (Cout <= 64, P < 65536)
-    bf16 2 11x13    64  32 G8  act              <bf16, 2, 2, 8, 1, 0>    dcn.hip:631
-    bf16 2 11x13    64  64 G16 pre              <bf16, 2, 2, 8, 0, 0>    dcn.hip:631
-    f32  1 16x32    64  64 G16 act              <f32, 2, 2, 4, 1, 1>     dcn.hip:633  (Cout <= 64)
-    f32  2 11x13    32  48 G8  act              <f32, 2, 2, 4, 1, 0>     dcn.hip:633
-    f32  2 11x13    64  64 G16 pre              <f32, 2, 2, 4, 0, 0>     dcn.hip:633
-    f32  1 8x16    128 128 G16 act              <f32, 4, 1, 8, 1, 1>     dcn.hip:633  (Cout > 64)
-    f32  2 9x23     64 128 G8  act              <f32, 4, 1, 8, 1, 0>     dcn.hip:633
-    f32  2 9x23    128 128 G16 pre              <f32, 4, 1, 8, 0, 0>     dcn.hip:633
-(bf16 ACTIVATED && ONEFRAME also has the dot2 / prefetch forms of launch_dcn_v, chosen by environment switches only.)
+DCN (flair_dcn_align) cases and the instantiation each selects.  launch_dcn picks ACTIVATED = raw_activated and ONEFRAME = activated and H*W a multiple of the pixel tile 32 * NPF:
+    case (dtype, F, H, W, Cin/2, Cout, G, act)   instantiation <E, NCF, NPF, TPP, ACTIVATED, ONEFRAME>   branch condition
+    bf16 2 64x128  128 128 G16 act              <bf16, 4, 2, 16, 1, 1>   (Cout > 64, P >= 16384, Cin/2 % 128 == 0)
+    bf16 2 65x127  128 128 G16 act              <bf16, 4, 2, 16, 1, 0>
+    bf16 2 64x128  128 128 G16 pre              <bf16, 4, 2, 16, 0, 0>
+    bf16 2 64x128   64 128 G8  act              <bf16, 4, 2, 8, 1, 1>    (Cout > 64, P >= 16384, Cin/2 = 64)
+    bf16 2 65x127   64 128 G8  act              <bf16, 4, 2, 8, 1, 0>
+    bf16 2 64x128   64 128 G16 pre              <bf16, 4, 2, 8, 0, 0>
+    bf16 1 12x16   128 128 G16 act              <bf16, 4, 1, 8, 1, 1>    (Cout > 64, P < 16384)
+    bf16 2 9x23     64  96 G8  act              <bf16, 4, 1, 8, 1, 0>
+    bf16 2 9x23    128 128 G16 pre              <bf16, 4, 1, 8, 0, 0>
+    bf16 4 128x128  64  64 G16 act              <bf16, 2, 4, 8, 1, 1>    (Cout <= 64, P >= 65536)
+    bf16 5 121x109  64  64 G8  act              <bf16, 2, 4, 8, 1, 0>
+    bf16 4 128x128  64  64 G16 pre              <bf16, 2, 4, 8, 0, 0>
+    bf16 1 16x32    64  64 G16 act              <bf16, 2, 2, 8, 1, 1>    (Cout <= 64, P < 65536)
+    bf16 2 11x13    64  32 G8  act              <bf16, 2, 2, 8, 1, 0>
+    bf16 2 11x13    64  64 G16 pre              <bf16, 2, 2, 8, 0, 0>
+    f32  1 16x32    64  64 G16 act              <f32, 2, 2, 4, 1, 1>     (Cout <= 64)
+    f32  2 11x13    32  48 G8  act              <f32, 2, 2, 4, 1, 0>
+    f32  2 11x13    64  64 G16 pre              <f32, 2, 2, 4, 0, 0>
+    f32  1 8x16    128 128 G16 act              <f32, 4, 1, 8, 1, 1>     (Cout > 64)
+    f32  2 9x23     64 128 G8  act              <f32, 4, 1, 8, 1, 0>
+    f32  2 9x23    128 128 G16 pre              <f32, 4, 1, 8, 0, 0>
 The float64 reference runs on the last frame of multi-frame cases (frames are independent); (b) covers every frame."""
 
 

@@ -171,7 +171,7 @@ def main():
               f"({rows[-1]['workgroups']} workgroups)", flush=True)
     if "--json" in sys.argv:
         with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump({"kernel": "attn_mfma_bf16_kernel", "peak_TFLOP_s": PEAK_TFLOPS, "rows": rows}, f, indent=1)
+            json.dump({"kernel": "attn_mfma_bf16_v2_kernel", "peak_TFLOP_s": PEAK_TFLOPS, "rows": rows}, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
-"""The c -> 27*G offset convolution of one frame: FLAIR_CONV_RESIDENT=0|1 forms of flair_conv_chain (c = 64, 256^2) and the
-LDS-DMA conv kernel (c = 128, 128^2), hipGraph replays of 20 back-to-back launches.  python tools/bench_conv6.py"""
+"""The c -> 27*G offset convolution of one frame: flair_conv_chain (c = 64, 256^2) and the LDS-DMA conv kernel (c = 128, 128^2),
+hipGraph replays of 20 back-to-back launches.  python tools/bench_conv6.py"""
 import torch
 from flair_amd import ops
 

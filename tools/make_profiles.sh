@@ -36,8 +36,6 @@ python tools/bench_attn.py --json $OUT/attn_isolated.json > $OUT/attn_isolated.t
 python tools/bench_gn.py > $OUT/gn_isolated.txt 2>/dev/null
 python tools/bench_dcn.py > $OUT/dcn_isolated.txt 2>/dev/null
 python tools/bench_chain.py > $OUT/chain_isolated.txt 2>/dev/null
-bash tools/ab_bench.sh $OUT/ab > /dev/null 2>&1
-cat $OUT/ab/ab.log
 # rows 8f-1 / 8f-4: the CodeFormer prior alone, and the 512^2 x 10-frame step without / with it
 timeout -k 10 300 python tools/bench_codeformer.py --json $OUT/codeformer.json > $OUT/codeformer.txt 2>/dev/null
 rm -f $OUT/bench_512x10_aux.jsonl
