@@ -1,0 +1,107 @@
+"""Command line: ``python -m flair_amd restore TASK VIDEO_DIR OUTPUT_DIR [options]`` and the four demo presets.
+
+The options of the reference's ``main()`` keep their names and defaults (``scripts/video_sample.py:249-263``); the
+presets are its ``x8_bicubic_demo`` ... ``jpeg_demo`` commands (:500-556).  Several videos go through one call with
+``--output-root DIR`` (each to ``DIR/<video dir name>``); under ``torch.distributed.run`` the videos are split over the
+ranks (flair_amd.pipeline.restore_many) and rank 0 reads the checkpoints once and ships them to the others.
+"""
+import argparse
+import json
+import os
+import sys
+
+from . import pipeline as pl
+
+
+def _add_common(p):
+    p.add_argument("--weights", default="./checkpoints", metavar="DIR",
+                   help="directory with flair_<task>.pt, codeformer.pth, the detector and parsing_parsenet.pth")
+    p.add_argument("--kernels", default=pl.DEFAULT_KERNELS, metavar="PATH",
+                   help="the blur kernels .mat file (MATLAB v5) of the gaussian and jpeg tasks")
+    p.add_argument("--device", default=None, help="default: cuda (cuda:LOCAL_RANK under torch.distributed.run)")
+    p.add_argument("--size", type=int, default=512, help="frame side of the restored video")
+    p.add_argument("--steps", type=int, default=100, help="sampler steps (respacing of the diffusion)")
+    p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
+    p.add_argument("--det-model", choices=tuple(pl.DETECTOR_FILES), default="retinaface_resnet50")
+    p.add_argument("--no-prior", action="store_true", help="identity prior instead of CodeFormer (no codeformer.pth)")
+    p.add_argument("--model-kwargs", default=None, metavar="JSON", help="overrides of the task's model configuration")
+    p.add_argument("--no-graph", action="store_true", help="run the network eagerly instead of replaying hipGraphs")
+    p.add_argument("--seed", type=int, default=None, help="seed torch's generators before every video")
+
+
+def _add_hparams(p, d):
+    p.add_argument("--t-start", type=int, default=d["t_start"])
+    p.add_argument("--jpeg-qf", type=int, default=d["jpeg_qf"])
+    p.add_argument("--w", type=float, default=d["w"])
+    p.add_argument("--tau", type=int, default=d["tau"])
+    p.add_argument("--aligned", action="store_true", default=d["aligned"],
+                   help="frames are aligned 512 x 512 faces: run the prior on whole frames, no face detection")
+    p.add_argument("--rho", type=float, default=d["rho"])
+    p.add_argument("--noise-level", type=float, default=d["noise_level"])
+    p.add_argument("--zeta", type=float, default=d["zeta"])
+
+
+def make_parser():
+    ap = argparse.ArgumentParser(prog="python -m flair_amd", description="FLAIR face video restoration on MI355X")
+    sub = ap.add_subparsers(dest="command", required=True)
+    r = sub.add_parser("restore", help="restore one video (VIDEO_DIR OUTPUT_DIR) or several (VIDEO_DIR... --output-root)")
+    r.add_argument("task", choices=pl.TASK_NAMES)
+    r.add_argument("paths", nargs="+", metavar="PATH", help="VIDEO_DIR OUTPUT_DIR, or VIDEO_DIR... with --output-root")
+    r.add_argument("--output-root", default=None, metavar="DIR", help="write every VIDEO_DIR to DIR/<its name>")
+    _add_hparams(r, pl.MAIN_DEFAULTS)
+    _add_common(r)
+    for name, demo in pl.DEMOS.items():
+        d = sub.add_parser(name, help=f"{demo['task']}: {demo['video_path']} -> {demo['output_path']}")
+        _add_hparams(d, dict(pl.MAIN_DEFAULTS, **{k: v for k, v in demo.items() if k in pl.MAIN_DEFAULTS}))
+        _add_common(d)
+    return ap
+
+
+def jobs_of(args):
+    """The (video_dir, output_dir) pairs of a parsed command line."""
+    if args.command in pl.DEMOS:
+        demo = pl.DEMOS[args.command]
+        return demo["task"], [(demo["video_path"], demo["output_path"])]
+    if args.output_root is None:
+        if len(args.paths) != 2:
+            raise SystemExit("restore: give VIDEO_DIR OUTPUT_DIR, or several VIDEO_DIRs with --output-root DIR")
+        jobs = [tuple(args.paths)]
+    else:
+        jobs = [(v, os.path.join(args.output_root, os.path.basename(os.path.normpath(v)))) for v in args.paths]
+    for v, _ in jobs:
+        if not os.path.isdir(v):
+            raise SystemExit(f"restore: {v} is not a directory")
+    return args.task, jobs
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    task, jobs = jobs_of(args)
+    import torch
+    import torch.distributed as dist
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        if torch.cuda.is_available():
+            torch.cuda.set_device(local)
+        dist.init_process_group("nccl" if torch.cuda.is_available() else "gloo")
+        device = args.device or (f"cuda:{local}" if torch.cuda.is_available() else "cpu")
+    else:
+        device = args.device or "cuda"
+    try:
+        torch.set_grad_enabled(False)
+        p = pl.build_pipeline(task, args.weights, device=device, size=args.size, dtype=args.dtype, steps=args.steps,
+                              kernels_path=args.kernels, prior=not args.no_prior, det_model=args.det_model,
+                              model_kwargs=json.loads(args.model_kwargs) if args.model_kwargs else None,
+                              graph=not args.no_graph)
+        hp = dict(aligned=args.aligned, t_start=args.t_start, jpeg_qf=args.jpeg_qf, w=args.w, tau=args.tau,
+                  rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
+        pl.restore_many(jobs, lambda v, o: p.restore_video_files(v, o, **hp))
+    finally:
+        if dist.is_available() and dist.is_initialized():
+            dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

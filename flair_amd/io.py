@@ -158,17 +158,20 @@ def iter_windows(paths, device, length=video.FRAME_SLICE_LEN, overlap=video.OVER
 
 
 def restore_video_files(task, video_path, output_path, model, diffusion, restore_fn_for, *, size, device,
-                        length=video.FRAME_SLICE_LEN, overlap=video.OVERLAP, **kw):
+                        length=video.FRAME_SLICE_LEN, overlap=video.OVERLAP, aligned=True, face_helper=None, **kw):
     """``scripts/video_sample.py:334-492`` end to end: frame files in, restored ``{i:04d}.png`` out, with
     decode / upload / sampling / download / encode overlapped.  ``kw`` goes to ``video.restore_window``
-    (aux_model, vsrpp_weights_fn, hp, tau, t_start, noise_fn, q_noise_fn).  Returns the number of frames written."""
+    (aux_model, vsrpp_weights_fn, hp, tau, t_start, noise_fn, q_noise_fn).  ``aligned=False`` detects every window's
+    faces on the main thread before its first step (video.window_faces) while the reader thread decodes the next
+    window.  Returns the number of frames written."""
     paths = list_frames(video_path)
     writer = _Writer(output_path)
     prev_recon, written = None, 0
     try:
         for wi, (idx, degraded01) in enumerate(iter_windows(paths, device, length, overlap)):
             keep, prev_recon = video.restore_window(task, degraded01, model, diffusion, restore_fn_for, size=size,
-                                                    prev_recon=prev_recon, overlap=overlap, window_index=wi, **kw)
+                                                    prev_recon=prev_recon, overlap=overlap, window_index=wi, aligned=aligned,
+                                                    face_helper=face_helper, frame_indices=idx, **kw)
             writer.submit(written, keep)
             written += keep.shape[0]
     finally:

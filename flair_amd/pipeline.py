@@ -1,0 +1,292 @@
+"""A restoration task wired end to end: what ``main()`` of the reference's ``scripts/video_sample.py`` builds.
+
+``build_pipeline(task, weights_dir, device=...)`` returns a ``Pipeline`` holding the diffusion (``DIFFUSION_CONFIG``,
+:35-75, respaced ``"100"`` uniform, :266-283), the network (``MODEL_CONFIG``, :77-156, bf16 through
+``convert_to_fp16``), the task operator (``get_A_func``, :190-247) and its data-consistency step (``RESTORE_FUNC``,
+:174-199), the CodeFormer prior (:405-414, :450-452), the face-parsing weights of the bicubic tasks (:427-444) and a
+``FaceRestoreHelper`` built on a loaded RetinaFace and ParseNet (:351).  Every network reads its checkpoint from
+``weights_dir`` under the reference's file names; a missing file is an error, never a randomly initialised network.
+
+Everything per step runs on the HIP kernels the pieces already use; this module is host-side wiring only.  The
+command line (``python -m flair_amd``) is ``flair_amd.__main__``.
+"""
+import os
+import time
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from . import io as fio
+from . import ops
+from . import parallel
+from . import workload as wl
+from .guided_diffusion import gaussian_diffusion as gd
+
+TASK_NAMES = ("x8_bicubic", "x16_bicubic", "gaussian", "jpeg")
+
+# scripts/video_sample.py:35-75
+_BICUBIC_DIFFUSION = dict(diffusion_steps=2000, noise_schedule="face_bicubic", model_mean_type=gd.ModelMeanType.EPSILON,
+                          model_var_type=gd.ModelVarType.FIXED_SMALL, loss_type=gd.LossType.MSE, rescale_timesteps=False)
+_BLUR_DIFFUSION = dict(diffusion_steps=1000, noise_schedule="face_blur", model_mean_type=gd.ModelMeanType.EPSILON,
+                       model_var_type=gd.ModelVarType.LEARNED_RANGE, loss_type=gd.LossType.RESCALED_MSE,
+                       rescale_timesteps=False)
+DIFFUSION_CONFIG = {"x8_bicubic": dict(_BICUBIC_DIFFUSION), "x16_bicubic": dict(_BICUBIC_DIFFUSION),
+                    "gaussian": dict(_BLUR_DIFFUSION), "jpeg": dict(_BLUR_DIFFUSION)}
+
+# scripts/video_sample.py:77-156 (the 512 x 512 networks of the released checkpoints)
+_SR3_CONFIG = dict(image_size=512, in_channel=6, out_channel=3, inner_channel=64, norm_groups=16,
+                   channel_mults=(1, 2, 4, 8, 16), attn_res=(64, 32), vsrpp_res=(512, 256), spatial_attn=False,
+                   temporal_attn=True, res_blocks=1, dropout=0.0, dtype=torch.float16, cross_frame_module=True,
+                   use_checkpoint=True, num_frames=7, head_dim=64)
+_BLUR_CONFIG = dict(image_size=512, in_channels=6, model_channels=128, out_channels=6, num_res_blocks=2,
+                    attention_resolutions=(512 // 32, 512 // 16, 512 // 8), rnn_resolutions=(1, 2),
+                    channel_mult=(0.5, 1, 1, 2, 2, 4, 4), use_fp16=True, num_head_channels=64, resblock_updown=True,
+                    use_scale_shift_norm=True, temporal_block=True, use_checkpoint=True)
+MODEL_CONFIG = {"x8_bicubic": dict(_SR3_CONFIG), "x16_bicubic": dict(_SR3_CONFIG),
+                "gaussian": dict(_BLUR_CONFIG), "jpeg": dict(_BLUR_CONFIG)}
+
+# main()'s defaults (scripts/video_sample.py:249-263) and the four demo commands (:500-556)
+MAIN_DEFAULTS = dict(t_start=-1, jpeg_qf=-1, w=0.5, tau=5, aligned=False, rho=0.5, noise_level=12.75, zeta=-1.0)
+DEMOS = {
+    "x8-bicubic-demo": dict(task="x8_bicubic", video_path="./data/x8_bicubic", output_path="./output/x8_bicubic",
+                            w=0.85, rho=0.85, noise_level=0.0),
+    "x16-bicubic-demo": dict(task="x16_bicubic", video_path="./data/x16_bicubic", output_path="./output/x16_bicubic",
+                             w=0.7, rho=0.85, noise_level=0.0),
+    "gaussian-demo": dict(task="gaussian", video_path="./data/gaussian", output_path="./output/gaussian",
+                          w=0.75, rho=0.25, noise_level=2.55, zeta=1.0),
+    "jpeg-demo": dict(task="jpeg", video_path="./data/jpeg", output_path="./output/jpeg",
+                      w=0.5, rho=0.5, noise_level=12.75, zeta=1.0, jpeg_qf=60),
+}
+
+# checkpoint file names of the reference (CKPT_PATH, :165-171; the facelib downloads, facelib/detection/__init__.py,
+# facelib/parsing/__init__.py)
+DETECTOR_FILES = {"retinaface_resnet50": ("resnet50", "detection_Resnet50_Final.pth"),
+                  "retinaface_mobile0.25": ("mobile0.25", "detection_mobilenet0.25_Final.pth")}
+PARSER_FILE = "parsing_parsenet.pth"
+CODEFORMER_FILE = "codeformer.pth"
+DEFAULT_KERNELS = "./miscs/kernels_12.mat"
+
+
+def model_file(task):
+    return f"flair_{task}.pt"
+
+
+def _check_task(task):
+    if task not in TASK_NAMES:
+        raise ValueError(f"unknown task {task!r}: one of {', '.join(TASK_NAMES)}")
+
+
+def model_config(task, size=512):
+    """MODEL_CONFIG[task] for clips of ``size`` x ``size``: the attention / propagation resolutions scale with the size
+    as in workload.sr3_config / script_util.blur_unet_config (at 512 this is the reference's table)."""
+    _check_task(task)
+    cfg = dict(MODEL_CONFIG[task])
+    cfg["image_size"] = size
+    if "bicubic" in task:
+        cfg["attn_res"] = (size // 8, size // 16)
+        cfg["vsrpp_res"] = (size, size // 2)
+    else:
+        cfg["attention_resolutions"] = (size // 32, size // 16, size // 8)
+    return cfg
+
+
+def create_diffusion(task, steps=100):
+    """The SpacedDiffusion of main() (video_sample.py:266-283): DIFFUSION_CONFIG[task] respaced ``str(steps)``, uniform."""
+    from .guided_diffusion.respace import SpacedDiffusion, space_timesteps
+    _check_task(task)
+    cfg = dict(DIFFUSION_CONFIG[task])
+    n = cfg.pop("diffusion_steps")
+    cfg["use_timesteps"] = space_timesteps(n, str(steps), "uniform")
+    cfg["betas"] = gd.get_named_beta_schedule(cfg["noise_schedule"], n)
+    return SpacedDiffusion(**cfg)
+
+
+def load_blur_kernel(path):
+    """``kernels[0, 3]`` of the reference's ``miscs/kernels_12.mat`` (video_sample.py:231-242) as a float32 array.
+    Read with scipy.io.loadmat, which reads MATLAB v5 files (the reference's is one); a v7.3 (HDF5) file is refused
+    with a message that says so."""
+    import scipy.io
+    from scipy.io.matlab import matfile_version
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"blur kernel file {path} not found (the reference's miscs/kernels_12.mat; --kernels PATH)")
+    with open(path, "rb") as f:
+        try:
+            major, minor = matfile_version(f)
+        except Exception as exc:
+            raise ValueError(f"{path}: not a MATLAB .mat file ({exc})") from exc
+    if major == 2:
+        raise ValueError(f"{path}: a MATLAB v7.3 (HDF5) .mat file; only v5 .mat files are read (scipy.io.loadmat): "
+                         "save the kernels with MATLAB's save(..., '-v7') or scipy.io.savemat")
+    if major != 1:
+        raise ValueError(f"{path}: a MATLAB v{4 if major == 0 else major} .mat file; only v5 .mat files are read")
+    mat = scipy.io.loadmat(path)
+    if "kernels" not in mat:
+        raise ValueError(f"{path}: no 'kernels' variable")
+    return np.asarray(mat["kernels"][0, 3], dtype=np.float32)
+
+
+def _required_files(task, weights_dir, det_model, prior):
+    files = [model_file(task)]
+    if prior:
+        files.append(CODEFORMER_FILE)
+    files += [DETECTOR_FILES[det_model][1], PARSER_FILE]
+    return [os.path.join(str(weights_dir), f) for f in files]
+
+
+class Pipeline:
+    """One task's networks and operators on one device; ``restore_video_files`` runs the reference's window loop over a
+    directory of frames (flair_amd.io.restore_video_files)."""
+
+    def __init__(self, task, model, diffusion, A_func, face_helper, aux_model, vsrpp_weights_fn, size, device):
+        self.task, self.model, self.diffusion, self.A_func = task, model, diffusion, A_func
+        self.face_helper, self.aux_model, self.vsrpp_weights_fn = face_helper, aux_model, vsrpp_weights_fn
+        self.size, self.device = size, torch.device(device)
+
+    def restore_fn_for(self, jpeg_qf=-1):
+        """RESTORE_FUNC[task] bound to the window's normalised degraded frames (video_sample.py:174-199, :455-459).
+        As in the reference only the jpeg task passes ``jpeg_qf`` on (:456-457)."""
+        A = self.A_func
+        if "bicubic" in self.task:
+            def for_window(deg_n):                        # bicubic_restore: A_pinv(A(x) - d)
+                T = deg_n.shape[1]
+                d_flat = deg_n[0].contiguous().reshape(T, -1)
+                return lambda x0: A.A_pinv(ops.axpby(A.A(x0.reshape(T, -1)), d_flat, 1.0, -1.0)).reshape(x0.shape)
+            return for_window
+        from .guided_diffusion.jpeg import jpeg_decode, jpeg_encode
+        qf = jpeg_qf if self.task == "jpeg" else -1
+
+        def for_window(deg_n):                            # gaussian_restore
+            lr = deg_n[0].contiguous()
+            return lambda x0: A.A_pinv(lr, x0, jpeg_encode=(lambda im: jpeg_encode(im, qf)) if qf != -1 else None,
+                                       jpeg_decode=(lambda im: jpeg_decode(im, qf)) if qf != -1 else None)
+        return for_window
+
+    def restore_video_files(self, video_path, output_path, *, aligned=MAIN_DEFAULTS["aligned"], t_start=-1, jpeg_qf=-1,
+                            w=MAIN_DEFAULTS["w"], tau=5, rho=MAIN_DEFAULTS["rho"],
+                            noise_level=MAIN_DEFAULTS["noise_level"], zeta=MAIN_DEFAULTS["zeta"], seed=None):
+        """Frame files of ``video_path`` -> ``output_path/{i:04d}.png`` (video_sample.py:334-492).  ``seed`` seeds
+        torch's generators first (the reference does not seed).  Returns the number of frames written."""
+        if seed is not None:
+            torch.manual_seed(int(seed))
+        hp = dict(w=w, rho=rho, noise_level=noise_level, zeta=zeta)
+        return fio.restore_video_files(
+            self.task, video_path, output_path, self.model, self.diffusion, self.restore_fn_for(jpeg_qf), size=self.size,
+            device=self.device, aligned=aligned, face_helper=self.face_helper, aux_model=self.aux_model,
+            vsrpp_weights_fn=self.vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start)
+
+
+def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=100, kernels_path=None, prior=True,
+                   det_model="retinaface_resnet50", model_kwargs=None, graph=True):
+    """Build ``task``'s Pipeline from the checkpoints in ``weights_dir``: ``flair_{task}.pt``, ``codeformer.pth`` (its
+    ``params_ema``; not read when ``prior=False``, which selects the identity prior), the detector's
+    ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` and ``parsing_parsenet.pth``, all loaded
+    strictly with ``weights_only=True``.  ``model_kwargs`` overrides entries of MODEL_CONFIG[task] (checkpoints of
+    other widths).  ``kernels_path``: the reference's ``miscs/kernels_12.mat`` (gaussian and jpeg tasks).
+
+    In an initialised torch.distributed world only rank 0 reads the files; the other ranks receive its weights (the
+    flagship network in its kernel-native packed form, parallel.broadcast_packed_weights; the small networks as fp32
+    parameters, parallel.broadcast_weights)."""
+    from .checkpoint import load_reference_checkpoint
+    from .guided_diffusion.face_restoration_helper import FaceRestoreHelper
+    from .guided_diffusion.parsenet import ParseNet
+    from .guided_diffusion.retinaface import RetinaFace
+    _check_task(task)
+    if det_model not in DETECTOR_FILES:
+        raise ValueError(f"det_model={det_model!r}: one of {', '.join(DETECTOR_FILES)}")
+    if dtype not in ("bf16", "fp32"):
+        raise ValueError(f"dtype={dtype!r}: 'bf16' or 'fp32'")
+    if prior and size != 512:
+        raise ValueError(f"the CodeFormer prior restores 512 x 512 faces (its code grid is 16 x 16): size={size} needs "
+                         "prior=False")
+    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    reads = not distributed or dist.get_rank() == 0
+    files = _required_files(task, weights_dir, det_model, prior)
+    if reads:
+        for f in files:
+            if not os.path.isfile(f):
+                raise FileNotFoundError(f"checkpoint {os.path.basename(f)} not found in {weights_dir} ({f})")
+    kernel = None
+    if "bicubic" not in task:
+        kernel = load_blur_kernel(kernels_path if kernels_path is not None else DEFAULT_KERNELS)
+    device = torch.device(device)
+
+    def load(net, path):
+        if reads:
+            load_reference_checkpoint(net, path, strict=True)
+        return net
+
+    # the network (video_sample.py:285-289)
+    cfg = model_config(task, size)
+    cfg.update({k: tuple(v) if isinstance(v, list) else v for k, v in (model_kwargs or {}).items()})   # JSON lists
+    if "bicubic" in task:
+        from .guided_diffusion.sr3 import UNet as Net
+    else:
+        from .guided_diffusion.unet_new import UNetModel as Net
+    model = load(Net(**cfg), files[0]).to(device).eval()
+    if dtype == "bf16":
+        model.convert_to_fp16()
+    else:
+        model.convert_to_fp32()
+    # the face helper's networks (facelib/detection/__init__.py, facelib/parsing/__init__.py)
+    det_path, parser_path = files[-2], files[-1]
+    det = load(RetinaFace(network_name=DETECTOR_FILES[det_model][0], half=False, device="cpu"), det_path).to(device).eval()
+    det.device = device
+    parser = load(ParseNet(in_size=512, out_size=512, parsing_ch=19), parser_path).to(device).eval()
+    gan = None
+    if prior:
+        from .guided_diffusion.codeformer import CodeFormer
+        gan = CodeFormer(dim_embd=512, codebook_size=1024, n_head=8, n_layers=9,
+                         connect_list=["32", "64", "128", "256"])
+        gan = load(gan, files[1]).to(device).eval()
+    if distributed:
+        parallel.broadcast_packed_weights(model, src=0)
+        for net in (det, parser, gan):
+            if net is not None:
+                parallel.broadcast_weights(net, src=0)
+    if graph and hasattr(model, "enable_hip_graph") and device.type == "cuda":
+        model.enable_hip_graph()
+    # the task operator (get_A_func, video_sample.py:190-247)
+    if "bicubic" in task:
+        from .guided_diffusion.restore_util import SRConv
+        factor = wl.TASKS[task]["factor"]
+        A_func = SRConv(wl.bicubic_taps(factor), 3, size, device, stride=factor)
+        weights_fn = wl.parsenet_weights_fn(parser, task)
+    else:
+        from .guided_diffusion import pseudoSR as psr
+        conf = psr.Get_pseudoSR_Conf(4)
+        conf.sigmoid_range_limit = False
+        conf.input_range = np.array(None)
+        A_func = psr.pseudoSR(conf, upscale_kernel=kernel, kernel_indx=10).WrapArchitecture_PyTorch().to(device)
+        weights_fn = None
+    helper = FaceRestoreHelper(face_size=size, det_model=det_model, device=device, face_det=det, face_parse=parser)
+    aux = wl.codeformer_aux(gan) if gan is not None else wl.identity_aux
+    diffusion = create_diffusion(task, steps)
+    return Pipeline(task, model, diffusion, A_func, helper, aux, weights_fn, size, device)
+
+
+def restore_many(jobs, restore_one, *, log=print):
+    """Restore independent videos: ``jobs`` is a list of (video_dir, output_dir); rank r of an initialised
+    torch.distributed world takes ``parallel.clips_for_rank(len(jobs), r, world)`` (every video is written by exactly
+    one rank), ``restore_one(video_dir, output_dir) -> frames written``.  Rank 0 logs one summary line.
+    Returns this rank's (video_dir, frames) list."""
+    distributed = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(), dist.get_world_size()) if distributed else (0, 1)
+    outs = [os.path.abspath(str(o)) for _, o in jobs]
+    if len(set(outs)) != len(outs):
+        raise ValueError("two videos would be written to the same output directory")
+    if distributed:
+        dist.barrier()
+    t0 = time.perf_counter()
+    done = []
+    for k in parallel.clips_for_rank(len(jobs), rank, world):
+        video_dir, out_dir = jobs[k]
+        done.append((str(video_dir), int(restore_one(video_dir, out_dir))))
+    every = parallel.gather_results(done, dst=0)
+    secs = time.perf_counter() - t0
+    if rank == 0:
+        frames = sum(n for part in every for _, n in part)
+        videos = sum(len(part) for part in every)
+        log(f"restored {videos} videos, {frames} frames in {secs:.2f} s ({frames / max(secs, 1e-9):.2f} frames/s) "
+            f"on {world} process{'es' if world > 1 else ''}")
+    return done
