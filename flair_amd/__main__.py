@@ -15,7 +15,8 @@ from . import pipeline as pl
 
 def _add_common(p):
     p.add_argument("--weights", default="./checkpoints", metavar="DIR",
-                   help="directory with flair_<task>.pt, codeformer.pth, the detector and parsing_parsenet.pth")
+                   help="directory with flair_<task>.pt, the prior's checkpoint (codeformer.pth or RestoreFormer.ckpt), "
+                        "the detector and parsing_parsenet.pth")
     p.add_argument("--kernels", default=pl.DEFAULT_KERNELS, metavar="PATH",
                    help="the blur kernels .mat file (MATLAB v5) of the gaussian and jpeg tasks")
     p.add_argument("--device", default=None, help="default: cuda (cuda:LOCAL_RANK under torch.distributed.run)")
@@ -23,6 +24,10 @@ def _add_common(p):
     p.add_argument("--steps", type=int, default=100, help="sampler steps (respacing of the diffusion)")
     p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
     p.add_argument("--det-model", choices=tuple(pl.DETECTOR_FILES), default="retinaface_resnet50")
+    p.add_argument("--prior", choices=tuple(pl.PRIOR_FILES), default=None,
+                   help="auxiliary face prior (default: codeformer, reading codeformer.pth; restoreformer reads "
+                        "RestoreFormer.ckpt)")
+    p.add_argument("--prior-kwargs", default=None, metavar="JSON", help="overrides of the prior's constructor arguments")
     p.add_argument("--no-prior", action="store_true", help="identity prior instead of CodeFormer (no codeformer.pth)")
     p.add_argument("--model-kwargs", default=None, metavar="JSON", help="overrides of the task's model configuration")
     p.add_argument("--no-graph", action="store_true", help="run the network eagerly instead of replaying hipGraphs")
@@ -74,9 +79,19 @@ def jobs_of(args):
     return args.task, jobs
 
 
+def prior_of(args):
+    """The ``prior`` argument of build_pipeline for a parsed command line."""
+    if args.no_prior and args.prior is not None:
+        raise SystemExit("restore: --no-prior and --prior exclude each other")
+    if args.no_prior:
+        return False
+    return args.prior or "codeformer"
+
+
 def main(argv=None):
     args = make_parser().parse_args(argv)
     task, jobs = jobs_of(args)
+    prior = prior_of(args)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -91,9 +106,10 @@ def main(argv=None):
     try:
         torch.set_grad_enabled(False)
         p = pl.build_pipeline(task, args.weights, device=device, size=args.size, dtype=args.dtype, steps=args.steps,
-                              kernels_path=args.kernels, prior=not args.no_prior, det_model=args.det_model,
+                              kernels_path=args.kernels, prior=prior, det_model=args.det_model,
                               model_kwargs=json.loads(args.model_kwargs) if args.model_kwargs else None,
-                              graph=not args.no_graph)
+                              graph=not args.no_graph,
+                              prior_kwargs=json.loads(args.prior_kwargs) if args.prior_kwargs else None)
         hp = dict(aligned=args.aligned, t_start=args.t_start, jpeg_qf=args.jpeg_qf, w=args.w, tau=args.tau,
                   rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
         pl.restore_many(jobs, lambda v, o: p.restore_video_files(v, o, **hp))

@@ -815,6 +815,23 @@ def argmax_codebook(logits, n_codes, codebook, *, forced_idx=None, out=None):
     return out, idx
 
 
+def vq_nearest(z, codebook, *, forced_idx=None, out=None):
+    """Nearest codebook row per pixel under the f32 squared distance (RestoreFormer's VectorQuantizer): z (F,H,W,D)
+    clip tensor, codebook (N, D) f32 -> (codes (F,H,W,D) in z's dtype, idx (F*H*W,) int32).  ``forced_idx`` replaces
+    the search (tests)."""
+    F_, H, W, D = z.shape
+    N = codebook.shape[0]
+    assert codebook.dtype == torch.float32 and codebook.is_contiguous() and codebook.shape[1] == D
+    if out is None:
+        out = torch.empty((F_, H, W, D), dtype=z.dtype, device=z.device)
+    idx = torch.empty((F_ * H * W,), dtype=torch.int32, device=z.device)
+    if forced_idx is not None:
+        assert forced_idx.dtype == torch.int32 and forced_idx.is_contiguous() and forced_idx.numel() == idx.numel()
+    check(lib().flair_vq_nearest_nhwc(ptr(z), dtype_code(z), _ld(z), ctypes.c_long(F_ * H * W), D, ptr(codebook), N,
+                                      ptr(forced_idx), ptr(idx), ptr(out), _ld(out), stream()), "flair_vq_nearest_nhwc")
+    return out, idx
+
+
 def adain(content, style, *, eps=1e-5, out=None):
     F_, H, W, C = content.shape
     assert style.shape == content.shape and style.dtype == content.dtype

@@ -3,7 +3,8 @@
 ``build_pipeline(task, weights_dir, device=...)`` returns a ``Pipeline`` holding the diffusion (``DIFFUSION_CONFIG``,
 :35-75, respaced ``"100"`` uniform, :266-283), the network (``MODEL_CONFIG``, :77-156, bf16 through
 ``convert_to_fp16``), the task operator (``get_A_func``, :190-247) and its data-consistency step (``RESTORE_FUNC``,
-:174-199), the CodeFormer prior (:405-414, :450-452), the face-parsing weights of the bicubic tasks (:427-444) and a
+:174-199), the CodeFormer prior (:405-414, :450-452) or, on request, the reference's RestoreFormer prior
+(guided_diffusion/restoreformer.py), the face-parsing weights of the bicubic tasks (:427-444) and a
 ``FaceRestoreHelper`` built on a loaded RetinaFace and ParseNet (:351).  Every network reads its checkpoint from
 ``weights_dir`` under the reference's file names; a missing file is an error, never a randomly initialised network.
 
@@ -65,6 +66,9 @@ DETECTOR_FILES = {"retinaface_resnet50": ("resnet50", "detection_Resnet50_Final.
                   "retinaface_mobile0.25": ("mobile0.25", "detection_mobilenet0.25_Final.pth")}
 PARSER_FILE = "parsing_parsenet.pth"
 CODEFORMER_FILE = "codeformer.pth"
+# the auxiliary face priors build_pipeline(prior=...) offers, with their checkpoint files (RestoreFormer: the RestoreFormer
+# project's release name; guided_diffusion/restoreformer.py of the reference)
+PRIOR_FILES = {"codeformer": CODEFORMER_FILE, "restoreformer": "RestoreFormer.ckpt"}
 DEFAULT_KERNELS = "./miscs/kernels_12.mat"
 
 
@@ -126,10 +130,23 @@ def load_blur_kernel(path):
     return np.asarray(mat["kernels"][0, 3], dtype=np.float32)
 
 
+def prior_name(prior):
+    """build_pipeline's ``prior`` argument -> a key of PRIOR_FILES, or None for the identity prior: True means
+    "codeformer" and False / None the identity, as before a second prior existed."""
+    if prior is True:
+        return "codeformer"
+    if prior is False or prior is None:
+        return None
+    if isinstance(prior, str) and prior in PRIOR_FILES:
+        return prior
+    raise ValueError(f"prior={prior!r}: one of {', '.join(map(repr, PRIOR_FILES))}, True (= 'codeformer'), False or None")
+
+
 def _required_files(task, weights_dir, det_model, prior):
     files = [model_file(task)]
-    if prior:
-        files.append(CODEFORMER_FILE)
+    name = prior_name(prior)
+    if name is not None:
+        files.append(PRIOR_FILES[name])
     files += [DETECTOR_FILES[det_model][1], PARSER_FILE]
     return [os.path.join(str(weights_dir), f) for f in files]
 
@@ -177,12 +194,16 @@ class Pipeline:
 
 
 def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=100, kernels_path=None, prior=True,
-                   det_model="retinaface_resnet50", model_kwargs=None, graph=True):
-    """Build ``task``'s Pipeline from the checkpoints in ``weights_dir``: ``flair_{task}.pt``, ``codeformer.pth`` (its
-    ``params_ema``; not read when ``prior=False``, which selects the identity prior), the detector's
-    ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` and ``parsing_parsenet.pth``, all loaded
-    strictly with ``weights_only=True``.  ``model_kwargs`` overrides entries of MODEL_CONFIG[task] (checkpoints of
-    other widths).  ``kernels_path``: the reference's ``miscs/kernels_12.mat`` (gaussian and jpeg tasks).
+                   det_model="retinaface_resnet50", model_kwargs=None, graph=True, prior_kwargs=None):
+    """Build ``task``'s Pipeline from the checkpoints in ``weights_dir``: ``flair_{task}.pt``, the prior's checkpoint,
+    the detector's ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` and ``parsing_parsenet.pth``,
+    all loaded strictly with ``weights_only=True``.  ``model_kwargs`` overrides entries of MODEL_CONFIG[task]
+    (checkpoints of other widths).  ``kernels_path``: the reference's ``miscs/kernels_12.mat`` (gaussian and jpeg tasks).
+
+    ``prior``: ``"codeformer"`` (or True, the default) reads ``codeformer.pth`` (its ``params_ema``);
+    ``"restoreformer"`` reads ``RestoreFormer.ckpt`` (a plain state dict, or a training checkpoint whose ``state_dict``
+    holds the network under ``vqvae.``); False / None selects the identity prior and reads neither.  ``prior_kwargs``
+    overrides the prior's constructor arguments (RestoreFormer's ``head_size`` is not recorded in a checkpoint).
 
     In an initialised torch.distributed world only rank 0 reads the files; the other ranks receive its weights (the
     flagship network in its kernel-native packed form, parallel.broadcast_packed_weights; the small networks as fp32
@@ -196,8 +217,10 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         raise ValueError(f"det_model={det_model!r}: one of {', '.join(DETECTOR_FILES)}")
     if dtype not in ("bf16", "fp32"):
         raise ValueError(f"dtype={dtype!r}: 'bf16' or 'fp32'")
-    if prior and size != 512:
-        raise ValueError(f"the CodeFormer prior restores 512 x 512 faces (its code grid is 16 x 16): size={size} needs "
+    prior = prior_name(prior)
+    if prior is not None and size != 512:
+        label = {"codeformer": "CodeFormer", "restoreformer": "RestoreFormer"}[prior]
+        raise ValueError(f"the {label} prior restores 512 x 512 faces (its code grid is 16 x 16): size={size} needs "
                          "prior=False")
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     reads = not distributed or dist.get_rank() == 0
@@ -234,11 +257,15 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     det.device = device
     parser = load(ParseNet(in_size=512, out_size=512, parsing_ch=19), parser_path).to(device).eval()
     gan = None
-    if prior:
+    pkw = {k: tuple(v) if isinstance(v, list) else v for k, v in (prior_kwargs or {}).items()}   # JSON lists
+    if prior == "codeformer":
         from .guided_diffusion.codeformer import CodeFormer
-        gan = CodeFormer(dim_embd=512, codebook_size=1024, n_head=8, n_layers=9,
-                         connect_list=["32", "64", "128", "256"])
+        gan = CodeFormer(**dict(dict(dim_embd=512, codebook_size=1024, n_head=8, n_layers=9,
+                                     connect_list=["32", "64", "128", "256"]), **pkw))
         gan = load(gan, files[1]).to(device).eval()
+    elif prior == "restoreformer":
+        from .guided_diffusion.restoreformer import VQVAEGANMultiHeadTransformer
+        gan = load(VQVAEGANMultiHeadTransformer(**pkw), files[1]).to(device).eval()
     if distributed:
         parallel.broadcast_packed_weights(model, src=0)
         for net in (det, parser, gan):
@@ -260,7 +287,11 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         A_func = psr.pseudoSR(conf, upscale_kernel=kernel, kernel_indx=10).WrapArchitecture_PyTorch().to(device)
         weights_fn = None
     helper = FaceRestoreHelper(face_size=size, det_model=det_model, device=device, face_det=det, face_parse=parser)
-    aux = wl.codeformer_aux(gan) if gan is not None else wl.identity_aux
+    aux = wl.identity_aux
+    if prior == "codeformer":
+        aux = wl.codeformer_aux(gan)
+    elif prior == "restoreformer":
+        aux = wl.restoreformer_aux(gan)
     diffusion = create_diffusion(task, steps)
     return Pipeline(task, model, diffusion, A_func, helper, aux, weights_fn, size, device)
 

@@ -77,6 +77,12 @@ def codeformer_aux(gan):
     return aux_model
 
 
+def restoreformer_aux(net):
+    """``aux_model`` around a RestoreFormer prior (guided_diffusion/restoreformer.py): its reconstruction ``dec`` of the
+    aligned 512x512 faces of pred_xstart."""
+    return lambda x0, *a, **k: net(x0)[0]
+
+
 # ------------------------------------------------------------------ bicubic tasks (sr3.UNet)
 def sr3_config(image_size, use_fp16=True):
     """MODEL_CONFIG['x8_bicubic'] of scripts/video_sample.py:78-96 at clip side `image_size`

@@ -60,7 +60,7 @@ typedef enum {
 const char* flair_last_error(void);
 /* ABI version of this header: bumped whenever entry points are added or a struct changes
  * (3: round 2; 4: + face crop / paste entries, flair_bcast_weights; 5: round 4 entries; 6: + calibration launches;
- * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc).
+ * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc; 9: + flair_vq_nearest_nhwc).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -426,6 +426,13 @@ int flair_attention_wide(const flair_attn_params* p, const void* qkv, void* out,
  * y[row][0..D) = codebook[idx[row]] (VectorQuantizer.get_codebook_feat, :82-94).  codebook: [N][D] f32.
  * forced_idx (or NULL): use these indices instead of the arg-max (tests).  idx may be NULL. */
 int flair_argmax_codebook(const void* logits, int dtype, int ld, long rows, int N, const float* codebook, int D,
+                          const int* forced_idx, int* idx, void* y, int y_ld, hipStream_t stream);
+/* Nearest codebook row of every token (VectorQuantizer.forward of RestoreFormer, restoreformer.py:43-62): idx[row] =
+ * argmin_n |z|^2 + |e_n|^2 - 2 z.e_n over the f32 distances (first index on ties, as torch.min), z = the D channels of
+ * row `row` of an NHWC tensor (stride ld, dtype F32 / BF16, read as f32), and y[row][0..D) = codebook[idx[row]] in
+ * that dtype.  codebook: [N][D] f32, 16-byte aligned; D a multiple of 4, <= 1024.  forced_idx (or NULL): use these
+ * indices instead of the search (tests; z may then be NULL).  idx may be NULL. */
+int flair_vq_nearest_nhwc(const void* z, int dtype, int ld, long rows, int D, const float* codebook, int N,
                           const int* forced_idx, int* idx, void* y, int y_ld, hipStream_t stream);
 /* adaptive_instance_normalization(content, style) of codeformer.py:437-470 on [frames][HW][C] tensors:
  * per (frame, channel) mean and sqrt(unbiased variance + eps) of both, y = (content - mc) / sc * ss + ms. */
