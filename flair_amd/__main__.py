@@ -15,7 +15,7 @@ from . import pipeline as pl
 
 def _add_common(p):
     p.add_argument("--weights", default="./checkpoints", metavar="DIR",
-                   help="directory with flair_<task>.pt, the prior's checkpoint (codeformer.pth or RestoreFormer.ckpt), "
+                   help="directory with flair_<task>.pt, the prior's checkpoint (codeformer.pth, RestoreFormer.ckpt or VQFR_v2.pth), "
                         "the detector and parsing_parsenet.pth")
     p.add_argument("--kernels", default=pl.DEFAULT_KERNELS, metavar="PATH",
                    help="the blur kernels .mat file (MATLAB v5) of the gaussian and jpeg tasks")
@@ -26,7 +26,7 @@ def _add_common(p):
     p.add_argument("--det-model", choices=tuple(pl.DETECTOR_FILES), default="retinaface_resnet50")
     p.add_argument("--prior", choices=tuple(pl.PRIOR_FILES), default=None,
                    help="auxiliary face prior (default: codeformer, reading codeformer.pth; restoreformer reads "
-                        "RestoreFormer.ckpt)")
+                        "RestoreFormer.ckpt, vqfrv2 VQFR_v2.pth)")
     p.add_argument("--prior-kwargs", default=None, metavar="JSON", help="overrides of the prior's constructor arguments")
     p.add_argument("--no-prior", action="store_true", help="identity prior instead of CodeFormer (no codeformer.pth)")
     p.add_argument("--model-kwargs", default=None, metavar="JSON", help="overrides of the task's model configuration")

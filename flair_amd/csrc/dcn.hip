@@ -17,6 +17,9 @@
 //          single 96-byte run (bf16) and consecutive taps share cache lines
 //   dy,dx(g,k) = M*tanh(raw..) + flow_g.{y,x};  flow_g = flow1 (g < G/2) else flow2
 //   m(g,k)     = sigmoid(raw..)
+//   (OFFS, the host's raw_activated: 0 as above; 1 the producing convolution already applied M*tanh / sigmoid;
+//   2 VQFR's DCNv2Pack (vqfr.py:341-380): dy,dx = raw.. as they are, m = sigmoid(raw..), flows null and
+//   x0 / x1 the two channel halves of one input)
 //   Y[p][co]   = bias[co] + sum_{k,ci} Wt[co][k][ci] * m(g(ci),k) * bilinear(X[ci], p + pk + d(g(ci),k))
 //
 // Same MFMA operand roles as conv.hip (weights = A operand, gathered pixels = B operand,
@@ -40,7 +43,7 @@ struct DcnArgs {
     void* y; int yLd;
     int F, H, W, Cout, G;
     float maxMag;
-    int activated;       // raw holds finished residues / masks (FLAIR_ACT_DCN_OFFSETS upstream)
+    int activated;       // 1: raw holds finished residues / masks (FLAIR_ACT_DCN_OFFSETS upstream); 2: raw offsets
     long P;
     unsigned xBytes[2], rawBytes, wBytes;
 };
@@ -120,9 +123,10 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // PFD = gather register sets in flight (2: the loads of step k+1 fly while step k is blended; 3: also step k+2 --
 // for the c = 128 tiles, where only 8 wavefronts per CU exist to hide the gather round trip; 1 (round 4, the c = 64 per-frame form): the
 // loads of a step are waited for in the same step, at 64 VGPRs, and a SECOND workgroup on the CU hides them).
-template <typename E, int NCF, int NPF, int TPP, bool ACTIVATED, bool ONEFRAME, int PFD, bool DOT2>
+template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME, int PFD, bool DOT2>
 __global__ __launch_bounds__(32 * NPF * TPP, (PFD == 1 ? 8 : NCF >= 4 ? 32 * NPF * TPP / 256 : 4)) void dcn_kernel(DcnArgs a) {
-    static_assert(DOT2 == (sizeof(E) == 2 && ACTIVATED && ONEFRAME), "the dot2 blend exactly for the bf16 per-frame activated forms");
+    static_assert(DOT2 == (sizeof(E) == 2 && OFFS == 1 && ONEFRAME), "the dot2 blend exactly for the bf16 per-frame activated forms");
+    static_assert(OFFS != 2 || !ONEFRAME, "raw offsets: the general (batched) form only");
     prefetch_kernargs<sizeof(DcnArgs)>();
     constexpr int NT = 32 * NPF * TPP, NW = NT / 64;
 
@@ -143,8 +147,11 @@ __global__ __launch_bounds__(32 * NPF * TPP, (PFD == 1 ? 8 : NCF >= 4 ? 32 * NPF
     constexpr int BUF = (TC + TP) * CPR * 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int G = a.G;
-    const int slabPieces = 3 * G * (int)ESZ / 16;
-    const int rawPitch = 3 * G * (int)ESZ + 16;               // +16 B: spreads pixels over banks
+    // OFFS == 2 also takes G = 4, whose bf16 slab of 24 bytes is fetched as two 16-byte pieces (the next tap's first values,
+    // or the row padding that the host requires, ride along) and staged in 16-byte granular LDS rows
+    const int slabBytes = OFFS == 2 ? (3 * G * (int)ESZ + 15) & ~15 : 3 * G * (int)ESZ;
+    const int slabPieces = slabBytes / 16;
+    const int rawPitch = slabBytes + 16;                      // +16 B: spreads pixels over banks
     char* sraw = smem;
     char* stile = smem + 2 * TP * rawPitch;
 
@@ -236,12 +243,16 @@ __global__ __launch_bounds__(32 * NPF * TPP, (PFD == 1 ? 8 : NCF >= 4 ? 32 * NPF
         // block-uniform `second` below
         const bool second = cb * BKE >= halfC;                // block-uniform (halfC % BKE == 0)
         const float2 fl = second ? fl2 : fl1;
-        // ACTIVATED (compile time): the residues and the mask are used as stored, no transcendental per group
+        // OFFS == 1 (compile time): the residues and the mask are used as stored, no transcendental per group
         float sy = phm1 + (float)ikh + fl.y, sx = pwm1 + (float)ikw + fl.x, mk;
-        if constexpr (ACTIVATED) {
+        if constexpr (OFFS == 1) {
             sy += ry;
             sx += rx;
             mk = rm;
+        } else if constexpr (OFFS == 2) {
+            sy += ry;
+            sx += rx;
+            mk = __builtin_amdgcn_rcpf(1.f + __expf(-rm));
         } else {
             sy += a.maxMag * fast_tanh(ry);
             sx += a.maxMag * fast_tanh(rx);
@@ -534,7 +545,7 @@ __global__ __launch_bounds__(32 * NPF * TPP, (PFD == 1 ? 8 : NCF >= 4 ? 32 * NPF
 
 }  // namespace
 
-template <typename E, int NCF, int NPF, int TPP, bool ACTIVATED, bool ONEFRAME, bool DOT2, int PFDSEL = 0>
+template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME, bool DOT2, int PFDSEL = 0>
 static int launch_dcn_v2(const DcnArgs& a0, hipStream_t stream) {
     constexpr int PFD = PFDSEL > 0 ? PFDSEL : NCF >= 4 && TPP <= 8 ? 3 : 2;
     DcnArgs a = a0;
@@ -544,33 +555,33 @@ static int launch_dcn_v2(const DcnArgs& a0, hipStream_t stream) {
         a.xBytes[1] = (unsigned)(((hw - 1) * a.xLd[1] + half) * sizeof(E));
     }
     constexpr int NT = 32 * NPF * TPP, TP = 32 * NPF, TC = 32 * NCF;
-    const int rawPitch = 3 * a.G * (int)sizeof(E) + 16;
+    const int rawPitch = (OFFS == 2 ? (3 * a.G * (int)sizeof(E) + 15) & ~15 : 3 * a.G * (int)sizeof(E)) + 16;
     const size_t lds = (size_t)2 * TP * rawPitch + 2 * (TC + TP) * TPP * 16;
     static LdsAttrOnce attr;
     {
-        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&dcn_kernel<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, PFD, DOT2>));
+        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&dcn_kernel<E, NCF, NPF, TPP, OFFS, ONEFRAME, PFD, DOT2>));
         FLAIR_CHECK(e == hipSuccess, "flair_dcn_align: hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL((dcn_kernel<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, PFD, DOT2>), dim3(cdiv(a.P, TP)), dim3(NT), lds, stream, a);
+    hipLaunchKernelGGL((dcn_kernel<E, NCF, NPF, TPP, OFFS, ONEFRAME, PFD, DOT2>), dim3(cdiv(a.P, TP)), dim3(NT), lds, stream, a);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
 
 // The dot2 blend for the bf16 per-frame activated forms of the recurrence; the f32 blend everywhere else
-template <typename E, int NCF, int NPF, int TPP, bool ACTIVATED, bool ONEFRAME>
+template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME>
 static int launch_dcn_v(const DcnArgs& a, hipStream_t stream) {
-    if constexpr (sizeof(E) == 2 && ACTIVATED && ONEFRAME) {
+    if constexpr (sizeof(E) == 2 && OFFS == 1 && ONEFRAME) {
         if constexpr (NCF == 2 && NPF == 4) {
             // ONE gather register set (64 VGPRs instead of 106) so that TWO 16-wave workgroups share a CU (2 x 78 KB of LDS, 8 waves per SIMD): at
             // 106 VGPRs a 256^2 frame's 512 workgroups ran as two rounds of one workgroup per CU, every barrier idling the CU for the skew of
             // its 16 waves; now the other workgroup's waves fill the barrier skew and the gather round trips that the second register set hid.
             // Alignment family 7.86 / 7.98 -> 7.03 / 7.10 ms per step, step 78.07 / 77.61 -> 77.13 / 77.00 ms (same box).
-            return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, true, 1>(a, stream);
+            return launch_dcn_v2<E, NCF, NPF, TPP, OFFS, ONEFRAME, true, 1>(a, stream);
         } else {
-            return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, true>(a, stream);
+            return launch_dcn_v2<E, NCF, NPF, TPP, OFFS, ONEFRAME, true>(a, stream);
         }
     } else {
-        return launch_dcn_v2<E, NCF, NPF, TPP, ACTIVATED, ONEFRAME, false>(a, stream);
+        return launch_dcn_v2<E, NCF, NPF, TPP, OFFS, ONEFRAME, false>(a, stream);
     }
 }
 
@@ -578,9 +589,57 @@ template <typename E, int NCF, int NPF, int TPP>
 static int launch_dcn(const DcnArgs& a, hipStream_t stream) {
     // the recurrence calls per frame with activated offsets; everything else takes the general kernel
     const bool oneframe = ((long)a.H * a.W) % (32 * NPF) == 0;
-    if (a.activated && oneframe) return launch_dcn_v<E, NCF, NPF, TPP, true, true>(a, stream);
-    if (a.activated) return launch_dcn_v<E, NCF, NPF, TPP, true, false>(a, stream);
-    return launch_dcn_v<E, NCF, NPF, TPP, false, false>(a, stream);
+    if (a.activated && oneframe) return launch_dcn_v<E, NCF, NPF, TPP, 1, true>(a, stream);
+    if (a.activated) return launch_dcn_v<E, NCF, NPF, TPP, 1, false>(a, stream);
+    return launch_dcn_v<E, NCF, NPF, TPP, 0, false>(a, stream);
+}
+
+// ---- raw_activated = 2: VQFR's DCNv2Pack (TextureWarpingModule, vqfr.py:341-427) on faces batched as frames, c = 64 .. 512.
+// Separate instantiations (OFFS = 2, general form), so the forms above keep their code.  A workgroup covers all the
+// couts of its tile (TC = 64 or 128); wider outputs are computed as cout slices of TC by separate launches over the same
+// gathers (c >= 256 only occurs at 64^2 and below, where the gathers are cheap).
+struct VqfrTile {
+    int bke, tc;        // K elements per step, couts per launch
+};
+
+static VqfrTile vqfr_tile(const flair_dcn_params* p) {
+    if (p->dtype == FLAIR_BF16) {
+        if ((p->Cin / 2) % 64 != 0) return {32, 64};                  // c = 64 (512^2): four threads per pixel, 32-channel K steps
+        if (p->Cout <= 64) return {64, 64};
+        const long P = (long)p->F * p->H * p->W;
+        return {P >= 64 * 256 && (p->Cin / 2) % 128 == 0 ? 128 : 64, 128};
+    }
+    return p->Cout <= 64 ? VqfrTile{16, 64} : VqfrTile{32, 128};
+}
+
+template <typename E>
+static int launch_dcn_vqfr(const flair_dcn_params* p, const DcnArgs& a, hipStream_t stream) {
+    if constexpr (sizeof(E) == 2) {
+        if ((a.Cin / 2) % 64 != 0) return launch_dcn_v<E, 2, 4, 4, 2, false>(a, stream);
+        if (a.Cout <= 64) return a.P >= 128 * 512 ? launch_dcn_v<E, 2, 4, 8, 2, false>(a, stream) : launch_dcn_v<E, 2, 2, 8, 2, false>(a, stream);
+        if (a.P >= 64 * 256 && (a.Cin / 2) % 128 == 0) return launch_dcn_v<E, 4, 2, 16, 2, false>(a, stream);
+        if (a.P >= 64 * 256) return launch_dcn_v<E, 4, 2, 8, 2, false>(a, stream);
+        return launch_dcn_v<E, 4, 1, 8, 2, false>(a, stream);
+    } else {
+        (void)p;
+        return a.Cout <= 64 ? launch_dcn_v<E, 2, 2, 4, 2, false>(a, stream) : launch_dcn_v<E, 4, 1, 8, 2, false>(a, stream);
+    }
+}
+
+static int dcn_vqfr(const flair_dcn_params* p, const DcnArgs& a0, hipStream_t stream) {
+    const VqfrTile t = vqfr_tile(p);
+    const int esz = p->dtype == FLAIR_BF16 ? 2 : 4;
+    for (int co0 = 0; co0 < p->Cout; co0 += t.tc) {
+        DcnArgs a = a0;
+        a.Cout = p->Cout - co0 < t.tc ? p->Cout - co0 : t.tc;
+        a.w = static_cast<const char*>(a0.w) + (size_t)co0 * 9 * p->Cin * esz;
+        a.bias = a0.bias ? a0.bias + co0 : nullptr;
+        a.y = static_cast<char*>(a0.y) + (size_t)co0 * esz;
+        a.wBytes = (unsigned)((unsigned long long)a.Cout * 9 * p->Cin * esz);
+        const int rc = p->dtype == FLAIR_BF16 ? launch_dcn_vqfr<bf16_t>(p, a, stream) : launch_dcn_vqfr<float>(p, a, stream);
+        if (rc != FLAIR_OK) return rc;
+    }
+    return FLAIR_OK;
 }
 
 extern "C" int flair_dcn_align(const flair_dcn_params* p, const void* x0, const void* x1, const void* raw,
@@ -588,15 +647,21 @@ extern "C" int flair_dcn_align(const flair_dcn_params* p, const void* x0, const 
                                hipStream_t stream) {
     FLAIR_CHECK(p && x0 && x1 && raw && w && y, "flair_dcn_align: null argument");
     FLAIR_CHECK(p->dtype == FLAIR_F32 || p->dtype == FLAIR_BF16, "flair_dcn_align: bad dtype");
+    FLAIR_CHECK(p->raw_activated >= 0 && p->raw_activated <= 2, "flair_dcn_align: raw_activated = %d (0, 1 or 2)", p->raw_activated);
+    const bool vqfr = p->raw_activated == 2;
+    FLAIR_CHECK(!vqfr || (!flow1 && !flow2), "flair_dcn_align: raw_activated = 2 takes no flows");
     const int vec = p->dtype == FLAIR_BF16 ? 8 : 4;
-    const int bke = vec * (p->Cout <= 64 && p->dtype != FLAIR_BF16 ? 4 : 8);      // K elements per step of the chosen tile
+    // K elements per step of the chosen tile
+    const int bke = vqfr ? vqfr_tile(p).bke : vec * (p->Cout <= 64 && p->dtype != FLAIR_BF16 ? 4 : 8);
     const int esz = p->dtype == FLAIR_BF16 ? 2 : 4;
     const int cpg = p->G > 0 ? p->Cin / p->G : 0;
-    FLAIR_CHECK(p->G > 0 && p->G % 8 == 0 && p->G <= 16 && p->Cin % p->G == 0 && cpg % vec == 0 &&
-                    (cpg & (cpg - 1)) == 0 && (p->Cin / 2) % bke == 0,
+    FLAIR_CHECK(p->G > 0 && (p->G % 8 == 0 || (vqfr && p->G == 4)) && p->G <= 16 && p->Cin % p->G == 0 && cpg % vec == 0 &&
+                    (cpg & (cpg - 1)) == 0 && (p->Cin / 2) % bke == 0 && (!vqfr || p->Cin <= 1024),
                 "flair_dcn_align: Cin=%d G=%d not supported", p->Cin, p->G);
-    FLAIR_CHECK(p->Cout % 4 == 0 && p->Cout <= 128 && p->raw_ld >= 27 * p->G && (p->raw_ld * esz) % 16 == 0,
-                "flair_dcn_align: Cout (<=128) / raw_ld");
+    FLAIR_CHECK(p->Cout > 0 && p->Cout % 4 == 0 && (vqfr ? p->Cout <= 1024 : p->Cout <= 128) && p->raw_ld >= 27 * p->G &&
+                    (p->raw_ld * esz) % 16 == 0,
+                "flair_dcn_align: Cout = %d (a multiple of 4, <= 128; <= 1024 with raw_activated = 2) / raw_ld = %d (>= 27 G, "
+                "16-byte granular)", p->Cout, p->raw_ld);
     FLAIR_CHECK(p->x_ld[0] >= p->Cin / 2 && p->x_ld[1] >= p->Cin / 2 && (p->x_ld[0] * esz) % 16 == 0 &&
                     (p->x_ld[1] * esz) % 16 == 0 && ((uintptr_t)x0) % 16 == 0 && ((uintptr_t)x1) % 16 == 0 &&
                     ((uintptr_t)raw) % 16 == 0 && p->y_ld >= p->Cout,
@@ -619,6 +684,7 @@ extern "C" int flair_dcn_align(const flair_dcn_params* p, const void* x0, const 
                 "flair_dcn_align: F*H*W = %ld pixels (limit 2^23 per call: call per frame)", a.P);
     a.xBytes[0] = (unsigned)b0; a.xBytes[1] = (unsigned)b1; a.rawBytes = (unsigned)((br + 15) / 16 * 16);
     a.wBytes = (unsigned)((unsigned long long)p->Cout * 9 * p->Cin * esz);
+    if (vqfr) return dcn_vqfr(p, a, stream);
     // Tile choice (measured on per-frame 256^2 / 128^2 calls, profiles/README.md).  c=64: 64 pixels x 64
     // couts with 8 threads per pixel, so one gather instruction fetches the whole 128-byte channel row of a
     // corner (two waves share each MFMA pair, K split); c=128: 32 pixels x 128 couts, 8 threads per pixel.

@@ -252,6 +252,39 @@ __global__ void nearest2x_kernel(const E* x, int xLd, long F, int Hi, int Wi, in
     }
 }
 
+// bilinear, align_corners=False, of feature maps (VQFR's TextureWarpingModule: inpfeat down by 2^i, the offsets up by 2,
+// vqfr.py:409-414, :470-475): resize_kernel's arithmetic on 16-byte channel chunks.  One thread computes one chunk of one
+// output pixel from four chunk loads (resize_kernel: one channel from four scalar loads).
+template <typename E>
+__global__ void bilinear_vec_kernel(const E* x, int xLd, long F, int Hi, int Wi, int C, int Ho, int Wo, E* y, int yLd) {
+    constexpr int VEC = ET<E>::VEC;
+    const int cv = C / VEC;
+    const long total = F * Ho * Wo * cv;
+    const float sx = (float)Wi / (float)Wo, sy = (float)Hi / (float)Ho;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % cv) * VEC;
+        const long p = i / cv;
+        const int wo = (int)(p % Wo);
+        const int ho = (int)((p / Wo) % Ho);
+        const long f = p / ((long)Wo * Ho);
+        const E* fb = x + f * Hi * Wi * xLd + c;
+        const float rx = fmaxf(sx * ((float)wo + 0.5f) - 0.5f, 0.f);
+        const float ry = fmaxf(sy * ((float)ho + 0.5f) - 0.5f, 0.f);
+        const int x0 = (int)rx, y0 = (int)ry;
+        const int x1 = x0 + (x0 < Wi - 1 ? 1 : 0), y1 = y0 + (y0 < Hi - 1 ? 1 : 0);
+        const float ax = rx - (float)x0, ay = ry - (float)y0;
+        float v00[VEC], v01[VEC], v10[VEC], v11[VEC], r[VEC];
+        Vec16<E>::load(fb + ((long)y0 * Wi + x0) * xLd, v00);
+        Vec16<E>::load(fb + ((long)y0 * Wi + x1) * xLd, v01);
+        Vec16<E>::load(fb + ((long)y1 * Wi + x0) * xLd, v10);
+        Vec16<E>::load(fb + ((long)y1 * Wi + x1) * xLd, v11);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+            r[e] = (1.f - ay) * ((1.f - ax) * v00[e] + ax * v01[e]) + ay * ((1.f - ax) * v10[e] + ax * v11[e]);
+        Vec16<E>::store(y + p * yLd + c, r);
+    }
+}
+
 // mode: 0 bilinear align_corners=False, 1 bilinear align_corners=True, 2 bicubic
 // (align_corners=False, A=-0.75, border-clamped taps), 3 2x2 average pool, 4 nearest.
 template <typename E>
@@ -375,6 +408,19 @@ extern "C" int flair_resize_nhwc(const void* x, int dtype, int x_ld, int F, int 
             else
                 hipLaunchKernelGGL(nearest2x_kernel<float>, dim3(grid_for(n / vec)), dim3(256), 0, stream, (const float*)x,
                                    x_ld, (long)F, Hi, Wi, C, (float*)y, y_ld);
+            FLAIR_LAUNCH_CHECK();
+            return FLAIR_OK;
+        }
+        // feature maps (16 channels and more: images and flows keep the scalar kernel)
+        if (mode == 0 && C >= 16 && C % vec == 0 && x_ld % vec == 0 && y_ld % vec == 0 && scale_c0 == 1.f && scale_c1 == 1.f &&
+            ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 &&
+            (dtype == FLAIR_BF16 || dtype == FLAIR_F32)) {
+            if (dtype == FLAIR_BF16)
+                hipLaunchKernelGGL(bilinear_vec_kernel<bf16_t>, dim3(grid_for(n / vec)), dim3(256), 0, stream, (const bf16_t*)x,
+                                   x_ld, (long)F, Hi, Wi, C, Ho, Wo, (bf16_t*)y, y_ld);
+            else
+                hipLaunchKernelGGL(bilinear_vec_kernel<float>, dim3(grid_for(n / vec)), dim3(256), 0, stream, (const float*)x,
+                                   x_ld, (long)F, Hi, Wi, C, Ho, Wo, (float*)y, y_ld);
             FLAIR_LAUNCH_CHECK();
             return FLAIR_OK;
         }

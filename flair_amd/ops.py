@@ -495,7 +495,9 @@ def dcn_raw_permutation(groups):
 
 def dcn_align(x0, x1, raw, flow1, flow2, weight, bias, cout, *, groups=16, max_mag=10.0, out=None, raw_activated=False):
     """raw: conv_offset output in TAP-MAJOR channel order (see dcn_raw_permutation); raw_activated: the producing
-    convolution already applied ACT_DCN_OFFSETS (max_mag * tanh on the residues, sigmoid on the masks)."""
+    convolution already applied ACT_DCN_OFFSETS (max_mag * tanh on the residues, sigmoid on the masks); 2: VQFR's
+    DCNv2Pack (offsets as they are, sigmoid on the masks; no flows, x0 | x1 the channel halves of one input:
+    see dcn_pack)."""
     F_, H, W, ch = x0.shape
     p = DcnParams()
     p.dtype = dtype_code(x0)
@@ -520,6 +522,16 @@ def dcn_align(x0, x1, raw, flow1, flow2, weight, bias, cout, *, groups=16, max_m
                   x0.element_size() * px * (2 * ch + 27 * groups + cout), launch,
                   ("dcn", F_, H, W, ch, cout, groups, flow2 is not None))
     return out
+
+
+def dcn_pack(x, raw, weight, bias, cout, *, groups, out=None):
+    """VQFR's DCNv2Pack.forward after conv_offset (vqfr.py:352-380): modulated deformable 3x3 convolution of the clip
+    tensor x with the offsets of ``raw`` taken as they are and sigmoid(mask) (flair_dcn_align, raw_activated = 2).
+    raw: conv_offset's output in tap-major order (dcn_raw_permutation), pixel stride 16-byte granular."""
+    c = x.shape[3]
+    assert c % 2 == 0
+    return dcn_align(x[..., :c // 2], x[..., c // 2:], raw, None, None, weight, bias, cout, groups=groups, out=out,
+                     raw_activated=2)
 
 
 def scale_pixels(x, wmap):
@@ -719,6 +731,19 @@ def dwconv(x, w_dw, b_dw, *, stride, pw=None, act=ACT_LRELU01, out=None):
     assert tuple(out.shape[:3]) == (T, Ho, Wo) and out.shape[3] >= cout and out.dtype == torch.float32
     check(lib().flair_dwconv_nhwc(ptr(x), _ld(x), T, H, W, C, stride, ptr(_f32(w_dw)), ptr(_f32(b_dw)), ptr(_f32(w_pw)),
                                   ptr(_f32(b_pw)), cout, act, ptr(out), _ld(out), stream()), "flair_dwconv_nhwc")
+    return out
+
+
+def dwconv7(x, w, b, *, out=None):
+    """Depthwise 7x7 convolution, stride 1, zero padding 3 (flair_dwconv7_nhwc) of an f32 / bf16 clip tensor:
+    w [49][C] f32 tap-major, b [C] f32 or None -> (T, H, W, C) in x's dtype (f32 accumulation)."""
+    T, H, W, C = x.shape
+    assert tuple(w.shape) == (49, C)
+    if out is None:
+        out = torch.empty((T, H, W, C), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape[:3]) == (T, H, W) and out.shape[3] >= C and out.dtype == x.dtype
+    check(lib().flair_dwconv7_nhwc(ptr(x), _ld(x), dtype_code(x), T, H, W, C, ptr(_f32(w)), ptr(_f32(b)), ptr(out),
+                                   _ld(out), stream()), "flair_dwconv7_nhwc")
     return out
 
 

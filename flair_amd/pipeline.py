@@ -3,8 +3,8 @@
 ``build_pipeline(task, weights_dir, device=...)`` returns a ``Pipeline`` holding the diffusion (``DIFFUSION_CONFIG``,
 :35-75, respaced ``"100"`` uniform, :266-283), the network (``MODEL_CONFIG``, :77-156, bf16 through
 ``convert_to_fp16``), the task operator (``get_A_func``, :190-247) and its data-consistency step (``RESTORE_FUNC``,
-:174-199), the CodeFormer prior (:405-414, :450-452) or, on request, the reference's RestoreFormer prior
-(guided_diffusion/restoreformer.py), the face-parsing weights of the bicubic tasks (:427-444) and a
+:174-199), the CodeFormer prior (:405-414, :450-452) or, on request, the reference's RestoreFormer or VQFR v2 prior
+(guided_diffusion/restoreformer.py, guided_diffusion/vqfr.py), the face-parsing weights of the bicubic tasks (:427-444) and a
 ``FaceRestoreHelper`` built on a loaded RetinaFace and ParseNet (:351).  Every network reads its checkpoint from
 ``weights_dir`` under the reference's file names; a missing file is an error, never a randomly initialised network.
 
@@ -68,7 +68,16 @@ PARSER_FILE = "parsing_parsenet.pth"
 CODEFORMER_FILE = "codeformer.pth"
 # the auxiliary face priors build_pipeline(prior=...) offers, with their checkpoint files (RestoreFormer: the RestoreFormer
 # project's release name; guided_diffusion/restoreformer.py of the reference)
-PRIOR_FILES = {"codeformer": CODEFORMER_FILE, "restoreformer": "RestoreFormer.ckpt"}
+PRIOR_FILES = {"codeformer": CODEFORMER_FILE, "restoreformer": "RestoreFormer.ckpt", "vqfrv2": "VQFR_v2.pth"}
+PRIOR_LABELS = {"codeformer": "CodeFormer", "restoreformer": "RestoreFormer", "vqfrv2": "VQFR"}
+# VQFRv2's constructor arguments in the VQFR project's published v2 release configuration (its options file for VQFR v2:
+# base_channels 64, channel_multipliers [1, 2, 2, 4, 4, 8], two encoder and two decoder blocks with attention, code_dim
+# 256, inpfeat_dim 32, align_opt cond_channels 32 / deformable_groups 4, "Predict" code selection).  The reference tree
+# does not record them and they cannot be checked offline; a wrong value fails loudly in the strict load of
+# VQFR_v2.pth, and prior_kwargs overrides any of them.
+VQFR_CONFIG = dict(base_channels=64, channel_multipliers=(1, 2, 2, 4, 4, 8), num_enc_blocks=2, use_enc_attention=True,
+                   num_dec_blocks=2, use_dec_attention=True, code_dim=256, inpfeat_dim=32, code_selection_mode="Predict",
+                   align_opt={"cond_channels": 32, "deformable_groups": 4})
 DEFAULT_KERNELS = "./miscs/kernels_12.mat"
 
 
@@ -202,8 +211,11 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
 
     ``prior``: ``"codeformer"`` (or True, the default) reads ``codeformer.pth`` (its ``params_ema``);
     ``"restoreformer"`` reads ``RestoreFormer.ckpt`` (a plain state dict, or a training checkpoint whose ``state_dict``
-    holds the network under ``vqvae.``); False / None selects the identity prior and reads neither.  ``prior_kwargs``
-    overrides the prior's constructor arguments (RestoreFormer's ``head_size`` is not recorded in a checkpoint).
+    holds the network under ``vqvae.``); ``"vqfrv2"`` reads ``VQFR_v2.pth`` (a state dict, or BasicSR's
+    ``params_ema`` / ``params``) into VQFRv2 built with VQFR_CONFIG; False / None selects the identity prior and reads
+    none of them.  ``prior_kwargs`` overrides the prior's constructor arguments (RestoreFormer's ``head_size`` is not
+    recorded in a checkpoint); for VQFR it may also hold ``fidelity_ratio`` (default 1.0, the reference forward's),
+    which is passed to every call of the prior instead of the constructor.
 
     In an initialised torch.distributed world only rank 0 reads the files; the other ranks receive its weights (the
     flagship network in its kernel-native packed form, parallel.broadcast_packed_weights; the small networks as fp32
@@ -219,8 +231,7 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         raise ValueError(f"dtype={dtype!r}: 'bf16' or 'fp32'")
     prior = prior_name(prior)
     if prior is not None and size != 512:
-        label = {"codeformer": "CodeFormer", "restoreformer": "RestoreFormer"}[prior]
-        raise ValueError(f"the {label} prior restores 512 x 512 faces (its code grid is 16 x 16): size={size} needs "
+        raise ValueError(f"the {PRIOR_LABELS[prior]} prior restores 512 x 512 faces (its code grid is 16 x 16): size={size} needs "
                          "prior=False")
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     reads = not distributed or dist.get_rank() == 0
@@ -266,6 +277,10 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     elif prior == "restoreformer":
         from .guided_diffusion.restoreformer import VQVAEGANMultiHeadTransformer
         gan = load(VQVAEGANMultiHeadTransformer(**pkw), files[1]).to(device).eval()
+    elif prior == "vqfrv2":
+        from .guided_diffusion.vqfr import VQFRv2
+        fidelity_ratio = float(pkw.pop("fidelity_ratio", 1.0))
+        gan = load(VQFRv2(**dict(VQFR_CONFIG, **pkw)), files[1]).to(device).eval()
     if distributed:
         parallel.broadcast_packed_weights(model, src=0)
         for net in (det, parser, gan):
@@ -292,6 +307,8 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         aux = wl.codeformer_aux(gan)
     elif prior == "restoreformer":
         aux = wl.restoreformer_aux(gan)
+    elif prior == "vqfrv2":
+        aux = wl.vqfr_aux(gan, fidelity_ratio)
     diffusion = create_diffusion(task, steps)
     return Pipeline(task, model, diffusion, A_func, helper, aux, weights_fn, size, device)
 

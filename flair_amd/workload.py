@@ -83,6 +83,12 @@ def restoreformer_aux(net):
     return lambda x0, *a, **k: net(x0)[0]
 
 
+def vqfr_aux(net, fidelity_ratio=1.0):
+    """``aux_model`` around a VQFR v2 prior (guided_diffusion/vqfr.py): its ``main_dec`` of the aligned 512x512 faces of
+    pred_xstart at ``fidelity_ratio`` (1.0: the reference forward's default)."""
+    return lambda x0, *a, **k: net(x0, fidelity_ratio)["main_dec"]
+
+
 # ------------------------------------------------------------------ bicubic tasks (sr3.UNet)
 def sr3_config(image_size, use_fp16=True):
     """MODEL_CONFIG['x8_bicubic'] of scripts/video_sample.py:78-96 at clip side `image_size`

@@ -60,7 +60,8 @@ typedef enum {
 const char* flair_last_error(void);
 /* ABI version of this header: bumped whenever entry points are added or a struct changes
  * (3: round 2; 4: + face crop / paste entries, flair_bcast_weights; 5: round 4 entries; 6: + calibration launches;
- * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc; 9: + flair_vq_nearest_nhwc).
+ * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc; 9: + flair_vq_nearest_nhwc;
+ * 10: + flair_dwconv7_nhwc, flair_dcn_params.raw_activated = 2 (VQFR's DCNv2Pack)).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -271,6 +272,13 @@ int flair_maxpool3x3s2_nhwc(const void* x, int x_ld, int dtype, int F, int H, in
 int flair_dwconv_nhwc(const float* x, int x_ld, int T, int H, int W, int C, int stride, const float* w_dw,
                       const float* b_dw, const float* w_pw, const float* b_pw, int Cout, int act, float* y,
                       int y_ld, hipStream_t stream);
+/* Depthwise 7x7 convolution of VQFR's TextureWarpingModule (`nn.Conv2d(c, c, groups=c, kernel_size=7, padding=3)`,
+ * vqfr.py:394) on [T][H][W][x_ld] clip tensors, dtype F32 / BF16 (f32 accumulation):
+ *   y[t][h][w][c] = bias[c] + sum_{i,j < 7} w[7i + j][c] * x[t][h + i - 3][w + j - 3][c]   (zero outside the frame)
+ * stride 1, same size out.  w: [49][C] f32 (tap-major), bias: [C] f32 or NULL.  C a multiple of 8 (bf16) / 4 (f32);
+ * x_ld >= C and y_ld >= C multiples of that; x, y, w, bias 16-byte aligned. */
+int flair_dwconv7_nhwc(const void* x, int x_ld, int dtype, int T, int H, int W, int C, const float* w,
+                       const float* bias, void* y, int y_ld, hipStream_t stream);
 /* x[f][p][c] += bias[f][c]  (AttentionbottleBlock h + emb_out, unet_new.py:426-428). */
 int flair_add_frame_bias(void* x, int dtype, int ld, int C, int F, long HW, const float* bias,
                          int bias_ld, hipStream_t stream);
@@ -360,7 +368,11 @@ int flair_resize_nhwc(const void* x, int dtype, int x_ld, int F, int Hi, int Wi,
  *           caller permutes the output channels of the last conv_offset convolution once,
  *           when it packs that layer's weights).  G in {8, 16}; Cin/G a power of two.
  *   flow1, flow2 : [F][H][W][2] f32 or NULL (zero);  w : [Cout][9][Cin];  bias f32
- *   x_ld[i] >= Cin/2 and raw_ld multiples of 16 bytes; x0, x1, raw 16-byte aligned; y_ld >= Cout */
+ *   x_ld[i] >= Cin/2 and raw_ld multiples of 16 bytes; x0, x1, raw 16-byte aligned; y_ld >= Cout
+ * raw_activated = 2 is the DCNv2Pack of VQFR's TextureWarpingModule (vqfr.py:341-427): the offsets are taken as they
+ * are and only the mask goes through a sigmoid; flow1 = flow2 = NULL and x0 | x1 are the two channel halves of the one
+ * input (x_main).  It also takes G = 4 and Cout up to 1024 (computed as cout slices of 64 or 128 in separate launches);
+ * Cin from 64 (bf16: 32-channel K steps when Cin / 2 is not a multiple of 64). */
 typedef struct {
     int dtype;
     int F, H, W;
@@ -369,7 +381,8 @@ typedef struct {
     int raw_ld, y_ld;
     float max_residue_magnitude;
     int raw_activated; /* 1: raw already holds max_residue_magnitude*tanh / sigmoid values
-                        * (produced with FLAIR_ACT_DCN_OFFSETS); 0: pre-activations */
+                        * (produced with FLAIR_ACT_DCN_OFFSETS); 0: pre-activations;
+                        * 2: offsets as they are, mask = sigmoid (max_residue_magnitude unused) */
 } flair_dcn_params;
 int flair_dcn_align(const flair_dcn_params* p, const void* x0, const void* x1, const void* raw,
                     const float* flow1, const float* flow2, const void* w, const float* bias,
