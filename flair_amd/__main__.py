@@ -16,7 +16,7 @@ from . import pipeline as pl
 def _add_common(p):
     p.add_argument("--weights", default="./checkpoints", metavar="DIR",
                    help="directory with flair_<task>.pt, the prior's checkpoint (codeformer.pth, RestoreFormer.ckpt or VQFR_v2.pth), "
-                        "the detector and parsing_parsenet.pth")
+                        "the detector and the parser's parsing_parsenet.pth / parsing_bisenet.pth")
     p.add_argument("--kernels", default=pl.DEFAULT_KERNELS, metavar="PATH",
                    help="the blur kernels .mat file (MATLAB v5) of the gaussian and jpeg tasks")
     p.add_argument("--device", default=None, help="default: cuda (cuda:LOCAL_RANK under torch.distributed.run)")
@@ -24,6 +24,9 @@ def _add_common(p):
     p.add_argument("--steps", type=int, default=100, help="sampler steps (respacing of the diffusion)")
     p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
     p.add_argument("--det-model", choices=tuple(pl.DETECTOR_FILES), default="retinaface_resnet50")
+    p.add_argument("--parser", choices=tuple(pl.PARSER_FILES), default="parsenet",
+                   help="face parser of the unaligned branch and the bicubic tasks' weights (parsenet reads "
+                        "parsing_parsenet.pth, bisenet parsing_bisenet.pth)")
     p.add_argument("--prior", choices=tuple(pl.PRIOR_FILES), default=None,
                    help="auxiliary face prior (default: codeformer, reading codeformer.pth; restoreformer reads "
                         "RestoreFormer.ckpt, vqfrv2 VQFR_v2.pth)")
@@ -109,7 +112,8 @@ def main(argv=None):
                               kernels_path=args.kernels, prior=prior, det_model=args.det_model,
                               model_kwargs=json.loads(args.model_kwargs) if args.model_kwargs else None,
                               graph=not args.no_graph,
-                              prior_kwargs=json.loads(args.prior_kwargs) if args.prior_kwargs else None)
+                              prior_kwargs=json.loads(args.prior_kwargs) if args.prior_kwargs else None,
+                              parser=args.parser)
         hp = dict(aligned=args.aligned, t_start=args.t_start, jpeg_qf=args.jpeg_qf, w=args.w, tau=args.tau,
                   rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
         pl.restore_many(jobs, lambda v, o: p.restore_video_files(v, o, **hp))

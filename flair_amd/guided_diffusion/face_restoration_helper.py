@@ -20,7 +20,9 @@ import torch
 
 from .. import ops
 
-# facelib/utils/face_restoration_helper.py:283-303
+# facelib/utils/face_restoration_helper.py:283-303, written for ParseNet's label order (the only parser the reference pairs it
+# with).  It is the default for BiSeNet too: parsing_bisenet.pth's label order cannot be inspected offline, so that pairing is
+# PARITY UNPINNED; FaceRestoreHelper(mask_colormap=...) replaces the list.
 MASK_COLORMAP = [0, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 0, 0, 0, 0, 0]
 
 
@@ -45,11 +47,13 @@ class FaceRestoreHelper(object):
     """``FaceRestoreHelper(face_size=512, device=..., face_parse=ParseNet)``: the crop / paste half of the reference class."""
 
     def __init__(self, face_size=512, crop_ratio=(1, 1), det_model="retinaface_resnet50", save_ext="png",
-                 template_3points=False, device=None, face_parse=None, detector=None, face_det=None):
+                 template_3points=False, device=None, face_parse=None, detector=None, face_det=None, mask_colormap=None):
         assert crop_ratio[0] >= 1 and crop_ratio[1] >= 1, "crop ration only supports >=1"
         self.face_size = (int(face_size * crop_ratio[1]), int(face_size * crop_ratio[0]))    # (w, h), as the reference
         self.device = torch.device(device if device is not None else "cuda")
-        self.face_parse = face_parse          # flair_amd.guided_diffusion.parsenet.ParseNet (needed by inverse_faces)
+        self.face_parse = face_parse          # a parser with parse_indices(x): parsenet.ParseNet or bisenet.BiSeNet (inverse_faces)
+        # paste-mask value per parsing class (None: the reference's 19-entry list)
+        self.mask_colormap = [float(v) for v in (MASK_COLORMAP if mask_colormap is None else mask_colormap)]
         self.detector = detector              # optional external object with a get_crop_face method (e.g. the reference's helper)
         self.face_det = face_det              # flair_amd.guided_diffusion.retinaface.RetinaFace (built on first use when None)
         self.det_model = det_model
@@ -134,7 +138,7 @@ class FaceRestoreHelper(object):
     def _consts(self, dev):
         c = self._const.get(dev)
         if c is None:
-            c = (torch.tensor(MASK_COLORMAP, dtype=torch.float64, device=dev),
+            c = (torch.tensor(self.mask_colormap, dtype=torch.float64, device=dev),
                  torch.from_numpy(gaussian_kernel(101, 26.0)).to(dev))
             self._const[dev] = c
         return c
@@ -174,15 +178,12 @@ class FaceRestoreHelper(object):
     def inverse_faces(self, restored_face_imgs, affine_matrices):
         """(B, 3, h, w) restored faces -> (faces warped back (B, 3, h, w) in [-1, 1], paste masks (B, 1, h, w) float32)."""
         if self.face_parse is None:
-            raise RuntimeError("FaceRestoreHelper.inverse_faces needs face_parse=ParseNet(...) (facelib/parsing/parsenet.py)")
+            raise RuntimeError("FaceRestoreHelper.inverse_faces needs face_parse=ParseNet(...) or BiSeNet(...) (facelib/parsing/)")
         x = restored_face_imgs.float().contiguous()
         B, _, h, w = x.shape
         lut, kern = self._consts(x.device)
-        net = self.face_parse
-        logits = net.out_mask_conv.run(net._features(x))                       # face_parse(x)[0], still NHWC
-        _, idx = ops.argmax_codebook(logits, net.parsing_ch, torch.zeros((net.parsing_ch, 1), dtype=torch.float32,
-                                                                          device=x.device))
-        mask = ops.face_mask_blur(idx, B, h, w, lut, kern, repeats=2, edge=10, div=255.0)
+        idx = self.face_parse.parse_indices(x)                                  # face_parse(x)[0].argmax(dim=1), (B, h, w) int32
+        mask = ops.face_mask_blur(idx.reshape(-1), B, h, w, lut, kern, repeats=2, edge=10, div=255.0)
         # warpAffine(., inverse_affine) inverts its argument again: dst -> src = inv(inv(M)), rounded as OpenCV rounds it
         minv = self._minv(affine_matrices, x.device, twice=True)
         inv_faces = ops.warp_affine_cubic(x, minv, (h, w), pre=True, post=True)

@@ -13,7 +13,9 @@ eval] -> [LeakyReLU(0.2)] -- is ONE ``flair_conv_nhwc`` launch: reflection paddi
 (``reflect_pad``), the eval-mode BatchNorm is folded into the packed weights and bias, the activation and the
 residual adds sit in the conv epilogue.  It runs once per window (not per denoising step), in float32.
 
-RetinaFace detection / landmark alignment (the other half of row 4) is not provided.
+RetinaFace detection / landmark alignment (the other half of row 4) is ``retinaface.py``; the reference's other parser,
+BiSeNet, is ``bisenet.py``.  Both parsers offer ``parse_indices`` and ``face_weight``, which is all that
+``FaceRestoreHelper.inverse_faces`` and ``workload.parsenet_weights_fn`` use of them.
 """
 import math
 
@@ -162,6 +164,14 @@ class ParseNet(nn.Module):
         mask = self.out_mask_conv.run(y)
         img = self.out_img_conv.run(y)
         return ops.clip_to_nchw(mask, self.parsing_ch), ops.clip_to_nchw(img, 3)
+
+    @torch.no_grad()
+    def parse_indices(self, x):
+        """``face_parse(x)[0].argmax(dim=1)`` (face_restoration_helper.py:279-281): (B, H, W) int32, without leaving the GPU."""
+        logits = self.out_mask_conv.run(self._features(x))                     # face_parse(x)[0], still NHWC
+        _, idx = ops.argmax_codebook(logits, self.parsing_ch, torch.zeros((self.parsing_ch, 1), dtype=torch.float32,
+                                                                          device=x.device))
+        return idx.view(logits.shape[:3])
 
     @torch.no_grad()
     def face_weight(self, frames, w_face):

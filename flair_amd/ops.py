@@ -913,3 +913,49 @@ def face_blend(x0, face, mask):
     out = torch.empty_like(x0)
     check(lib().flair_face_blend(ptr(x0), ptr(face), ptr(mask), N, C, H, W, ptr(out), stream()), "flair_face_blend")
     return out
+
+
+# --------------------------------------------------------------------------- BiSeNet face parsing (parse.hip)
+def global_avgpool(x, out=None):
+    """F.avg_pool2d(x, x.size()[2:]) of a clip tensor (flair_global_avgpool_nhwc): (F, H, W, C) -> (F, C) float32 means."""
+    F_, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((F_, C), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape[0] == F_ and out.shape[1] >= C and out.stride(1) == 1
+    check(lib().flair_global_avgpool_nhwc(ptr(x), dtype_code(x), _ld(x), F_, H, W, C, ptr(out), out.stride(0), stream()),
+          "flair_global_avgpool_nhwc")
+    return out
+
+
+def channel_gate(x, gate, *, logit=False, add_x=False, bias=None, add=None, out=None):
+    """x * g (+ x) (+ bias) (+ add) on a clip tensor (flair_channel_gate_nhwc).  gate, bias: (F, C) float32 per (frame,
+    channel); ``logit``: gate holds pre-sigmoid logits; ``add``: a clip tensor of x's shape and dtype.  out may be x."""
+    F_, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((F_, H, W, C), dtype=x.dtype, device=x.device)
+    for t in (gate, bias):
+        assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == (F_, C) and t.stride(1) == 1)
+    assert add is None or (add.dtype == x.dtype and add.shape == x.shape)
+    assert out.dtype == x.dtype and tuple(out.shape[:3]) == (F_, H, W) and out.shape[3] >= C
+    check(lib().flair_channel_gate_nhwc(ptr(x), _ld(x), dtype_code(x), F_, ctypes.c_long(H * W), C, ptr(gate), gate.stride(0),
+                                        int(logit), int(add_x), ptr(bias), bias.stride(0) if bias is not None else 0,
+                                        ptr(add), _ld(add) if add is not None else 0, ptr(out), _ld(out), stream()),
+          "flair_channel_gate_nhwc")
+    return out
+
+
+def upsample_argmax(logits, n_classes, size, table=None):
+    """argmax over the classes of F.interpolate(logits, size, mode='bilinear', align_corners=True), first index on ties,
+    without the enlarged tensor (flair_upsample_argmax_nhwc).  logits: (F, h, w, >= n_classes) clip tensor;
+    table: optional (n_classes, D) float32 -> (idx (F, H, W) int32, table[idx] (F, H, W, D) float32 or None)."""
+    F_, h, w, _ = logits.shape
+    H, W = size
+    idx = torch.empty((F_, H, W), dtype=torch.int32, device=logits.device)
+    y, D = None, 0
+    if table is not None:
+        assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[0] == n_classes
+        D = table.shape[1]
+        y = torch.empty((F_, H, W, D), dtype=torch.float32, device=logits.device)
+    check(lib().flair_upsample_argmax_nhwc(ptr(logits), dtype_code(logits), _ld(logits), F_, h, w, n_classes, H, W, ptr(table), D,
+                                           ptr(idx), ptr(y), D, stream()), "flair_upsample_argmax_nhwc")
+    return idx, y

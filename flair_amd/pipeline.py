@@ -5,7 +5,7 @@
 ``convert_to_fp16``), the task operator (``get_A_func``, :190-247) and its data-consistency step (``RESTORE_FUNC``,
 :174-199), the CodeFormer prior (:405-414, :450-452) or, on request, the reference's RestoreFormer or VQFR v2 prior
 (guided_diffusion/restoreformer.py, guided_diffusion/vqfr.py), the face-parsing weights of the bicubic tasks (:427-444) and a
-``FaceRestoreHelper`` built on a loaded RetinaFace and ParseNet (:351).  Every network reads its checkpoint from
+``FaceRestoreHelper`` built on a loaded RetinaFace and face parser (ParseNet or BiSeNet, :351).  Every network reads its checkpoint from
 ``weights_dir`` under the reference's file names; a missing file is an error, never a randomly initialised network.
 
 Everything per step runs on the HIP kernels the pieces already use; this module is host-side wiring only.  The
@@ -65,6 +65,8 @@ DEMOS = {
 DETECTOR_FILES = {"retinaface_resnet50": ("resnet50", "detection_Resnet50_Final.pth"),
                   "retinaface_mobile0.25": ("mobile0.25", "detection_mobilenet0.25_Final.pth")}
 PARSER_FILE = "parsing_parsenet.pth"
+# the face parsers build_pipeline(parser=...) offers (facelib/parsing/__init__.py:8-25), with their checkpoint files
+PARSER_FILES = {"parsenet": PARSER_FILE, "bisenet": "parsing_bisenet.pth"}
 CODEFORMER_FILE = "codeformer.pth"
 # the auxiliary face priors build_pipeline(prior=...) offers, with their checkpoint files (RestoreFormer: the RestoreFormer
 # project's release name; guided_diffusion/restoreformer.py of the reference)
@@ -151,12 +153,12 @@ def prior_name(prior):
     raise ValueError(f"prior={prior!r}: one of {', '.join(map(repr, PRIOR_FILES))}, True (= 'codeformer'), False or None")
 
 
-def _required_files(task, weights_dir, det_model, prior):
+def _required_files(task, weights_dir, det_model, prior, parser="parsenet"):
     files = [model_file(task)]
     name = prior_name(prior)
     if name is not None:
         files.append(PRIOR_FILES[name])
-    files += [DETECTOR_FILES[det_model][1], PARSER_FILE]
+    files += [DETECTOR_FILES[det_model][1], PARSER_FILES[parser]]
     return [os.path.join(str(weights_dir), f) for f in files]
 
 
@@ -203,9 +205,10 @@ class Pipeline:
 
 
 def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=100, kernels_path=None, prior=True,
-                   det_model="retinaface_resnet50", model_kwargs=None, graph=True, prior_kwargs=None):
+                   det_model="retinaface_resnet50", model_kwargs=None, graph=True, prior_kwargs=None, parser="parsenet"):
     """Build ``task``'s Pipeline from the checkpoints in ``weights_dir``: ``flair_{task}.pt``, the prior's checkpoint,
-    the detector's ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` and ``parsing_parsenet.pth``,
+    the detector's ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` and the parser's
+    ``parsing_parsenet.pth`` (``parser="parsenet"``, the default) or ``parsing_bisenet.pth`` (``parser="bisenet"``),
     all loaded strictly with ``weights_only=True``.  ``model_kwargs`` overrides entries of MODEL_CONFIG[task]
     (checkpoints of other widths).  ``kernels_path``: the reference's ``miscs/kernels_12.mat`` (gaussian and jpeg tasks).
 
@@ -227,6 +230,8 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     _check_task(task)
     if det_model not in DETECTOR_FILES:
         raise ValueError(f"det_model={det_model!r}: one of {', '.join(DETECTOR_FILES)}")
+    if parser not in PARSER_FILES:
+        raise ValueError(f"parser={parser!r}: one of {', '.join(PARSER_FILES)}")
     if dtype not in ("bf16", "fp32"):
         raise ValueError(f"dtype={dtype!r}: 'bf16' or 'fp32'")
     prior = prior_name(prior)
@@ -235,7 +240,7 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
                          "prior=False")
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     reads = not distributed or dist.get_rank() == 0
-    files = _required_files(task, weights_dir, det_model, prior)
+    files = _required_files(task, weights_dir, det_model, prior, parser)
     if reads:
         for f in files:
             if not os.path.isfile(f):
@@ -266,7 +271,11 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     det_path, parser_path = files[-2], files[-1]
     det = load(RetinaFace(network_name=DETECTOR_FILES[det_model][0], half=False, device="cpu"), det_path).to(device).eval()
     det.device = device
-    parser = load(ParseNet(in_size=512, out_size=512, parsing_ch=19), parser_path).to(device).eval()
+    if parser == "bisenet":
+        from .guided_diffusion.bisenet import BiSeNet
+        parser = load(BiSeNet(num_class=19), parser_path).to(device).eval()
+    else:
+        parser = load(ParseNet(in_size=512, out_size=512, parsing_ch=19), parser_path).to(device).eval()
     gan = None
     pkw = {k: tuple(v) if isinstance(v, list) else v for k, v in (prior_kwargs or {}).items()}   # JSON lists
     if prior == "codeformer":

@@ -123,7 +123,8 @@ def bicubic_taps(factor, a=-0.5):
 
 
 def parsenet_weights_fn(parser, task):
-    """``vsrpp_weights_fn`` for flair_amd.video built on a ParseNet (flair_amd.guided_diffusion.parsenet): the
+    """``vsrpp_weights_fn`` for flair_amd.video built on a face parser with a ``face_weight`` method
+    (flair_amd.guided_diffusion.parsenet.ParseNet or flair_amd.guided_diffusion.bisenet.BiSeNet): the
     per-pixel propagation weights of scripts/video_sample.py:427-444 -- background (parsing class 0) pixels get
     TASKS[task]['face_weight'] (0.93 for x8, 0.98 for x16 bicubic), the rest 1 -- as (1, T, 1, S, S)."""
     w_face = TASKS[task]["face_weight"]

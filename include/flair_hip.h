@@ -61,7 +61,8 @@ const char* flair_last_error(void);
 /* ABI version of this header: bumped whenever entry points are added or a struct changes
  * (3: round 2; 4: + face crop / paste entries, flair_bcast_weights; 5: round 4 entries; 6: + calibration launches;
  * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc; 9: + flair_vq_nearest_nhwc;
- * 10: + flair_dwconv7_nhwc, flair_dcn_params.raw_activated = 2 (VQFR's DCNv2Pack)).
+ * 10: + flair_dwconv7_nhwc, flair_dcn_params.raw_activated = 2 (VQFR's DCNv2Pack);
+ * 11: + flair_global_avgpool_nhwc, flair_channel_gate_nhwc, flair_upsample_argmax_nhwc (BiSeNet face parsing)).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -454,6 +455,33 @@ int flair_adain_nhwc(const void* content, int c_ld, const void* style, int s_ld,
 /* Fuse_sft_block tail (codeformer.py:595-596): y = dec + w * (dec * scale + shift) over n dense elements. */
 int flair_sft_fuse(const void* dec, const void* scale, const void* shift, float w, int dtype, long n, void* y,
                    hipStream_t stream);
+
+/* ------------------------------------------------------------- BiSeNet face parsing (facelib/parsing/bisenet.py)
+ * The second parser of facelib/parsing/__init__.py:8-25.  Its convolutions, the stem pool, the residual sums and the nearest
+ * enlargements run on the entry points above; these are the pieces only it needs.  All three take F32 / BF16 NHWC tensors
+ * with explicit pixel strides, refuse a stride or pointer that breaks their 16-byte accesses with FLAIR_ERR_ARG, and use no
+ * float atomics (fixed summation order: a replayed graph gives the same bits). */
+/* F.avg_pool2d(feat, feat.size()[2:]) (bisenet.py:45, :70, :100): y[f][c] = mean over the H*W pixels of x[f][.][.][c], f32.
+ * C and x_ld multiples of 4 (F32) / 8 (BF16), x 16-byte aligned; y: [F][y_ld] f32, y_ld >= C. */
+int flair_global_avgpool_nhwc(const void* x, int dtype, int x_ld, int F, int H, int W, int C, float* y, int y_ld,
+                              hipStream_t stream);
+/* y = x * g[f][c] (+ x if add_x) (+ bias[f][c]) (+ a) on [F][HW] pixels of C channels.  gate: [F][gate_ld] f32, a gate or,
+ * with gate_is_logit != 0, its pre-sigmoid logit (g = 1 / (1 + exp(-gate))); bias: [F][bias_ld] f32 or NULL; a: a full
+ * tensor of x's dtype (pixel stride a_ld) or NULL.  One launch each for torch.mul(feat, atten) + avg_up of arm32
+ * (bisenet.py:49, :74-75: avg_up is a 1x1 map enlarged by nearest, i.e. `bias`), arm16(feat16) + feat32_up (:79-80: `a`)
+ * and feat * atten + feat of FeatureFusionModule (:105-106: add_x).  y may alias x.  C, x_ld, y_ld, a_ld multiples of
+ * 4 (F32) / 8 (BF16); x, y, a 16-byte aligned. */
+int flair_channel_gate_nhwc(const void* x, int x_ld, int dtype, int F, long HW, int C, const float* gate, int gate_ld,
+                            int gate_is_logit, int add_x, const float* bias, int bias_ld, const void* a, int a_ld,
+                            void* y, int y_ld, hipStream_t stream);
+/* idx[f][Y][X] = argmax_n of F.interpolate(logits, (H, W), mode='bilinear', align_corners=True)[f][n][Y][X] (bisenet.py:127
+ * followed by the .argmax(dim=1) of facelib/utils/face_restoration_helper.py:279-281 and scripts/video_sample.py:428-429),
+ * first index on ties, without the enlarged tensor: logits [F][h][w] pixels of N <= 32 classes (pixel stride ld >= N, dtype
+ * F32 / BF16, blended in f32 with ATen's arithmetic: source = dst * (h - 1) / (H - 1) in float, the four-term blend).
+ * H == h, W == w is the plain arg-max.  idx: [F][H][W] int32 (or NULL); y (or NULL): [F][H][W] rows of f32, stride y_ld,
+ * y[row][0..D) = table[idx[row]] with table [N][D] f32 (the face_weight table of video_sample.py:431). */
+int flair_upsample_argmax_nhwc(const void* logits, int dtype, int ld, int F, int h, int w, int N, int H, int W,
+                               const float* table, int D, int* idx, float* y, int y_ld, hipStream_t stream);
 
 /* ------------------------------------------------------------- un-aligned prior branch: face crop / inverse paste
  * (second half; gaussian_diffusion.py:476-493 calls facelib/utils/face_restoration_helper.py:225-254

@@ -1,10 +1,13 @@
 """Cost per sampler step of the unaligned prior branch (gaussian_diffusion.py:476-493) at 512 x 512, random weights.
 
-The branch crops the faces out of x0 and x_t, runs CodeFormer on the crops, parses the restored faces (ParseNet),
-blurs the parsing mask and pastes the faces back; the aligned branch runs CodeFormer on the whole frames.  Both are timed
-here on a window of --frames frames, with a full-size CodeFormer and ParseNet (random weights) and one face per frame.
+The branch crops the faces out of x0 and x_t, runs CodeFormer on the crops, parses the restored faces (ParseNet or
+BiSeNet), blurs the parsing mask and pastes the faces back; the aligned branch runs CodeFormer on the whole frames.  Both
+are timed here on a window of --frames frames, with a full-size CodeFormer and parser (random weights) and one face per
+frame.
 
     python tools/bench_unaligned.py --frames 10      # one JSON line: ms per step of each part and of both branches
+    python tools/bench_unaligned.py --parser both    # one line per parser, same process, plus the BiSeNet tail and the
+                                                     # small-kernel timings (fused vs unfused arg-max, pool / gate launches)
 """
 import argparse
 import json
@@ -22,20 +25,71 @@ def main():
     ap.add_argument("--frames", type=int, default=10)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--parser", choices=("parsenet", "bisenet", "both"), default="parsenet")
     a = ap.parse_args()
-    from flair_amd import ops
-    from flair_amd import workload as wl
     from flair_amd.guided_diffusion.codeformer import CodeFormer
-    from flair_amd.guided_diffusion.face_restoration_helper import FaceRestoreHelper
-    from flair_amd.guided_diffusion.parsenet import ParseNet
-    from flair_amd.guided_diffusion.retinaface_utils import estimate_affine_partial
     torch.set_grad_enabled(False)
     dev = torch.device("cuda:0")
-    T, S = a.frames, 512
     torch.manual_seed(0)
     gan = CodeFormer(dim_embd=512, codebook_size=1024, n_head=8, n_layers=9,
                      connect_list=["32", "64", "128", "256"]).to(dev).eval()
-    parser = ParseNet(in_size=512, out_size=512, parsing_ch=19).to(dev).eval()
+    for k, name in enumerate(("parsenet", "bisenet") if a.parser == "both" else (a.parser,)):
+        run(a, dev, gan, name, with_aligned=k == 0)
+
+
+def make_parser(name, dev):
+    if name == "bisenet":
+        from flair_amd.guided_diffusion.bisenet import BiSeNet
+        return BiSeNet(num_class=19).to(dev).eval()
+    from flair_amd.guided_diffusion.parsenet import ParseNet
+    return ParseNet(in_size=512, out_size=512, parsing_ch=19).to(dev).eval()
+
+
+def replay_us(fn, iters=20, warmup=3):
+    """Microseconds per call of ``fn`` (device events around ``iters`` back-to-back calls, after ``warmup``)."""
+    for _ in range(warmup):
+        fn()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    for _ in range(iters):
+        fn()
+    ev1.record()
+    torch.cuda.synchronize()
+    return 1e3 * ev0.elapsed_time(ev1) / iters
+
+
+def bisenet_kernels(T, S, dev):
+    """The fused arg-max tail against the unfused composition of launches (bilinear align_corners=True resize to full size,
+    then flair_argmax_codebook), and the pool / gate launches at BiSeNet's four shapes: microseconds per launch."""
+    from flair_amd import ops
+    g = torch.Generator(device=dev).manual_seed(2)
+    logits = torch.randn(T, S // 8, S // 8, 20, device=dev, generator=g)
+    zero = torch.zeros((19, 1), dtype=torch.float32, device=dev)
+    big = torch.empty((T, S, S, 20), dtype=torch.float32, device=dev)
+    code = torch.empty((T, S, S, 1), dtype=torch.float32, device=dev)
+
+    def unfused():
+        ops.resize(logits, (S, S), 1, channels=19, out=big)
+        return ops.argmax_codebook(big, 19, zero, out=code)[1]
+    out = {"tail_fused_us": replay_us(lambda: ops.upsample_argmax(logits, 19, (S, S))),
+           "tail_unfused_us": replay_us(unfused)}
+    same = (ops.upsample_argmax(logits, 19, (S, S))[0].reshape(-1) == unfused()).float().mean().item()
+    out["tail_fused_equals_unfused_share"] = same
+    for C, s in ((512, S // 32), (128, S // 32), (128, S // 16), (256, S // 8)):
+        x = torch.randn(T, s, s, C, device=dev, generator=g)
+        gate = torch.randn(T, C, device=dev, generator=g)
+        out[f"pool_c{C}_{s}x{s}_us"] = replay_us(lambda: ops.global_avgpool(x))
+        out[f"gate_c{C}_{s}x{s}_us"] = replay_us(lambda: ops.channel_gate(x, gate, logit=True, add=x, out=x))
+    return out
+
+
+def run(a, dev, gan, parser_name, with_aligned=True):
+    from flair_amd import ops
+    from flair_amd import workload as wl
+    from flair_amd.guided_diffusion.face_restoration_helper import FaceRestoreHelper
+    from flair_amd.guided_diffusion.retinaface_utils import estimate_affine_partial
+    T, S = a.frames, 512
+    parser = make_parser(parser_name, dev)
     helper = FaceRestoreHelper(face_size=S, device=dev, face_parse=parser)
     tpl = helper.face_template
     # one face per frame, 70 % of the template's size, drifting across the window
@@ -65,7 +119,7 @@ def main():
         return aux(x0, None, xt)
 
     res = {}
-    for name, fn in (("unaligned_branch", unaligned), ("aligned_branch", aligned)):
+    for name, fn in (("unaligned_branch", unaligned), ("aligned_branch", aligned))[:2 if with_aligned else 1]:
         for _ in range(a.warmup):
             fn()
         torch.cuda.synchronize()
@@ -79,7 +133,11 @@ def main():
         res[name + "_ms"] = ev0.elapsed_time(ev1) / a.iters
         for part, evs in parts.items():
             res[part + "_ms"] = sum(e0.elapsed_time(e1) for e0, e1 in evs) / len(evs)
-    res.update(frames=T, size=S, iters=a.iters, device=torch.cuda.get_device_name(0))
+    faces = helper.get_crop_face_from_affine_matrices(x0, mats)
+    res["parser_forward_ms"] = replay_us(lambda: parser.parse_indices(faces), a.iters, a.warmup) / 1e3
+    if parser_name == "bisenet":
+        res.update(bisenet_kernels(T, S, dev))
+    res.update(parser=parser_name, frames=T, size=S, iters=a.iters, device=torch.cuda.get_device_name(0))
     print(json.dumps(res))
 
 
