@@ -23,6 +23,12 @@ void flair_set_error(const char* fmt, ...);
             return FLAIR_ERR_ARG;         \
         }                                 \
     } while (0)
+// A channel view moved in 16-byte pieces of `vec` elements: its pixel stride holds the C channels and is 16-byte granular,
+// and its base pointer is 16-byte aligned.  `fn` and `name` are string literals (the entry and the argument).
+#define FLAIR_CHECK_VIEW(fn, name, ptr, ld, C, vec)                                                                   \
+    FLAIR_CHECK((ld) >= (C) && (ld) % (vec) == 0 && reinterpret_cast<uintptr_t>(ptr) % 16 == 0,                        \
+                fn ": " name " stride/alignment: " name "_ld = %d must be >= C = %d and a multiple of %d elements, " \
+                name " = %p 16-byte aligned", (int)(ld), (int)(C), (int)(vec), (const void*)(ptr))
 #define FLAIR_LAUNCH_CHECK()                                                  \
     do {                                                                      \
         hipError_t e_ = hipGetLastError();                                    \

@@ -67,7 +67,7 @@ __global__ void linear_f32_kernel(const float* x, int M, int K, const float* w, 
             for (int j = 0; j < 8; ++j) wv[j] = k0 + 64 * j < K ? wr[k0 + 64 * j] : 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const int k = k0 + 64 * j < K ? k0 + 64 * j : lane;
+                const int k = k0 + 64 * j < K ? k0 + 64 * j : 0;     // past K the weight is 0: any staged element (0 < K) does
 #pragma unroll
                 for (int m = 0; m < MMAX; ++m)
                     if (m < M) acc[m] = fmaf(xs[m * K + k], wv[j], acc[m]);
@@ -469,16 +469,21 @@ extern "C" int flair_learned_range_variance(const float* model_out, int N, int C
 extern "C" int flair_gated_blend(const void* x, int x_ld, const void* m, int m_ld, const float* gate, int gate_ld,
                                  int dtype, int C, int F, long HW, void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(x && m && gate && y && C > 0 && F > 0 && HW > 0 && gate_ld >= C, "flair_gated_blend: bad argument");
+    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_gated_blend: bad dtype");
+    {
+        const int vec = dtype == FLAIR_BF16 ? 8 : 4;
+        FLAIR_CHECK_VIEW("flair_gated_blend", "x", x, x_ld, C, vec);
+        FLAIR_CHECK_VIEW("flair_gated_blend", "m", m, m_ld, C, vec);
+        FLAIR_CHECK_VIEW("flair_gated_blend", "y", y, y_ld, C, vec);
+    }
     if (dtype == FLAIR_BF16) {
         FLAIR_CHECK(C % 8 == 0, "flair_gated_blend: C %% 8");
         hipLaunchKernelGGL(gated_blend_kernel<bf16_t>, dim3(grid_for(F * HW * (C / 8))), dim3(256), 0, stream,
                            (const bf16_t*)x, x_ld, (const bf16_t*)m, m_ld, gate, gate_ld, C, F, HW, (bf16_t*)y, y_ld);
-    } else if (dtype == FLAIR_F32) {
+    } else {
         FLAIR_CHECK(C % 4 == 0, "flair_gated_blend: C %% 4");
         hipLaunchKernelGGL(gated_blend_kernel<float>, dim3(grid_for(F * HW * (C / 4))), dim3(256), 0, stream,
                            (const float*)x, x_ld, (const float*)m, m_ld, gate, gate_ld, C, F, HW, (float*)y, y_ld);
-    } else {
-        FLAIR_CHECK(false, "flair_gated_blend: bad dtype");
     }
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;

@@ -256,9 +256,14 @@ extern "C" int flair_layernorm_nhwc(const void* x, int dtype, int x_ld, long row
     FLAIR_CHECK(x && gamma && beta && y, "flair_layernorm_nhwc: null argument");
     FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_layernorm_nhwc: bad dtype %d", dtype);
     const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(rows > 0 && C > 0 && C % vec == 0 && C <= 64 * 4 * vec, "flair_layernorm_nhwc: C=%d unsupported", C);
-    FLAIR_CHECK(x_ld % vec == 0 && y_ld % vec == 0 && (!y2 || (y2_ld % vec == 0 && pos && pos_rows > 0)),
-                "flair_layernorm_nhwc: strides / positional table");
+    FLAIR_CHECK(rows > 0 && C > 0 && C % vec == 0 && C <= 64 * 4 * vec,
+                "flair_layernorm_nhwc: C=%d unsupported (a multiple of %d, at most %d)", C, vec, 64 * 4 * vec);
+    FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "x", x, x_ld, C, vec);
+    FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "y", y, y_ld, C, vec);
+    if (y2) {
+        FLAIR_CHECK(pos && pos_rows > 0, "flair_layernorm_nhwc: y2 needs the positional table");
+        FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "y2", y2, y2_ld, C, vec);
+    }
     const dim3 grid((unsigned)((rows + 3) / 4));
     if (dtype == FLAIR_BF16)
         hipLaunchKernelGGL((layernorm_kernel<bf16_t, 4>), grid, dim3(256), 0, stream, (const bf16_t*)x, x_ld, rows, C, gamma,
@@ -279,6 +284,19 @@ extern "C" int flair_attention_wide(const flair_attn_params* p, const void* qkv,
     FLAIR_CHECK(p->ld % vec == 0 && p->q_off % vec == 0 && p->k_off % vec == 0 && p->v_off % vec == 0 &&
                     p->head_stride % vec == 0,
                 "flair_attention_wide: offsets/strides must be multiples of %d elements", vec);
+    {
+        const int mo = p->q_off > p->k_off ? (p->q_off > p->v_off ? p->q_off : p->v_off)
+                                           : (p->k_off > p->v_off ? p->k_off : p->v_off);
+        FLAIR_CHECK(p->q_off >= 0 && p->k_off >= 0 && p->v_off >= 0 && p->head_stride >= 0 &&
+                        (long)mo + (long)(p->heads - 1) * p->head_stride + p->head_dim <= p->ld,
+                    "flair_attention_wide: the last head's channels (offset %d + %d * head_stride %d + head_dim %d) exceed ld = %d",
+                    mo, p->heads - 1, p->head_stride, p->head_dim, p->ld);
+        FLAIR_CHECK((long)p->heads * p->head_dim <= p->out_ld && p->out_ld % vec == 0,
+                    "flair_attention_wide: out_ld = %d must be >= heads * head_dim = %d and a multiple of %d elements", p->out_ld,
+                    p->heads * p->head_dim, vec);
+        FLAIR_CHECK(reinterpret_cast<uintptr_t>(qkv) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+                    "flair_attention_wide: qkv = %p / out = %p must be 16-byte aligned", qkv, (const void*)out);
+    }
     const size_t lds = (size_t)16 * (p->head_dim + p->L) * sizeof(float);
     FLAIR_CHECK(lds <= 128 * 1024, "flair_attention_wide: head_dim %d + L %d tokens exceed the LDS tile", p->head_dim, p->L);
     WideAttn a;
@@ -337,6 +355,10 @@ extern "C" int flair_sft_fuse(const void* dec, const void* scale, const void* sh
     FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_sft_fuse: bad dtype %d", dtype);
     const int vec = dtype == FLAIR_BF16 ? 8 : 4;
     FLAIR_CHECK(n > 0 && n % vec == 0, "flair_sft_fuse: n=%ld must be a multiple of %d", n, vec);
+    FLAIR_CHECK(reinterpret_cast<uintptr_t>(dec) % 16 == 0, "flair_sft_fuse: dec = %p must be 16-byte aligned", dec);
+    FLAIR_CHECK(reinterpret_cast<uintptr_t>(scale) % 16 == 0, "flair_sft_fuse: scale = %p must be 16-byte aligned", scale);
+    FLAIR_CHECK(reinterpret_cast<uintptr_t>(shift) % 16 == 0, "flair_sft_fuse: shift = %p must be 16-byte aligned", shift);
+    FLAIR_CHECK(reinterpret_cast<uintptr_t>(y) % 16 == 0, "flair_sft_fuse: y = %p must be 16-byte aligned", (const void*)y);
     const long nvec = n / vec;
     long blocks = (nvec + 255) / 256;
     if (blocks > 4096) blocks = 4096;

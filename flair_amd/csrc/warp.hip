@@ -367,16 +367,20 @@ extern "C" int flair_flow_warp(const void* x, int dtype, int x_ld, const float* 
                 "flair_flow_warp: bad argument");
     FLAIR_CHECK((unsigned long long)F * H * W * x_ld * (dtype == FLAIR_BF16 ? 2 : 4) < 0x80000000ull,
                 "flair_flow_warp: the source clip spans >= 2 GiB (32-bit gather offsets): call per frame");
+    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_flow_warp: bad dtype");
+    {
+        const int vec = dtype == FLAIR_BF16 ? 8 : 4;
+        FLAIR_CHECK_VIEW("flair_flow_warp", "x", x, x_ld, C, vec);
+        FLAIR_CHECK_VIEW("flair_flow_warp", "y", y, y_ld, C, vec);
+    }
     if (dtype == FLAIR_BF16) {
-        FLAIR_CHECK(C % 8 == 0 && x_ld % 8 == 0 && y_ld % 8 == 0, "flair_flow_warp: bf16 needs C %% 8 == 0");
+        FLAIR_CHECK(C % 8 == 0, "flair_flow_warp: bf16 needs C %% 8 == 0");
         hipLaunchKernelGGL(flow_warp_kernel<bf16_t>, dim3(grid_for((long)F * H * W * (C / 8))), dim3(256), 0, stream,
                            (const bf16_t*)x, x_ld, flow, flow_ld, F, H, W, C, border, (bf16_t*)y, y_ld);
-    } else if (dtype == FLAIR_F32) {
-        FLAIR_CHECK(C % 4 == 0 && x_ld % 4 == 0 && y_ld % 4 == 0, "flair_flow_warp: f32 needs C %% 4 == 0");
+    } else {
+        FLAIR_CHECK(C % 4 == 0, "flair_flow_warp: f32 needs C %% 4 == 0");
         hipLaunchKernelGGL(flow_warp_kernel<float>, dim3(grid_for((long)F * H * W * (C / 4))), dim3(256), 0, stream,
                            (const float*)x, x_ld, flow, flow_ld, F, H, W, C, border, (float*)y, y_ld);
-    } else {
-        FLAIR_CHECK(false, "flair_flow_warp: bad dtype");
     }
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
@@ -445,7 +449,14 @@ extern "C" int flair_vsrpp_warp2(const void* prop, int prop_ld, const void* feat
     const int vec = dtype == FLAIR_BF16 ? 8 : 4;
     FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_vsrpp_warp2: bad dtype");
     FLAIR_CHECK(C % vec == 0, "flair_vsrpp_warp2: C %% %d", vec);
-    FLAIR_CHECK((unsigned long long)H * W * prop_ld * (16 / vec) < 0x80000000ull && (unsigned long long)H * W * feat2_ld * (16 / vec) < 0x80000000ull,
+    FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "prop", prop, prop_ld, C, vec);
+    FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "cond1", cond1, cond1_ld, C, vec);
+    if (flow2) {
+        FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "feat2", feat2, feat2_ld, C, vec);
+        FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "cond2", cond2, cond2_ld, C, vec);
+    }
+    FLAIR_CHECK((unsigned long long)H * W * prop_ld * (16 / vec) < 0x80000000ull &&
+                    (!flow2 || (unsigned long long)H * W * feat2_ld * (16 / vec) < 0x80000000ull),
                 "flair_vsrpp_warp2: a source frame spans >= 2 GiB");
     const dim3 grid(grid_for((long)H * W * (C / vec)), flow2 ? 2 : 1);
     if (dtype == FLAIR_BF16)
@@ -464,21 +475,32 @@ extern "C" int flair_vsrpp_prep(const void* prop, int prop_ld, const void* feat2
                                 const float* flow_prev, int dtype, int H, int W, int C, void* cond1, int cond1_ld,
                                 void* cond2, int cond2_ld, float* flow2_out, void* flowpad, int pad_ld,
                                 hipStream_t stream) {
-    FLAIR_CHECK(prop && flow1 && cond1 && flowpad && H > 0 && W > 0 && C > 0 && pad_ld >= 4,
-                "flair_vsrpp_prep: bad argument");
+    FLAIR_CHECK(prop && flow1 && cond1 && flowpad && H > 0 && W > 0 && C > 0, "flair_vsrpp_prep: bad argument");
     FLAIR_CHECK(!flow_prev || (feat2 && cond2 && flow2_out), "flair_vsrpp_prep: second-order inputs incomplete");
+    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_vsrpp_prep: bad dtype");
+    {
+        const int vec = dtype == FLAIR_BF16 ? 8 : 4;
+        FLAIR_CHECK_VIEW("flair_vsrpp_prep", "prop", prop, prop_ld, C, vec);
+        FLAIR_CHECK_VIEW("flair_vsrpp_prep", "cond1", cond1, cond1_ld, C, vec);
+        if (flow_prev) {
+            FLAIR_CHECK_VIEW("flair_vsrpp_prep", "feat2", feat2, feat2_ld, C, vec);
+            FLAIR_CHECK_VIEW("flair_vsrpp_prep", "cond2", cond2, cond2_ld, C, vec);
+        }
+        // flowpad is a convolution input segment (conv_offset[0]'s fourth): that entry's stride / alignment rule
+        FLAIR_CHECK(pad_ld >= 4 && pad_ld % vec == 0 && reinterpret_cast<uintptr_t>(flowpad) % 16 == 0,
+                    "flair_vsrpp_prep: flowpad stride/alignment: pad_ld = %d must be >= 4 and a multiple of %d elements, "
+                    "flowpad = %p 16-byte aligned", pad_ld, vec, (const void*)flowpad);
+    }
     if (dtype == FLAIR_BF16) {
         FLAIR_CHECK(C % 8 == 0, "flair_vsrpp_prep: C %% 8");
         hipLaunchKernelGGL(vsrpp_prep_kernel<bf16_t>, dim3(grid_for((long)H * W * (C / 8))), dim3(256), 0, stream,
                            (const bf16_t*)prop, prop_ld, (const bf16_t*)feat2, feat2_ld, flow1, flow_prev, H, W, C,
                            (bf16_t*)cond1, cond1_ld, (bf16_t*)cond2, cond2_ld, flow2_out, (bf16_t*)flowpad, pad_ld);
-    } else if (dtype == FLAIR_F32) {
+    } else {
         FLAIR_CHECK(C % 4 == 0, "flair_vsrpp_prep: C %% 4");
         hipLaunchKernelGGL(vsrpp_prep_kernel<float>, dim3(grid_for((long)H * W * (C / 4))), dim3(256), 0, stream,
                            (const float*)prop, prop_ld, (const float*)feat2, feat2_ld, flow1, flow_prev, H, W, C,
                            (float*)cond1, cond1_ld, (float*)cond2, cond2_ld, flow2_out, (float*)flowpad, pad_ld);
-    } else {
-        FLAIR_CHECK(false, "flair_vsrpp_prep: bad dtype");
     }
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;

@@ -603,10 +603,15 @@ def axpby(x, y, a, b, out=None, lo=float("-inf"), hi=float("inf")):
     return out
 
 
-def learned_range_variance(model_out, C, min_log, max_log):
+def learned_range_variance(model_out, C, min_log, max_log, out=None):
+    """out: optional (variance, log_variance) pair of contiguous (N,C,H,W) f32 tensors."""
     N, C2, H, W = model_out.shape
-    var = torch.empty((N, C, H, W), dtype=torch.float32, device=model_out.device)
-    logvar = torch.empty_like(var)
+    if out is None:
+        var = torch.empty((N, C, H, W), dtype=torch.float32, device=model_out.device)
+        logvar = torch.empty_like(var)
+    else:
+        var, logvar = out
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == (N, C, H, W) for t in out)
     check(lib().flair_learned_range_variance(ptr(model_out), N, C, H, W, ctypes.c_float(min_log),
                                              ctypes.c_float(max_log), ptr(var), ptr(logvar), stream()),
           "flair_learned_range_variance")
@@ -615,12 +620,14 @@ def learned_range_variance(model_out, C, min_log, max_log):
 
 # ------------------------------------------------------------------- degradation ops
 def depthwise_filter(x, filt, *, pad, out_stride=1, out_offset=0, stuff=1, stuff_offset=0, out_hw=None,
-                     reflect=False):
-    """x: (N,C,H,W) f32; filt: (kh,kw) f32 device tensor shared by all planes."""
+                     reflect=False, out=None):
+    """x: (N,C,H,W) f32; filt: (kh,kw) f32 device tensor shared by all planes; out: optional contiguous (N,C,*out_hw)."""
     N, C, H, W = x.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and filt.dtype == torch.float32 and filt.is_contiguous()
     Ho, Wo = out_hw
-    out = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (N, C, Ho, Wo)
     check(lib().flair_depthwise_filter(ptr(x), N * C, H, W, ptr(filt), filt.shape[0], filt.shape[1], pad,
                                        out_stride, out_offset, stuff, stuff_offset, Ho, Wo, int(reflect), ptr(out),
                                        stream()),
@@ -644,25 +651,30 @@ def jpeg_roundtrip(x, q_luma, q_chroma, dct8, want_levels=False):
     return (out, [luma, chroma]) if want_levels else out
 
 
-def matmul(a, b):
-    """Batched f32 matmul; a: (B,M,K) or (M,K) shared; b: (B,K,N) or (K,N) shared."""
+def matmul(a, b, out=None):
+    """Batched f32 matmul; a: (B,M,K) or (M,K) shared; b: (B,K,N) or (K,N) shared; out: optional contiguous (B,M,N)."""
     assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
     batch = a.shape[0] if a.dim() == 3 else (b.shape[0] if b.dim() == 3 else 1)
     M, K = a.shape[-2:]
     N = b.shape[-1]
     assert b.shape[-2] == K
-    out = torch.empty((batch, M, N), dtype=torch.float32, device=a.device)
+    if out is None:
+        out = torch.empty((batch, M, N), dtype=torch.float32, device=a.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (batch, M, N)
     check(lib().flair_matmul_f32(ptr(a), ctypes.c_long(M * K if a.dim() == 3 else 0), ptr(b),
                                  ctypes.c_long(K * N if b.dim() == 3 else 0), ptr(out), batch, M, N, K, stream()),
           "flair_matmul_f32")
     return out
 
 
-def gather_mac(x, outer, lin, inner, fov, w):
-    """Resizer step: x viewed [outer][lin][inner] f32; fov int32 (taps,Lout); w f32 (taps,Lout)."""
+def gather_mac(x, outer, lin, inner, fov, w, out=None):
+    """Resizer step: x viewed [outer][lin][inner] f32; fov int32 (taps,Lout); w f32 (taps,Lout); out: optional contiguous
+    (outer, Lout, inner)."""
     taps, lout = fov.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and fov.dtype == torch.int32 and w.dtype == torch.float32
-    out = torch.empty((outer, lout, inner), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((outer, lout, inner), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (outer, lout, inner)
     check(lib().flair_gather_mac_f32(ptr(x), ctypes.c_long(outer), lin, ctypes.c_long(inner), ptr(fov.contiguous()),
                                      ptr(w.contiguous()), taps, lout, ptr(out), stream()), "flair_gather_mac_f32")
     return out

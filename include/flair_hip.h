@@ -252,7 +252,9 @@ int flair_affine_channels_f32(const float* x, int x_ld, int C, long P, float a, 
                               float hi, const float* sub, const float* mul, float* y, int y_ld,
                               hipStream_t stream);
 /* y = x + sigmoid(gate[f][c]) * (m - x): TemporalWrapper2's emb-gated residual mix
- * (sr3.py:203-226).  x, m, y: [F][HW] pixels of C channels; gate: [F][gate_ld] f32 logits. */
+ * (sr3.py:203-226).  x, m, y: [F][HW] pixels of C channels; gate: [F][gate_ld] f32 logits.
+ *   strides: x_ld / m_ld / y_ld at least C and multiples of 16 bytes, C a multiple of 4 (f32) / 8 (bf16); x, m, y 16-byte
+ *            aligned (FLAIR_ERR_ARG naming the argument otherwise); gate rows may have any stride gate_ld >= C. */
 int flair_gated_blend(const void* x, int x_ld, const void* m, int m_ld, const float* gate, int gate_ld,
                       int dtype, int C, int F, long HW, void* y, int y_ld, hipStream_t stream);
 /* y = act(x0 + x1) on P pixels of C channels (x1 may be NULL): the residual sum of the RetinaFace detector's ResNet-50
@@ -329,7 +331,9 @@ int flair_temporal_attention(const flair_tattn_params* p, const void* qkv, const
 /* ------------------------------------------------------------------ warps / resize
  * flow_warp (mmedit; unet_new.py:706,718,719): y[p] = bilinear(x, p + flow[p]),
  * flow [F][H][W] pixels of (dx,dy) f32, flow_ld floats apart; align_corners=True, zeros
- * (border=0) or border padding. */
+ * (border=0) or border padding.
+ *   strides: x_ld / y_ld at least C and multiples of 16 bytes, C a multiple of 4 (f32) / 8 (bf16); x, y 16-byte aligned;
+ *            flow_ld even and >= 2; the source clip spans < 2 GiB (FLAIR_ERR_ARG otherwise). */
 int flair_flow_warp(const void* x, int dtype, int x_ld, const float* flow, int flow_ld, int F,
                     int H, int W, int C, int border, void* y, int y_ld, hipStream_t stream);
 /* out = f1 + warp(f2, f1) on flow fields (unet_new.py:716-718). */
@@ -338,14 +342,21 @@ int flair_flow_compose(const float* f1, const float* f2, int F, int H, int W, fl
 /* The two warps of one BasicVSR++ propagation step with both flows given (unet_new.py:706,719):
  * cond1 = warp(prop, flow1), cond2 = warp(feat2, flow2); flow2 == NULL: first-order step (cond1 only).
  * The second-order flow (unet_new.py:716-718) depends on the optical flows alone, so the caller composes it
- * once per clip (flair_vsrpp_prep on the first denoising step) and reuses it for the other steps. */
+ * once per clip (flair_vsrpp_prep on the first denoising step) and reuses it for the other steps.
+ * One frame: tensors are [H][W][*]; the flows are dense [H][W][2] f32.
+ *   strides: prop_ld / feat2_ld / cond1_ld / cond2_ld at least C and multiples of 16 bytes, C a multiple of 4 (f32) /
+ *            8 (bf16); prop, feat2, cond1, cond2 16-byte aligned (FLAIR_ERR_ARG naming the argument otherwise; feat2 and
+ *            cond2 are looked at on a second-order step only); a source frame of H * W * ld elements spans < 2 GiB. */
 int flair_vsrpp_warp2(const void* prop, int prop_ld, const void* feat2, int feat2_ld, const float* flow1,
                       const float* flow2, int dtype, int H, int W, int C, void* cond1, int cond1_ld,
                       void* cond2, int cond2_ld, hipStream_t stream);
 /* One BasicVSR++ propagation step's alignment inputs in one launch (unet_new.py:704-722):
  * cond1 = warp(prop, flow1); flow2 = flow1 + warp(flow_prev, flow1); cond2 = warp(feat2, flow2);
- * flowpad[p][0..3] = (flow1, flow2) in the activation dtype.  flow_prev == NULL: first-order
- * step (cond2 / flow2_out untouched, flowpad[2..3] = 0).  One frame: tensors are [H][W][*]. */
+ * flowpad[p][0..3] = (flow1, flow2) in the activation dtype (channels 4 .. pad_ld - 1 are left as they are).
+ * flow_prev == NULL: first-order step (cond2 / flow2_out untouched, flowpad[2..3] = 0).  One frame: tensors are
+ * [H][W][*]; flow1, flow_prev and flow2_out are dense [H][W][2] f32.
+ *   strides: as flair_vsrpp_warp2 for prop / feat2 / cond1 / cond2; flowpad is an input segment of the offset convolution,
+ *            so pad_ld is at least 4 and a multiple of 16 bytes and flowpad 16-byte aligned (FLAIR_ERR_ARG otherwise). */
 int flair_vsrpp_prep(const void* prop, int prop_ld, const void* feat2, int feat2_ld,
                      const float* flow1, const float* flow_prev, int dtype, int H, int W, int C,
                      void* cond1, int cond1_ld, void* cond2, int cond2_ld, float* flow2_out,
@@ -427,14 +438,21 @@ int flair_gather_mac_f32(const float* x, long outer, int Lin, long inner, const 
  * aux_model(pred_xstart, t, x)).  Its convolutions, GroupNorms, 1x1 projections and 8 x 64 multi-head attention
  * run on the entry points above; these are the pieces only the prior needs. */
 /* nn.LayerNorm(C) over the channels of each of `rows` pixels (codeformer.py:541-542, :639), eps inside the
- * square root.  Optional second output y2 = y + pos[row % pos_rows][C] (q = k = norm(x) + pos, :561-562). */
+ * square root.  Optional second output y2 = y + pos[row % pos_rows][C] (q = k = norm(x) + pos, :561-562).
+ *   limits : C a multiple of 4 (f32) / 8 (bf16), at most 1024 (f32) / 2048 (bf16): a wave holds the row, four 16-byte
+ *            pieces per lane.
+ *   strides: x_ld / y_ld / y2_ld at least C and multiples of 16 bytes; x, y, y2 16-byte aligned (FLAIR_ERR_ARG naming the
+ *            argument otherwise; y2_ld is looked at only when y2 is given); gamma, beta, pos dense f32. */
 int flair_layernorm_nhwc(const void* x, int dtype, int x_ld, long rows, int C, const float* gamma,
                          const float* beta, float eps, void* y, int y_ld, const float* pos, int pos_rows,
                          void* y2, int y2_ld, hipStream_t stream);
 /* Attention with heads of any width (AttnBlock.forward, codeformer.py:217-241: one head of C = 512 over the 256
  * pixels of the 16x16 level).  Same layout contract as flair_qkv_attention; head_dim a multiple of 8 (bf16) / 4
  * (f32), 64 * (head_dim + L) bytes of LDS <= 128 KiB.  A 16-row VALU kernel: flair_qkv_attention calls it only for
- * widths it has no MFMA kernel for (multiples of 8 other than 32, 64, 128 and 192 ... 1024 in steps of 64). */
+ * widths it has no MFMA kernel for (multiples of 8 other than 32, 64, 128 and 192 ... 1024 in steps of 64).
+ *   strides: ld, out_ld, q_off, k_off, v_off and head_stride multiples of 16 bytes; the last head fits its row,
+ *            max(q_off, k_off, v_off) + (heads - 1) * head_stride + head_dim <= ld, and heads * head_dim <= out_ld; qkv and
+ *            out 16-byte aligned (FLAIR_ERR_ARG otherwise: the rules of flair_qkv_attention). */
 int flair_attention_wide(const flair_attn_params* p, const void* qkv, void* out, hipStream_t stream);
 /* idx[row] = argmax_n logits[row][n] (softmax + topk(1) of codeformer.py:727-728; first index on ties) and
  * y[row][0..D) = codebook[idx[row]] (VectorQuantizer.get_codebook_feat, :82-94).  codebook: [N][D] f32.
@@ -452,7 +470,9 @@ int flair_vq_nearest_nhwc(const void* z, int dtype, int ld, long rows, int D, co
  * per (frame, channel) mean and sqrt(unbiased variance + eps) of both, y = (content - mc) / sc * ss + ms. */
 int flair_adain_nhwc(const void* content, int c_ld, const void* style, int s_ld, int dtype, int frames, int HW,
                      int C, float eps, void* y, int y_ld, hipStream_t stream);
-/* Fuse_sft_block tail (codeformer.py:595-596): y = dec + w * (dec * scale + shift) over n dense elements. */
+/* Fuse_sft_block tail (codeformer.py:595-596): y = dec + w * (dec * scale + shift) over n dense elements.
+ *   strides: none (dense); n a multiple of 4 (f32) / 8 (bf16); dec, scale, shift, y 16-byte aligned (FLAIR_ERR_ARG naming
+ *            the pointer otherwise). */
 int flair_sft_fuse(const void* dec, const void* scale, const void* shift, float w, int dtype, long n, void* y,
                    hipStream_t stream);
 

@@ -123,27 +123,42 @@ def test_jpeg_roundtrip_vs_oracle(dev, qf):
     assert frac_bad <= 5e-3, (frac_bad, diff.max().item())
 
 
-@pytest.mark.parametrize("qf", [10, 60, 90])
-def test_jpeg_quantised_levels_bit_exact(dev, qf):
-    """The integer stage of the codec: the levels round(DCT / q) the HIP path quantises to (what the reference's
-    jpeg_encode returns, jpeg.py:108-114) equal the oracle's integers exactly, except where the oracle's own
-    pre-rounding value sits within 2e-3 of a .5 boundary (an f32 last-bit difference in a DCT sum may round either
-    way there); such coefficients must differ by at most one level and be rare."""
-    from flair_amd.guided_diffusion.jpeg import jpeg_encode
-    from oracle import degrade as odeg
-    g = torch.Generator().manual_seed(100 + qf)
+def _jpeg_image(seed, S):
+    g = torch.Generator().manual_seed(seed)
     base = torch.rand(2, 3, 8, 8, generator=g) * 2 - 1
-    x = (torch.nn.functional.interpolate(base, (64, 64), mode="bilinear") + 0.1 * torch.randn(2, 3, 64, 64, generator=g)).clamp(-1, 1)
-    ref_luma, ref_chroma = odeg.jpeg_encode(x, qf)
-    # the oracle's values just before .round(): recompute them with the same helpers
+    return (torch.nn.functional.interpolate(base, (S, S), mode="bilinear") + 0.1 * torch.randn(2, 3, S, S, generator=g)).clamp(-1, 1)
+
+
+def _jpeg_pre_rounding(x, qf):
+    """The oracle's luma / chroma values just before .round(), recomputed with its own helpers."""
+    from oracle import degrade as odeg
+    S = x.shape[-1]
     xx = (x + 1) / 2 * 255
     m = torch.tensor([[0.299, 0.587, 0.114], [-0.1687, -0.3313, 0.5], [0.5, -0.4187, -0.0813]])
     ycc = torch.einsum("nchw,kc->nkhw", xx, m).clone()
     ycc[:, 1:] += 128
     q1, q2 = odeg.quant_tables(qf)
     D = odeg._dct_matrix()
-    pre_l = odeg._unblocks(odeg._lin2d(odeg._blocks(ycc[:, 0:1]).reshape(-1, 8, 8) - 128, D).view(-1, 1, 8, 8) / q1, 2, 1, 64)
-    pre_c = odeg._unblocks(odeg._lin2d(odeg._blocks(ycc[:, 1:, ::2, ::2]).reshape(-1, 8, 8) - 128, D).view(-1, 2, 8, 8) / q2, 2, 2, 32)
+    pre_l = odeg._unblocks(odeg._lin2d(odeg._blocks(ycc[:, 0:1]).reshape(-1, 8, 8) - 128, D).view(-1, 1, 8, 8) / q1, 2, 1, S)
+    pre_c = odeg._unblocks(odeg._lin2d(odeg._blocks(ycc[:, 1:, ::2, ::2]).reshape(-1, 8, 8) - 128, D).view(-1, 2, 8, 8) / q2, 2, 2,
+                           S // 2)
+    return pre_l, pre_c
+
+
+# S = 64 keeps the ids it had before the size became a parameter
+@pytest.mark.parametrize("qf,S", [pytest.param(qf, S, id=str(qf) if S == 64 else f"{qf}-S{S}")
+                                  for S in (64, 16, 48) for qf in (10, 60, 90)])
+def test_jpeg_quantised_levels_bit_exact(dev, qf, S):
+    """The integer stage of the codec: the levels round(DCT / q) the HIP path quantises to (what the reference's
+    jpeg_encode returns, jpeg.py:108-114) equal the oracle's integers exactly, except where the oracle's own
+    pre-rounding value sits within 2e-3 of a .5 boundary (an f32 last-bit difference in a DCT sum may round either
+    way there); such coefficients must differ by at most one level and be rare.  S = 16: one chroma block per plane and
+    image; S = 48: block counts (36 luma, 9 chroma per plane) that are no power of two."""
+    from flair_amd.guided_diffusion.jpeg import jpeg_encode
+    from oracle import degrade as odeg
+    x = _jpeg_image(100 + qf, S)
+    ref_luma, ref_chroma = odeg.jpeg_encode(x, qf)
+    pre_l, pre_c = _jpeg_pre_rounding(x, qf)
     assert torch.equal(pre_l.round(), ref_luma) and torch.equal(pre_c.round(), ref_chroma)
     got_luma, got_chroma = (t.cpu() for t in jpeg_encode(x.to(dev), qf))
     from tests.util import parity_log
@@ -155,7 +170,24 @@ def test_jpeg_quantised_levels_bit_exact(dev, qf):
         assert (got - ref).abs().max().item() <= 1.0 and near_tie.float().mean().item() < 0.01
         report.append(f"{name}: {int(near_tie.sum())} of {near_tie.numel()} coefficients within 2e-3 of a .5 boundary "
                       f"({100 * near_tie.float().mean().item():.3f} %, exempt), {int((got != ref).sum())} of them one level off")
-    parity_log(f"JPEG quantised levels qf={qf} (2 x 3 x 64 x 64): bit-exact outside the exempt set; " + "; ".join(report))
+    parity_log(f"JPEG quantised levels qf={qf} (2 x 3 x {S} x {S}): bit-exact outside the exempt set; " + "; ".join(report))
+
+
+@pytest.mark.parametrize("S,qf,seed", [(16, 10, 110), (16, 30, 6), (48, 10, 88), (48, 30, 41)])
+def test_jpeg_roundtrip_small_sizes_every_pixel(dev, S, qf, seed):
+    """jpeg_decode(jpeg_encode(x)) at 16 and 48 pixels, where one flipped level would be 12.5 % / 1.4 % of the image
+    and the 0.5 % pixel cap of test_jpeg_roundtrip_vs_oracle would mean nothing.  The seeds were picked on the CPU so that
+    no coefficient of the oracle comes within 2e-3 of a .5 boundary (asserted first), so no level can flip and every
+    pixel must agree to the 1e-4 that test allows outside flipped blocks."""
+    from flair_amd.guided_diffusion.jpeg import jpeg_decode, jpeg_encode
+    from oracle import degrade as odeg
+    x = _jpeg_image(seed, S)
+    for pre in _jpeg_pre_rounding(x, qf):
+        assert not (((pre - pre.floor()) - 0.5).abs() < 2e-3).any(), "the seed no longer avoids the .5 boundaries"
+    ref = odeg.jpeg_decode(odeg.jpeg_encode(x, qf), qf)
+    got = jpeg_decode(jpeg_encode(x.to(dev), qf), qf).cpu()
+    err = (got - ref).abs().max().item()
+    assert err <= 1e-4, f"jpeg round trip S={S} qf={qf}: max|err|={err:.3e} > 1e-4"
 
 
 @pytest.mark.parametrize("f", [8, 16])

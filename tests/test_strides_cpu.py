@@ -296,3 +296,185 @@ def test_affine_and_dwconv_refuse_strides():
     _refused(lib.flair_dwconv_nhwc(P16, 10, 1, 4, 4, 8, 1, P16, P16, None, None, 8, 2, P16, 8, None), "x_ld = 10")
     _refused(lib.flair_dwconv_nhwc(P16, 8, 1, 4, 4, 8, 1, P16, P16, None, None, 8, 2, P16, 6, None), "y_ld = 6")
     _refused(lib.flair_dwconv_nhwc(P8, 8, 1, 4, 4, 8, 1, P16, P16, None, None, 8, 2, P16, 8, None), "flair_dwconv_nhwc")
+
+
+# ------------------------------------------------------------------------------------------------ prior / warp / sampler
+# The entries below move 16-byte pieces at p * ld + c0: every stride holds the C channels and is 16-byte granular, every
+# tensor pointer is 16-byte aligned.  One refusal per argument, each naming it.
+def _vsrpp(which, dtype, *, C=64, ld=None, ptr=None, pad_ld=None, second=True):
+    """ld / ptr: {name: value} overrides of prop / feat2 / cond1 / cond2 (flowpad: ptr only)."""
+    lib = _lib()
+    ld, ptr = dict(ld or {}), dict(ptr or {})
+    l = {n: ld.get(n, C) for n in ("prop", "feat2", "cond1", "cond2")}
+    q = {n: ptr.get(n, P16) for n in ("prop", "feat2", "cond1", "cond2", "flowpad")}
+    flow2 = P16 if second else None
+    if which == "warp2":
+        return lib.flair_vsrpp_warp2(q["prop"], l["prop"], q["feat2"] if second else None, l["feat2"] if second else 0, P16,
+                                     flow2, dtype, 8, 8, C, q["cond1"], l["cond1"], q["cond2"] if second else None,
+                                     l["cond2"] if second else 0, None)
+    return lib.flair_vsrpp_prep(q["prop"], l["prop"], q["feat2"] if second else None, l["feat2"] if second else 0, P16,
+                                flow2, dtype, 8, 8, C, q["cond1"], l["cond1"], q["cond2"] if second else None,
+                                l["cond2"] if second else 0, P16 if second else None, q["flowpad"],
+                                (32 if dtype else 16) if pad_ld is None else pad_ld, None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("which", ["warp2", "prep"])
+def test_vsrpp_entries_refuse_strides(which, dtype):
+    g = 8 if dtype else 4
+    fn = f"flair_vsrpp_{which}"
+    for name in ("prop", "feat2", "cond1", "cond2"):
+        _refused(_vsrpp(which, dtype, ld={name: 64 - g}), fn, f"{name} stride/alignment", f"{name}_ld = {64 - g}")
+        _refused(_vsrpp(which, dtype, ld={name: 64 + g // 2}), fn, f"{name} stride/alignment", f"{name}_ld = {64 + g // 2}")
+        _refused(_vsrpp(which, dtype, ptr={name: P8}), fn, f"{name} stride/alignment")
+    # a first-order step has no feat2 / cond2, and still checks prop / cond1
+    _refused(_vsrpp(which, dtype, ld={"prop": 64 - g}, second=False), fn, "prop stride/alignment")
+    _refused(_vsrpp(which, dtype, ptr={"cond1": P8}, second=False), fn, "cond1 stride/alignment")
+    _refused(_vsrpp(which, 2), fn, "bad dtype")
+    _refused(_vsrpp(which, -1), fn, "bad dtype")
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_vsrpp_prep_refuses_a_bad_flowpad(dtype):
+    g = 8 if dtype else 4
+    _refused(_vsrpp("prep", dtype, pad_ld=0), "flowpad stride/alignment", "pad_ld = 0")
+    _refused(_vsrpp("prep", dtype, pad_ld=2), "flowpad stride/alignment", "pad_ld = 2")
+    _refused(_vsrpp("prep", dtype, pad_ld=4 * g + g // 2), "flowpad stride/alignment", f"pad_ld = {4 * g + g // 2}")
+    _refused(_vsrpp("prep", dtype, ptr={"flowpad": P8}), "flowpad stride/alignment")
+    _refused(_vsrpp("prep", dtype, ptr={"flowpad": P2} if dtype else {"flowpad": P8}, second=False), "flowpad stride/alignment")
+
+
+def _blend(dtype, C=64, x_ld=64, m_ld=64, y_ld=64, x=P16, m=P16, y=P16):
+    return _lib().flair_gated_blend(x, x_ld, m, m_ld, P16, C, dtype, C, 2, ctypes.c_long(16), y, y_ld, None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_gated_blend_refuses_strides(dtype):
+    g = 8 if dtype else 4
+    for name in ("x", "m", "y"):
+        _refused(_blend(dtype, **{f"{name}_ld": 64 - g}), "flair_gated_blend", f"{name} stride/alignment", f"{name}_ld = {64 - g}")
+        _refused(_blend(dtype, **{f"{name}_ld": 64 + g // 2}), "flair_gated_blend", f"{name} stride/alignment",
+                 f"{name}_ld = {64 + g // 2}")
+        _refused(_blend(dtype, **{name: P8}), "flair_gated_blend", f"{name} stride/alignment")
+    _refused(_lib().flair_gated_blend(P16, 64, P16, 64, P16, 56, dtype, 64, 2, ctypes.c_long(16), P16, 64, None),
+             "flair_gated_blend")                                                              # gate_ld below C
+
+
+def _ln(dtype, C=64, x_ld=None, y_ld=None, y2_ld=None, x=P16, y=P16, y2=P16):
+    ld = lambda v: C if v is None else v
+    return _lib().flair_layernorm_nhwc(x, dtype, ld(x_ld), ctypes.c_long(7), C, P16, P16, ctypes.c_float(1e-5), y, ld(y_ld),
+                                       P16 if y2 is not None else None, 7 if y2 is not None else 0, y2, ld(y2_ld), None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_layernorm_refuses_strides(dtype):
+    g = 8 if dtype else 4
+    for name in ("x", "y", "y2"):
+        _refused(_ln(dtype, **{f"{name}_ld": 64 - g}), "flair_layernorm_nhwc", f"{name} stride/alignment", f"{name}_ld = {64 - g}")
+        _refused(_ln(dtype, **{f"{name}_ld": 64 + g // 2}), "flair_layernorm_nhwc", f"{name} stride/alignment")
+        _refused(_ln(dtype, **{name: P8}), "flair_layernorm_nhwc", f"{name} stride/alignment")
+    # without the second output its stride is not looked at, the others still are
+    _refused(_ln(dtype, y2=None, y2_ld=0, y_ld=64 - g), "y stride/alignment")
+    # one 16-byte piece per lane and four pieces: C <= 1024 (f32) / 2048 (bf16)
+    limit = 64 * 4 * g
+    _refused(_ln(dtype, C=limit + g), "flair_layernorm_nhwc", f"C={limit + g}", f"at most {limit}")
+    _refused(_ln(dtype, C=limit, x_ld=limit - g), "x stride/alignment")          # the limit itself passes the C check
+
+
+def _wide(dtype, *, L=35, heads=3, d=40, ld=None, out_ld=None, offs=None, head_stride=None, qkv=P16, out=P16):
+    from flair_amd import ops
+    C = heads * d
+    p = ops.AttnParams()
+    p.dtype, p.frames, p.L, p.heads, p.head_dim = dtype, 1, L, heads, d
+    p.ld = 3 * C if ld is None else ld
+    p.out_ld = C if out_ld is None else out_ld
+    p.q_off, p.k_off, p.v_off = offs or (0, C, 2 * C)
+    p.head_stride = d if head_stride is None else head_stride
+    p.scale = 0.125
+    return _lib().flair_attention_wide(ctypes.byref(p), qkv, out, None)
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_attention_wide_refuses_strides(dtype):
+    g = 8 if dtype else 4
+    C = 120
+    _refused(_wide(dtype, ld=3 * C - g), "flair_attention_wide", "exceed ld = %d" % (3 * C - g))
+    _refused(_wide(dtype, ld=3 * C + g, offs=(0, C, 2 * C + 2 * g)), "flair_attention_wide", "exceed ld")   # v of the last head
+    _refused(_wide(dtype, ld=3 * C, offs=(2 * C + g, C, 0)), "flair_attention_wide", "exceed ld")           # q the highest
+    _refused(_wide(dtype, heads=1, d=C, ld=2 * C, head_stride=2 * C, offs=(0, C + g, C)), "exceed ld")      # k the highest
+    _refused(_wide(dtype, ld=9 * C, head_stride=3 * C, offs=(0, 40, 80), out_ld=C - g), "flair_attention_wide",
+             f"out_ld = {C - g}", f"heads * head_dim = {C}")
+    _refused(_wide(dtype, out_ld=C + g // 2), "flair_attention_wide", f"out_ld = {C + g // 2}")
+    _refused(_wide(dtype, qkv=P8), "flair_attention_wide", "16-byte aligned")
+    _refused(_wide(dtype, out=P8), "flair_attention_wide", "16-byte aligned")
+    _refused(_wide(dtype, ld=3 * C + g // 2), "flair_attention_wide", "multiples of")
+    _refused(_wide(dtype, offs=(-g, C, 2 * C)), "flair_attention_wide", "exceed ld")
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_sft_fuse_refuses_misaligned_pointers(dtype):
+    lib = _lib()
+    n = ctypes.c_long(64)
+    w = ctypes.c_float(0.5)
+    for i, name in enumerate(("dec", "scale", "shift", "y")):
+        for bad in (P8, P2):
+            a = [P16, P16, P16, P16]
+            a[i] = bad
+            _refused(lib.flair_sft_fuse(a[0], a[1], a[2], w, dtype, n, a[3], None), "flair_sft_fuse", f"{name} = ",
+                     "16-byte aligned")
+
+
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_flow_warp_refuses_strides(dtype):
+    lib = _lib()
+    g = 8 if dtype else 4
+
+    def warp(x=P16, x_ld=64, y=P16, y_ld=64):
+        return lib.flair_flow_warp(x, dtype, x_ld, P16, 2, 1, 4, 4, 64, 0, y, y_ld, None)
+    _refused(warp(x_ld=64 - g), "flair_flow_warp", "x stride/alignment", f"x_ld = {64 - g}")
+    _refused(warp(y_ld=64 - g), "flair_flow_warp", "y stride/alignment", f"y_ld = {64 - g}")
+    _refused(warp(x_ld=64 + g // 2), "flair_flow_warp", "x stride/alignment")
+    _refused(warp(y_ld=64 + g // 2), "flair_flow_warp", "y stride/alignment")
+    _refused(warp(x=P8), "flair_flow_warp", "x stride/alignment")
+    _refused(warp(y=P8), "flair_flow_warp", "y stride/alignment")
+
+
+# ------------------------------------------------------------------------------------------------ the finite input guard
+def test_a_finite_guard_wins_an_arg_max_that_reads_past_n():
+    """tests/test_gpu_prior_strides.py surrounds flair_argmax_codebook's logits with ARGMAX_FILL instead of NaN: `NaN > best`
+    is false, so an arg-max that read one channel past N would never pick a NaN guard; it always picks this one."""
+    from tests.util import ARGMAX_FILL
+    assert ARGMAX_FILL == float(torch.tensor(ARGMAX_FILL, dtype=torch.bfloat16))      # exact in bf16
+    for dtype in (torch.float32, torch.bfloat16):
+        N = 37
+        buf, view = guarded(1, 2, 3, N, dtype, "cpu", coff=8, ld=N + 16, fill=ARGMAX_FILL)
+        logits = torch.randn(1, 2, 3, N, generator=torch.Generator().manual_seed(0)) * 50
+        view.copy_(logits.to(dtype))
+        rows = buf[1].reshape(6, -1).float()
+        assert torch.equal(rows[:, 8:8 + N].argmax(1), logits.to(dtype).float().reshape(6, N).argmax(1))
+        assert torch.all(rows[:, 8:8 + N + 1].argmax(1) == N)           # one channel too many: the guard wins, every row
+        assert torch.all(rows[:, 7:8 + N].argmax(1) == 0)               # one channel before the view: likewise
+        nan_buf, nan_view = guarded(1, 2, 3, N, dtype, "cpu", coff=8, ld=N + 16, fill=IN_FILL)
+        nan_view.copy_(logits.to(dtype))
+        r = nan_buf[1].reshape(6, -1).float()[:, 8:8 + N + 1]
+        best = torch.full((6,), float("-inf"))
+        pick = torch.zeros(6, dtype=torch.long)
+        for n in range(N + 1):                                          # the kernel's `v > best` scan: NaN never wins
+            win = r[:, n] > best
+            best, pick = torch.where(win, r[:, n], best), torch.where(win, torch.full_like(pick, n), pick)
+        assert torch.all(pick < N)
+
+
+def test_flat_guard_flags_strays():
+    from tests.util import assert_flat_untouched, flat_guarded
+    buf, v, before = flat_guarded((2, 3, 4), torch.bfloat16, "cpu", OUT_FILL, torch.arange(24.0))
+    assert buf.numel() == 24 + 128 and v.is_contiguous() and v.data_ptr() == buf[64:].data_ptr()
+    v.mul_(2)
+    assert_flat_untouched(buf, before, v)
+    with pytest.raises(AssertionError, match="read-only"):
+        assert_flat_untouched(buf, before)
+    for i in (63, 64 + 24):
+        b2 = buf.clone()
+        b2[i] = 0.0
+        with pytest.raises(AssertionError, match="outside the tensor"):
+            assert_flat_untouched(b2, before, b2[64:88].view(2, 3, 4))

@@ -73,6 +73,9 @@ def fixture_threads():
 # changes it).  The guards also keep stray accesses inside the test's own allocation.
 IN_FILL = float("nan")
 OUT_FILL = -1232.0          # exact in bf16 and f32
+# Around the logits of an arg-max: `NaN > best` is false, so a NaN guard never shows a read past the last class; a finite
+# value above every logit (exact in bf16) wins instead and changes the index.
+ARGMAX_FILL = 30720.0       # 15 * 2^11
 
 
 def guarded(T, H, W, C, dtype, dev, *, coff=0, ld=None, fill=OUT_FILL):
@@ -111,3 +114,30 @@ def assert_untouched(buf, before, view=None, what=""):
         where = "outside the view" if view is not None else "in a read-only buffer"
         raise AssertionError(f"{what}: {n} element(s) changed {where}, first at {idx}: "
                              f"{before[tuple(idx)].item()!r} -> {buf[tuple(idx)].item()!r}")
+
+
+def flat_guarded(shape, dtype, dev, fill, src=None, pad=64):
+    """A dense tensor of `shape` inside a longer 1-D allocation of `fill`, for entries that take no stride: pad elements
+    before and after (a multiple of 16 bytes in every dtype here, so the slice keeps the allocation's alignment).
+    -> (buf, dense view, copy of buf taken after `src` was written)."""
+    n = 1
+    for d in shape:
+        n *= d
+    buf = torch.full((n + 2 * pad,), fill, dtype=dtype, device=dev)
+    v = buf[pad:pad + n].view(shape)
+    if src is not None:
+        v.copy_(src.to(dev, dtype).view(shape))
+    return buf, v, buf.clone()
+
+
+def assert_flat_untouched(buf, before, view=None, what=""):
+    """The 1-D allocation is bitwise equal to `before` outside the dense slice `view` (everywhere when view is None)."""
+    changed = bits(buf) != bits(before)
+    if view is not None:
+        o = view.storage_offset() - buf.storage_offset()
+        changed[o:o + view.numel()] = False
+    n = int(changed.sum().item())
+    if n:
+        i = int(changed.nonzero()[0].item())
+        where = "outside the tensor" if view is not None else "in a read-only buffer"
+        raise AssertionError(f"{what}: {n} element(s) changed {where}, first at {i}: {before[i].item()!r} -> {buf[i].item()!r}")
