@@ -44,6 +44,11 @@ def _add_hparams(p, d):
     p.add_argument("--tau", type=int, default=d["tau"])
     p.add_argument("--aligned", action="store_true", default=d["aligned"],
                    help="frames are aligned 512 x 512 faces: run the prior on whole frames, no face detection")
+    p.add_argument("--faces", choices=("largest", "all"), default="largest",
+                   help="unaligned frames: run the prior on the largest face of every frame, each of which needs one "
+                        "(largest), or on every detected face, where frames may have none (all)")
+    p.add_argument("--max-faces", type=int, default=4, metavar="N",
+                   help="with --faces all: at most N faces per frame, largest first (bounds the prior's cost)")
     p.add_argument("--rho", type=float, default=d["rho"])
     p.add_argument("--noise-level", type=float, default=d["noise_level"])
     p.add_argument("--zeta", type=float, default=d["zeta"])
@@ -91,10 +96,23 @@ def prior_of(args):
     return args.prior or "codeformer"
 
 
+def faces_of(args):
+    """The ``faces`` / ``max_faces`` arguments of restore_video_files for a parsed command line (--max-faces is only read
+    with --faces all)."""
+    if args.faces != "all":
+        return {}
+    if args.aligned:
+        raise SystemExit("restore: --faces all belongs to unaligned frames (drop --aligned)")
+    if args.max_faces < 1:
+        raise SystemExit("restore: --max-faces must be at least 1")
+    return dict(faces="all", max_faces=args.max_faces)
+
+
 def main(argv=None):
     args = make_parser().parse_args(argv)
     task, jobs = jobs_of(args)
     prior = prior_of(args)
+    faces = faces_of(args)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -116,6 +134,7 @@ def main(argv=None):
                               parser=args.parser)
         hp = dict(aligned=args.aligned, t_start=args.t_start, jpeg_qf=args.jpeg_qf, w=args.w, tau=args.tau,
                   rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
+        hp.update(faces)
         pl.restore_many(jobs, lambda v, o: p.restore_video_files(v, o, **hp))
     finally:
         if dist.is_available() and dist.is_initialized():

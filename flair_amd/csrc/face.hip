@@ -6,6 +6,9 @@
 //       parsing arg-max -> MASK_COLORMAP -> 2 x cv2.GaussianBlur(mask, (101, 101), 26) on a float64 mask
 //       -> 10-pixel border zeroed, / 255 -> cv2.warpAffine(face | mask, inverse_affine, INTER_CUBIC)
 //   gaussian_diffusion.py:491  x_with_face = x0 * (1 - inv_mask) + inv_face * inv_mask
+// flair_warp_affine_cubic_indexed crops several faces out of one frame (:225-254 with a frame index per matrix);
+// flair_face_paste runs the two warps of :264-335 and the blend of :491 per output pixel for every face of the frame, in list
+// order -- a composition of the reference's per-face operations (the reference itself pastes one face per frame).
 // The reference round-trips every frame through numpy / OpenCV on the host, twice per step.  Here the
 // frames never leave HBM.  The arithmetic follows OpenCV 4.4's published algorithms (imgwarp.cpp: fixed-point
 // coordinates with 10 + 5 fractional bits, 32 x 32 table of a = -0.75 cubic weights held in float, the
@@ -30,18 +33,10 @@ __device__ __forceinline__ void cubic_coeffs(float x, float (&c)[4]) {
     c[3] = 1.f - c[0] - c[1] - c[2];
 }
 
-// T = element / accumulator type of the image (float frames, double masks); weights are float in both cases
-template <typename T>
-__global__ __launch_bounds__(256) void warp_affine_cubic_kernel(const T* src, int C, int Hs, int Ws, const double* minv,
-                                                                int Hd, int Wd, float b0, float b1, float b2, float b3,
-                                                                int pre, int post, float* dst, long total) {
+// Fixed-point source position of destination pixel (x, y) under the dst -> src matrix M (imgwarp.cpp WarpAffineInvoker):
+// (sx, sy) is the first of the 4 x 4 taps, cx / cy the weights of its columns / rows
+__device__ __forceinline__ void affine_taps(const double* M, int x, int y, int& sx, int& sy, float (&cx)[4], float (&cy)[4]) {
 #pragma clang fp contract(off)
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int x = (int)(i % Wd);
-    const int y = (int)((i / Wd) % Hd);
-    const int n = (int)(i / ((long)Wd * Hd));
-    const double* M = minv + 6 * n;
     const double ABS = (double)(1 << AB_BITS);
     const int round_delta = (1 << AB_BITS) / INTER_TAB / 2;
     // cvRound = round-half-to-even, as rint in the default rounding mode
@@ -49,20 +44,32 @@ __global__ __launch_bounds__(256) void warp_affine_cubic_kernel(const T* src, in
     const int X0 = (int)rint((M[1] * y + M[2]) * ABS) + round_delta;
     const int Y0 = (int)rint((M[4] * y + M[5]) * ABS) + round_delta;
     const int X = (X0 + adelta) >> (AB_BITS - INTER_BITS), Y = (Y0 + bdelta) >> (AB_BITS - INTER_BITS);
-    int sx = X >> INTER_BITS, sy = Y >> INTER_BITS;
+    sx = X >> INTER_BITS;
+    sy = Y >> INTER_BITS;
     sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);      // saturate_cast<short>
     sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
     sx -= 1;
     sy -= 1;
-    float cx[4], cy[4];
     cubic_coeffs((float)(X & (INTER_TAB - 1)) * (1.f / INTER_TAB), cx);
     cubic_coeffs((float)(Y & (INTER_TAB - 1)) * (1.f / INTER_TAB), cy);
-    const float border[4] = {b0, b1, b2, b3};
-    const long plane = (long)Hs * Ws;
-    const T* S0 = src + (long)n * C * plane;
-    const bool inner = (unsigned)sx < (unsigned)(Ws - 3 > 0 ? Ws - 3 : 0) && (unsigned)sy < (unsigned)(Hs - 3 > 0 ? Hs - 3 : 0);
-    const bool outside = sx >= Ws || sx + 4 <= 0 || sy >= Hs || sy + 4 <= 0;
-    auto fetch = [&](const T* P, long off) -> T {
+}
+
+__device__ __forceinline__ bool taps_inner(int sx, int sy, int Hs, int Ws) {
+    return (unsigned)sx < (unsigned)(Ws - 3 > 0 ? Ws - 3 : 0) && (unsigned)sy < (unsigned)(Hs - 3 > 0 ? Hs - 3 : 0);
+}
+
+__device__ __forceinline__ bool taps_outside(int sx, int sy, int Hs, int Ws) {
+    return sx >= Ws || sx + 4 <= 0 || sy >= Hs || sy + 4 <= 0;
+}
+
+// One BORDER_CONSTANT cubic sample of the plane P (Hs x Ws) at the taps of affine_taps.  T = element / accumulator type of
+// the image (float frames, double masks); weights are float in both cases.  This is the only copy of the tap arithmetic
+// and its rounding order: the crop / inverse-warp kernel and the paste kernel both call it.
+template <typename T>
+__device__ __forceinline__ T cubic_sample(const T* P, int Hs, int Ws, int sx, int sy, const float (&cx)[4],
+                                          const float (&cy)[4], T cv, int pre, bool inner, bool outside) {
+#pragma clang fp contract(off)
+    auto fetch = [&](long off) -> T {
         T v = P[off];
         if (pre) {                                               // VF.normalize(x, [-1]*3, [2]*3).clamp(0, 1) * 255
             float f = ((float)v + 1.f) / 2.f;
@@ -71,43 +78,112 @@ __global__ __launch_bounds__(256) void warp_affine_cubic_kernel(const T* src, in
         }
         return v;
     };
-    for (int k = 0; k < C; ++k) {
-        const T* P = S0 + k * plane;
-        const T cv = (T)border[k & 3];
-        T sum;
-        if (outside) {
-            sum = cv;
-        } else if (inner) {
-            // imgwarp.cpp remapBicubic: the four taps of a row are summed first (left to right), then the row sum is
-            // added to the running sum -- sum = row0; sum += row1; ... -- which rounds differently from 16 sequential adds
-            sum = 0;
+    T sum;
+    if (outside) {
+        sum = cv;
+    } else if (inner) {
+        // imgwarp.cpp remapBicubic: the four taps of a row are summed first (left to right), then the row sum is
+        // added to the running sum -- sum = row0; sum += row1; ... -- which rounds differently from 16 sequential adds
+        sum = 0;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                T row = fetch(P, (long)(sy + r) * Ws + sx) * (T)(cy[r] * cx[0]);
+        for (int r = 0; r < 4; ++r) {
+            T row = fetch((long)(sy + r) * Ws + sx) * (T)(cy[r] * cx[0]);
 #pragma unroll
-                for (int c = 1; c < 4; ++c) row = row + fetch(P, (long)(sy + r) * Ws + sx + c) * (T)(cy[r] * cx[c]);
-                sum = r == 0 ? row : sum + row;
-            }
-        } else {
-            sum = cv;                                            // cv * ONE, then (S - cv) * w for the taps inside the image
+            for (int c = 1; c < 4; ++c) row = row + fetch((long)(sy + r) * Ws + sx + c) * (T)(cy[r] * cx[c]);
+            sum = r == 0 ? row : sum + row;
+        }
+    } else {
+        sum = cv;                                                // cv * ONE, then (S - cv) * w for the taps inside the image
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int yi = sy + r;
-                if ((unsigned)yi >= (unsigned)Hs) continue;
+        for (int r = 0; r < 4; ++r) {
+            const int yi = sy + r;
+            if ((unsigned)yi >= (unsigned)Hs) continue;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int xi = sx + c;
-                    if ((unsigned)xi < (unsigned)Ws) sum += (fetch(P, (long)yi * Ws + xi) - cv) * (T)(cy[r] * cx[c]);
-                }
+            for (int c = 0; c < 4; ++c) {
+                const int xi = sx + c;
+                if ((unsigned)xi < (unsigned)Ws) sum += (fetch((long)yi * Ws + xi) - cv) * (T)(cy[r] * cx[c]);
             }
         }
-        float o = (float)sum;                                    // .astype(np.float32)
-        if (post) {                                              // / 255 -> VF.normalize(., .5, .5) -> clamp(-1, 1)
-            o = ((o / 255.0f) - 0.5f) / 0.5f;
-            o = fminf(fmaxf(o, -1.f), 1.f);
-        }
-        dst[((long)n * C + k) * Hd * Wd + (long)y * Wd + x] = o;
     }
+    return sum;
+}
+
+// .astype(np.float32), then / 255 -> VF.normalize(., .5, .5) -> clamp(-1, 1) when post
+__device__ __forceinline__ float warp_post(float o, int post) {
+#pragma clang fp contract(off)
+    if (post) {
+        o = ((o / 255.0f) - 0.5f) / 0.5f;
+        o = fminf(fmaxf(o, -1.f), 1.f);
+    }
+    return o;
+}
+
+// Output image n is sampled from source image src_index[n] (n itself when src_index is null)
+template <typename T>
+__global__ __launch_bounds__(256) void warp_affine_cubic_kernel(const T* src, const int* src_index, int Nsrc, int C, int Hs,
+                                                                int Ws, const double* minv, int Hd, int Wd, float b0, float b1,
+                                                                float b2, float b3, int pre, int post, float* dst, long total) {
+#pragma clang fp contract(off)
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int x = (int)(i % Wd);
+    const int y = (int)((i / Wd) % Hd);
+    const int n = (int)(i / ((long)Wd * Hd));
+    int s = n;
+    if (src_index) {                                             // the wrapper checks the range; the clamp keeps a bad list in bounds
+        s = src_index[n];
+        s = s < 0 ? 0 : (s >= Nsrc ? Nsrc - 1 : s);
+    }
+    int sx, sy;
+    float cx[4], cy[4];
+    affine_taps(minv + 6 * n, x, y, sx, sy, cx, cy);
+    const float border[4] = {b0, b1, b2, b3};
+    const long plane = (long)Hs * Ws;
+    const T* S0 = src + (long)s * C * plane;
+    const bool inner = taps_inner(sx, sy, Hs, Ws), outside = taps_outside(sx, sy, Hs, Ws);
+    for (int k = 0; k < C; ++k) {
+        const T sum = cubic_sample<T>(S0 + k * plane, Hs, Ws, sx, sy, cx, cy, (T)border[k & 3], pre, inner, outside);
+        dst[((long)n * C + k) * Hd * Wd + (long)y * Wd + x] = warp_post((float)sum, post);
+    }
+}
+
+// inverse_faces' two warps and the blend of gaussian_diffusion.py:491 per output pixel, for every face of the pixel's frame:
+// one thread per pixel, the C channels in registers, faces[frame_start[t] .. frame_start[t + 1]) blended in list order
+__global__ __launch_bounds__(256) void face_paste_kernel(const float* x0, int C, int H, int W, const float* faces,
+                                                         const double* masks, const double* minv, int K, int h, int w,
+                                                         const int* frame_start, float* out, long total) {
+#pragma clang fp contract(off)
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int x = (int)(i % W);
+    const int y = (int)((i / W) % H);
+    const int t = (int)(i / ((long)W * H));
+    const long P = (long)H * W, p = (long)y * W + x, fp = (long)h * w;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = k < C ? x0[((long)t * C + k) * P + p] : 0.f;
+    int k0 = frame_start[t], k1 = frame_start[t + 1];           // the wrapper checks the list; the clamp keeps a bad one in bounds
+    k0 = k0 < 0 ? 0 : k0;
+    k1 = k1 > K ? K : k1;
+    for (int f = k0; f < k1; ++f) {
+        int sx, sy;
+        float cx[4], cy[4];
+        affine_taps(minv + 6 * f, x, y, sx, sy, cx, cy);
+        // all 16 taps outside the face: the mask sample is 0 and v * (1 - 0) + face * 0 returns v's bits
+        if (taps_outside(sx, sy, h, w)) continue;
+        const bool inner = taps_inner(sx, sy, h, w);
+        const float m = (float)cubic_sample<double>(masks + f * fp, h, w, sx, sy, cx, cy, 0.0, 0, inner, false);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < C) {
+                const float s = cubic_sample<float>(faces + ((long)f * C + k) * fp, h, w, sx, sy, cx, cy, 0.f, 1, inner, false);
+                v[k] = v[k] * (1.f - m) + warp_post(s, 1) * m;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < C) out[((long)t * C + k) * P + p] = v[k];
 }
 
 __device__ __forceinline__ int reflect101(int i, int n) {
@@ -179,22 +255,57 @@ __global__ __launch_bounds__(256) void face_blend_kernel(const float* x0, const 
 
 }  // namespace
 
+static int launch_warp_affine_cubic(const void* src, int src_is_f64, const int* src_index, int Nsrc, int N, int C, int Hs,
+                                    int Ws, const double* minv, int Hd, int Wd, const float* border, int pre, int post,
+                                    float* dst, hipStream_t stream) {
+    const long total = (long)N * Hd * Wd;
+    const int grid = cdiv(total, 256);
+    float b[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < C; ++k) b[k] = border[k];
+    if (src_is_f64)
+        hipLaunchKernelGGL(warp_affine_cubic_kernel<double>, dim3(grid), dim3(256), 0, stream, (const double*)src, src_index,
+                           Nsrc, C, Hs, Ws, minv, Hd, Wd, b[0], b[1], b[2], b[3], 0, 0, dst, total);
+    else
+        hipLaunchKernelGGL(warp_affine_cubic_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)src, src_index,
+                           Nsrc, C, Hs, Ws, minv, Hd, Wd, b[0], b[1], b[2], b[3], pre, post, dst, total);
+    FLAIR_LAUNCH_CHECK();
+    return FLAIR_OK;
+}
+
 extern "C" int flair_warp_affine_cubic(const void* src, int src_is_f64, int N, int C, int Hs, int Ws, const double* minv,
                                        int Hd, int Wd, const float* border, int pre, int post, float* dst,
                                        hipStream_t stream) {
     FLAIR_CHECK(src && minv && dst && border, "flair_warp_affine_cubic: null argument");
     FLAIR_CHECK(N > 0 && C > 0 && C <= 4 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0, "flair_warp_affine_cubic: shape");
     FLAIR_CHECK(!src_is_f64 || (!pre && !post), "flair_warp_affine_cubic: the f64 form has no value transforms");
-    const long total = (long)N * Hd * Wd;
-    const int grid = cdiv(total, 256);
-    float b[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < C; ++k) b[k] = border[k];
-    if (src_is_f64)
-        hipLaunchKernelGGL(warp_affine_cubic_kernel<double>, dim3(grid), dim3(256), 0, stream, (const double*)src, C, Hs, Ws,
-                           minv, Hd, Wd, b[0], b[1], b[2], b[3], 0, 0, dst, total);
-    else
-        hipLaunchKernelGGL(warp_affine_cubic_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)src, C, Hs, Ws,
-                           minv, Hd, Wd, b[0], b[1], b[2], b[3], pre, post, dst, total);
+    return launch_warp_affine_cubic(src, src_is_f64, nullptr, N, N, C, Hs, Ws, minv, Hd, Wd, border, pre, post, dst, stream);
+}
+
+extern "C" int flair_warp_affine_cubic_indexed(const void* src, int src_is_f64, int Nsrc, const int* src_index, int N, int C,
+                                               int Hs, int Ws, const double* minv, int Hd, int Wd, const float* border,
+                                               int pre, int post, float* dst, hipStream_t stream) {
+    FLAIR_CHECK(src && src_index && minv && dst && border, "flair_warp_affine_cubic_indexed: null argument");
+    FLAIR_CHECK(N >= 0 && Nsrc > 0 && C > 0 && C <= 4 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0,
+                "flair_warp_affine_cubic_indexed: shape (N = %d >= 0, Nsrc = %d > 0, 0 < C = %d <= 4, sizes > 0)", N, Nsrc, C);
+    FLAIR_CHECK(!src_is_f64 || (!pre && !post), "flair_warp_affine_cubic_indexed: the f64 form has no value transforms");
+    if (N == 0) return FLAIR_OK;
+    return launch_warp_affine_cubic(src, src_is_f64, src_index, Nsrc, N, C, Hs, Ws, minv, Hd, Wd, border, pre, post, dst,
+                                    stream);
+}
+
+extern "C" int flair_face_paste(const float* x0, int T, int C, int H, int W, const float* faces, const double* masks,
+                                const double* minv, int K, int h, int w, const int* frame_start, float* out,
+                                hipStream_t stream) {
+    FLAIR_CHECK(x0 && out, "flair_face_paste: null x0 / out");
+    FLAIR_CHECK(frame_start, "flair_face_paste: null frame_start");
+    FLAIR_CHECK(K >= 0 && T > 0 && C > 0 && C <= 4 && H > 0 && W > 0,
+                "flair_face_paste: shape (K = %d >= 0, T = %d > 0, 0 < C = %d <= 4, H, W > 0)", K, T, C);
+    FLAIR_CHECK(K == 0 || (faces && masks && minv && h > 0 && w > 0),
+                "flair_face_paste: K = %d faces need faces, masks, minv and a positive face size", K);
+    const long total = (long)T * H * W;
+    FLAIR_CHECK(out + total * C <= x0 || x0 + total * C <= out, "flair_face_paste: out may not alias x0");
+    hipLaunchKernelGGL(face_paste_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, x0, C, H, W, faces, masks, minv, K,
+                       h > 0 ? h : 1, w > 0 ? w : 1, frame_start, out, total);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }

@@ -71,6 +71,7 @@ class FaceRestoreHelper(object):
             self.face_template[:, 0] += face_size * (crop_ratio[1] - 1) / 2
         self._const = {}
         self._minv_cache = {}
+        self._index_cache = {}
 
     # -- detection half (facelib/utils/face_restoration_helper.py:122-224): RetinaFace on the HIP kernels, landmark alignment on
     # the host (five points per face), the crop itself by flair_warp_affine_cubic
@@ -135,6 +136,32 @@ class FaceRestoreHelper(object):
         cropped = self.get_crop_face_from_affine_matrices(x[find_face_idx].contiguous(), affine_matrices)
         return cropped, affine_matrices, find_face_idx
 
+    def get_crop_faces_all(self, bathed_imgs, eye_dist_threshold=None, max_faces=None, face_template_resize=None,
+                           face_template_x_offset=None, face_template_y_offset=None):
+        """Every face of every frame (extension; the reference keeps one per frame): (B, 3, H, W) frames in [-1, 1] ->
+        (cropped faces (K, 3, face_h, face_w) in [-1, 1] or None, K affine matrices, face_frames: the frame of every face,
+        non-decreasing).  A frame may have no face or several (retinaface_utils.select_faces: largest first, at most
+        ``max_faces`` per frame); K = 0 gives (None, [], [])."""
+        if self.detector is not None:
+            raise NotImplementedError("flair_amd: get_crop_faces_all needs the package's own detector (face_det): an external "
+                                      "detector= object returns faces without their frames")
+        from .retinaface_utils import select_faces
+        face_template_resize = 1.0 if face_template_resize is None else face_template_resize
+        face_template_x_offset = 0.0 if face_template_x_offset is None else face_template_x_offset
+        face_template_y_offset = 0.0 if face_template_y_offset is None else face_template_y_offset
+        x = bathed_imgs.float().contiguous().to(self.device)
+        B, _, H, W = x.shape
+        dets = self._detector().batched_detect_faces(x, 0.5, pre=(127.5, 127.5, 0.0, 255.0), keep_empty=True)
+        if len(dets) != B:
+            raise RuntimeError(f"batched_detect_faces(keep_empty=True) returned {len(dets)} entries for {B} frames")
+        template = np.stack([self.face_template[:, 0] + face_template_x_offset,
+                             self.face_template[:, 1] + face_template_y_offset], axis=1) * face_template_resize
+        affine_matrices, face_frames = select_faces(dets, H, W, template, template_3points=self.template_3points,
+                                                    eye_dist_threshold=eye_dist_threshold, max_faces=max_faces)
+        if len(affine_matrices) == 0:
+            return None, [], []
+        return self.get_crop_face_from_affine_matrices(x, affine_matrices, face_frames), affine_matrices, face_frames
+
     def _consts(self, dev):
         c = self._const.get(dev)
         if c is None:
@@ -159,16 +186,48 @@ class FaceRestoreHelper(object):
             self._minv_cache[key] = hit
         return hit
 
-    def get_crop_face_from_affine_matrices(self, bathed_imgs, affine_matrices):
+    def _index(self, values, dev):
+        """A host list of ints as an int32 device tensor, cached by content like _minv (same reason)."""
+        key = (tuple(int(v) for v in values), str(dev))
+        hit = self._index_cache.get(key)
+        if hit is None:
+            hit = torch.tensor(key[0], dtype=torch.int32).to(dev)
+            if len(self._index_cache) >= 64:
+                self._index_cache.clear()
+            self._index_cache[key] = hit
+        return hit
+
+    @staticmethod
+    def frame_starts(face_frames, T):
+        """CSR form of a sorted face -> frame list: frame t owns faces starts[t] .. starts[t + 1] - 1."""
+        frames = [int(f) for f in face_frames]
+        if any(a > b for a, b in zip(frames, frames[1:])) or (frames and not 0 <= frames[0] <= frames[-1] < T):
+            raise ValueError(f"face_frames must be non-decreasing with entries in [0, {T}) (got {frames})")
+        starts, k = [0], 0
+        for t in range(T):
+            while k < len(frames) and frames[k] == t:
+                k += 1
+            starts.append(k)
+        return starts
+
+    def get_crop_face_from_affine_matrices(self, bathed_imgs, affine_matrices, face_frames=None):
         """(B, 3, H, W) in [-1, 1] -> (B, 3, face_h, face_w) in [-1, 1]: per frame
         ``cv2.warpAffine(clamp((x+1)/2, 0, 1)*255, M, face_size, INTER_CUBIC, BORDER_CONSTANT, (135, 133, 132))``,
-        ``/ 255``, ``(y - 0.5) / 0.5``, clamp -- one launch for the batch."""
+        ``/ 255``, ``(y - 0.5) / 0.5``, clamp -- one launch for the batch.
+        ``face_frames`` (extension): matrix k crops frame face_frames[k] -> (K, 3, face_h, face_w), read straight from
+        the frames by flair_warp_affine_cubic_indexed (no gathered copy of them)."""
         if len(affine_matrices) == 0:
             return None
         x = bathed_imgs.float().contiguous()
+        w, h = self.face_size
+        if face_frames is not None:
+            if len(face_frames) != len(affine_matrices):
+                raise ValueError("one frame index per affine matrix is needed")
+            return ops.warp_affine_cubic(x, self._minv(affine_matrices, x.device), (h, w), border=(135.0, 133.0, 132.0),
+                                         pre=True, post=True, src_index=self._index(face_frames, x.device),
+                                         src_index_host=face_frames)
         if len(affine_matrices) != x.shape[0]:
             raise ValueError("one affine matrix per frame is needed")
-        w, h = self.face_size
         return ops.warp_affine_cubic(x, self._minv(affine_matrices, x.device), (h, w), border=(135.0, 133.0, 132.0),
                                      pre=True, post=True)
 
@@ -189,3 +248,28 @@ class FaceRestoreHelper(object):
         inv_faces = ops.warp_affine_cubic(x, minv, (h, w), pre=True, post=True)
         inv_masks = ops.warp_affine_cubic(mask, minv, (h, w))
         return inv_faces, inv_masks
+
+    def paste_faces(self, x0, restored_faces, affine_matrices, face_frames):
+        """inverse_faces and the blend of gaussian_diffusion.py:491 for any number of faces per frame (extension): the K
+        restored faces ((K, 3, h, w) in [-1, 1], face k of frame face_frames[k], sorted by frame) are parsed and masked as
+        in inverse_faces, then warped back and blended into x0 (T, 3, H, W) by one flair_face_paste launch, in list order
+        (a later face of a frame lands on top of an earlier one).  Frames without a face come back as x0.  -> x_with_face."""
+        if self.face_parse is None:
+            raise RuntimeError("FaceRestoreHelper.paste_faces needs face_parse=ParseNet(...) or BiSeNet(...) (facelib/parsing/)")
+        x0 = x0.float().contiguous()
+        T = x0.shape[0]
+        if len(face_frames) != len(affine_matrices):
+            raise ValueError("one frame index per affine matrix is needed")
+        starts = self.frame_starts(face_frames, T)
+        dev = x0.device
+        if len(affine_matrices) == 0:
+            return ops.face_paste(x0, None, None, None, self._index(starts, dev), starts)
+        x = restored_faces.float().contiguous()
+        K, _, h, w = x.shape
+        if K != len(affine_matrices):
+            raise ValueError(f"{K} restored faces for {len(affine_matrices)} affine matrices")
+        lut, kern = self._consts(dev)
+        idx = self.face_parse.parse_indices(x)
+        mask = ops.face_mask_blur(idx.reshape(-1), K, h, w, lut, kern, repeats=2, edge=10, div=255.0)
+        minv = self._minv(affine_matrices, dev, twice=True)
+        return ops.face_paste(x0, x, mask, minv, self._index(starts, dev), starts)

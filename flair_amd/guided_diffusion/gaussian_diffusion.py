@@ -224,10 +224,11 @@ class GaussianDiffusion:
     def p_sample(self, model, x, t, clip_denoised=True, model_kwargs=None, restore_fn=None,
                  affine_matrices=None, face_restore_helper=None, aux_model=None, w=0.5,
                  start_timestep=None, tau=None, aligned=False, rho=0.35, prev_recon=None, gamma=None,
-                 noise=None, _step=None):
+                 noise=None, _step=None, face_frames=None):
         """One generalised-DDIM step (gaussian_diffusion.py:423-517).  ``w`` / ``gamma`` may be
         python floats or the broadcast tensors the reference passes (their first element is
-        used: the loop's values are uniform)."""
+        used: the loop's values are uniform).  ``face_frames`` (extension, aligned=False only): the frame of every
+        affine matrix, sorted -- a frame may then have no face or several; an empty list is the step with the prior off."""
         i = _uniform_step(t) if _step is None else _step
         out = self.p_mean_variance(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
                                    _step=i, _moments=False)
@@ -243,7 +244,15 @@ class GaussianDiffusion:
             start_timestep = self.num_timesteps - 1
         if tau is None:
             tau = 0
-        if aux_model is not None and i <= start_timestep and i >= tau:
+        if face_frames is not None:
+            if aligned:
+                raise ValueError("face_frames belongs to aligned=False (the aligned prior sees whole frames)")
+            if affine_matrices is None or len(face_frames) != len(affine_matrices):
+                raise ValueError("face_frames needs one entry per affine matrix")
+            if any(not 0 <= int(f) < x.shape[0] for f in face_frames):
+                raise ValueError(f"face_frames entries must be in [0, {x.shape[0]})")
+        no_faces = face_frames is not None and len(face_frames) == 0   # a window without any face: the prior is off
+        if aux_model is not None and i <= start_timestep and i >= tau and not no_faces:
             # NB: the reference evaluates the aux prior on the data-consistent x0; the fused
             # kernel applies consistency + blend in one pass, so materialise that x0 first.
             if restored is not None:
@@ -253,7 +262,19 @@ class GaussianDiffusion:
                 else:
                     x0c = ops.axpby(x0, restored, 1.0, -g)
                 x0, restored = x0c, None
-            if not aligned:
+            if not aligned and face_frames is not None:
+                # the branch below for K faces in T frames: crops read through a frame index, the prior on the K crops,
+                # one paste launch that leaves frames without a face as x0
+                if face_restore_helper is None:
+                    raise ValueError("aligned=False needs face_restore_helper and affine_matrices "
+                                     "(gaussian_diffusion.py:476-483)")
+                aux_face = face_restore_helper.get_crop_face_from_affine_matrices(x0, affine_matrices, face_frames)
+                aux_xt = face_restore_helper.get_crop_face_from_affine_matrices(x, affine_matrices, face_frames)
+                K = len(face_frames)                            # t is uniform: one entry per crop, without an index upload
+                tk = t if K == t.shape[0] else th.full((K,), i, device=t.device, dtype=t.dtype)
+                aux_face = aux_model(aux_face, tk, aux_xt)
+                aux = face_restore_helper.paste_faces(x0, aux_face, affine_matrices, face_frames)
+            elif not aligned:
                 # gaussian_diffusion.py:476-493: crop the faces out of x0 and x_t with the window's affine matrices, run
                 # the prior on the crops, warp its output back and paste it through the blurred parsing mask -- all on
                 # the GPU (flair_amd.guided_diffusion.face_restoration_helper; the reference goes through numpy / cv2)
@@ -300,7 +321,7 @@ class GaussianDiffusion:
     def sample(self, model, noise, model_kwargs, restore_fn, face_restore_helper, aux_model, post_fn,
                clip_denoised=True, sample_mode="ddpm", device=None, progress=False, w=0.5, tau=None,
                aligned=False, affine_matrices=None, rho=0.35, noise_level=None, prev_recon=None,
-               zeta=-1, t_start=-1, noise_fn=None):
+               zeta=-1, t_start=-1, noise_fn=None, face_frames=None):
         """gaussian_diffusion.py:372-421."""
         if tau is None:
             tau = 0
@@ -311,12 +332,12 @@ class GaussianDiffusion:
             model_kwargs=model_kwargs, progress=progress, device=device, restore_fn=restore_fn,
             face_restore_helper=face_restore_helper, aux_model=aux_model, post_fn=post_fn, w=w, tau=tau,
             aligned=aligned, affine_matrices=affine_matrices, rho=rho, noise_level=noise_level,
-            prev_recon=prev_recon, zeta=zeta, t_start=t_start, noise_fn=noise_fn)
+            prev_recon=prev_recon, zeta=zeta, t_start=t_start, noise_fn=noise_fn, face_frames=face_frames)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, model_kwargs=None, device=None,
                       progress=False, affine_matrices=None, restore_fn=None, face_restore_helper=None,
                       aux_model=None, post_fn=None, w=0.5, tau=None, aligned=False, rho=0.35,
-                      noise_level=None, prev_recon=None, zeta=-1, t_start=-1, noise_fn=None):
+                      noise_level=None, prev_recon=None, zeta=-1, t_start=-1, noise_fn=None, face_frames=None):
         """gaussian_diffusion.py:519-587.  ``noise_fn(step_index, like)`` (extension) supplies the
         per-step gaussian draw instead of ``th.randn_like`` so runs can share a noise tape."""
         final = None
@@ -325,7 +346,7 @@ class GaussianDiffusion:
                 device=device, progress=progress, restore_fn=restore_fn, affine_matrices=affine_matrices,
                 face_restore_helper=face_restore_helper, aux_model=aux_model, w=w, tau=tau,
                 aligned=aligned, rho=rho, noise_level=noise_level, prev_recon=prev_recon, zeta=zeta,
-                t_start=t_start, noise_fn=noise_fn):
+                t_start=t_start, noise_fn=noise_fn, face_frames=face_frames):
             if post_fn is not None:
                 post_fn(sample)
             final = sample
@@ -362,7 +383,7 @@ class GaussianDiffusion:
                                   device=None, progress=False, affine_matrices=None,
                                   face_restore_helper=None, aux_model=None, restore_fn=None, w=0.5,
                                   tau=None, aligned=False, rho=0.35, noise_level=None, prev_recon=None,
-                                  zeta=-1, t_start=-1, noise_fn=None):
+                                  zeta=-1, t_start=-1, noise_fn=None, face_frames=None):
         """gaussian_diffusion.py:589-689."""
         if device is None:
             device = next(model.parameters()).device
@@ -400,7 +421,7 @@ class GaussianDiffusion:
                                     face_restore_helper=face_restore_helper, aux_model=aux_model,
                                     w=float(np.float32(ws[i])), start_timestep=start_timestep, tau=tau,
                                     aligned=aligned, rho=rho, prev_recon=prev_recon,
-                                    gamma=float(np.float32(gammas[i])), noise=z, _step=i)
+                                    gamma=float(np.float32(gammas[i])), noise=z, _step=i, face_frames=face_frames)
                 img = out["sample"]
                 out["t"] = t
                 yield out

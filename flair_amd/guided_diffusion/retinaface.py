@@ -428,9 +428,12 @@ class RetinaFace(nn.Module):
         return np.concatenate((dets[keep, :], landmarks[keep]), axis=1)
 
     @torch.no_grad()
-    def batched_detect_faces(self, frames, conf_threshold=0.8, nms_threshold=0.4, use_origin_size=True, pre=None):
+    def batched_detect_faces(self, frames, conf_threshold=0.8, nms_threshold=0.4, use_origin_size=True, pre=None,
+                             keep_empty=False):
         """frames: (B, 3, H, W) float tensor in [0, 255] (what FaceRestoreHelper.get_crop_face passes).  Returns a list with
-        one (n_i, 15) array per frame that has detections (frames without are skipped, retinaface.py:393-395)."""
+        one (n_i, 15) array per frame that has detections (frames without are skipped, retinaface.py:393-395).
+        ``keep_empty`` (extension): one entry per frame instead, a (0, 15) array for a frame without a detection, so the
+        caller can pair faces with frames (FaceRestoreHelper.get_crop_faces_all)."""
         if not use_origin_size:
             raise NotImplementedError("flair_amd: use_origin_size=False is not built")
         self.resize = 1
@@ -442,6 +445,8 @@ class RetinaFace(nn.Module):
         for loc, conf, ldm in zip(b_loc, b_conf, b_ldm):
             inds = conf > conf_threshold
             if not inds.any():
+                if keep_empty:
+                    final.append(np.zeros((0, 15), dtype=np.float32))
                 continue
             dets = np.concatenate((loc[inds], conf[inds, None]), axis=1).astype(np.float32)
             ldm = ldm[inds]

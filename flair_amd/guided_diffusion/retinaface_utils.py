@@ -170,3 +170,38 @@ def get_center_face(det_faces, h=0, w=0, center=None):
     dist = [np.linalg.norm(np.array([(d[0] + d[2]) / 2, (d[1] + d[3]) / 2]) - c) for d in det_faces]
     i = dist.index(min(dist))
     return det_faces[i], i
+
+
+def select_faces(dets_per_frame, H, W, template, *, template_3points=False, eye_dist_threshold=None, max_faces=None):
+    """Which detections of every frame get the prior, and their alignment (extension: the reference keeps one face per
+    frame, facelib/utils/face_restoration_helper.py:166-199).  dets_per_frame: one (n_t, 15) array per frame (box, score,
+    five landmarks; ``batched_detect_faces(..., keep_empty=True)``), n_t = 0 for a frame without a face.  Per frame: drop
+    the detections whose eye distance is below ``eye_dist_threshold`` (:170-174), order the rest by decreasing box area
+    clamped to the H x W image (get_largest_face's area; ties keep the detector's order), keep the first ``max_faces``
+    (None: all) and fit each to ``template`` with estimate_affine_partial.  Returns (affine_matrices, face_frames): face k
+    belongs to frame face_frames[k], which is non-decreasing.  With max_faces=1 and a face in every frame these are the
+    matrices of get_crop_face(only_keep_largest=True)."""
+    if max_faces is not None and max_faces < 1:
+        raise ValueError("max_faces must be at least 1 (or None for every face)")
+
+    def loc(v, length):
+        return 0 if v < 0 else (length if v > length else v)
+    n = 11 if template_3points else 15
+    affine_matrices, face_frames = [], []
+    for t, bboxes in enumerate(dets_per_frame):
+        kept = []
+        for bbox in bboxes:
+            eye_dist = np.linalg.norm([bbox[5] - bbox[7], bbox[6] - bbox[8]])
+            if eye_dist_threshold is not None and eye_dist < eye_dist_threshold:
+                continue
+            kept.append(bbox)
+        areas = [(loc(d[2], W) - loc(d[0], W)) * (loc(d[3], H) - loc(d[1], H)) for d in kept]
+        order = sorted(range(len(kept)), key=lambda i: -areas[i])          # stable: ties keep detector order
+        for i in order[:max_faces]:
+            landmark = np.array([[kept[i][j], kept[i][j + 1]] for j in range(5, n, 2)])
+            M = estimate_affine_partial(landmark, template)
+            if M is None:                                                  # degenerate landmarks: nothing to align to
+                continue
+            affine_matrices.append(M)
+            face_frames.append(t)
+    return affine_matrices, face_frames

@@ -891,9 +891,20 @@ def sft_fuse(dec, scale, shift, w, out=None):
 
 
 # --------------------------------------------------------------------------- un-aligned prior branch (face crop / paste)
-def warp_affine_cubic(src, minv, out_hw, *, border=(0.0, 0.0, 0.0), pre=False, post=False):
+def _refuse(cond, what):
+    if not cond:
+        raise ValueError(what)
+
+
+def warp_affine_cubic(src, minv, out_hw, *, border=(0.0, 0.0, 0.0), pre=False, post=False, src_index=None,
+                      src_index_host=None):
     """cv2.warpAffine(INTER_CUBIC, BORDER_CONSTANT) per image (flair_warp_affine_cubic).  src: (N,C,Hs,Ws) f32 or f64
-    (masks, C = 1); minv: (N, 6) float64 DEVICE tensor, the dst -> src matrices; -> (N,C,Hd,Wd) f32."""
+    (masks, C = 1); minv: (N, 6) float64 DEVICE tensor, the dst -> src matrices; -> (N,C,Hd,Wd) f32.
+    ``src_index`` ((K,) int32 DEVICE tensor, with ``src_index_host``, the same K numbers as a host sequence, which is what
+    gets range-checked): output k is cropped from src[src_index[k]] with minv[k] (flair_warp_affine_cubic_indexed),
+    minv is (K, 6) and the result (K,C,Hd,Wd)."""
+    if src_index is not None:
+        return _warp_affine_cubic_indexed(src, minv, out_hw, border, pre, post, src_index, src_index_host)
     N, C, Hs, Ws = src.shape
     assert src.is_contiguous() and src.dtype in (torch.float32, torch.float64)
     assert minv.dtype == torch.float64 and minv.is_contiguous() and tuple(minv.shape) == (N, 6) and minv.is_cuda
@@ -902,6 +913,66 @@ def warp_affine_cubic(src, minv, out_hw, *, border=(0.0, 0.0, 0.0), pre=False, p
     b = (ctypes.c_float * 4)(*([float(v) for v in border] + [0.0] * 4)[:4])
     check(lib().flair_warp_affine_cubic(ptr(src), int(src.dtype == torch.float64), N, C, Hs, Ws, ptr(minv), Hd, Wd, b,
                                         int(pre), int(post), ptr(out), stream()), "flair_warp_affine_cubic")
+    return out
+
+
+def _warp_affine_cubic_indexed(src, minv, out_hw, border, pre, post, src_index, src_index_host):
+    what = "flair_warp_affine_cubic_indexed"
+    _refuse(src.dim() == 4 and src.dtype in (torch.float32, torch.float64) and src.is_contiguous(),
+            f"{what}: src must be a contiguous (N,C,Hs,Ws) float32 or float64 tensor")
+    Nsrc, C, Hs, Ws = src.shape
+    _refuse(src_index.dim() == 1 and src_index.dtype == torch.int32 and src_index.is_contiguous(),
+            f"{what}: src_index must be a contiguous (K,) int32 tensor")
+    K = src_index.shape[0]
+    _refuse(minv.dtype == torch.float64 and minv.is_contiguous() and tuple(minv.shape) == (K, 6),
+            f"{what}: minv must be a contiguous ({K}, 6) float64 tensor")
+    _refuse(src_index_host is not None and len(src_index_host) == K,
+            f"{what}: src_index_host (the {K} indices on the host) is needed for the range check")
+    _refuse(all(0 <= int(i) < Nsrc for i in src_index_host), f"{what}: src_index outside [0, {Nsrc})")
+    for t in (src, minv, src_index):
+        ptr(t)                                              # CPU tensors are refused (FlairHipError)
+    Hd, Wd = out_hw
+    out = torch.empty((K, C, Hd, Wd), dtype=torch.float32, device=src.device)
+    b = (ctypes.c_float * 4)(*([float(v) for v in border] + [0.0] * 4)[:4])
+    check(lib().flair_warp_affine_cubic_indexed(ptr(src), int(src.dtype == torch.float64), Nsrc, ptr(src_index), K, C, Hs, Ws,
+                                                ptr(minv), Hd, Wd, b, int(pre), int(post), ptr(out), stream()), what)
+    return out
+
+
+def face_paste(x0, faces, masks, minv, frame_start, frame_start_host, out=None):
+    """Paste K restored faces into T frames through their blurred masks in one launch (flair_face_paste): per pixel and per
+    face of the pixel's frame, in list order, v = v * (1 - m) + f * m with f / m the inverse cubic warps of the face / its
+    f64 mask -- what warp_affine_cubic(face), warp_affine_cubic(mask) and face_blend give face by face, bit for bit.
+    x0: (T,C,H,W) f32, C <= 4; faces: (K,C,h,w) f32; masks: (K,1,h,w) f64; minv: (K,6) f64; frame_start: (T+1,) int32 DEVICE
+    tensor and ``frame_start_host`` the same numbers on the host (checked here: non-decreasing from 0 to K); K = 0 (faces,
+    masks, minv None or empty) copies x0.  -> (T,C,H,W) f32, never x0's storage."""
+    what = "flair_face_paste"
+    _refuse(x0.dim() == 4 and x0.dtype == torch.float32 and x0.is_contiguous(), f"{what}: x0 must be a contiguous (T,C,H,W) float32 tensor")
+    T, C, H, W = x0.shape
+    K = 0 if faces is None else faces.shape[0]
+    h = w = 0
+    if K > 0:
+        _refuse(faces.dim() == 4 and faces.dtype == torch.float32 and faces.is_contiguous() and faces.shape[1] == C,
+                f"{what}: faces must be a contiguous (K,{C},h,w) float32 tensor")
+        h, w = faces.shape[2:]
+        _refuse(masks is not None and masks.dtype == torch.float64 and masks.is_contiguous() and tuple(masks.shape) == (K, 1, h, w),
+                f"{what}: masks must be a contiguous ({K},1,{h},{w}) float64 tensor")
+        _refuse(minv is not None and minv.dtype == torch.float64 and minv.is_contiguous() and tuple(minv.shape) == (K, 6),
+                f"{what}: minv must be a contiguous ({K},6) float64 tensor")
+    else:
+        faces = masks = minv = None
+    _refuse(frame_start.dtype == torch.int32 and frame_start.is_contiguous() and tuple(frame_start.shape) == (T + 1,),
+            f"{what}: frame_start must be a contiguous ({T + 1},) int32 tensor")
+    fs = [int(v) for v in frame_start_host]
+    _refuse(len(fs) == T + 1 and fs[0] == 0 and fs[-1] == K and all(a <= b for a, b in zip(fs, fs[1:])),
+            f"{what}: frame_start must be non-decreasing, start at 0 and end at K = {K} (got {fs})")
+    for t in (x0, faces, masks, minv, frame_start):
+        ptr(t)                                              # CPU tensors are refused (FlairHipError)
+    if out is None:
+        out = torch.empty_like(x0)
+    _refuse(out.dtype == torch.float32 and out.is_contiguous() and out.shape == x0.shape, f"{what}: out must match x0")
+    check(lib().flair_face_paste(ptr(x0), T, C, H, W, ptr(faces), ptr(masks), ptr(minv), K, h, w, ptr(frame_start), ptr(out),
+                                 stream()), what)
     return out
 
 

@@ -192,16 +192,19 @@ class Pipeline:
 
     def restore_video_files(self, video_path, output_path, *, aligned=MAIN_DEFAULTS["aligned"], t_start=-1, jpeg_qf=-1,
                             w=MAIN_DEFAULTS["w"], tau=5, rho=MAIN_DEFAULTS["rho"],
-                            noise_level=MAIN_DEFAULTS["noise_level"], zeta=MAIN_DEFAULTS["zeta"], seed=None):
+                            noise_level=MAIN_DEFAULTS["noise_level"], zeta=MAIN_DEFAULTS["zeta"], seed=None,
+                            faces="largest", max_faces=None):
         """Frame files of ``video_path`` -> ``output_path/{i:04d}.png`` (video_sample.py:334-492).  ``seed`` seeds
-        torch's generators first (the reference does not seed).  Returns the number of frames written."""
+        torch's generators first (the reference does not seed).  ``faces="all"`` (aligned=False only): the prior runs on
+        every detected face, at most ``max_faces`` per frame, and frames may have none (video.restore_window).  Returns
+        the number of frames written."""
         if seed is not None:
             torch.manual_seed(int(seed))
         hp = dict(w=w, rho=rho, noise_level=noise_level, zeta=zeta)
         return fio.restore_video_files(
             self.task, video_path, output_path, self.model, self.diffusion, self.restore_fn_for(jpeg_qf), size=self.size,
             device=self.device, aligned=aligned, face_helper=self.face_helper, aux_model=self.aux_model,
-            vsrpp_weights_fn=self.vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start)
+            vsrpp_weights_fn=self.vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, faces=faces, max_faces=max_faces)
 
 
 def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=100, kernels_path=None, prior=True,

@@ -89,15 +89,26 @@ def rnn_input(degraded_norm_clip, size):
     return _affine(big, 1.0, 0.0, -1.0, 1.0)
 
 
-def window_faces(face_helper, init_n, window_index=0, frame_indices=None):
+FACES = ("largest", "all")
+
+
+def window_faces(face_helper, init_n, window_index=0, frame_indices=None, faces="largest", max_faces=None):
     """Affine matrices of the window's faces (video_sample.py:446-448): one per frame, estimated on the normalised init
     frames ((T, 3, S, S) in [-1, 1]) with the largest face of every frame kept.  A frame without a face is a
-    ValueError naming the window and the frame's index in the video (the reference fails later, inside the sampler)."""
+    ValueError naming the window and the frame's index in the video (the reference fails later, inside the sampler).
+    ``faces="all"`` (extension) returns (matrices, face_frames) instead: every face of every frame, largest first and at
+    most ``max_faces`` per frame, face k in frame face_frames[k] of the window; frames without a face are simply absent
+    from the list, and a window without any gives ([], [])."""
+    if faces not in FACES:
+        raise ValueError(f"faces={faces!r}: one of {', '.join(FACES)}")
     T = init_n.shape[0]
     frames = list(frame_indices) if frame_indices is not None else list(range(T))
     if init_n.shape[-1] != face_helper.face_size[0] or init_n.shape[-2] != face_helper.face_size[1]:
         raise ValueError(f"aligned=False pastes faces at the helper's face size {face_helper.face_size}: frames of "
                          f"{tuple(init_n.shape[-2:])} must match it (video_sample.py restores 512 x 512 frames)")
+    if faces == "all":
+        _, mats, face_frames = face_helper.get_crop_faces_all(init_n, eye_dist_threshold=0.1, max_faces=max_faces)
+        return mats, face_frames
     _, mats, idx = face_helper.get_crop_face(init_n, only_keep_largest=True, eye_dist_threshold=0.1)
     if mats is None or len(idx) < T:
         # the helper pairs the detector's per-frame lists with the frames in order, so a frame without a detection
@@ -112,12 +123,14 @@ def window_faces(face_helper, init_n, window_index=0, frame_indices=None):
 
 def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, prev_recon=None, overlap=OVERLAP,
                    window_index=0, aux_model=wl.identity_aux, vsrpp_weights_fn=None, hp=None, tau=5, t_start=-1,
-                   noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, frame_indices=None):
+                   noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, frame_indices=None, faces="largest",
+                   max_faces=None):
     """One window of the loop (video_sample.py:371-485).  degraded01: (1, T, 3, h, w) in [0, 1] on the GPU;
     prev_recon: the previous window's last ``overlap`` results ((1, <=overlap, 3, S, S), [-1, 1] domain) or None.
     ``aligned=False`` (the reference's default, :275) detects the faces of the window's init frames with
     ``face_helper`` before the first step (:446-448) and runs the prior on their crops (:460-479); frame_indices
-    (the window's frames in the video) only name frames in its errors.
+    (the window's frames in the video) only name frames in its errors.  ``faces="all"`` (with aligned=False) runs the
+    prior on every detected face, at most ``max_faces`` per frame, and lets frames -- or the whole window -- have none.
     Returns (frames01 of the frames this window contributes, (T', 3, S, S) in [0, 1]; next prev_recon)."""
     hp = hp or wl.TASKS[task]
     dev = degraded01.device
@@ -125,11 +138,16 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
     deg = degraded01[0].float().contiguous()                                      # (T,3,h,w) in [0,1]
     T = deg.shape[0]
     init_n = init_frames(task, deg, size)[None]                                   # (1,T,3,S,S) in [-1,1]
-    mats = None
+    mats, face_frames = None, None
+    if faces not in FACES:
+        raise ValueError(f"faces={faces!r}: one of {', '.join(FACES)}")
     if not aligned:
         if face_helper is None:
             raise ValueError("aligned=False needs face_helper (a FaceRestoreHelper with a detector and a face parser)")
-        mats = window_faces(face_helper, init_n[0], wi, frame_indices)
+        if faces == "all":
+            mats, face_frames = window_faces(face_helper, init_n[0], wi, frame_indices, faces="all", max_faces=max_faces)
+        else:
+            mats = window_faces(face_helper, init_n[0], wi, frame_indices)
     deg_n, deg_n_clip = normalise(deg)
     deg_n = deg_n[None]
     t0 = diffusion.num_timesteps - 1 if t_start == -1 else t_start
@@ -145,7 +163,8 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
         restore_fn=restore_fn_for(deg_n), post_fn=None, face_restore_helper=None if aligned else face_helper,
         aux_model=aux_model, w=hp["w"], tau=tau, affine_matrices=mats, aligned=aligned, sample_mode="ddpm", rho=hp["rho"],
         noise_level=hp["noise_level"], prev_recon=prev_recon, zeta=hp["zeta"], t_start=t_start,
-        noise_fn=(lambda it, like, _wi=wi: noise_fn(_wi, it, like)) if noise_fn is not None else None)
+        noise_fn=(lambda it, like, _wi=wi: noise_fn(_wi, it, like)) if noise_fn is not None else None,
+        **({} if face_frames is None else dict(face_frames=face_frames)))
     keep = sample if prev_recon is None else sample[overlap:]                    # (T',3,S,S), [-1,1] domain
     nxt = keep[-overlap:].clone()[None] if overlap > 0 else None                 # (1,<=overlap,3,S,S), :481-483
     frames01 = _affine(_to_clip(keep.contiguous()), 0.5, 0.5, 0.0, 1.0)          # (clamp(x,-1,1)+1)/2
@@ -154,14 +173,14 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
 
 def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, aux_model=wl.identity_aux,
                   vsrpp_weights_fn=None, hp=None, tau=5, t_start=-1, length=FRAME_SLICE_LEN, overlap=OVERLAP,
-                  noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None):
+                  noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, faces="largest", max_faces=None):
     """degraded01: (1, N, 3, h, w) frames in [0, 1] on the GPU.  Returns (N, 3, size, size) in [0, 1].
 
     restore_fn_for(degraded_norm_window (1,T,3,h,w)) -> restore_fn(x0) is the data-consistency
     operator of the window (video_sample.py:455-459); vsrpp_weights_fn(init_norm (1,T,3,S,S)) supplies
     the per-pixel propagation weights of the bicubic tasks (face parsing, :427-444) and defaults to 1.0;
-    noise_fn / q_noise_fn(window_index, like) let tests share one noise tape with the oracle; aligned / face_helper:
-    see restore_window.
+    noise_fn / q_noise_fn(window_index, like) let tests share one noise tape with the oracle; aligned / face_helper /
+    faces / max_faces: see restore_window.
     (File-to-file form with decode / upload / encode overlapped: flair_amd.io.restore_video_files.)"""
     dev = degraded01.device
     n_frames = degraded01.shape[1]
@@ -173,7 +192,7 @@ def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, a
             task, degraded01[:, idx[0]:idx[-1] + 1], model, diffusion, restore_fn_for, size=size,
             prev_recon=prev_recon, overlap=overlap, window_index=wi, aux_model=aux_model,
             vsrpp_weights_fn=vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, noise_fn=noise_fn, q_noise_fn=q_noise_fn,
-            aligned=aligned, face_helper=face_helper, frame_indices=idx)
+            aligned=aligned, face_helper=face_helper, frame_indices=idx, faces=faces, max_faces=max_faces)
         out[filled:filled + frames01.shape[0]].copy_(frames01)
         filled += frames01.shape[0]
     return out[:filled]

@@ -62,7 +62,8 @@ const char* flair_last_error(void);
  * (3: round 2; 4: + face crop / paste entries, flair_bcast_weights; 5: round 4 entries; 6: + calibration launches;
  * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc; 9: + flair_vq_nearest_nhwc;
  * 10: + flair_dwconv7_nhwc, flair_dcn_params.raw_activated = 2 (VQFR's DCNv2Pack);
- * 11: + flair_global_avgpool_nhwc, flair_channel_gate_nhwc, flair_upsample_argmax_nhwc (BiSeNet face parsing)).
+ * 11: + flair_global_avgpool_nhwc, flair_channel_gate_nhwc, flair_upsample_argmax_nhwc (BiSeNet face parsing);
+ * 12: + flair_warp_affine_cubic_indexed, flair_face_paste (several faces per frame, frames without a face)).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -515,6 +516,25 @@ int flair_upsample_argmax_nhwc(const void* logits, int dtype, int ld, int F, int
  * clamp((y / 255 - 0.5) / 0.5, -1, 1) to the result (:246-253); dst: [N][C][Hd][Wd] f32.  C <= 4. */
 int flair_warp_affine_cubic(const void* src, int src_is_f64, int N, int C, int Hs, int Ws, const double* minv,
                             int Hd, int Wd, const float* border, int pre, int post, float* dst, hipStream_t stream);
+/* flair_warp_affine_cubic with a source index per output image: dst image n is cropped from src image src_index[n]
+ * (DEVICE int32 [N], every entry in [0, Nsrc)), so several faces come out of one frame without a copy of the frame
+ * (face_restoration_helper.py:225-254 applied per face).  src: [Nsrc][C][Hs][Ws]; minv: [N][6]; dst: [N][C][Hd][Wd].  Same
+ * kernel and arithmetic as flair_warp_affine_cubic: with src_index = 0 .. N-1 the two agree bit for bit.  N = 0 is a no-op. */
+int flair_warp_affine_cubic_indexed(const void* src, int src_is_f64, int Nsrc, const int* src_index, int N, int C, int Hs,
+                                    int Ws, const double* minv, int Hd, int Wd, const float* border, int pre, int post,
+                                    float* dst, hipStream_t stream);
+/* The paste of any number of faces per frame in one launch: per output pixel, v = x0, then for every face k of the pixel's
+ * frame in list order  f = flair_warp_affine_cubic(faces[k], minv[k], pre = 1, post = 1, border 0),
+ * m = (float) flair_warp_affine_cubic(masks[k], minv[k]) (the f64 form),  v = v * (1 - m) + f * m  -- inverse_faces' two warps
+ * (face_restoration_helper.py:264-335) and the blend of gaussian_diffusion.py:491 composed per face; a later face lands on top
+ * of an earlier one, and the result equals those three launches applied face by face bit for bit.  (The reference pastes
+ * exactly one face per frame.)  x0, out: [T][C][H][W] f32, C <= 4, out may not overlap x0; faces: [K][C][h][w] f32 in
+ * [-1, 1]; masks: [K][1][h][w] f64 (flair_face_mask_blur's result); minv: DEVICE [K][6] doubles, dst -> src; frame_start:
+ * DEVICE int32 [T + 1], faces sorted by frame, frame t owns faces frame_start[t] .. frame_start[t + 1] - 1 (non-decreasing,
+ * frame_start[0] = 0, frame_start[T] = K: checked by the caller on its host copy).  (H, W) and (h, w) are independent.
+ * K = 0 copies x0 (faces, masks, minv may then be null). */
+int flair_face_paste(const float* x0, int T, int C, int H, int W, const float* faces, const double* masks, const double* minv,
+                     int K, int h, int w, const int* frame_start, float* out, hipStream_t stream);
 /* The paste mask of inverse_faces (face_restoration_helper.py:283-317): mask = lut[parse_idx] (MASK_COLORMAP, DEVICE
  * doubles [nlut]), `repeats` x cv2.GaussianBlur(mask, (ksize, ksize), sigma) in float64 with BORDER_REFLECT_101 (kern:
  * DEVICE doubles [ksize] = cv2.getGaussianKernel), the `edge` outermost pixels zeroed, / div.  parse_idx: [N][H][W]

@@ -8,6 +8,9 @@ frame.
     python tools/bench_unaligned.py --frames 10      # one JSON line: ms per step of each part and of both branches
     python tools/bench_unaligned.py --parser both    # one line per parser, same process, plus the BiSeNet tail and the
                                                      # small-kernel timings (fused vs unfused arg-max, pool / gate launches)
+    python tools/bench_unaligned.py --faces-per-frame 1 2   # one more line per count: the branch with that many faces in
+                                                     # every frame (face_frames path) and the fused paste against the
+                                                     # warp + warp + blend launches on the same data
 """
 import argparse
 import json
@@ -26,6 +29,8 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--parser", choices=("parsenet", "bisenet", "both"), default="parsenet")
+    ap.add_argument("--faces-per-frame", type=int, nargs="*", default=[], metavar="F",
+                    help="also time the several-faces path with F faces in every frame (one JSON line per F)")
     a = ap.parse_args()
     from flair_amd.guided_diffusion.codeformer import CodeFormer
     torch.set_grad_enabled(False)
@@ -35,6 +40,8 @@ def main():
                      connect_list=["32", "64", "128", "256"]).to(dev).eval()
     for k, name in enumerate(("parsenet", "bisenet") if a.parser == "both" else (a.parser,)):
         run(a, dev, gan, name, with_aligned=k == 0)
+        for F in a.faces_per_frame:
+            run_faces(a, dev, gan, name, F)
 
 
 def make_parser(name, dev):
@@ -138,6 +145,55 @@ def run(a, dev, gan, parser_name, with_aligned=True):
     if parser_name == "bisenet":
         res.update(bisenet_kernels(T, S, dev))
     res.update(parser=parser_name, frames=T, size=S, iters=a.iters, device=torch.cuda.get_device_name(0))
+    print(json.dumps(res))
+
+
+def run_faces(a, dev, gan, parser_name, F):
+    """The branch with F faces in every frame (sampler's face_frames path: indexed crops, the prior on T * F crops, parsing,
+    mask blur, one flair_face_paste), and the paste alone against what it replaces: per layer of faces a warp of the faces,
+    a warp of the masks and a blend over the window (3 F launches)."""
+    from flair_amd import ops
+    from flair_amd import workload as wl
+    from flair_amd.guided_diffusion.face_restoration_helper import FaceRestoreHelper
+    from flair_amd.guided_diffusion.retinaface_utils import estimate_affine_partial
+    T, S = a.frames, 512
+    if F < 1:
+        raise SystemExit("--faces-per-frame needs counts >= 1")
+    helper = FaceRestoreHelper(face_size=S, device=dev, face_parse=make_parser(parser_name, dev))
+    tpl = helper.face_template
+    # face j of frame k: 70 % / (1 + j / 2) of the template's size, drifting across the window, neighbours overlapping
+    mats = [estimate_affine_partial(tpl * (0.7 / (1 + 0.5 * j)) + np.array([60.0 + 4 * k + 110.0 * j, 90.0 - 2 * k + 40.0 * j]), tpl)
+            for k in range(T) for j in range(F)]
+    face_frames = [k for k in range(T) for _ in range(F)]
+    g = torch.Generator(device=dev).manual_seed(1)
+    x0 = torch.rand(T, 3, S, S, device=dev, generator=g) * 2 - 1
+    xt = torch.randn(T, 3, S, S, device=dev, generator=g)
+    aux = wl.codeformer_aux(gan)
+
+    def branch():
+        f = helper.get_crop_face_from_affine_matrices(x0, mats, face_frames)
+        ft = helper.get_crop_face_from_affine_matrices(xt, mats, face_frames)
+        return helper.paste_faces(x0, aux(f, None, ft), mats, face_frames)
+    res = {"unaligned_branch_ms": replay_us(branch, a.iters, a.warmup) / 1e3}
+    # the paste alone, on the faces and masks of this window
+    faces = aux(helper.get_crop_face_from_affine_matrices(x0, mats, face_frames), None, None).float().contiguous()
+    lut, kern = helper._consts(dev)
+    masks = ops.face_mask_blur(helper.face_parse.parse_indices(faces).reshape(-1), T * F, S, S, lut, kern)
+    minv = helper._minv(mats, dev, twice=True)
+    starts = helper.frame_starts(face_frames, T)
+    starts_dev = helper._index(starts, dev)
+    layers = [(faces[j::F].contiguous(), masks[j::F].contiguous(), minv[j::F].contiguous()) for j in range(F)]
+
+    def three_launches():
+        v = x0
+        for f, m, mi in layers:
+            v = ops.face_blend(v, ops.warp_affine_cubic(f, mi, (S, S), pre=True, post=True), ops.warp_affine_cubic(m, mi, (S, S)))
+        return v
+    res["paste_fused_us"] = replay_us(lambda: ops.face_paste(x0, faces, masks, minv, starts_dev, starts))
+    res["paste_three_launches_us"] = replay_us(three_launches)
+    res["paste_fused_equals_three_launches"] = bool(torch.equal(ops.face_paste(x0, faces, masks, minv, starts_dev, starts),
+                                                                three_launches()))
+    res.update(parser=parser_name, frames=T, faces_per_frame=F, size=S, iters=a.iters, device=torch.cuda.get_device_name(0))
     print(json.dumps(res))
 
 
