@@ -55,7 +55,7 @@ class FaceRestoreHelper(object):
         # paste-mask value per parsing class (None: the reference's 19-entry list)
         self.mask_colormap = [float(v) for v in (MASK_COLORMAP if mask_colormap is None else mask_colormap)]
         self.detector = detector              # optional external object with a get_crop_face method (e.g. the reference's helper)
-        self.face_det = face_det              # flair_amd.guided_diffusion.retinaface.RetinaFace (built on first use when None)
+        self.face_det = face_det              # retinaface.RetinaFace (built on first use when None) or a loaded yolov5face.YoloDetector
         self.det_model = det_model
         self.template_3points = template_3points
         self.crop_ratio = crop_ratio
@@ -78,7 +78,8 @@ class FaceRestoreHelper(object):
     def _detector(self):
         if self.face_det is None:
             if "retinaface" not in self.det_model:
-                raise NotImplementedError(f"flair_amd: det_model={self.det_model!r} is not built (retinaface_resnet50 only)")
+                raise NotImplementedError(f"flair_amd: det_model={self.det_model!r} is not built by the helper (it never runs a "
+                                          "random-weight YOLOv5-face): pass a loaded yolov5face.YoloDetector as face_det=")
             from .retinaface import RetinaFace
             # random initialisation: load detection_Resnet50_Final.pth with face_det.load_state_dict(torch.load(path,
             # weights_only=True)) -- the reference downloads it at construction (facelib/detection/__init__.py:25-48)

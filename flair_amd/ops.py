@@ -1042,3 +1042,72 @@ def upsample_argmax(logits, n_classes, size, table=None):
     check(lib().flair_upsample_argmax_nhwc(ptr(logits), dtype_code(logits), _ld(logits), F_, h, w, n_classes, H, W, ptr(table), D,
                                            ptr(idx), ptr(y), D, stream()), "flair_upsample_argmax_nhwc")
     return idx, y
+
+
+# --------------------------------------------------------------------------- YOLOv5-face detectors (detect.hip)
+def maxpool2x2s2(x, out=None):
+    """nn.MaxPool2d(2, 2, ceil_mode=True) on a clip tensor (flair_maxpool2x2s2_nhwc); out: optional (T, ceil(H/2), ceil(W/2),
+    >= C) view, e.g. a channel slice of a wider buffer."""
+    T, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((T, (H + 1) // 2, (W + 1) // 2, C), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (T, (H + 1) // 2, (W + 1) // 2, C) and out.dtype == x.dtype
+    check(lib().flair_maxpool2x2s2_nhwc(ptr(x), _ld(x), dtype_code(x), T, H, W, C, ptr(out), _ld(out), stream()),
+          "flair_maxpool2x2s2_nhwc")
+    return out
+
+
+def spp_maxpool(buf, C, ks):
+    """SPP's three stride-1 max pools in place (flair_spp_maxpool_nhwc): reads channels [0, C) of the (T, H, W, >= 4C) clip
+    tensor ``buf`` and writes MaxPool2d(ks[j], 1, ks[j] // 2) of them into channels [(j + 1) C, (j + 2) C), j = 0, 1, 2."""
+    T, H, W, cb = buf.shape
+    assert cb >= 4 * C and len(ks) == 3
+    check(lib().flair_spp_maxpool_nhwc(ptr(buf), _ld(buf), dtype_code(buf), T, H, W, C, int(ks[0]), int(ks[1]), int(ks[2]),
+                                       stream()), "flair_spp_maxpool_nhwc")
+    return buf
+
+
+def channel_interleave(a, b, out=None):
+    """channel_shuffle(torch.cat((a, b), 1), 2) on clip tensors (flair_channel_interleave_nhwc): out[..., 2i] = a[..., i],
+    out[..., 2i + 1] = b[..., i].  a, b: (T, H, W, C) views (any pixel stride); out: optional (T, H, W, 2C) view."""
+    T, H, W, C = a.shape
+    assert b.shape == a.shape and b.dtype == a.dtype
+    if out is None:
+        out = torch.empty((T, H, W, 2 * C), dtype=a.dtype, device=a.device)
+    assert tuple(out.shape) == (T, H, W, 2 * C) and out.dtype == a.dtype
+    check(lib().flair_channel_interleave_nhwc(ptr(a), _ld(a), ptr(b), _ld(b), dtype_code(a), C, ctypes.c_long(T * H * W),
+                                              ptr(out), _ld(out), stream()), "flair_channel_interleave_nhwc")
+    return out
+
+
+def yolo_face_decode(x, na, stride, anchor_grid, z, row0, no=16):
+    """Detect's inference decode of one level (flair_yolo_face_decode): x (B, ny, nx, >= na * 16) f32 head output ->
+    rows [row0, row0 + na ny nx) of z (B, N, 16) f32.  anchor_grid: na (w, h) pairs in pixels (host floats)."""
+    B, ny, nx, _ = x.shape
+    assert x.dtype == torch.float32 and z.dtype == torch.float32 and z.is_contiguous() and z.dim() == 3 and z.shape[0] == B
+    assert z.shape[2] == 16
+    flat = [float(v) for pair in anchor_grid for v in pair]
+    assert len(flat) == 2 * na
+    arr = (ctypes.c_float * len(flat))(*flat)
+    check(lib().flair_yolo_face_decode(ptr(x), _ld(x), B, ny, nx, int(na), int(no), ctypes.c_float(stride), arr, ptr(z),
+                                       ctypes.c_long(z.shape[1]), ctypes.c_long(row0), stream()), "flair_yolo_face_decode")
+    return z
+
+
+def letterbox(src, new_hw, top_left, out_hw, *, pre=(1.0, 0.0, float("-inf"), float("inf")), scale=1.0, pad_value=114.0 / 255.0,
+              out=None):
+    """(B, 3, H, W) f32 NCHW frames -> (B, Ho, Wo, 16) f32 clip tensor (flair_letterbox_nhwc): the frames mapped to
+    clamp(a x + b, lo, hi) (pre), resized to new_hw when that differs from (H, W), times ``scale``, placed at top_left in a
+    field of ``pad_value``; channels 3..15 are zero."""
+    B, C, H, W = src.shape
+    assert C == 3 and src.dtype == torch.float32 and src.is_contiguous()
+    Ho, Wo = out_hw
+    if out is None:
+        out = torch.empty((B, Ho, Wo, 16), dtype=torch.float32, device=src.device)
+    assert tuple(out.shape) == (B, Ho, Wo, 16) and out.dtype == torch.float32
+    a, b, lo, hi = pre
+    check(lib().flair_letterbox_nhwc(ptr(src), B, H, W, int(new_hw[0]), int(new_hw[1]), int(top_left[0]), int(top_left[1]), Ho, Wo,
+                                     ctypes.c_float(a), ctypes.c_float(b), ctypes.c_float(lo), ctypes.c_float(hi),
+                                     ctypes.c_float(scale), ctypes.c_float(pad_value), ptr(out), _ld(out), stream()),
+          "flair_letterbox_nhwc")
+    return out

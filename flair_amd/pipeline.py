@@ -63,7 +63,8 @@ DEMOS = {
 # checkpoint file names of the reference (CKPT_PATH, :165-171; the facelib downloads, facelib/detection/__init__.py,
 # facelib/parsing/__init__.py)
 DETECTOR_FILES = {"retinaface_resnet50": ("resnet50", "detection_Resnet50_Final.pth"),
-                  "retinaface_mobile0.25": ("mobile0.25", "detection_mobilenet0.25_Final.pth")}
+                  "retinaface_mobile0.25": ("mobile0.25", "detection_mobilenet0.25_Final.pth"),
+                  "YOLOv5l": ("yolov5l", "yolov5l-face.pth"), "YOLOv5n": ("yolov5n", "yolov5n-face.pth")}
 PARSER_FILE = "parsing_parsenet.pth"
 # the face parsers build_pipeline(parser=...) offers (facelib/parsing/__init__.py:8-25), with their checkpoint files
 PARSER_FILES = {"parsenet": PARSER_FILE, "bisenet": "parsing_bisenet.pth"}
@@ -210,7 +211,8 @@ class Pipeline:
 def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=100, kernels_path=None, prior=True,
                    det_model="retinaface_resnet50", model_kwargs=None, graph=True, prior_kwargs=None, parser="parsenet"):
     """Build ``task``'s Pipeline from the checkpoints in ``weights_dir``: ``flair_{task}.pt``, the prior's checkpoint,
-    the detector's ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` and the parser's
+    the detector's ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` / ``yolov5l-face.pth`` /
+    ``yolov5n-face.pth`` (``det_model``: the RetinaFace bodies or the YOLOv5-face detectors) and the parser's
     ``parsing_parsenet.pth`` (``parser="parsenet"``, the default) or ``parsing_bisenet.pth`` (``parser="bisenet"``),
     all loaded strictly with ``weights_only=True``.  ``model_kwargs`` overrides entries of MODEL_CONFIG[task]
     (checkpoints of other widths).  ``kernels_path``: the reference's ``miscs/kernels_12.mat`` (gaussian and jpeg tasks).
@@ -272,7 +274,12 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         model.convert_to_fp32()
     # the face helper's networks (facelib/detection/__init__.py, facelib/parsing/__init__.py)
     det_path, parser_path = files[-2], files[-1]
-    det = load(RetinaFace(network_name=DETECTOR_FILES[det_model][0], half=False, device="cpu"), det_path).to(device).eval()
+    if det_model.startswith("YOLOv5"):                  # init_yolov5face_model, facelib/detection/__init__.py:51-81
+        from .guided_diffusion.yolov5face import YoloDetector
+        det = YoloDetector(DETECTOR_FILES[det_model][0], device="cpu", allow_random_init=not reads)
+        det_net = det.detector = load(det.detector, det_path).to(device).eval()
+    else:
+        det = det_net = load(RetinaFace(network_name=DETECTOR_FILES[det_model][0], half=False, device="cpu"), det_path).to(device).eval()
     det.device = device
     if parser == "bisenet":
         from .guided_diffusion.bisenet import BiSeNet
@@ -295,7 +302,7 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         gan = load(VQFRv2(**dict(VQFR_CONFIG, **pkw)), files[1]).to(device).eval()
     if distributed:
         parallel.broadcast_packed_weights(model, src=0)
-        for net in (det, parser, gan):
+        for net in (det_net, parser, gan):
             if net is not None:
                 parallel.broadcast_weights(net, src=0)
     if graph and hasattr(model, "enable_hip_graph") and device.type == "cuda":

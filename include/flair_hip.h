@@ -63,7 +63,9 @@ const char* flair_last_error(void);
  * 7: flair_tattn_params.head_dim; 8: + flair_dwconv_nhwc; 9: + flair_vq_nearest_nhwc;
  * 10: + flair_dwconv7_nhwc, flair_dcn_params.raw_activated = 2 (VQFR's DCNv2Pack);
  * 11: + flair_global_avgpool_nhwc, flair_channel_gate_nhwc, flair_upsample_argmax_nhwc (BiSeNet face parsing);
- * 12: + flair_warp_affine_cubic_indexed, flair_face_paste (several faces per frame, frames without a face)).
+ * 12: + flair_warp_affine_cubic_indexed, flair_face_paste (several faces per frame, frames without a face);
+ * 13: + flair_maxpool2x2s2_nhwc, flair_spp_maxpool_nhwc, flair_channel_interleave_nhwc, flair_yolo_face_decode,
+ *     flair_letterbox_nhwc (the YOLOv5-face detectors)).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -544,6 +546,46 @@ int flair_face_mask_blur(const int* parse_idx, int N, int H, int W, const double
 /* x0 * (1 - mask) + face * mask (gaussian_diffusion.py:491); x0, face, out: [N][C][H][W] f32; mask: [N][1][H][W] f32. */
 int flair_face_blend(const float* x0, const float* face, const float* mask, int N, int C, int H, int W, float* out,
                      hipStream_t stream);
+
+/* ------------------------------------------------------------- YOLOv5-face detectors (facelib/detection/yolov5face)
+ * The operations of YOLOv5n / YOLOv5l that are neither a convolution (flair_conv_nhwc with FLAIR_ACT_SILU, flair_dwconv_nhwc)
+ * nor a nearest enlargement (flair_resize_nhwc).  Clip tensors [F][H][W][ld]; every view's pixel stride may exceed its
+ * channel count (channels past C are never written), pointers and strides are 16-byte granular, and every entry validates
+ * before it launches (FLAIR_ERR_ARG with a message that names the argument).
+ *
+ * flair_maxpool2x2s2_nhwc: nn.MaxPool2d(kernel_size=2, stride=2, ceil_mode=True) of StemBlock (models/common.py:63, :70):
+ *   [F][H][W][C] -> [F][(H+1)/2][(W+1)/2][C], windows clipped at the bottom / right edge.  F32 / BF16, C a multiple of
+ *   4 / 8; bit-exact.  y is usually the second channel slice of the buffer stem_3 reads (the torch.cat of :71). */
+int flair_maxpool2x2s2_nhwc(const void* x, int x_ld, int dtype, int F, int H, int W, int C, void* y, int y_ld,
+                            hipStream_t stream);
+/* The three nn.MaxPool2d(k, stride 1, padding k // 2) of SPP (models/common.py:173-184) in one launch: reads channels
+ * [0, C) of buf ([F][H][W][ld], ld >= 4 C) and writes the pools for k0 < k1 < k2 (odd, 3 .. 13) into channels [C, 2C),
+ * [2C, 3C), [3C, 4C) of the same buffer -- so SPP.cv1 writes slice 0 and SPP.cv2 reads one 4C-channel segment, the
+ * torch.cat of :184.  Padding behaves as -inf; bit-exact.  F32 / BF16, C a multiple of 4 / 8. */
+int flair_spp_maxpool_nhwc(void* buf, int ld, int dtype, int F, int H, int W, int C, int k0, int k1, int k2,
+                           hipStream_t stream);
+/* torch.cat((a, b), 1) followed by channel_shuffle(., 2) of ShuffleV2Block (models/common.py:25-34, :163-170):
+ * y[p][2i] = a[p][i], y[p][2i+1] = b[p][i] on P pixels; a, b: C channels each (a is usually the untouched half of a
+ * stride-1 unit's input, a strided view), y: 2C channels.  F32 / BF16, C a multiple of 4 / 8; bit-exact. */
+int flair_channel_interleave_nhwc(const void* a, int a_ld, const void* b, int b_ld, int dtype, int C, long P, void* y,
+                                  int y_ld, hipStream_t stream);
+/* Detect.forward's inference branch for one level (models/yolo.py:52-86) on the head convolution's NHWC output
+ * x: [B][ny][nx][x_ld] f32 with channel a * 16 + j = output j of anchor a (what view(bs, na, no, ny, nx).permute(0, 1, 3,
+ * 4, 2) reorders).  Writes rows [b][row0 + a ny nx + y nx + x][0..16) of z: [B][N][16] f32 (three launches fill z; no
+ * torch.cat): columns 0-1 (2 sigmoid - 0.5 + grid) * stride, 2-3 (2 sigmoid)^2 * anchor_grid, 4 and 15 sigmoid, 5-14
+ * v * anchor_grid + grid * stride.  anchor_grid: HOST array [na][2] (w, h) in pixels (copied into the launch arguments);
+ * na <= 8; no must be 16 (nc = 1); row0 + na ny nx <= N. */
+int flair_yolo_face_decode(const float* x, int x_ld, int B, int ny, int nx, int na, int no, float stride,
+                           const float* anchor_grid, float* z, long N, long row0, hipStream_t stream);
+/* YoloDetector._preprocess with letterbox (face_detector.py:56-79, utils/datasets.py:5-35) in one launch:
+ * src: [B][3][H][W] f32 NCHW frames -> y: [B][Ho][Wo][y_ld] f32 clip tensor, channels 0-2 the image, 3-15 zero.
+ * Every source value is first mapped to clamp(a x + b, lo, hi); the new_h x new_w interior at (top, left) is that image
+ * (copied when new_h == H and new_w == W, else sampled bilinearly with half-pixel centres and clamped edges, cv2.INTER_LINEAR
+ * on floats = F.interpolate(mode="bilinear", align_corners=False) at an explicit size) times s; every other pixel is
+ * pad_value (114 / 255).  The host computes new_h, new_w, top, left, Ho, Wo as the reference does. */
+int flair_letterbox_nhwc(const float* src, int B, int H, int W, int new_h, int new_w, int top, int left, int Ho, int Wo,
+                         float a, float b, float lo, float hi, float s, float pad_value, float* y, int y_ld,
+                         hipStream_t stream);
 
 /* ------------------------------------------------------------- multi-GPU start-up
  * The only collective of the path: in-place RCCL broadcast of the kernel-native weight blob (flair_amd.checkpoint.export_packed:
