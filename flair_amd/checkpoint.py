@@ -10,6 +10,8 @@ Files are read with ``weights_only=True``: nothing in the pickle is executed.
 """
 import torch
 
+from .guided_diffusion.packing import invalidate_packed
+
 
 def load_reference_checkpoint(model, path, strict=True):
     """Load a reference checkpoint (a plain state dict, or a dict holding one under ``params_ema`` / ``params`` /
@@ -23,8 +25,7 @@ def load_reference_checkpoint(model, path, strict=True):
     if not isinstance(obj, dict) or not all(isinstance(v, torch.Tensor) for v in obj.values()):
         raise ValueError(f"{path}: not a tensor state dict")
     report = model.load_state_dict(obj, strict=strict)
-    if hasattr(model, "_packed_key"):
-        model._packed_key = None           # kernel-native weight copies are stale now
+    invalidate_packed(model)               # kernel-native weight copies are stale now
     return report
 
 
@@ -32,13 +33,11 @@ def load_reference_checkpoint(model, path, strict=True):
 # What the kernels read is not the fp32 state dict but its one-time repack (``_ensure_packed``): conv weights
 # as [Cout][taps][Cin] in the compute dtype (offset convolutions tap-major), the batched embedding matrix,
 # folded temporal-attention codes, f32 biases / norm parameters.  ``export_packed`` lays all of it out in ONE
-# flat device buffer (256-byte aligned pieces) plus a small description; ``import_packed`` rebuilds the models'
-# packed attributes as views into such a buffer.  This is the unit the multi-GPU start-up ships
-# (flair_amd.parallel.broadcast_packed_weights): 0.83 GB for unet_new.UNetModel in
-# bf16 instead of the 1.65 GB fp32 master copy plus a repack on every rank.
-PACKED_ATTRS = ("_pk", "_pk_w", "_pk_b", "_emb_w", "_emb_b", "_te", "_head_w", "_head_b", "_head_g", "_head_be",
-                "_plain", "_silu", "_mlp", "_fin")
-INT_ATTRS = ("film_off", "plain_off", "silu_off")
+# flat device buffer (256-byte aligned pieces) plus a small description; ``import_packed`` rebuilds every module's
+# ``_pk`` (the one attribute ``pack`` fills, for every network: guided_diffusion/packing.py) as views into such a
+# buffer.  This is the unit the multi-GPU start-up ships (flair_amd.parallel.broadcast_packed_weights, SURVEY.md
+# 8e / 8f row 3): 0.83 GB for unet_new.UNetModel in bf16 instead of the 1.65 GB fp32 master copy plus a repack on
+# every rank.
 _ALIGN = 256
 
 
@@ -75,12 +74,8 @@ def export_packed(model, device=None):
     model._ensure_packed(device)
     tensors, entries = [], []
     for name, mod in model.named_modules():
-        for attr in PACKED_ATTRS:
-            if attr in mod.__dict__:
-                entries.append((name, attr, _flatten(mod.__dict__[attr], tensors)))
-        ints = {a: int(mod.__dict__[a]) for a in INT_ATTRS if a in mod.__dict__}
-        if ints:
-            entries.append((name, "__ints__", ("V", ints)))
+        if "_pk" in mod.__dict__:
+            entries.append((name, _flatten(mod._pk, tensors)))
     layout, off = [], 0
     for t in tensors:
         nbytes = t.numel() * t.element_size()
@@ -108,17 +103,9 @@ def import_packed(model, meta, blob):
         nbytes = n * torch.empty((), dtype=dtype).element_size()
         tensors.append(blob[off:off + nbytes].view(dtype).view(shape))
     mods = dict(model.named_modules())
-    for name, attr, node in meta["entries"]:
-        mod = mods[name]
-        if attr == "__ints__":
-            for k, v in node[1].items():
-                setattr(mod, k, v)
-        else:
-            mod.__dict__[attr] = _rebuild(node, tensors)
+    for name, node in meta["entries"]:
+        mods[name]._pk = _rebuild(node, tensors)
+    invalidate_packed(model)                        # whatever was derived from the old copies goes
     model.dtype = {"torch.bfloat16": torch.bfloat16, "torch.float32": torch.float32}[meta["dtype"]]
     model._packed_key = (model.dtype, blob.device)
     model._packed_blob = blob                       # keeps the storage alive
-    if hasattr(model, "_flow_cache"):
-        model._flow_cache = {}
-    if hasattr(model, "_graphs"):
-        model._graphs = {}

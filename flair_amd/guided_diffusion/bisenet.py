@@ -28,7 +28,13 @@ import torch.nn as nn
 
 from .. import _lib, ops
 from .. import ops as A
-from .retinaface import _conv, _fold, _fold_bn
+from .packing import PackedModel, dev_f32, fold_bn, pad_cout, packed_conv, run_conv
+
+
+def _matrix(conv, bn, device):
+    """A 1x1 convolution (+ eval BatchNorm) on a one-pixel map as ops.linear's (weight, bias), f32."""
+    w, b = fold_bn(conv, bn)
+    return w.reshape(w.shape[0], -1).to(device).contiguous(), b.to(device).contiguous()
 
 
 class ConvBNReLU(nn.Module):
@@ -42,12 +48,12 @@ class ConvBNReLU(nn.Module):
         self.bn = nn.BatchNorm2d(out_chan)
 
     def pack(self, dtype, device):
-        self._p = _fold(self.conv, self.bn, dtype, device)
-        w, b = _fold_bn(self.conv, self.bn)                     # the same layer on a 1x1 map (conv_avg): a matrix
-        self._lin = (w.reshape(w.shape[0], -1).to(device).contiguous(), b.to(device).contiguous()) if w.shape[2] == 1 else None
+        self._pk = packed_conv(self.conv, self.bn, dtype, device)
+        if self.conv.kernel_size[0] == 1:                       # the same layer on a 1x1 map (conv_avg): a matrix
+            self._pk["lin"] = _matrix(self.conv, self.bn, device)
 
     def run(self, x):
-        return _conv(x, self._p, self.conv, A.ACT_RELU)
+        return run_conv(x, self._pk, self.conv, A.ACT_RELU)
 
 
 class BiSeNetOutput(nn.Module):
@@ -59,14 +65,12 @@ class BiSeNetOutput(nn.Module):
         self.conv_out = nn.Conv2d(mid_chan, num_class, kernel_size=1, bias=False)
 
     def pack(self, dtype, device):
-        self.conv.pack(dtype, device)
         g = 16 // torch.empty((), dtype=dtype).element_size()    # class vectors padded to whole 16-byte chunks
-        n = self.conv_out.out_channels
-        self._p = _fold(self.conv_out, None, dtype, device, cout_pad=(n + g - 1) // g * g)
+        self._pk = packed_conv(self.conv_out, None, dtype, device, cout_pad=pad_cout(self.conv_out.out_channels, g))
 
     def run(self, x):
         feat = self.conv.run(x)
-        return _conv(feat, self._p, self.conv_out, A.ACT_NONE), feat
+        return run_conv(feat, self._pk, self.conv_out), feat
 
 
 def _linear(x, w, b, act=A.ACT_NONE):
@@ -87,14 +91,13 @@ class AttentionRefinementModule(nn.Module):
         self.sigmoid_atten = nn.Sigmoid()
 
     def pack(self, dtype, device):
-        self.conv.pack(dtype, device)
-        w, b = _fold_bn(self.conv_atten, self.bn_atten)
-        self._w, self._b = w.reshape(w.shape[0], -1).to(device).contiguous(), b.to(device).contiguous()
+        w, b = _matrix(self.conv_atten, self.bn_atten, device)
+        self._pk = dict(w=w, b=b)
 
     def run(self, x, bias=None, add=None):
         """torch.mul(feat, atten) plus what the caller adds to it next: a per-(frame, channel) term or a full tensor."""
         feat = self.conv.run(x)
-        logit = _linear(ops.global_avgpool(feat), self._w, self._b)
+        logit = _linear(ops.global_avgpool(feat), self._pk["w"], self._pk["b"])
         return ops.channel_gate(feat, logit, logit=True, bias=bias, add=add, out=feat)
 
 
@@ -114,13 +117,15 @@ class BasicBlock(nn.Module):
                                             nn.BatchNorm2d(out_chan))
 
     def pack(self, dtype, device):
-        self._p = [_fold(self.conv1, self.bn1, dtype, device), _fold(self.conv2, self.bn2, dtype, device)]
-        self._pd = _fold(self.downsample[0], self.downsample[1], dtype, device) if self.downsample is not None else None
+        self._pk = dict(c1=packed_conv(self.conv1, self.bn1, dtype, device), c2=packed_conv(self.conv2, self.bn2, dtype, device))
+        if self.downsample is not None:
+            self._pk["down"] = packed_conv(self.downsample[0], self.downsample[1], dtype, device)
 
     def run(self, x):
-        shortcut = _conv(x, self._pd, self.downsample[0], A.ACT_NONE) if self._pd is not None else x
-        h = _conv(x, self._p[0], self.conv1, A.ACT_RELU)
-        h = _conv(h, self._p[1], self.conv2, A.ACT_NONE)
+        pk = self._pk
+        shortcut = run_conv(x, pk["down"], self.downsample[0]) if "down" in pk else x
+        h = run_conv(x, pk["c1"], self.conv1, A.ACT_RELU)
+        h = run_conv(h, pk["c2"], self.conv2)
         return ops.add_act(shortcut, h, A.ACT_RELU, out=h)           # relu(shortcut + residual)
 
 
@@ -143,13 +148,10 @@ class ResNet18(nn.Module):
         self.layer4 = create_layer_basic(256, 512, bnum=2, stride=2)
 
     def pack(self, dtype, device):
-        self._p = _fold(self.conv1, self.bn1, dtype, device)
-        for m in self.modules():
-            if isinstance(m, BasicBlock):
-                m.pack(dtype, device)
+        self._pk = packed_conv(self.conv1, self.bn1, dtype, device)
 
     def run(self, x):
-        h = ops.maxpool3x3s2(_conv(x, self._p, self.conv1, A.ACT_RELU))
+        h = ops.maxpool3x3s2(run_conv(x, self._pk, self.conv1, A.ACT_RELU))
         feats = []
         for i in range(1, 5):
             for blk in getattr(self, f"layer{i}"):
@@ -170,19 +172,14 @@ class ContextPath(nn.Module):
         self.conv_head16 = ConvBNReLU(128, 128, ks=3, stride=1, padding=1)
         self.conv_avg = ConvBNReLU(512, 128, ks=1, stride=1, padding=0)
 
-    def pack(self, dtype, device):
-        self.resnet.pack(dtype, device)
-        for m in (self.arm16, self.arm32, self.conv_head32, self.conv_head16, self.conv_avg):
-            m.pack(dtype, device)
-
     def run(self, x):
         feat8, feat16, feat32 = self.resnet.run(x)
         # avg_up: conv_avg on the 1x1 pooled map, enlarged by nearest = one value per (frame, channel)
-        avg = _linear(ops.global_avgpool(feat32), *self.conv_avg._lin, act=A.ACT_RELU)
+        avg = _linear(ops.global_avgpool(feat32), *self.conv_avg._pk["lin"], act=A.ACT_RELU)
         feat32_sum = self.arm32.run(feat32, bias=avg)
-        feat32_up = self.conv_head32.run(ops.resize(feat32_sum, tuple(feat16.shape[1:3]), 4))
+        feat32_up = self.conv_head32.run(ops.resize(feat32_sum, tuple(feat16.shape[1:3]), ops.RESIZE_NEAREST))
         feat16_sum = self.arm16.run(feat16, add=feat32_up)
-        feat16_up = self.conv_head16.run(ops.resize(feat16_sum, tuple(feat8.shape[1:3]), 4))
+        feat16_up = self.conv_head16.run(ops.resize(feat16_sum, tuple(feat8.shape[1:3]), ops.RESIZE_NEAREST))
         return feat8, feat16_up, feat32_up
 
 
@@ -198,18 +195,16 @@ class FeatureFusionModule(nn.Module):
         self.sigmoid = nn.Sigmoid()
 
     def pack(self, dtype, device):
-        self.convblk.pack(dtype, device)
-        self._w1 = self.conv1.weight.detach().float().reshape(self.conv1.out_channels, -1).to(device).contiguous()
-        self._w2 = self.conv2.weight.detach().float().reshape(self.conv2.out_channels, -1).to(device).contiguous()
+        self._pk = dict(w1=dev_f32(self.conv1.weight.detach().reshape(self.conv1.out_channels, -1), device),
+                        w2=dev_f32(self.conv2.weight.detach().reshape(self.conv2.out_channels, -1), device))
 
     def run(self, fsp, fcp):
-        wp, b, cout = self.convblk._p
-        feat = ops.conv([fsp, fcp], wp, b, cout, (1, 1, 1), act=A.ACT_RELU)          # convblk(torch.cat([fsp, fcp], dim=1))
-        logit = _linear(_linear(ops.global_avgpool(feat), self._w1, None, act=A.ACT_RELU), self._w2, None)
+        feat = self.convblk.run([fsp, fcp])                                          # convblk(torch.cat([fsp, fcp], dim=1))
+        logit = _linear(_linear(ops.global_avgpool(feat), self._pk["w1"], None, act=A.ACT_RELU), self._pk["w2"], None)
         return ops.channel_gate(feat, logit, logit=True, add_x=True, out=feat)       # feat * atten + feat
 
 
-class BiSeNet(nn.Module):
+class BiSeNet(PackedModel, nn.Module):
     """bisenet.py:111-140."""
 
     def __init__(self, num_class):
@@ -222,28 +217,6 @@ class BiSeNet(nn.Module):
         self.conv_out = BiSeNetOutput(256, 256, num_class)
         self.conv_out16 = BiSeNetOutput(128, 64, num_class)
         self.conv_out32 = BiSeNetOutput(128, 64, num_class)
-        self.dtype = torch.float32
-        self._packed_key = None
-
-    def load_state_dict(self, *args, **kwargs):
-        out = super().load_state_dict(*args, **kwargs)
-        self._packed_key = None                 # folded / packed weights are rebuilt on the next forward
-        return out
-
-    def convert_to_bf16(self):
-        self.dtype, self._packed_key = torch.bfloat16, None
-        return self
-
-    def convert_to_fp32(self):
-        self.dtype, self._packed_key = torch.float32, None
-        return self
-
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key != key:
-            for m in (self.cp, self.ffm, self.conv_out, self.conv_out16, self.conv_out32):
-                m.pack(self.dtype, device)
-            self._packed_key = key
 
     def _to_clip(self, x):
         if not x.is_cuda:

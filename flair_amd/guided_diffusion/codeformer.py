@@ -25,31 +25,10 @@ import torch.nn as nn
 
 from .. import ops
 from .. import ops as A
+from .packing import PackedModel, dev_f32, pack_w
+from .vqgan_blocks import GN_EPS, AttnBlock, Downsample, HeadConv, NormOut, ResBlock, Upsample, normalize  # noqa: F401
 
 CH_MULT = (1, 2, 2, 4, 4, 8)
-GN_EPS = 1e-6
-
-
-def _dev(p, device):
-    return p.detach().to(device=device, dtype=torch.float32).contiguous()
-
-
-def _pack(w, dtype, device, segs=None, cout_pad=None):
-    """(Cout, Cin, kh, kw) or (Cout, Cin) f32 -> packed [Cout][taps][Cin] in ``dtype``."""
-    w = w.detach().to(device)
-    if w.dim() == 2:
-        w = w[:, :, None, None]
-    cin = w.shape[1]
-    return ops.pack_conv_weight(w, segs or [(cin, ops.pad_channels(cin, dtype))], dtype, cout_pad)
-
-
-def normalize(in_channels):
-    """codeformer.py:9-12."""
-    return nn.GroupNorm(num_groups=32, num_channels=in_channels, eps=GN_EPS, affine=True)
-
-
-def _gn(x, pk, name, act=A.ACT_NONE, x1=None):
-    return ops.group_norm(x, pk[name + "_g"], pk[name + "_b"], x1=x1, eps=GN_EPS, act=act, frames_per_stat=1)
 
 
 class VectorQuantizer(nn.Module):
@@ -63,121 +42,10 @@ class VectorQuantizer(nn.Module):
         self.embedding.weight.data.uniform_(-1.0 / codebook_size, 1.0 / codebook_size)
 
 
-class Downsample(nn.Module):
-    """codeformer.py:138-149: F.pad(x, (0, 1, 0, 1)) + 3x3 stride-2 conv without padding."""
-
-    def __init__(self, in_channels):
-        super().__init__()
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
-
-    def pack(self, dtype, device):
-        self._pk = dict(w=_pack(self.conv.weight, dtype, device), b=_dev(self.conv.bias, device))
-
-    def run(self, x):
-        return ops.conv(x, self._pk["w"], self._pk["b"], self.conv.out_channels, (1, 3, 3), stride=2, asym_pad=True)
-
-
-class Upsample(nn.Module):
-    """codeformer.py:152-163: nearest x2, then 3x3 conv."""
-
-    def __init__(self, in_channels):
-        super().__init__()
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
-
-    def pack(self, dtype, device):
-        self._pk = dict(w=_pack(self.conv.weight, dtype, device), b=_dev(self.conv.bias, device))
-
-    def run(self, x):
-        up = ops.resize(x, (2 * x.shape[1], 2 * x.shape[2]), 4)
-        return ops.conv(up, self._pk["w"], self._pk["b"], self.conv.out_channels, (1, 3, 3))
-
-
-class ResBlock(nn.Module):
-    """codeformer.py:166-195."""
-
-    def __init__(self, in_channels, out_channels=None):
-        super().__init__()
-        self.in_channels = in_channels
-        self.out_channels = in_channels if out_channels is None else out_channels
-        self.norm1 = normalize(in_channels)
-        self.conv1 = nn.Conv2d(in_channels, self.out_channels, kernel_size=3, stride=1, padding=1)
-        self.norm2 = normalize(self.out_channels)
-        self.conv2 = nn.Conv2d(self.out_channels, self.out_channels, kernel_size=3, stride=1, padding=1)
-        if self.in_channels != self.out_channels:
-            self.conv_out = nn.Conv2d(in_channels, self.out_channels, kernel_size=1, stride=1, padding=0)
-
-    def pack(self, dtype, device, split=None):
-        """split: widths of the two implicitly concatenated input segments (Fuse_sft_block.encode_enc)."""
-        segs = [(s, s) for s in split] if split else None
-        self._pk = dict(w1=_pack(self.conv1.weight, dtype, device), b1=_dev(self.conv1.bias, device),
-                        w2=_pack(self.conv2.weight, dtype, device), b2=_dev(self.conv2.bias, device),
-                        n1_g=_dev(self.norm1.weight, device), n1_b=_dev(self.norm1.bias, device),
-                        n2_g=_dev(self.norm2.weight, device), n2_b=_dev(self.norm2.bias, device))
-        if self.in_channels != self.out_channels:
-            self._pk["ws"] = _pack(self.conv_out.weight, dtype, device, segs)
-            self._pk["bs"] = _dev(self.conv_out.bias, device)
-
-    def run(self, x, x1=None):
-        pk, co = self._pk, self.out_channels
-        h = _gn(x, pk, "n1", A.ACT_SILU, x1=x1)
-        h = ops.conv(h, pk["w1"], pk["b1"], co, (1, 3, 3))
-        h = _gn(h, pk, "n2", A.ACT_SILU)
-        if "ws" in pk:
-            skip = ops.conv([x] if x1 is None else [x, x1], pk["ws"], pk["bs"], co, (1, 1, 1))
-        else:
-            assert x1 is None
-            skip = x
-        return ops.conv(h, pk["w2"], pk["b2"], co, (1, 3, 3), res0=skip)
-
-
-class AttnBlock(nn.Module):
-    """codeformer.py:198-241: GroupNorm, 1x1 q / k / v, one attention head of width C, 1x1 proj_out, residual."""
-
-    def __init__(self, in_channels):
-        super().__init__()
-        self.in_channels = in_channels
-        self.norm = normalize(in_channels)
-        self.q = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.k = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.v = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.proj_out = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-
-    def pack(self, dtype, device):
-        wqkv = torch.cat([self.q.weight, self.k.weight, self.v.weight], dim=0)
-        self._pk = dict(n_g=_dev(self.norm.weight, device), n_b=_dev(self.norm.bias, device),
-                        wqkv=_pack(wqkv, dtype, device),
-                        bqkv=_dev(torch.cat([self.q.bias, self.k.bias, self.v.bias]), device),
-                        wp=_pack(self.proj_out.weight, dtype, device), bp=_dev(self.proj_out.bias, device))
-
-    def run(self, x):
-        pk, c = self._pk, self.in_channels
-        qkv = ops.conv(_gn(x, pk, "n"), pk["wqkv"], pk["bqkv"], 3 * c, (1, 1, 1))
-        a = ops.attention_wide(qkv, 1, c, q_off=0, k_off=c, v_off=2 * c, head_stride=c)
-        return ops.conv(a, pk["wp"], pk["bp"], c, (1, 1, 1), res0=x)
-
-
-class _Conv(nn.Conv2d):
-    """A bare 3x3 convolution entry of encoder.blocks / generator.blocks (conv_in / conv_out)."""
-
-    def pack(self, dtype, device):
-        cpad = (self.out_channels + 3) // 4 * 4
-        b = _dev(self.bias, device)
-        if cpad != self.out_channels:
-            b = torch.cat([b, b.new_zeros(cpad - self.out_channels)]).contiguous()
-        self._pk = dict(w=_pack(self.weight, dtype, device, cout_pad=cpad), b=b, cout=cpad)
-
-    def run(self, x):
-        return ops.conv(x, self._pk["w"], self._pk["b"], self._pk["cout"], (1, 3, 3))
-
-
-class _Norm(nn.GroupNorm):
-    """The final ``normalize`` entry (no activation follows it: codeformer.py:288-292, :341-347)."""
-
-    def pack(self, dtype, device):
-        self._pk = dict(n_g=_dev(self.weight, device), n_b=_dev(self.bias, device))
-
-    def run(self, x):
-        return _gn(x, self._pk, "n")
+# Downsample (codeformer.py:138-149), Upsample (:152-163), ResBlock (:166-195, shortcut ``conv_out``) and AttnBlock
+# (:198-241, one head of width C on flair_attention_wide) are the shared blocks as they stand.  encoder.blocks /
+# generator.blocks begin and end with a bare 3x3 convolution (HeadConv); no activation follows the final ``normalize``
+# (NormOut: codeformer.py:288-292, :341-347).
 
 
 class Encoder(nn.Module):
@@ -187,7 +55,7 @@ class Encoder(nn.Module):
         super().__init__()
         curr_res = resolution
         in_ch_mult = (1,) + tuple(ch_mult)
-        blocks = [_Conv(in_channels, nf, kernel_size=3, stride=1, padding=1)]
+        blocks = [HeadConv(in_channels, nf, kernel_size=3, stride=1, padding=1)]
         block_in_ch = nf
         for i in range(len(ch_mult)):
             block_in_ch = nf * in_ch_mult[i]
@@ -201,8 +69,8 @@ class Encoder(nn.Module):
                 blocks.append(Downsample(block_in_ch))
                 curr_res //= 2
         blocks += [ResBlock(block_in_ch, block_in_ch), AttnBlock(block_in_ch), ResBlock(block_in_ch, block_in_ch)]
-        n = _Norm(32, block_in_ch, eps=GN_EPS, affine=True)
-        blocks += [n, _Conv(block_in_ch, emb_dim, kernel_size=3, stride=1, padding=1)]
+        n = NormOut(block_in_ch)
+        blocks += [n, HeadConv(block_in_ch, emb_dim, kernel_size=3, stride=1, padding=1)]
         self.blocks = nn.ModuleList(blocks)
 
 
@@ -213,7 +81,7 @@ class Generator(nn.Module):
         super().__init__()
         block_in_ch = nf * ch_mult[-1]
         curr_res = img_size // 2 ** (len(ch_mult) - 1)
-        blocks = [_Conv(emb_dim, block_in_ch, kernel_size=3, stride=1, padding=1),
+        blocks = [HeadConv(emb_dim, block_in_ch, kernel_size=3, stride=1, padding=1),
                   ResBlock(block_in_ch, block_in_ch), AttnBlock(block_in_ch), ResBlock(block_in_ch, block_in_ch)]
         for i in reversed(range(len(ch_mult))):
             block_out_ch = nf * ch_mult[i]
@@ -225,8 +93,8 @@ class Generator(nn.Module):
             if i != 0:
                 blocks.append(Upsample(block_in_ch))
                 curr_res *= 2
-        blocks += [_Norm(32, block_in_ch, eps=GN_EPS, affine=True),
-                   _Conv(block_in_ch, 3, kernel_size=3, stride=1, padding=1)]
+        blocks += [NormOut(block_in_ch),
+                   HeadConv(block_in_ch, 3, kernel_size=3, stride=1, padding=1)]
         self.blocks = nn.ModuleList(blocks)
 
 
@@ -247,13 +115,13 @@ class TransformerSALayer(nn.Module):
     def pack(self, dtype, device):
         e, at = self.embed_dim, self.self_attn
         self._pk = dict(
-            wqk=_pack(at.in_proj_weight[:2 * e], dtype, device), bqk=_dev(at.in_proj_bias[:2 * e], device),
-            wv=_pack(at.in_proj_weight[2 * e:], dtype, device), bv=_dev(at.in_proj_bias[2 * e:], device),
-            wo=_pack(at.out_proj.weight, dtype, device), bo=_dev(at.out_proj.bias, device),
-            w1=_pack(self.linear1.weight, dtype, device), b1=_dev(self.linear1.bias, device),
-            w2=_pack(self.linear2.weight, dtype, device), b2=_dev(self.linear2.bias, device),
-            n1_g=_dev(self.norm1.weight, device), n1_b=_dev(self.norm1.bias, device),
-            n2_g=_dev(self.norm2.weight, device), n2_b=_dev(self.norm2.bias, device))
+            wqk=pack_w(at.in_proj_weight[:2 * e], dtype, device), bqk=dev_f32(at.in_proj_bias[:2 * e], device),
+            wv=pack_w(at.in_proj_weight[2 * e:], dtype, device), bv=dev_f32(at.in_proj_bias[2 * e:], device),
+            wo=pack_w(at.out_proj.weight, dtype, device), bo=dev_f32(at.out_proj.bias, device),
+            w1=pack_w(self.linear1.weight, dtype, device), b1=dev_f32(self.linear1.bias, device),
+            w2=pack_w(self.linear2.weight, dtype, device), b2=dev_f32(self.linear2.bias, device),
+            n1_g=dev_f32(self.norm1.weight, device), n1_b=dev_f32(self.norm1.bias, device),
+            n2_g=dev_f32(self.norm2.weight, device), n2_b=dev_f32(self.norm2.bias, device))
 
     def run(self, tgt, pos):
         pk, e = self._pk, self.embed_dim
@@ -275,19 +143,19 @@ class Fuse_sft_block(nn.Module):
         super().__init__()
         self.in_ch, self.out_ch = in_ch, out_ch
         self.encode_enc = ResBlock(2 * in_ch, out_ch)
+        self.encode_enc.split = (in_ch, in_ch)      # cat[enc, dec] arrives as two segments
         self.scale = nn.Sequential(nn.Conv2d(in_ch, out_ch, kernel_size=3, padding=1), nn.LeakyReLU(0.2, True),
                                    nn.Conv2d(out_ch, out_ch, kernel_size=3, padding=1))
         self.shift = nn.Sequential(nn.Conv2d(in_ch, out_ch, kernel_size=3, padding=1), nn.LeakyReLU(0.2, True),
                                    nn.Conv2d(out_ch, out_ch, kernel_size=3, padding=1))
 
     def pack(self, dtype, device):
-        self.encode_enc.pack(dtype, device, split=[self.in_ch, self.in_ch])
         # the first convolutions of both branches read the same tensor: one launch, 2 * out_ch outputs
         self._pk = dict(
-            w0=_pack(torch.cat([self.scale[0].weight, self.shift[0].weight], dim=0), dtype, device),
-            b0=_dev(torch.cat([self.scale[0].bias, self.shift[0].bias]), device),
-            ws=_pack(self.scale[2].weight, dtype, device), bs=_dev(self.scale[2].bias, device),
-            wh=_pack(self.shift[2].weight, dtype, device), bh=_dev(self.shift[2].bias, device))
+            w0=pack_w(torch.cat([self.scale[0].weight, self.shift[0].weight], dim=0), dtype, device),
+            b0=dev_f32(torch.cat([self.scale[0].bias, self.shift[0].bias]), device),
+            ws=pack_w(self.scale[2].weight, dtype, device), bs=dev_f32(self.scale[2].bias, device),
+            wh=pack_w(self.shift[2].weight, dtype, device), bh=dev_f32(self.shift[2].bias, device))
 
     def run(self, enc_feat, dec_feat, w=1.0):
         pk, co = self._pk, self.out_ch
@@ -318,7 +186,7 @@ class VQAutoEncoder(nn.Module):
             load_reference_checkpoint(self, model_path)
 
 
-class CodeFormer(VQAutoEncoder):
+class CodeFormer(PackedModel, VQAutoEncoder):
     """codeformer.py:600-753."""
 
     def __init__(self, dim_embd=512, n_head=8, n_layers=9, codebook_size=1024, latent_size=256,
@@ -344,35 +212,14 @@ class CodeFormer(VQAutoEncoder):
         for f_size in self.connect_list:
             in_ch = self.channels[f_size]
             self.fuse_convs_dict[f_size] = Fuse_sft_block(in_ch, in_ch)
-        self.dtype = torch.float32
-        self._packed_key = None
 
-    def convert_to_bf16(self):
-        self.dtype = torch.bfloat16
-        self._packed_key = None
-        return self
-
-    def load_state_dict(self, *args, **kwargs):
-        out = super().load_state_dict(*args, **kwargs)
-        self._packed_key = None                 # kernel-native weight copies are rebuilt on the next forward
-        return out
-
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key == key:
-            return
-        dt = self.dtype
-        fused_inputs = {id(f.encode_enc) for f in self.fuse_convs_dict.values()}   # packed by their Fuse_sft_block
-        for m in self.modules():
-            if hasattr(m, "pack") and m is not self and id(m) not in fused_inputs:
-                m.pack(dt, device)
+    def pack(self, dtype, device):
         self._pk = dict(
-            pos=_dev(self.position_emb, device),
-            wf=_pack(self.feat_emb.weight, dt, device), bf=_dev(self.feat_emb.bias, device),
-            hn_g=_dev(self.idx_pred_layer[0].weight, device), hn_b=_dev(self.idx_pred_layer[0].bias, device),
-            wi=_pack(self.idx_pred_layer[1].weight, dt, device),
-            codebook=_dev(self.quantize.embedding.weight, device))
-        self._packed_key = key
+            pos=dev_f32(self.position_emb, device),
+            wf=pack_w(self.feat_emb.weight, dtype, device), bf=dev_f32(self.feat_emb.bias, device),
+            hn_g=dev_f32(self.idx_pred_layer[0].weight, device), hn_b=dev_f32(self.idx_pred_layer[0].bias, device),
+            wi=pack_w(self.idx_pred_layer[1].weight, dtype, device),
+            codebook=dev_f32(self.quantize.embedding.weight, device))
 
     @torch.no_grad()
     def forward(self, x, w=0, detach_16=True, code_only=False, adain=False, code_idx=None):

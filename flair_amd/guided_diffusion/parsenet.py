@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from .. import ops
 from .. import ops as A
+from .packing import PackedModel, packed_conv, run_conv
 
 
 class NormLayer(nn.Module):
@@ -57,25 +58,14 @@ class ConvLayer(nn.Module):
         self.norm = NormLayer(out_channels, norm_type=norm_type)
 
     def pack(self, dtype, device):
-        w = self.conv2d.weight.detach().float()
-        b = self.conv2d.bias.detach().float() if self.conv2d.bias is not None else w.new_zeros(self.out_channels)
-        if self.norm.norm_type == "bn":                       # eval-mode BatchNorm folded into the convolution
-            bn = self.norm.norm
-            g = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-            w = w * g.view(-1, 1, 1, 1)
-            b = (b - bn.running_mean.detach().float()) * g + bn.bias.detach().float()
-        cpad = (self.out_channels + 3) // 4 * 4
-        cin = self.in_channels
-        self._w = ops.pack_conv_weight(w.to(device), [(cin, ops.pad_channels(cin, dtype))], dtype, cpad)
-        b = b.to(device)
-        self._b = torch.cat([b, b.new_zeros(cpad - self.out_channels)]).contiguous()
-        self._cout = cpad
+        bn = self.norm.norm if self.norm.norm_type == "bn" else None      # eval-mode BatchNorm folded into the convolution
+        self._pk = packed_conv(self.conv2d, bn, dtype, device)
 
     def run(self, x, res0=None, res1=None):
         if self.scale == "up":
-            x = ops.resize(x, (2 * x.shape[1], 2 * x.shape[2]), 4)
-        return ops.conv(x, self._w, self._b, self._cout, (1, 3, 3), stride=2 if self.scale == "down" else 1,
-                        reflect_pad=True, act=A.ACT_LRELU02 if self.act else A.ACT_NONE, res0=res0, res1=res1)
+            x = ops.resize(x, (2 * x.shape[1], 2 * x.shape[2]), ops.RESIZE_NEAREST)
+        return run_conv(x, self._pk, self.conv2d, A.ACT_LRELU02 if self.act else A.ACT_NONE, reflect_pad=True,
+                        res0=res0, res1=res1)
 
 
 class ResidualBlock(nn.Module):
@@ -94,7 +84,7 @@ class ResidualBlock(nn.Module):
         return self.conv2.run(self.conv1.run(x), res0=ident, res1=extra)
 
 
-class ParseNet(nn.Module):
+class ParseNet(PackedModel, nn.Module):
     """parsenet.py:131-194."""
 
     def __init__(self, in_size=128, out_size=128, min_feat_size=32, base_ch=64, parsing_ch=19, res_depth=10,
@@ -124,21 +114,6 @@ class ParseNet(nn.Module):
         self.decoder = nn.Sequential(*decoder)
         self.out_img_conv = ConvLayer(ch_clip(head_ch), 3)
         self.out_mask_conv = ConvLayer(ch_clip(head_ch), parsing_ch)
-        self.dtype = torch.float32
-        self._packed_key = None
-
-    def load_state_dict(self, *args, **kwargs):
-        out = super().load_state_dict(*args, **kwargs)
-        self._packed_key = None                 # folded / packed weights are rebuilt on the next forward
-        return out
-
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key != key:
-            for m in self.modules():
-                if isinstance(m, ConvLayer):
-                    m.pack(self.dtype, device)
-            self._packed_key = key
 
     def _features(self, x):
         """(B, 3, H, W) f32 in [-1, 1] -> decoder output clip tensor (B, H, W, C)."""

@@ -27,13 +27,11 @@ import torch.nn as nn
 
 from .. import ops
 from .. import ops as A
-from .codeformer import GN_EPS, _dev, _gn, _pack
+from . import vqgan_blocks as vb
+from .packing import PackedModel, dev_f32, pack_w
 from .unet_new import qkv_head_width
-
-
-def Normalize(in_channels):
-    """restoreformer.py:116-119."""
-    return nn.GroupNorm(num_groups=32, num_channels=in_channels, eps=GN_EPS, affine=True)
+from .vqgan_blocks import HeadConv, NormOut, gn
+from .vqgan_blocks import normalize as Normalize          # restoreformer.py:116-119
 
 
 class VectorQuantizer(nn.Module):
@@ -47,90 +45,46 @@ class VectorQuantizer(nn.Module):
         self.embedding.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)
 
     def pack(self, dtype, device):
-        self._pk = dict(codebook=_dev(self.embedding.weight, device))
+        self._pk = dict(codebook=dev_f32(self.embedding.weight, device))
 
     def run(self, z, forced_idx=None):
         return ops.vq_nearest(z, self._pk["codebook"], forced_idx=forced_idx)
 
 
-class Upsample(nn.Module):
-    """restoreformer.py:122-135: nearest x2, then a 3x3 convolution."""
+def _with_conv(with_conv):
+    if not with_conv:
+        raise NotImplementedError("flair_amd: RestoreFormer resamples with convolutions (resamp_with_conv=True)")
+    return with_conv
+
+
+class Upsample(vb.Upsample):
+    """restoreformer.py:122-135."""
 
     def __init__(self, in_channels, with_conv):
-        super().__init__()
-        if not with_conv:
-            raise NotImplementedError("flair_amd: RestoreFormer resamples with convolutions (resamp_with_conv=True)")
-        self.with_conv = with_conv
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
-
-    def pack(self, dtype, device):
-        self._pk = dict(w=_pack(self.conv.weight, dtype, device), b=_dev(self.conv.bias, device))
-
-    def run(self, x):
-        up = ops.resize(x, (2 * x.shape[1], 2 * x.shape[2]), ops.RESIZE_NEAREST)
-        return ops.conv(up, self._pk["w"], self._pk["b"], self.conv.out_channels, (1, 3, 3))
+        super().__init__(in_channels)
+        self.with_conv = _with_conv(with_conv)
 
 
-class Downsample(nn.Module):
-    """restoreformer.py:138-155: F.pad(x, (0, 1, 0, 1)) + 3x3 stride-2 convolution without padding."""
+class Downsample(vb.Downsample):
+    """restoreformer.py:138-155."""
 
     def __init__(self, in_channels, with_conv):
-        super().__init__()
-        if not with_conv:
-            raise NotImplementedError("flair_amd: RestoreFormer resamples with convolutions (resamp_with_conv=True)")
-        self.with_conv = with_conv
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
-
-    def pack(self, dtype, device):
-        self._pk = dict(w=_pack(self.conv.weight, dtype, device), b=_dev(self.conv.bias, device))
-
-    def run(self, x):
-        return ops.conv(x, self._pk["w"], self._pk["b"], self.conv.out_channels, (1, 3, 3), stride=2, asym_pad=True)
+        super().__init__(in_channels)
+        self.with_conv = _with_conv(with_conv)
 
 
-class ResnetBlock(nn.Module):
-    """restoreformer.py:158-215.  The network never passes a timestep embedding (temb is None throughout), so a
-    ``temb_proj`` built for ``temb_channels > 0`` is a parameter container only; dropout is inference-time identity."""
+class ResnetBlock(vb.ResBlock):
+    """restoreformer.py:158-215; the shortcut is ``nin_shortcut`` (1x1) or ``conv_shortcut`` (3x3).  The network never
+    passes a timestep embedding (temb is None throughout), so a ``temb_proj`` built for ``temb_channels > 0`` is a
+    parameter container only; dropout is inference-time identity."""
 
     def __init__(self, *, in_channels, out_channels=None, conv_shortcut=False, dropout, temb_channels=512):
-        super().__init__()
-        self.in_channels = in_channels
-        out_channels = in_channels if out_channels is None else out_channels
-        self.out_channels = out_channels
+        super().__init__(in_channels, out_channels, shortcut_kernel=3 if conv_shortcut else 1,
+                         shortcut="conv_shortcut" if conv_shortcut else "nin_shortcut")
         self.use_conv_shortcut = conv_shortcut
-        self.norm1 = Normalize(in_channels)
-        self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)
         if temb_channels > 0:
-            self.temb_proj = nn.Linear(temb_channels, out_channels)
-        self.norm2 = Normalize(out_channels)
+            self.temb_proj = nn.Linear(temb_channels, self.out_channels)
         self.dropout = nn.Dropout(dropout)
-        self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
-        if self.in_channels != self.out_channels:
-            if self.use_conv_shortcut:
-                self.conv_shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)
-            else:
-                self.nin_shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, padding=0)
-
-    def pack(self, dtype, device):
-        self._pk = dict(w1=_pack(self.conv1.weight, dtype, device), b1=_dev(self.conv1.bias, device),
-                        w2=_pack(self.conv2.weight, dtype, device), b2=_dev(self.conv2.bias, device),
-                        n1_g=_dev(self.norm1.weight, device), n1_b=_dev(self.norm1.bias, device),
-                        n2_g=_dev(self.norm2.weight, device), n2_b=_dev(self.norm2.bias, device))
-        if self.in_channels != self.out_channels:
-            sc = self.conv_shortcut if self.use_conv_shortcut else self.nin_shortcut
-            self._pk["ws"] = _pack(sc.weight, dtype, device)
-            self._pk["bs"] = _dev(sc.bias, device)
-
-    def run(self, x):
-        pk, co = self._pk, self.out_channels
-        h = _gn(x, pk, "n1", A.ACT_SILU)
-        h = ops.conv(h, pk["w1"], pk["b1"], co, (1, 3, 3))
-        h = _gn(h, pk, "n2", A.ACT_SILU)
-        skip = x
-        if "ws" in pk:
-            k = 3 if self.use_conv_shortcut else 1
-            skip = ops.conv(x, pk["ws"], pk["bs"], co, (1, k, k))
-        return ops.conv(h, pk["w2"], pk["b2"], co, (1, 3, 3), res0=skip)
 
 
 class MultiHeadAttnBlock(nn.Module):
@@ -153,51 +107,27 @@ class MultiHeadAttnBlock(nn.Module):
         self.num = 0
 
     def pack(self, dtype, device):
-        self._pk = dict(n1_g=_dev(self.norm1.weight, device), n1_b=_dev(self.norm1.bias, device),
-                        n2_g=_dev(self.norm2.weight, device), n2_b=_dev(self.norm2.bias, device),
-                        wq=_pack(self.q.weight, dtype, device), bq=_dev(self.q.bias, device),
-                        wkv=_pack(torch.cat([self.k.weight, self.v.weight], dim=0), dtype, device),
-                        bkv=_dev(torch.cat([self.k.bias, self.v.bias]), device),
-                        wqkv=_pack(torch.cat([self.q.weight, self.k.weight, self.v.weight], dim=0), dtype, device),
-                        bqkv=_dev(torch.cat([self.q.bias, self.k.bias, self.v.bias]), device),
-                        wp=_pack(self.proj_out.weight, dtype, device), bp=_dev(self.proj_out.bias, device))
+        self._pk = dict(n1_g=dev_f32(self.norm1.weight, device), n1_b=dev_f32(self.norm1.bias, device),
+                        n2_g=dev_f32(self.norm2.weight, device), n2_b=dev_f32(self.norm2.bias, device),
+                        wq=pack_w(self.q.weight, dtype, device), bq=dev_f32(self.q.bias, device),
+                        wkv=pack_w(torch.cat([self.k.weight, self.v.weight], dim=0), dtype, device),
+                        bkv=dev_f32(torch.cat([self.k.bias, self.v.bias]), device),
+                        wqkv=pack_w(torch.cat([self.q.weight, self.k.weight, self.v.weight], dim=0), dtype, device),
+                        bqkv=dev_f32(torch.cat([self.q.bias, self.k.bias, self.v.bias]), device),
+                        wp=pack_w(self.proj_out.weight, dtype, device), bp=dev_f32(self.proj_out.bias, device))
 
     def run(self, x, y=None):
         pk, c = self._pk, self.in_channels
-        h_ = _gn(x, pk, "n1")
+        h_ = gn(x, pk, "n1")
         if y is None:
             qkv = ops.conv(h_, pk["wqkv"], pk["bqkv"], 3 * c, (1, 1, 1))
         else:
             assert y.shape == x.shape, (tuple(y.shape), tuple(x.shape))
             qkv = torch.empty(x.shape[:3] + (3 * c,), dtype=x.dtype, device=x.device)
-            ops.conv(_gn(y, pk, "n2"), pk["wq"], pk["bq"], c, (1, 1, 1), out=qkv[..., :c])
+            ops.conv(gn(y, pk, "n2"), pk["wq"], pk["bq"], c, (1, 1, 1), out=qkv[..., :c])
             ops.conv(h_, pk["wkv"], pk["bkv"], 2 * c, (1, 1, 1), out=qkv[..., c:])
         a = ops.qkv_attention(qkv, self.head_size, new_order=True)
         return ops.conv(a, pk["wp"], pk["bp"], c, (1, 1, 1), res0=x)
-
-
-class _Conv(nn.Conv2d):
-    """conv_in / conv_out: a bare 3x3 convolution, output channels padded to a multiple of 4."""
-
-    def pack(self, dtype, device):
-        cpad = (self.out_channels + 3) // 4 * 4
-        b = _dev(self.bias, device)
-        if cpad != self.out_channels:
-            b = torch.cat([b, b.new_zeros(cpad - self.out_channels)]).contiguous()
-        self._pk = dict(w=_pack(self.weight, dtype, device, cout_pad=cpad), b=b, cout=cpad)
-
-    def run(self, x):
-        return ops.conv(x, self._pk["w"], self._pk["b"], self._pk["cout"], (1, 3, 3))
-
-
-class _NormSwish(nn.GroupNorm):
-    """norm_out followed by nonlinearity() (restoreformer.py:406-407, :672-673)."""
-
-    def pack(self, dtype, device):
-        self._pk = dict(n_g=_dev(self.weight, device), n_b=_dev(self.bias, device))
-
-    def run(self, x):
-        return _gn(x, self._pk, "n", A.ACT_SILU)
 
 
 class MultiHeadEncoder(nn.Module):
@@ -214,7 +144,7 @@ class MultiHeadEncoder(nn.Module):
         self.resolution = resolution
         self.in_channels = in_channels
         self.enable_mid = enable_mid
-        self.conv_in = _Conv(in_channels, self.ch, kernel_size=3, stride=1, padding=1)
+        self.conv_in = HeadConv(in_channels, self.ch, kernel_size=3, stride=1, padding=1)
         curr_res = resolution
         in_ch_mult = (1,) + tuple(ch_mult)
         self.down = nn.ModuleList()
@@ -242,8 +172,8 @@ class MultiHeadEncoder(nn.Module):
             self.mid.attn_1 = MultiHeadAttnBlock(block_in, head_size)
             self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch,
                                            dropout=dropout)
-        self.norm_out = _NormSwish(32, block_in, eps=GN_EPS, affine=True)
-        self.conv_out = _Conv(block_in, 2 * z_channels if double_z else z_channels, kernel_size=3, stride=1, padding=1)
+        self.norm_out = NormOut(block_in, A.ACT_SILU)
+        self.conv_out = HeadConv(block_in, 2 * z_channels if double_z else z_channels, kernel_size=3, stride=1, padding=1)
 
     def run(self, x):
         """restoreformer.py:375-412 on a clip tensor -> {hs key: clip tensor}."""
@@ -287,7 +217,7 @@ class MultiHeadDecoderTransformer(nn.Module):
         block_in = ch * ch_mult[self.num_resolutions - 1]
         curr_res = resolution // 2 ** (self.num_resolutions - 1)
         self.z_shape = (1, z_channels, curr_res, curr_res)
-        self.conv_in = _Conv(z_channels, block_in, kernel_size=3, stride=1, padding=1)
+        self.conv_in = HeadConv(z_channels, block_in, kernel_size=3, stride=1, padding=1)
         if self.enable_mid:
             self.mid = nn.Module()
             self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch,
@@ -312,8 +242,8 @@ class MultiHeadDecoderTransformer(nn.Module):
                 up.upsample = Upsample(block_in, resamp_with_conv)
                 curr_res = curr_res * 2
             self.up.insert(0, up)
-        self.norm_out = _NormSwish(32, block_in, eps=GN_EPS, affine=True)
-        self.conv_out = _Conv(block_in, out_ch, kernel_size=3, stride=1, padding=1)
+        self.norm_out = NormOut(block_in, A.ACT_SILU)
+        self.conv_out = HeadConv(block_in, out_ch, kernel_size=3, stride=1, padding=1)
 
     def run(self, z, hs):
         """restoreformer.py:636-675 on clip tensors (``hs``: the encoder's NHWC features)."""
@@ -360,7 +290,7 @@ class Features(Mapping):
 STRIP_PREFIX = "vqvae."
 
 
-class VQVAEGANMultiHeadTransformer(nn.Module):
+class VQVAEGANMultiHeadTransformer(PackedModel, nn.Module):
     """restoreformer.py:764-861 (RestoreFormer).  The ``fix_*`` switches only set ``requires_grad`` (training)."""
 
     def __init__(self, n_embed=1024, embed_dim=256, ch=64, out_ch=3, ch_mult=(1, 2, 2, 4, 4, 8), num_res_blocks=2,
@@ -393,13 +323,6 @@ class VQVAEGANMultiHeadTransformer(nn.Module):
                 for p in m.parameters():
                     p.requires_grad = False
         self.in_channels, self.resolution, self.embed_dim, self.z_channels = in_channels, resolution, embed_dim, z_channels
-        self.dtype = torch.float32
-        self._packed_key = None
-
-    def convert_to_bf16(self):
-        self.dtype = torch.bfloat16
-        self._packed_key = None
-        return self
 
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         """The reference's names; also a RestoreFormer training checkpoint's ``state_dict`` (the network under
@@ -410,21 +333,12 @@ class VQVAEGANMultiHeadTransformer(nn.Module):
             state_dict = state_dict["state_dict"]
         if any(k.startswith(STRIP_PREFIX) for k in state_dict):
             state_dict = {k[len(STRIP_PREFIX):]: v for k, v in state_dict.items() if k.startswith(STRIP_PREFIX)}
-        out = super().load_state_dict(state_dict, strict=strict, **kwargs)
-        self._packed_key = None                 # kernel-native weight copies are rebuilt on the next forward
-        return out
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key == key:
-            return
-        dt = self.dtype
-        for m in self.modules():
-            if hasattr(m, "pack") and m is not self:
-                m.pack(dt, device)
-        self._pk = dict(wq=_pack(self.quant_conv.weight, dt, device), bq=_dev(self.quant_conv.bias, device),
-                        wpq=_pack(self.post_quant_conv.weight, dt, device), bpq=_dev(self.post_quant_conv.bias, device))
-        self._packed_key = key
+    def pack(self, dtype, device):
+        self._pk = dict(wq=pack_w(self.quant_conv.weight, dtype, device), bq=dev_f32(self.quant_conv.bias, device),
+                        wpq=pack_w(self.post_quant_conv.weight, dtype, device),
+                        bpq=dev_f32(self.post_quant_conv.bias, device))
 
     def _encode(self, input):
         """input (B, 3, r, r) f32 NCHW -> (z, hs): quant_conv's output and the encoder's features, clip tensors."""

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from .. import _lib, ops
 from .. import ops as A
+from .packing import PackedModel, fold_bn, pack_w, packed_conv, run_conv
 from .retinaface_utils import PriorBox, batched_decode, batched_decode_landm, decode, decode_landm, py_cpu_nms
 
 
@@ -44,51 +45,25 @@ def generate_config(network_name):
 
 
 class _ConvBN(nn.Sequential):
-    """conv_bn / conv_bn_no_relu / conv_bn1X1 of retinaface_net.py:6-24: Sequential(Conv2d(bias=False), BatchNorm2d[, LeakyReLU])."""
+    """conv_bn / conv_bn_no_relu / conv_bn1X1 of retinaface_net.py:6-24: Sequential(Conv2d(bias=False), BatchNorm2d[, LeakyReLU]).
+    relu_after: a ReLU the caller applies to the output (SSH's F.relu(cat(...))) rides in the epilogue; pad_out: the output
+    channels are padded to a whole K step (the zero channels feed a depthwise block)."""
 
-    def __init__(self, inp, oup, k, stride, leaky=None):
+    def __init__(self, inp, oup, k, stride, leaky=None, relu_after=False, pad_out=False):
         layers = [nn.Conv2d(inp, oup, k, stride, k // 2, bias=False), nn.BatchNorm2d(oup)]
         if leaky is not None:
             layers.append(nn.LeakyReLU(negative_slope=leaky, inplace=True))
         super().__init__(*layers)
-        self.leaky = leaky
+        assert leaky in (None, 0, 0.1)
+        self.leaky, self.pad_out = leaky, pad_out
+        self.act = (A.ACT_RELU if leaky == 0 else A.ACT_LRELU01) if leaky is not None else (A.ACT_RELU if relu_after else A.ACT_NONE)
 
-    def pack(self, dtype, device, relu_after=False, cout_pad=None):
-        self._p = _fold(self[0], self[1], dtype, device, cout_pad)
-        lk = self.leaky
-        self._act = (A.ACT_RELU if lk == 0 else A.ACT_LRELU01) if lk is not None else (A.ACT_RELU if relu_after else A.ACT_NONE)
-        assert lk in (None, 0, 0.1)
+    def pack(self, dtype, device):
+        cout_pad = ops.pad_channels(self[0].out_channels, dtype) if self.pad_out else None
+        self._pk = packed_conv(self[0], self[1], dtype, device, cout_pad)
 
     def run(self, x, out=None):
-        return _conv(x, self._p, self[0], self._act, out=out)
-
-
-def _fold_bn(conv, bn):
-    """conv's weight / bias (f32) with an eval-mode BatchNorm after it folded in (bn may be None)."""
-    w = conv.weight.detach().float()
-    b = conv.bias.detach().float() if conv.bias is not None else w.new_zeros(w.shape[0])
-    if bn is not None:
-        g = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-        w = w * g.view(-1, 1, 1, 1)
-        b = (b - bn.running_mean.detach().float()) * g + bn.bias.detach().float()
-    return w, b
-
-
-def _fold(conv, bn, dtype, device, cout_pad=None):
-    """Packed weights / bias of conv followed by an eval-mode BatchNorm (bn may be None); cout_pad: zero output channels
-    appended up to that width (default: the next multiple of 4)."""
-    w, b = _fold_bn(conv, bn)
-    cout, cin = w.shape[0], w.shape[1]
-    cpad = cout_pad if cout_pad is not None else (cout + 3) // 4 * 4
-    wp = ops.pack_conv_weight(w.to(device), [(cin, ops.pad_channels(cin, dtype))], dtype, cpad)
-    b = b.to(device)
-    return wp, torch.cat([b, b.new_zeros(cpad - cout)]).contiguous(), cpad
-
-
-def _conv(x, packed, conv, act, out=None, res0=None):
-    wp, b, cout = packed
-    k = conv.kernel_size[0]
-    return ops.conv(x, wp, b, cout, (1, k, k), stride=conv.stride[0], act=act, out=out, res0=res0)
+        return run_conv(x, self._pk, self[0], self.act, out=out)
 
 
 class Bottleneck(nn.Module):
@@ -107,15 +82,17 @@ class Bottleneck(nn.Module):
             self.downsample = downsample
 
     def pack(self, dtype, device):
-        self._p = [_fold(self.conv1, self.bn1, dtype, device), _fold(self.conv2, self.bn2, dtype, device),
-                   _fold(self.conv3, self.bn3, dtype, device)]
-        self._pd = _fold(self.downsample[0], self.downsample[1], dtype, device) if hasattr(self, "downsample") else None
+        self._pk = dict(c1=packed_conv(self.conv1, self.bn1, dtype, device), c2=packed_conv(self.conv2, self.bn2, dtype, device),
+                        c3=packed_conv(self.conv3, self.bn3, dtype, device))
+        if hasattr(self, "downsample"):
+            self._pk["down"] = packed_conv(self.downsample[0], self.downsample[1], dtype, device)
 
     def run(self, x):
-        ident = _conv(x, self._pd, self.downsample[0], A.ACT_NONE) if self._pd is not None else x
-        h = _conv(x, self._p[0], self.conv1, A.ACT_RELU)
-        h = _conv(h, self._p[1], self.conv2, A.ACT_RELU)
-        h = _conv(h, self._p[2], self.conv3, A.ACT_NONE)
+        pk = self._pk
+        ident = run_conv(x, pk["down"], self.downsample[0]) if "down" in pk else x
+        h = run_conv(x, pk["c1"], self.conv1, A.ACT_RELU)
+        h = run_conv(h, pk["c2"], self.conv2, A.ACT_RELU)
+        h = run_conv(h, pk["c3"], self.conv3)
         return ops.add_act(h, ident, A.ACT_RELU, out=h)          # out += identity; relu
 
 
@@ -138,13 +115,10 @@ class _ResNet50Body(nn.Module):
             setattr(self, f"layer{i + 1}", nn.Sequential(*layers))
 
     def pack(self, dtype, device):
-        self._p = _fold(self.conv1, self.bn1, dtype, device)
-        for m in self.modules():
-            if isinstance(m, Bottleneck):
-                m.pack(dtype, device)
+        self._pk = packed_conv(self.conv1, self.bn1, dtype, device)
 
     def run(self, x):
-        h = ops.maxpool3x3s2(_conv(x, self._p, self.conv1, A.ACT_RELU))
+        h = ops.maxpool3x3s2(run_conv(x, self._pk, self.conv1, A.ACT_RELU))
         outs = []
         for i in range(1, 5):
             for blk in getattr(self, f"layer{i}"):
@@ -172,17 +146,17 @@ class _ConvDW(nn.Sequential):
         assert dtype == torch.float32
         inp, oup = self[0].out_channels, self[3].out_channels
         cp, op = ops.pad_channels(inp, dtype), ops.pad_channels(oup, dtype)
-        wd, bd = _fold_bn(self[0], self[1])                                   # (inp, 1, 3, 3)
-        wp, bp = _fold_bn(self[3], self[4])                                   # (oup, inp, 1, 1)
+        wd, bd = fold_bn(self[0], self[1])                                    # (inp, 1, 3, 3)
+        wp, bp = fold_bn(self[3], self[4])                                    # (oup, inp, 1, 1)
         w_dw = torch.zeros(9, cp)
         w_dw[:, :inp] = wd.reshape(inp, 9).t()
-        w_pw = ops.pack_conv_weight(wp.to(device), [(inp, cp)], dtype, op)
-        self._p = (w_dw.to(device), F.pad(bd, (0, cp - inp)).to(device), w_pw, F.pad(bp, (0, op - oup)).to(device), op)
+        self._pk = dict(w_dw=w_dw.to(device), b_dw=F.pad(bd, (0, cp - inp)).to(device),
+                        w_pw=pack_w(wp, dtype, device, [(inp, cp)], op), b_pw=F.pad(bp, (0, op - oup)).to(device), cout=op)
 
     def run(self, x):
-        w_dw, b_dw, w_pw, b_pw, op = self._p
-        d = ops.dwconv(x, w_dw, b_dw, stride=self.stride, act=A.ACT_LRELU01)
-        return ops.conv(d, w_pw, b_pw, op, (1, 1, 1), act=A.ACT_LRELU01)
+        pk = self._pk
+        d = ops.dwconv(x, pk["w_dw"], pk["b_dw"], stride=self.stride, act=A.ACT_LRELU01)
+        return ops.conv(d, pk["w_pw"], pk["b_pw"], pk["cout"], (1, 1, 1), act=A.ACT_LRELU01)
 
 
 class _MobileNetV1Body(nn.Module):
@@ -192,16 +166,11 @@ class _MobileNetV1Body(nn.Module):
 
     def __init__(self):
         super().__init__()
-        self.stage1 = nn.Sequential(_ConvBN(3, 8, 3, 2, leaky=0.1), _ConvDW(8, 16, 1), _ConvDW(16, 32, 2), _ConvDW(32, 32, 1),
+        # the stem's zero channels 8..15 feed the first conv_dw
+        self.stage1 = nn.Sequential(_ConvBN(3, 8, 3, 2, leaky=0.1, pad_out=True), _ConvDW(8, 16, 1), _ConvDW(16, 32, 2), _ConvDW(32, 32, 1),
                                     _ConvDW(32, 64, 2), _ConvDW(64, 64, 1))
         self.stage2 = nn.Sequential(_ConvDW(64, 128, 2), *[_ConvDW(128, 128, 1) for _ in range(5)])
         self.stage3 = nn.Sequential(_ConvDW(128, 256, 2), _ConvDW(256, 256, 1))
-
-    def pack(self, dtype, device):
-        self.stage1[0].pack(dtype, device, cout_pad=ops.pad_channels(8, dtype))     # zero channels 8..15 feed the first conv_dw
-        for m in self.modules():
-            if isinstance(m, _ConvDW):
-                m.pack(dtype, device)
 
     def run(self, x):
         h = self.stage1[0].run(x)
@@ -220,17 +189,13 @@ class SSH(nn.Module):
         super().__init__()
         assert out_channel % 4 == 0
         leaky = 0.1 if out_channel <= 64 else 0
-        self.conv3X3 = _ConvBN(in_channel, out_channel // 2, 3, 1)
+        # F.relu(cat(...)) = the ReLU in the epilogue of each branch's last convolution
+        self.conv3X3 = _ConvBN(in_channel, out_channel // 2, 3, 1, relu_after=True)
         self.conv5X5_1 = _ConvBN(in_channel, out_channel // 4, 3, 1, leaky)
-        self.conv5X5_2 = _ConvBN(out_channel // 4, out_channel // 4, 3, 1)
+        self.conv5X5_2 = _ConvBN(out_channel // 4, out_channel // 4, 3, 1, relu_after=True)
         self.conv7X7_2 = _ConvBN(out_channel // 4, out_channel // 4, 3, 1, leaky)
-        self.conv7x7_3 = _ConvBN(out_channel // 4, out_channel // 4, 3, 1)
+        self.conv7x7_3 = _ConvBN(out_channel // 4, out_channel // 4, 3, 1, relu_after=True)
         self.out_channel = out_channel
-
-    def pack(self, dtype, device):
-        for m, relu_after in ((self.conv3X3, True), (self.conv5X5_1, False), (self.conv5X5_2, True), (self.conv7X7_2, False),
-                              (self.conv7x7_3, True)):
-            m.pack(dtype, device, relu_after)                   # F.relu(cat(...)) = the ReLU in each branch's epilogue
 
     def run(self, x):
         T, H, W, _ = x.shape
@@ -255,10 +220,6 @@ class FPN(nn.Module):
         self.merge1 = _ConvBN(out_channels, out_channels, 3, 1, leaky)
         self.merge2 = _ConvBN(out_channels, out_channels, 3, 1, leaky)
 
-    def pack(self, dtype, device):
-        for m in (self.output1, self.output2, self.output3, self.merge1, self.merge2):
-            m.pack(dtype, device)
-
     def run(self, feats):
         o1, o2, o3 = self.output1.run(feats[0]), self.output2.run(feats[1]), self.output3.run(feats[2])
         up3 = ops.resize(o3, (o2.shape[1], o2.shape[2]), ops.RESIZE_NEAREST)
@@ -278,10 +239,10 @@ class _Head(nn.Module):
         self.conv1x1 = nn.Conv2d(inchannels, num_anchors * k, kernel_size=(1, 1), stride=1, padding=0)
 
     def pack(self, dtype, device):
-        self._p = _fold(self.conv1x1, None, dtype, device)
+        self._pk = packed_conv(self.conv1x1, None, dtype, device)
 
     def run(self, x):
-        y = _conv(x, self._p, self.conv1x1, A.ACT_NONE)
+        y = run_conv(x, self._pk, self.conv1x1)
         return y[..., :self.conv1x1.out_channels].reshape(x.shape[0], -1, self.k)
 
 
@@ -312,7 +273,7 @@ def make_landmark_head(fpn_num=3, inchannels=64, anchor_num=2):
     return nn.ModuleList([LandmarkHead(inchannels, anchor_num) for _ in range(fpn_num)])
 
 
-class RetinaFace(nn.Module):
+class RetinaFace(PackedModel, nn.Module):
     """retinaface.py:79-418.  ``forward`` takes (B, 3, H, W) mean-subtracted float images (as the reference's does) and
     returns (bbox_regressions (B, N, 4), softmax(classifications) (B, N, 2), ldm_regressions (B, N, 10)) on the device."""
 
@@ -338,25 +299,12 @@ class RetinaFace(nn.Module):
         self.ClassHead = make_class_head(fpn_num=3, inchannels=oc)
         self.BboxHead = make_bbox_head(fpn_num=3, inchannels=oc)
         self.LandmarkHead = make_landmark_head(fpn_num=3, inchannels=oc)
-        self.dtype = torch.float32
-        self._packed_key = None
         self.to(self.device)
         self.eval()
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}   # detection/__init__.py:39-43
-        out = super().load_state_dict(sd, *args, **kwargs)
-        self._packed_key = None
-        return out
-
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key != key:
-            self.body.pack(self.dtype, device)
-            self.fpn.pack(self.dtype, device)
-            for m in (self.ssh1, self.ssh2, self.ssh3, *self.ClassHead, *self.BboxHead, *self.LandmarkHead):
-                m.pack(self.dtype, device)
-            self._packed_key = key
+        return super().load_state_dict(sd, *args, **kwargs)
 
     def _to_clip(self, inputs):
         if not inputs.is_cuda:

@@ -22,7 +22,8 @@ import torch.nn as nn
 
 from .. import ops
 from .nn_new import linear, zero_module
-from .unet_new import (A, BasicVSRPP, Ctx, PlaceHolder, SPyNet, TemporalAttention, _dev, _pack, normalization)
+from .packing import PackedModel, dev_f32, pack_w, packed_conv, pk_int, run_conv
+from .unet_new import A, BasicVSRPP, Ctx, PlaceHolder, SPyNet, TemporalAttention, normalization
 
 LazyReshaper2D = LazyReshaper3D = PlaceHolder
 
@@ -111,21 +112,24 @@ class ResnetBlock(nn.Module):
         self.block1 = Block(dim, dim_out, groups=norm_groups)
         self.block2 = Block(dim_out, dim_out, groups=norm_groups, dropout=dropout)
         self.res_conv = LazyReshaper2D(nn.Conv2d(dim, dim_out, 1)) if dim != dim_out else nn.Identity()
-        self.plain_off = 0
-        self._pk = None
 
-    def pack(self, dtype, device, split=None):
+    plain_off = pk_int("plain_off")
+
+    def pack(self, dtype, device, split=None, plain_off=0):
+        """plain_off / silu_off (below): where a module's noise-embedding linear starts in the network's two batched
+        matrices (Ctx.plain_all, Ctx.silu_all)."""
         c, co = self.dim, self.dim_out
         b1, b2 = self.block1.block, self.block2.block
         self._pk = dict(
-            g1=_dev(b1[0].wrapped_module.weight, device), be1=_dev(b1[0].wrapped_module.bias, device),
-            w1=_pack(b1[3].wrapped_module.weight, [(c, c)], dtype, device), b1=_dev(b1[3].wrapped_module.bias, device),
-            g2=_dev(b2[0].wrapped_module.weight, device), be2=_dev(b2[0].wrapped_module.bias, device),
-            w2=_pack(b2[3].wrapped_module.weight, [(co, co)], dtype, device), b2=_dev(b2[3].wrapped_module.bias, device))
+            plain_off=plain_off,
+            g1=dev_f32(b1[0].wrapped_module.weight, device), be1=dev_f32(b1[0].wrapped_module.bias, device),
+            w1=pack_w(b1[3].wrapped_module.weight, dtype, device, [(c, c)]), b1=dev_f32(b1[3].wrapped_module.bias, device),
+            g2=dev_f32(b2[0].wrapped_module.weight, device), be2=dev_f32(b2[0].wrapped_module.bias, device),
+            w2=pack_w(b2[3].wrapped_module.weight, dtype, device, [(co, co)]), b2=dev_f32(b2[3].wrapped_module.bias, device))
         if not isinstance(self.res_conv, nn.Identity):
             segs = [(s, s) for s in (split or [c])]
-            self._pk["ws"] = _pack(self.res_conv.wrapped_module.weight, segs, dtype, device)
-            self._pk["bs"] = _dev(self.res_conv.wrapped_module.bias, device)
+            self._pk["ws"] = pack_w(self.res_conv.wrapped_module.weight, dtype, device, segs)
+            self._pk["bs"] = dev_f32(self.res_conv.wrapped_module.bias, device)
 
     def run(self, ctx, x, x1=None):
         pk, co = self._pk, self.dim_out
@@ -133,7 +137,7 @@ class ResnetBlock(nn.Module):
         eps = self.block1.block[0].wrapped_module.eps
         h = ops.group_norm(x, pk["g1"], pk["be1"], x1=x1, groups=g, eps=eps, act=A.ACT_SILU)
         h = ops.conv(h, pk["w1"], pk["b1"], co, (1, 3, 3),
-                     frame_bias=ctx.plain_all[:, self.plain_off:self.plain_off + co])
+                     frame_bias=ctx.plain_all[:, pk["plain_off"]:pk["plain_off"] + co])
         h = ops.group_norm(h, pk["g2"], pk["be2"], groups=g, eps=eps, act=A.ACT_SILU)
         if "ws" in pk:
             skip = ops.conv([x] if x1 is None else [x, x1], pk["ws"], pk["bs"], co, (1, 1, 1))
@@ -162,25 +166,26 @@ class ResBlock(nn.Module):
             LazyReshaper3D(normalization(channels)), nn.SiLU(), nn.Dropout(p=dropout),
             zero_module(PlaceHolder(conv(channels, channels, kernel_size, padding=padding))))
         self.skip_connection = nn.Identity()
-        self.silu_off = 0
-        self._pk = None
 
-    def pack(self, dtype, device):
+    silu_off = pk_int("silu_off")
+
+    def pack(self, dtype, device, silu_off=0):
         c = self.channels
         self._pk = dict(
-            g1=_dev(self.in_layers[0].wrapped_module.weight, device), be1=_dev(self.in_layers[0].wrapped_module.bias, device),
-            w1=_pack(self.in_layers[2].wrapped_module.weight, [(c, c)], dtype, device),
-            b1=_dev(self.in_layers[2].wrapped_module.bias, device),
-            g2=_dev(self.out_layers[0].wrapped_module.weight, device), be2=_dev(self.out_layers[0].wrapped_module.bias, device),
-            w2=_pack(self.out_layers[3].wrapped_module.weight, [(c, c)], dtype, device),
-            b2=_dev(self.out_layers[3].wrapped_module.bias, device))
+            silu_off=silu_off,
+            g1=dev_f32(self.in_layers[0].wrapped_module.weight, device), be1=dev_f32(self.in_layers[0].wrapped_module.bias, device),
+            w1=pack_w(self.in_layers[2].wrapped_module.weight, dtype, device, [(c, c)]),
+            b1=dev_f32(self.in_layers[2].wrapped_module.bias, device),
+            g2=dev_f32(self.out_layers[0].wrapped_module.weight, device), be2=dev_f32(self.out_layers[0].wrapped_module.bias, device),
+            w2=pack_w(self.out_layers[3].wrapped_module.weight, dtype, device, [(c, c)]),
+            b2=dev_f32(self.out_layers[3].wrapped_module.bias, device))
 
     def run(self, ctx, x):
         pk, c = self._pk, self.channels
         k = self.kernel if self.dims == 3 else (1,) + self.kernel
         eps = self.in_layers[0].wrapped_module.eps
         h = ops.group_norm(x, pk["g1"], pk["be1"], eps=eps, act=A.ACT_SILU)
-        h = ops.conv(h, pk["w1"], pk["b1"], c, k, frame_bias=ctx.silu_all[:, self.silu_off:self.silu_off + c])
+        h = ops.conv(h, pk["w1"], pk["b1"], c, k, frame_bias=ctx.silu_all[:, pk["silu_off"]:pk["silu_off"] + c])
         h = ops.group_norm(h, pk["g2"], pk["be2"], eps=eps, act=A.ACT_SILU)
         return ops.conv(h, pk["w2"], pk["b2"], c, k, res0=x)
 
@@ -201,10 +206,15 @@ class TemporalWrapper2(nn.Module):
         self.wrapped_module = module
         self.dim = dim
         self.emb_layers = nn.Sequential(nn.SiLU(), zero_module(linear(time_emb_dim, dim)))
-        self.silu_off = 0
+
+    silu_off = pk_int("silu_off")
+
+    def pack(self, dtype, device, silu_off=0):
+        self._pk = dict(silu_off=silu_off)
 
     def blend(self, ctx, x, m):
-        return ops.gated_blend(x, m, ctx.silu_all[:, self.silu_off:self.silu_off + self.dim])
+        off = self._pk["silu_off"]
+        return ops.gated_blend(x, m, ctx.silu_all[:, off:off + self.dim])
 
 
 class FlowVSRPP(BasicVSRPP):
@@ -259,6 +269,12 @@ class Downsample(nn.Module):
         super().__init__()
         self.conv = nn.Conv2d(dim, dim, 3, 2, 1)
 
+    def pack(self, dtype, device):
+        self._pk = packed_conv(self.conv, None, dtype, device)
+
+    def run(self, x):
+        return run_conv(x, self._pk, self.conv)
+
 
 class Upsample(nn.Module):
     def __init__(self, dim):
@@ -266,8 +282,15 @@ class Upsample(nn.Module):
         self.up = nn.Upsample(scale_factor=2, mode="nearest")
         self.conv = nn.Conv2d(dim, dim, 3, padding=1)
 
+    def pack(self, dtype, device):
+        self._pk = packed_conv(self.conv, None, dtype, device)
 
-class UNet(nn.Module):
+    def run(self, x):
+        up = ops.resize(x, (2 * x.shape[1], 2 * x.shape[2]), ops.RESIZE_NEAREST)
+        return run_conv(up, self._pk, self.conv)
+
+
+class UNet(PackedModel, nn.Module):
     """sr3.py:317-525.  ``timesteps`` is the continuous noise level sqrt(acp_prev)[t+1] that
     respace._WrappedModel supplies (attribute ``takes_noise_level``)."""
 
@@ -329,7 +352,6 @@ class UNet(nn.Module):
                 res *= 2
         self.ups = nn.ModuleList(ups)
         self.final_conv = Block(pre, out_channel if out_channel is not None else in_channel, groups=norm_groups)
-        self._packed_key = None
         self._flow_cache = {}
         self._graphs = {}
         self.use_hip_graph = False
@@ -343,69 +365,41 @@ class UNet(nn.Module):
         return self
 
     # ---- dtype management --------------------------------------------------------------
-    def convert_to_fp16(self):
-        self.dtype = torch.bfloat16
-        self._packed_key = None
-        self._graphs = {}
+    convert_to_fp16 = PackedModel.convert_to_bf16        # the reference's name; bfloat16 is the reduced precision here
 
-    def convert_to_fp32(self):
-        self.dtype = torch.float32
-        self._packed_key = None
-        self._graphs = {}
-
-    def load_state_dict(self, *args, **kwargs):
-        out = super().load_state_dict(*args, **kwargs)
-        self._packed_key = None
-        self._graphs = {}
-        return out
+    def invalidate_packed(self):
+        super().invalidate_packed()
+        self._graphs, self._flow_cache = {}, {}      # captured launches and cached flows were made with the old copies
 
     # ---- packing -----------------------------------------------------------------------
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key == key:
-            return
-        dt = self.dtype
+    def _pack_all(self, dt, device):
         stem = self.downs[0].wrapped_module
-        stem._pk_w = _pack(stem.weight, [(self.in_channel, ops.pad_channels(self.in_channel, dt))], dt, device)
-        stem._pk_b = _dev(stem.bias, device)
+        stem._pk = packed_conv(stem, None, dt, device)
         plain_w, plain_b, silu_w, silu_b = [], [], [], []
         po = so = 0
         for m in self.modules():
             if isinstance(m, ResnetBlock):
-                m.pack(dt, device, self._skip_split.get(id(m)))
+                m.pack(dt, device, self._skip_split.get(id(m)), plain_off=po)
                 lin = m.noise_func.noise_func[0]
-                m.plain_off = po
-                plain_w.append(_dev(lin.weight, device)); plain_b.append(_dev(lin.bias, device))
+                plain_w.append(dev_f32(lin.weight, device)); plain_b.append(dev_f32(lin.bias, device))
                 po += lin.out_features
             elif isinstance(m, (ResBlock, TemporalWrapper2)):
-                if isinstance(m, ResBlock):
-                    m.pack(dt, device)
+                m.pack(dt, device, silu_off=so)
                 lin = m.emb_layers[1]
-                m.silu_off = so
-                silu_w.append(_dev(lin.weight, device)); silu_b.append(_dev(lin.bias, device))
+                silu_w.append(dev_f32(lin.weight, device)); silu_b.append(dev_f32(lin.bias, device))
                 so += lin.out_features
-            elif isinstance(m, (TemporalAttention, BasicVSRPP)):
+            elif isinstance(m, (TemporalAttention, BasicVSRPP, Downsample, Upsample)):
                 m.pack(dt, device)
-            elif isinstance(m, (Downsample, Upsample)):
-                c = m.conv.in_channels
-                m._pk_w = _pack(m.conv.weight, [(c, c)], dt, device)
-                m._pk_b = _dev(m.conv.bias, device)
-        self._plain = (torch.cat(plain_w).contiguous(), torch.cat(plain_b).contiguous())
-        self._silu = (torch.cat(silu_w).contiguous(), torch.cat(silu_b).contiguous())
         if self._shared_spynet[0] is not None:
             self._shared_spynet[0].to(device)
-            self._shared_spynet[0].pack(device)
-        mlp = self.noise_level_mlp
-        self._mlp = [_dev(p, device) for p in (mlp[1].weight, mlp[1].bias, mlp[3].weight, mlp[3].bias)]
-        fc = self.final_conv.block
-        cout = self.out_channel if self.out_channel is not None else self.in_channel
-        cpad = (cout + 3) // 4 * 4
-        cin = fc[3].wrapped_module.in_channels
-        self._fin = dict(g=_dev(fc[0].wrapped_module.weight, device), be=_dev(fc[0].wrapped_module.bias, device),
-                         w=_pack(fc[3].wrapped_module.weight, [(cin, cin)], dt, device, cout_pad=cpad),
-                         b=torch.cat([_dev(fc[3].wrapped_module.bias, device),
-                                      torch.zeros(cpad - cout, device=device)]).contiguous(), cout=cout, cpad=cpad)
-        self._packed_key = key
+            self._shared_spynet[0].pack(dt, device)
+        mlp, fc = self.noise_level_mlp, self.final_conv.block
+        self._pk = dict(
+            plain=(torch.cat(plain_w).contiguous(), torch.cat(plain_b).contiguous()),
+            silu=(torch.cat(silu_w).contiguous(), torch.cat(silu_b).contiguous()),
+            mlp=[dev_f32(p, device) for p in (mlp[1].weight, mlp[1].bias, mlp[3].weight, mlp[3].bias)],
+            fin_g=dev_f32(fc[0].wrapped_module.weight, device), fin_b=dev_f32(fc[0].wrapped_module.bias, device),
+            fin=packed_conv(fc[3].wrapped_module, None, dt, device))
         self._flow_cache = {}
 
     def reset_flow_cache(self):
@@ -505,10 +499,11 @@ class UNet(nn.Module):
         else:
             ctx.flows = self._flows_for(rnn, res_needed) if res_needed else {}
         pe = ops.timestep_embedding(level, self.inner_channel, sin_first=True)
-        e = ops.linear(pe, self._mlp[0], self._mlp[1], act_out=A.ACT_SILU)
-        emb = ops.linear(e, self._mlp[2], self._mlp[3])
-        ctx.plain_all = ops.linear(emb, self._plain[0], self._plain[1])
-        ctx.silu_all = ops.linear(emb, self._silu[0], self._silu[1], act_in=A.ACT_SILU)
+        pk = self._pk
+        e = ops.linear(pe, pk["mlp"][0], pk["mlp"][1], act_out=A.ACT_SILU)
+        emb = ops.linear(e, pk["mlp"][2], pk["mlp"][3])
+        ctx.plain_all = ops.linear(emb, pk["plain"][0], pk["plain"][1])
+        ctx.silu_all = ops.linear(emb, pk["silu"][0], pk["silu"][1], act_in=A.ACT_SILU)
         cin = ops.pad_channels(self.in_channel, dt)
         h = torch.zeros((T, H, W, cin), dtype=dt, device=dev)
         ops.nchw_to_clip(low_res, h, 0)
@@ -524,12 +519,10 @@ class UNet(nn.Module):
                 h = layer.run(ctx, h, feats.pop())
             else:
                 h = self._run_layer(ctx, layer, h)
-        f = self._fin
-        g = self.final_conv.groups
-        h = ops.group_norm(h, f["g"], f["be"], groups=g, eps=self.final_conv.block[0].wrapped_module.eps,
-                           act=A.ACT_SILU)
-        y = ops.conv(h, f["w"], f["b"], f["cpad"], (1, 3, 3))
-        return ops.clip_to_nchw(y, f["cout"])
+        fc = self.final_conv
+        h = ops.group_norm(h, pk["fin_g"], pk["fin_b"], groups=fc.groups, eps=fc.block[0].wrapped_module.eps, act=A.ACT_SILU)
+        y = run_conv(h, pk["fin"], fc.block[3].wrapped_module)
+        return ops.clip_to_nchw(y, fc.block[3].wrapped_module.out_channels)
 
     def _vsrpp_levels(self, size):
         """(resolution, module) of every BasicVSRPP in the network for an input of side `size`."""
@@ -552,12 +545,8 @@ class UNet(nn.Module):
         if isinstance(layer, ResnetBlocWithAttn):
             return layer.run(ctx, h)
         inner = layer.wrapped_module
-        if isinstance(inner, nn.Conv2d):
-            return ops.conv(h, inner._pk_w, inner._pk_b, inner.out_channels, (1, 3, 3))
-        if isinstance(inner, Downsample):
-            return ops.conv(h, inner._pk_w, inner._pk_b, inner.conv.out_channels, (1, 3, 3), stride=2)
-        if isinstance(inner, Upsample):
-            T, H, W, C = h.shape
-            up = ops.resize(h, (2 * H, 2 * W), ops.RESIZE_NEAREST)
-            return ops.conv(up, inner._pk_w, inner._pk_b, inner.conv.out_channels, (1, 3, 3))
+        if isinstance(inner, nn.Conv2d):                # the stem
+            return run_conv(h, inner._pk, inner)
+        if isinstance(inner, (Downsample, Upsample)):
+            return inner.run(h)
         raise TypeError(f"flair_amd: no executor for {type(inner).__name__}")

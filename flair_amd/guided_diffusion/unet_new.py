@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from .. import ops
 from .nn_new import conv_nd, linear, normalization, zero_module
+from .packing import PackedModel, dev_f32, pack_w, packed_conv, pk_int, run_conv
 
 A = ops  # activation codes live there
 
@@ -46,13 +47,6 @@ class TemporalWrapper(PlaceHolder):
     """unet_new.py:50-59 (skipped when ``enable_cross_frames`` is False)."""
 
 
-def _dev(p, device):
-    t = p.detach()
-    if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.to(device=device, dtype=torch.float32).contiguous()
-    return t
-
-
 class Ctx:
     """Per-forward execution context."""
 
@@ -63,10 +57,6 @@ class Ctx:
         self.flows = {}
         self.vsrpp_weights = None
         self.enable_cross_frames = True
-
-
-def _pack(w, segs, dtype, device, cout_pad=None):
-    return ops.pack_conv_weight(w.detach().to(device), segs, dtype, cout_pad)
 
 
 # --------------------------------------------------------------------------- ResBlock
@@ -96,31 +86,33 @@ class ResBlock(nn.Module):
             self.skip_connection = nn.Identity()
         else:
             self.skip_connection = PlaceHolder(conv_nd(dims, channels, self.out_channels, 1))
-        self.film_off = 0
-        self._pk = None
 
-    def pack(self, dtype, device, split=None):
-        """split: channel widths of the (implicitly concatenated) input segments."""
+    film_off = pk_int("film_off")
+
+    def pack(self, dtype, device, split=None, film_off=0):
+        """split: channel widths of the (implicitly concatenated) input segments; film_off: where this block's
+        emb_layers output starts in the network's batched embedding matrix (Ctx.film_all)."""
         c, co = self.channels, self.out_channels
         segs = [(s, s) for s in (split or [c])]
         self._pk = dict(
-            w1=_pack(self.in_layers[2].wrapped_module.weight, [(c, c)], dtype, device),
-            b1=_dev(self.in_layers[2].wrapped_module.bias, device),
-            w2=_pack(self.out_layers[3].wrapped_module.weight, [(co, co)], dtype, device),
-            b2=_dev(self.out_layers[3].wrapped_module.bias, device),
-            g1=_dev(self.in_layers[0].wrapped_module.weight, device),
-            be1=_dev(self.in_layers[0].wrapped_module.bias, device),
-            g2=_dev(self.out_layers[0].wrapped_module.weight, device),
-            be2=_dev(self.out_layers[0].wrapped_module.bias, device))
+            film_off=film_off,
+            w1=pack_w(self.in_layers[2].wrapped_module.weight, dtype, device, [(c, c)]),
+            b1=dev_f32(self.in_layers[2].wrapped_module.bias, device),
+            w2=pack_w(self.out_layers[3].wrapped_module.weight, dtype, device, [(co, co)]),
+            b2=dev_f32(self.out_layers[3].wrapped_module.bias, device),
+            g1=dev_f32(self.in_layers[0].wrapped_module.weight, device),
+            be1=dev_f32(self.in_layers[0].wrapped_module.bias, device),
+            g2=dev_f32(self.out_layers[0].wrapped_module.weight, device),
+            be2=dev_f32(self.out_layers[0].wrapped_module.bias, device))
         if not isinstance(self.skip_connection, nn.Identity):
-            self._pk["ws"] = _pack(self.skip_connection.wrapped_module.weight, segs, dtype, device)
-            self._pk["bs"] = _dev(self.skip_connection.wrapped_module.bias, device)
+            self._pk["ws"] = pack_w(self.skip_connection.wrapped_module.weight, dtype, device, segs)
+            self._pk["bs"] = dev_f32(self.skip_connection.wrapped_module.bias, device)
 
     def run(self, ctx, x, x1=None):
         pk = self._pk
         co = self.out_channels
         k = (1, 3, 3) if self.dims == 2 else (3, 3, 3)
-        film = ctx.film_all[:, self.film_off:self.film_off + 2 * co]
+        film = ctx.film_all[:, pk["film_off"]:pk["film_off"] + 2 * co]
         eps = self.in_layers[0].wrapped_module.eps
         if self.up or self.down:
             assert x1 is None
@@ -179,6 +171,7 @@ class AttentionBlock(nn.Module):
     """unet_new.py:332-377."""
 
     bottleneck = False
+    film_off = pk_int("film_off")
 
     def __init__(self, channels, num_heads=1, num_head_channels=-1, use_checkpoint=False,
                  use_new_attention_order=False):
@@ -197,16 +190,15 @@ class AttentionBlock(nn.Module):
         self.attention = (QKVAttention if use_new_attention_order else QKVAttentionLegacy)(self.num_heads)
         self.new_order = use_new_attention_order
         self.proj_out = zero_module(conv_nd(1, channels, channels, 1))
-        self.film_off = 0
-        self._pk = None
 
-    def pack(self, dtype, device):
+    def pack(self, dtype, device, film_off=0):
         c = self.channels
         self._pk = dict(
-            g=_dev(self.norm.wrapped_module.weight, device), be=_dev(self.norm.wrapped_module.bias, device),
-            wqkv=_pack(self.qkv.weight.unsqueeze(-1), [(c, c)], dtype, device), bqkv=_dev(self.qkv.bias, device),
-            wp=_pack(self.proj_out.weight.unsqueeze(-1), [(c, c)], dtype, device),
-            bp=_dev(self.proj_out.bias, device))
+            film_off=film_off,
+            g=dev_f32(self.norm.wrapped_module.weight, device), be=dev_f32(self.norm.wrapped_module.bias, device),
+            wqkv=pack_w(self.qkv.weight.unsqueeze(-1), dtype, device, [(c, c)]), bqkv=dev_f32(self.qkv.bias, device),
+            wp=pack_w(self.proj_out.weight.unsqueeze(-1), dtype, device, [(c, c)]),
+            bp=dev_f32(self.proj_out.bias, device))
 
     def run(self, ctx, x):
         pk, c = self._pk, self.channels
@@ -214,7 +206,7 @@ class AttentionBlock(nn.Module):
         qkv = ops.conv(n, pk["wqkv"], pk["bqkv"], 3 * c, (1, 1, 1))
         a = ops.qkv_attention(qkv, self.num_heads, new_order=self.new_order)
         if self.bottleneck:
-            ops.add_frame_bias(a, ctx.film_all[:, self.film_off:self.film_off + c])
+            ops.add_frame_bias(a, ctx.film_all[:, pk["film_off"]:pk["film_off"] + c])
         return ops.conv(a, pk["wp"], pk["bp"], c, (1, 1, 1), res0=x)
 
 
@@ -248,7 +240,6 @@ class TemporalAttention(nn.Module):
         self.attn = FalshAttn()
         self.proj = zero_module(PlaceHolder(conv_nd(2, channels, channels, 1)))
         self.norm = PlaceHolder(normalization(channels))
-        self._pk = None
 
     def pack(self, dtype, device):
         c, f = self.channels, self.num_frames
@@ -256,24 +247,24 @@ class TemporalAttention(nn.Module):
         # constants of the layer: fold them once (q bias, per-slot key bias).
         offs = torch.arange(f, dtype=torch.float32, device=device) - f // 2
         mid = f // 2
-        wq, wk, wv = (_dev(m.weight, device) for m in (self.q_linear, self.k_linear, self.v_linear))
+        wq, wk, wv = (dev_f32(m.weight, device) for m in (self.q_linear, self.k_linear, self.v_linear))
         if torch.device(device).type == "cuda":
             pe = ops.timestep_embedding(offs, c)
-            bq = ops.linear(pe[mid:mid + 1].contiguous(), wq, _dev(self.q_linear.bias, device))
+            bq = ops.linear(pe[mid:mid + 1].contiguous(), wq, dev_f32(self.q_linear.bias, device))
             kpos = ops.linear(torch.cat([pe[:mid], pe[mid + 1:]]).contiguous(), wk, None)
         else:   # host-side packing (multi-process CPU tests of the weight blob): the same one-time folding in torch
             freqs = torch.exp(-math.log(10000.0) * torch.arange(c // 2, dtype=torch.float32) / (c // 2))
             ang = offs[:, None] * freqs[None]
             pe = torch.cat([torch.cos(ang), torch.sin(ang)], dim=-1)
-            bq = pe[mid:mid + 1] @ wq.t() + _dev(self.q_linear.bias, device)
+            bq = pe[mid:mid + 1] @ wq.t() + dev_f32(self.q_linear.bias, device)
             kpos = torch.cat([pe[:mid], pe[mid + 1:]]) @ wk.t()
         wqkv = torch.cat([wq, wk, wv]).reshape(3 * c, c, 1, 1)
-        bqkv = torch.cat([bq.reshape(-1), _dev(self.k_linear.bias, device), _dev(self.v_linear.bias, device)])
+        bqkv = torch.cat([bq.reshape(-1), dev_f32(self.k_linear.bias, device), dev_f32(self.v_linear.bias, device)])
         self._pk = dict(
-            g=_dev(self.norm.wrapped_module.weight, device), be=_dev(self.norm.wrapped_module.bias, device),
-            wqkv=_pack(wqkv, [(c, c)], dtype, device), bqkv=bqkv.contiguous(), kpos=kpos,
-            wp=_pack(self.proj.wrapped_module.weight, [(c, c)], dtype, device),
-            bp=_dev(self.proj.wrapped_module.bias, device))
+            g=dev_f32(self.norm.wrapped_module.weight, device), be=dev_f32(self.norm.wrapped_module.bias, device),
+            wqkv=pack_w(wqkv, dtype, device, [(c, c)]), bqkv=bqkv.contiguous(), kpos=kpos,
+            wp=pack_w(self.proj.wrapped_module.weight, dtype, device, [(c, c)]),
+            bp=dev_f32(self.proj.wrapped_module.bias, device))
 
     def run(self, ctx, h):
         pk, c = self._pk, self.channels
@@ -306,10 +297,10 @@ class ResidualBlocksWithInputConv(nn.Module):
     def pack(self, dtype, device, split):
         c = self.main[0].out_channels
         rb = self.main[2][0]
-        return dict(w0=_pack(self.main[0].weight, [(s, s) for s in split], dtype, device),
-                    b0=_dev(self.main[0].bias, device),
-                    w1=_pack(rb.conv1.weight, [(c, c)], dtype, device), b1=_dev(rb.conv1.bias, device),
-                    w2=_pack(rb.conv2.weight, [(c, c)], dtype, device), b2=_dev(rb.conv2.bias, device))
+        return dict(w0=pack_w(self.main[0].weight, dtype, device, [(s, s) for s in split]),
+                    b0=dev_f32(self.main[0].bias, device),
+                    w1=pack_w(rb.conv1.weight, dtype, device, [(c, c)]), b1=dev_f32(rb.conv1.bias, device),
+                    w2=pack_w(rb.conv2.weight, dtype, device, [(c, c)]), b2=dev_f32(rb.conv2.bias, device))
 
 
 # Fused two-convolution launches (flair_conv_chain) replace pairs of dependent per-frame launches where the
@@ -359,11 +350,11 @@ class SecondOrderDeformableAlignment(nn.Module):
         perm = ops.dcn_raw_permutation(self.deform_groups)   # tap-major offsets for flair_dcn_align
         w6, b6 = co[6].weight.detach()[perm], co[6].bias.detach()[perm]
         return dict(
-            w0=_pack(co[0].weight, [(c, c), (c, c), (c, c), (4, ka)], dtype, device), b0=_dev(co[0].bias, device),
-            w2=_pack(co[2].weight, [(c, c)], dtype, device), b2=_dev(co[2].bias, device),
-            w4=_pack(co[4].weight, [(c, c)], dtype, device), b4=_dev(co[4].bias, device),
-            w6=_pack(w6, [(c, c)], dtype, device), b6=_dev(b6, device),
-            wd=_pack(self.weight, [(2 * c, 2 * c)], dtype, device), bd=_dev(self.bias, device))
+            w0=pack_w(co[0].weight, dtype, device, [(c, c), (c, c), (c, c), (4, ka)]), b0=dev_f32(co[0].bias, device),
+            w2=pack_w(co[2].weight, dtype, device, [(c, c)]), b2=dev_f32(co[2].bias, device),
+            w4=pack_w(co[4].weight, dtype, device, [(c, c)]), b4=dev_f32(co[4].bias, device),
+            w6=pack_w(w6, dtype, device, [(c, c)]), b6=dev_f32(b6, device),
+            wd=pack_w(self.weight, dtype, device, [(2 * c, 2 * c)]), bd=dev_f32(self.bias, device))
 
 
 class BasicVSRPP(nn.Module):
@@ -382,7 +373,6 @@ class BasicVSRPP(nn.Module):
             self.backbone[name] = ResidualBlocksWithInputConv((2 + i) * mid_channels, mid_channels, 1)
         self.reconstruction = ResidualBlocksWithInputConv(3 * mid_channels, mid_channels, 1)
         self.conv_last = zero_module(nn.Conv2d(mid_channels, mid_channels, 1, 1))
-        self._pk = None
 
     def pack(self, dtype, device):
         c = self.mid_channels
@@ -391,7 +381,7 @@ class BasicVSRPP(nn.Module):
             trunk={"backward_1": self.backbone["backward_1"].pack(dtype, device, [c, c]),
                    "forward_1": self.backbone["forward_1"].pack(dtype, device, [c, c, c])},
             recon=self.reconstruction.pack(dtype, device, [c, c, c]),
-            wl=_pack(self.conv_last.weight, [(c, c)], dtype, device), bl=_dev(self.conv_last.bias, device))
+            wl=pack_w(self.conv_last.weight, dtype, device, [(c, c)]), bl=dev_f32(self.conv_last.bias, device))
 
     def _propagate(self, ctx, hidden, flows, name, others, weight, wmaps, dest):
         """others: list of (T,H,W,c) feature stacks of earlier branches; dest: (T,H,W,c)
@@ -510,21 +500,20 @@ class SPyNet(nn.Module):
         self.basic_module = nn.ModuleList([SPyNetBasicModule() for _ in range(6)])
         self.register_buffer("mean", torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
         self.register_buffer("std", torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
-        self._pk = None
 
-    def pack(self, device):
-        f32 = torch.float32
+    def pack(self, dtype, device):
+        f32 = torch.float32                     # SPyNet stays f32 whatever the network's dtype
         levels = []
         for bm in self.basic_module:
             convs = [m.conv for m in bm.basic_module]
-            ws = [_pack(convs[0].weight, [(3, 4), (3, 4), (2, 8)], f32, device)]
-            ws += [_pack(convs[j].weight, [(convs[j].in_channels,) * 2], f32, device) for j in (1, 2, 3)]
-            ws.append(_pack(convs[4].weight, [(16, 16)], f32, device, cout_pad=4))
-            bs = [_dev(convs[j].bias, device) for j in range(4)]
-            bs.append(torch.cat([_dev(convs[4].bias, device), torch.zeros(2, device=device)]).contiguous())
+            ws = [pack_w(convs[0].weight, f32, device, [(3, 4), (3, 4), (2, 8)])]
+            ws += [pack_w(convs[j].weight, f32, device, [(convs[j].in_channels,) * 2]) for j in (1, 2, 3)]
+            ws.append(pack_w(convs[4].weight, f32, device, [(16, 16)], cout_pad=4))
+            bs = [dev_f32(convs[j].bias, device) for j in range(4)]
+            bs.append(torch.cat([dev_f32(convs[4].bias, device), torch.zeros(2, device=device)]).contiguous())
             levels.append((ws, bs))
-        mean = _dev(self.mean.reshape(-1), device)
-        istd = (1.0 / _dev(self.std.reshape(-1), device)).contiguous()
+        mean = dev_f32(self.mean.reshape(-1), device)
+        istd = (1.0 / dev_f32(self.std.reshape(-1), device)).contiguous()
         self._pk = dict(levels=levels, mean=mean, istd=istd)
 
     def run(self, ref, supp):
@@ -580,7 +569,7 @@ class TimestepEmbedSequential(nn.Sequential):
             elif isinstance(inner, (AttentionBlock, TemporalAttention, BasicVSRPP)):
                 h = inner.run(ctx, h)
             elif isinstance(inner, nn.Conv2d):      # the stem
-                h = ops.conv(h, inner._pk_w, inner._pk_b, inner.out_channels, (1, 3, 3))
+                h = run_conv(h, inner._pk, inner)
             elif isinstance(inner, nn.Identity):
                 pass
             else:
@@ -588,7 +577,7 @@ class TimestepEmbedSequential(nn.Sequential):
         return h
 
 
-class UNetModel(nn.Module):
+class UNetModel(PackedModel, nn.Module):
     """unet_new.py:901-1362 (same arguments; ``use_fp16`` / ``convert_to_fp16`` select bf16)."""
 
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks,
@@ -672,7 +661,6 @@ class UNetModel(nn.Module):
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(LazyReshaper3D(normalization(ch)), nn.SiLU(),
                                  zero_module(LazyReshaper2D(conv_nd(dims, input_ch, out_channels, 3, padding=1))))
-        self._packed_key = None
         self._flow_cache = {}
         self._graphs = {}
         self.use_hip_graph = False
@@ -686,23 +674,13 @@ class UNetModel(nn.Module):
         return self
 
     # ---- dtype management (reference names) ------------------------------------------
-    def convert_to_fp16(self):
-        """Reference: fp16 torso (unet_new.py:1224-1238).  Here: bfloat16 kernels (f32
-        accumulate; GroupNorm statistics, embeddings, flows and SPyNet stay f32)."""
-        self.dtype = torch.bfloat16
-        self._packed_key = None
-        self._graphs = {}
+    # Reference: fp16 torso (unet_new.py:1224-1238).  Here: bfloat16 kernels (f32 accumulate; GroupNorm statistics,
+    # embeddings, flows and SPyNet stay f32).
+    convert_to_fp16 = PackedModel.convert_to_bf16
 
-    def convert_to_fp32(self):
-        self.dtype = torch.float32
-        self._packed_key = None
-        self._graphs = {}
-
-    def load_state_dict(self, *args, **kwargs):
-        out = super().load_state_dict(*args, **kwargs)
-        self._packed_key = None
-        self._graphs = {}
-        return out
+    def invalidate_packed(self):
+        super().invalidate_packed()
+        self._graphs, self._flow_cache = {}, {}      # captured launches and cached flows were made with the old copies
 
     def reset_flow_cache(self):
         """Forget cached SPyNet flows (the sampler calls this at the start of every chain: flows are a
@@ -711,49 +689,31 @@ class UNetModel(nn.Module):
         self._flow_gen = getattr(self, "_flow_gen", 0) + 1
 
     # ---- weight packing ---------------------------------------------------------------
-    def _res_blocks(self):
-        for m in self.modules():
-            if isinstance(m, ResBlock):
-                yield m
-
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key == key:
-            return
-        dt = self.dtype
-        ka = ops.k_align(dt)
+    def _pack_all(self, dt, device):
         stem = self.input_blocks[0][0].wrapped_module
-        stem._pk_w = _pack(stem.weight, [(self.in_channels, ops.pad_channels(self.in_channels, dt))], dt, device)
-        stem._pk_b = _dev(stem.bias, device)
+        stem._pk = packed_conv(stem, None, dt, device)
         # first ResBlock of every output stage reads (h | skip) as two segments
         first_out = {id(st[0]): split for st, split in zip(self.output_blocks, self._skip_split)}
         ws, bs, off = [], [], 0
         for m in self.modules():
+            film = isinstance(m, ResBlock) or (isinstance(m, AttentionBlock) and m.bottleneck)
             if isinstance(m, ResBlock):
-                m.pack(dt, device, list(first_out[id(m)]) if id(m) in first_out else None)
-            elif isinstance(m, (AttentionBlock, TemporalAttention, BasicVSRPP)):
+                m.pack(dt, device, list(first_out[id(m)]) if id(m) in first_out else None, film_off=off)
+            elif isinstance(m, AttentionBlock):
+                m.pack(dt, device, film_off=off if film else 0)
+            elif isinstance(m, (TemporalAttention, BasicVSRPP, SPyNet)):
                 m.pack(dt, device)
-            else:
-                continue
-            if isinstance(m, ResBlock) or getattr(m, "bottleneck", False):
+            if film:                                  # has emb_layers: a slice of film_all
                 lin = m.emb_layers[1]
-                m.film_off = off
-                ws.append(_dev(lin.weight, device))
-                bs.append(_dev(lin.bias, device))
+                ws.append(dev_f32(lin.weight, device))
+                bs.append(dev_f32(lin.bias, device))
                 off += lin.out_features
-        self._emb_w = torch.cat(ws).contiguous()
-        self._emb_b = torch.cat(bs).contiguous()
-        self.spynet.pack(device)
-        self._te = [_dev(p, device) for p in (self.time_embed[0].weight, self.time_embed[0].bias,
-                                               self.time_embed[2].weight, self.time_embed[2].bias)]
-        head = self.out[2].wrapped_module
-        cpad = (self.out_channels + 3) // 4 * 4
-        self._head_w = _pack(head.weight, [(head.in_channels,) * 2], dt, device, cout_pad=cpad)
-        self._head_b = torch.cat([_dev(head.bias, device),
-                                  torch.zeros(cpad - self.out_channels, device=device)]).contiguous()
-        self._head_g = _dev(self.out[0].wrapped_module.weight, device)
-        self._head_be = _dev(self.out[0].wrapped_module.bias, device)
-        self._packed_key = key
+        self._pk = dict(
+            emb_w=torch.cat(ws).contiguous(), emb_b=torch.cat(bs).contiguous(),
+            te=[dev_f32(p, device) for p in (self.time_embed[0].weight, self.time_embed[0].bias,
+                                            self.time_embed[2].weight, self.time_embed[2].bias)],
+            head_g=dev_f32(self.out[0].wrapped_module.weight, device), head_b=dev_f32(self.out[0].wrapped_module.bias, device),
+            head=packed_conv(self.out[2].wrapped_module, None, dt, device))
         self._flow_cache = {}
 
     # ---- optical flow (once per clip) --------------------------------------------------
@@ -872,9 +832,10 @@ class UNetModel(nn.Module):
         ctx.flows = flows if flows is not None else self._flows_for(rnn)
         # timestep embedding MLP and every emb_layers linear of the network (f32)
         temb = ops.timestep_embedding(t.float().contiguous(), self.model_channels)
-        e = ops.linear(temb, self._te[0], self._te[1], act_out=A.ACT_SILU)
-        ctx.emb = ops.linear(e, self._te[2], self._te[3])
-        ctx.film_all = ops.linear(ctx.emb, self._emb_w, self._emb_b, act_in=A.ACT_SILU)
+        pk = self._pk
+        e = ops.linear(temb, pk["te"][0], pk["te"][1], act_out=A.ACT_SILU)
+        ctx.emb = ops.linear(e, pk["te"][2], pk["te"][3])
+        ctx.film_all = ops.linear(ctx.emb, pk["emb_w"], pk["emb_b"], act_in=A.ACT_SILU)
         # stem input: [x | low_res | 0...] as one K step of channels
         cin = ops.pad_channels(self.in_channels, dt)
         h = torch.zeros((T, H, W, cin), dtype=dt, device=dev)
@@ -894,6 +855,6 @@ class UNetModel(nn.Module):
             h = blk.run(ctx, h, hs.pop())
             if trace is not None:
                 trace.append((f"output_blocks.{i}", h))
-        h = ops.group_norm(h, self._head_g, self._head_be, eps=self.out[0].wrapped_module.eps, act=A.ACT_SILU)
-        y = ops.conv(h, self._head_w, self._head_b, self._head_w.shape[0], (1, 3, 3))
+        h = ops.group_norm(h, pk["head_g"], pk["head_b"], eps=self.out[0].wrapped_module.eps, act=A.ACT_SILU)
+        y = run_conv(h, pk["head"], self.out[2].wrapped_module)
         return ops.clip_to_nchw(y, self.out_channels)

@@ -33,16 +33,14 @@ import torch.nn as nn
 
 from .. import ops
 from .. import ops as A
-from .codeformer import GN_EPS, _dev, _gn, _pack
+from . import vqgan_blocks as vb
+from .packing import PackedModel, dev_f32, pack_w
 from .unet_new import qkv_head_width
+from .vqgan_blocks import Downsample, HeadConv, NormOut, Upsample, gn  # noqa: F401  (Downsample :83-94, Upsample :97-107)
 
 DCN_GROUPS = (4, 8, 16)          # flair_dcn_align's deformable groups (4 with raw offsets only)
 CODE_DIM = 256                   # fixed by L2VectorQuantizer(code_dim=256) and LayerNorm(256) (vqfr.py:536-547)
 RESOLUTION = 512                 # the 16 x 16 code grid (spatial_size) after len(channel_multipliers) - 1 = 5 halvings
-
-
-def _normalize(channels):
-    return nn.GroupNorm(num_groups=32, num_channels=channels, eps=GN_EPS, affine=True)
 
 
 class L2VectorQuantizer(nn.Module):
@@ -58,106 +56,36 @@ class L2VectorQuantizer(nn.Module):
         self.embedding.weight.data.uniform_(-1.0 / self.num_code, 1.0 / self.num_code)
 
     def pack(self, dtype, device):
-        self._pk = dict(codebook=_dev(self.embedding.weight, device))
+        self._pk = dict(codebook=dev_f32(self.embedding.weight, device))
 
     def run(self, z, forced_idx=None):
         return ops.vq_nearest(z, self._pk["codebook"], forced_idx=forced_idx)
 
 
-class Downsample(nn.Module):
-    """vqfr.py:83-94: F.pad(x, (0, 1, 0, 1)) + 3x3 stride-2 convolution without padding."""
+class ResnetBlock(vb.ResBlock):
+    """vqfr.py:110-144.  ``run(x, x1)`` takes the input as two channel parts (cat([x, x1]) of MainDecoder, :486), which
+    reach the 1x1 shortcut ``residual_func`` as two equal unpadded segments."""
 
-    def __init__(self, in_channels):
-        super().__init__()
-        self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
-
-    def pack(self, dtype, device):
-        self._pk = dict(w=_pack(self.conv.weight, dtype, device), b=_dev(self.conv.bias, device))
-
-    def run(self, x):
-        return ops.conv(x, self._pk["w"], self._pk["b"], self.conv.out_channels, (1, 3, 3), stride=2, asym_pad=True)
-
-
-class Upsample(nn.Module):
-    """vqfr.py:97-107: nearest x2, then a 3x3 convolution."""
-
-    def __init__(self, in_channels):
-        super().__init__()
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
-
-    def pack(self, dtype, device):
-        self._pk = dict(w=_pack(self.conv.weight, dtype, device), b=_dev(self.conv.bias, device))
-
-    def run(self, x):
-        up = ops.resize(x, (2 * x.shape[1], 2 * x.shape[2]), ops.RESIZE_NEAREST)
-        return ops.conv(up, self._pk["w"], self._pk["b"], self.conv.out_channels, (1, 3, 3))
-
-
-class ResnetBlock(nn.Module):
-    """vqfr.py:110-144.  ``run(x, x1)`` takes the input as two channel parts (cat([x, x1]) of MainDecoder, :486)."""
+    shortcut = "residual_func"
 
     def __init__(self, channels_in, channels_out):
-        super().__init__()
-        self.norm1 = _normalize(channels_in)
-        self.conv1 = nn.Conv2d(channels_in, channels_out, kernel_size=(3, 3), stride=(1, 1), padding=1)
-        self.norm2 = _normalize(channels_out)
-        self.conv2 = nn.Conv2d(channels_out, channels_out, kernel_size=(3, 3), stride=(1, 1), padding=1)
+        super().__init__(channels_in, channels_out)
         self.act = nn.SiLU(inplace=True)
-        if channels_in != channels_out:
-            self.residual_func = nn.Conv2d(channels_in, channels_out, kernel_size=1)
-        else:
+        if channels_in == channels_out:
             self.residual_func = nn.Identity()
         self.channels_in, self.channels_out = channels_in, channels_out
 
-    def pack(self, dtype, device):
-        self._pk = dict(w1=_pack(self.conv1.weight, dtype, device), b1=_dev(self.conv1.bias, device),
-                        w2=_pack(self.conv2.weight, dtype, device), b2=_dev(self.conv2.bias, device),
-                        n1_g=_dev(self.norm1.weight, device), n1_b=_dev(self.norm1.bias, device),
-                        n2_g=_dev(self.norm2.weight, device), n2_b=_dev(self.norm2.bias, device))
-        if self.channels_in != self.channels_out:
-            self._pk["ws"] = _pack(self.residual_func.weight, dtype, device)   # two-part inputs: equal unpadded segments
-            self._pk["bs"] = _dev(self.residual_func.bias, device)
 
-    def run(self, x, x1=None, out_scale=1.0):
-        """-> (conv2(...) + residual(x)) * out_scale."""
-        pk, co = self._pk, self.channels_out
-        h = _gn(x, pk, "n1", A.ACT_SILU, x1=x1)
-        h = ops.conv(h, pk["w1"], pk["b1"], co, (1, 3, 3))
-        h = _gn(h, pk, "n2", A.ACT_SILU)
-        xs = [x] if x1 is None else [x, x1]
-        if "ws" in pk:
-            skip = ops.conv(xs, pk["ws"], pk["bs"], co, (1, 1, 1))
-        else:
-            assert x1 is None
-            skip = x
-        return ops.conv(h, pk["w2"], pk["b2"], co, (1, 3, 3), res0=skip, out_scale=out_scale)
+class AttnBlock(vb.AttnBlock):
+    """vqfr.py:147-194: the single head runs on flair_qkv_attention (scale c**-0.5)."""
 
-
-class AttnBlock(nn.Module):
-    """vqfr.py:147-194: one head as wide as the channels over the h*w pixels, scale c**-0.5; q | k | v as three channel
-    slices of one buffer, the projection with the residual in its epilogue."""
+    @staticmethod
+    def attention(qkv, c):
+        return ops.qkv_attention(qkv, 1, new_order=True)
 
     def __init__(self, in_channels):
-        super().__init__()
-        self.in_channels = in_channels
         qkv_head_width(in_channels, 1)          # widths the attention kernels cannot run are refused here
-        self.norm = _normalize(in_channels)
-        self.q = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.k = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.v = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.proj_out = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-
-    def pack(self, dtype, device):
-        self._pk = dict(n_g=_dev(self.norm.weight, device), n_b=_dev(self.norm.bias, device),
-                        wqkv=_pack(torch.cat([self.q.weight, self.k.weight, self.v.weight], dim=0), dtype, device),
-                        bqkv=_dev(torch.cat([self.q.bias, self.k.bias, self.v.bias]), device),
-                        wp=_pack(self.proj_out.weight, dtype, device), bp=_dev(self.proj_out.bias, device))
-
-    def run(self, x):
-        pk, c = self._pk, self.in_channels
-        qkv = ops.conv(_gn(x, pk, "n"), pk["wqkv"], pk["bqkv"], 3 * c, (1, 1, 1))
-        a = ops.qkv_attention(qkv, 1, new_order=True)
-        return ops.conv(a, pk["wp"], pk["bp"], c, (1, 1, 1), res0=x)
+        super().__init__(in_channels)
 
 
 def _run_seq(seq, x):
@@ -166,19 +94,14 @@ def _run_seq(seq, x):
     return x
 
 
-def _pack_conv_out(seq, dtype, device):
-    """conv_out = Sequential(GroupNorm, SiLU, Conv2d 3x3): output channels padded to a multiple of 4."""
-    gn, conv = seq[0], seq[2]
-    cpad = (conv.out_channels + 3) // 4 * 4
-    b = _dev(conv.bias, device)
-    if cpad != conv.out_channels:
-        b = torch.cat([b, b.new_zeros(cpad - conv.out_channels)]).contiguous()
-    return dict(n_g=_dev(gn.weight, device), n_b=_dev(gn.bias, device),
-                w=_pack(conv.weight, dtype, device, cout_pad=cpad), b=b, cout=cpad)
+def _conv_out(channels, cout):
+    """conv_out = Sequential(GroupNorm, SiLU, Conv2d 3x3) with the reference's entry names; entry 1 is applied by entry 0."""
+    return nn.Sequential(NormOut(channels, A.ACT_SILU), nn.SiLU(inplace=True),
+                         HeadConv(channels, cout, kernel_size=3, padding=1))
 
 
-def _run_conv_out(pk, x):
-    return ops.conv(_gn(x, pk, "n", A.ACT_SILU), pk["w"], pk["b"], pk["cout"], (1, 3, 3))
+def _run_conv_out(seq, x):
+    return seq[2].run(seq[0].run(x))
 
 
 class VQGANEncoder(nn.Module):
@@ -188,7 +111,7 @@ class VQGANEncoder(nn.Module):
         super(VQGANEncoder, self).__init__()
         self.num_levels = len(channel_multipliers)
         self.num_blocks = num_blocks
-        self.conv_in = nn.Conv2d(3, base_channels * channel_multipliers[0], kernel_size=(3, 3), stride=(1, 1), padding=1)
+        self.conv_in = HeadConv(3, base_channels * channel_multipliers[0], kernel_size=(3, 3), stride=(1, 1), padding=1)
         self.blocks = nn.ModuleList()
         for i in range(self.num_levels):
             blocks = []
@@ -213,22 +136,14 @@ class VQGANEncoder(nn.Module):
                                             ResnetBlock(channels, channels))
         else:
             self.mid_blocks = nn.Sequential(ResnetBlock(channels, channels), ResnetBlock(channels, channels))
-        self.conv_out = nn.Sequential(
-            nn.GroupNorm(num_groups=32, num_channels=channels, eps=1e-6, affine=True),
-            nn.SiLU(inplace=True),
-            nn.Conv2d(channels, code_dim, kernel_size=3, padding=1),
-        )
-
-    def pack(self, dtype, device):
-        self._pk = dict(w_in=_pack(self.conv_in.weight, dtype, device), b_in=_dev(self.conv_in.bias, device),
-                        out=_pack_conv_out(self.conv_out, dtype, device))
+        self.conv_out = _conv_out(channels, code_dim)
 
     def run(self, x):
-        x = ops.conv(x, self._pk["w_in"], self._pk["b_in"], self.conv_in.out_channels, (1, 3, 3))
+        x = self.conv_in.run(x)
         for i in range(self.num_levels):
             x = _run_seq(self.blocks[i], x)
         x = _run_seq(self.mid_blocks, x)
-        return _run_conv_out(self._pk["out"], x)
+        return _run_conv_out(self.conv_out, x)
 
 
 class VQGANDecoder(nn.Module):
@@ -238,8 +153,8 @@ class VQGANDecoder(nn.Module):
         super(VQGANDecoder, self).__init__()
         self.num_levels = len(channel_multipliers)
         self.num_blocks = num_blocks
-        self.conv_in = nn.Conv2d(code_dim, base_channels * channel_multipliers[-1], kernel_size=(3, 3), stride=(1, 1),
-                                 padding=1)
+        self.conv_in = HeadConv(code_dim, base_channels * channel_multipliers[-1], kernel_size=(3, 3), stride=(1, 1),
+                                padding=1)
         self.blocks = nn.ModuleList()
         channels = base_channels * channel_multipliers[-1]
         if use_dec_attention:
@@ -265,19 +180,11 @@ class VQGANDecoder(nn.Module):
                     blocks.append(AttnBlock(channels))
             self.blocks.append(nn.Sequential(*blocks))
         channels = base_channels * channel_multipliers[0]
-        self.conv_out = nn.Sequential(
-            nn.GroupNorm(num_groups=32, num_channels=channels, eps=1e-6, affine=True),
-            nn.SiLU(inplace=True),
-            nn.Conv2d(channels, 3, kernel_size=3, padding=1),
-        )
-
-    def pack(self, dtype, device):
-        self._pk = dict(w_in=_pack(self.conv_in.weight, dtype, device), b_in=_dev(self.conv_in.bias, device),
-                        out=_pack_conv_out(self.conv_out, dtype, device))
+        self.conv_out = _conv_out(channels, 3)
 
     def run(self, x):
         dec_res = {}
-        x = ops.conv(x, self._pk["w_in"], self._pk["b_in"], self.conv_in.out_channels, (1, 3, 3))
+        x = self.conv_in.run(x)
         x = _run_seq(self.mid_blocks, x)
         for i, level in enumerate(reversed(range(self.num_levels))):
             x = _run_seq(self.blocks[i], x)
@@ -310,10 +217,10 @@ class DCNv2Pack(nn.Module):
         perm = ops.dcn_raw_permutation(G)       # tap-major offsets / masks for flair_dcn_align
         cpad = (27 * G + 7) // 8 * 8            # raw rows 16-byte granular in bf16 (27 * 4 = 108 channels is not)
         b = self.conv_offset.bias.detach()[perm]
-        self._pk = dict(wo=_pack(self.conv_offset.weight.detach()[perm], dtype, device, cout_pad=cpad),
-                        bo=_dev(torch.cat([b, b.new_zeros(cpad - 27 * G)]), device), cpad=cpad,
-                        w=_pack(self.weight, dtype, device, [(self.in_channels, self.in_channels)]),
-                        b=_dev(self.bias, device))
+        self._pk = dict(wo=pack_w(self.conv_offset.weight.detach()[perm], dtype, device, cout_pad=cpad),
+                        bo=dev_f32(torch.cat([b, b.new_zeros(cpad - 27 * G)]), device), cpad=cpad,
+                        w=pack_w(self.weight, dtype, device, [(self.in_channels, self.in_channels)]),
+                        b=dev_f32(self.bias, device))
 
     def run(self, x, feat):
         pk = self._pk
@@ -350,13 +257,13 @@ class TextureWarpingModule(nn.Module):
         o1, o2 = self.offset_conv1, self.offset_conv2
         w2 = o2[0].weight.detach().clone()
         w2[:, c:] *= 2                          # upsample_offset = interpolate(offset) * 2 (vqfr.py:470-476): exact
-        self._pk = dict(w_a=_pack(o1[0].weight, dtype, device, [(cc, cc), (c, c)]), b_a=_dev(o1[0].bias, device),
-                        na_g=_dev(o1[1].weight, device), na_b=_dev(o1[1].bias, device),
-                        w_dw=_dev(o1[3].weight.detach().reshape(c, 49).t(), device), b_dw=_dev(o1[3].bias, device),
-                        nb_g=_dev(o1[4].weight, device), nb_b=_dev(o1[4].bias, device),
-                        w_b=_pack(o1[6].weight, dtype, device), b_b=_dev(o1[6].bias, device),
-                        w_2=_pack(w2, dtype, device, [(c, c)] + ([(pc, pc)] if pc else [])),
-                        b_2=_dev(o2[0].bias, device), n2_g=_dev(o2[1].weight, device), n2_b=_dev(o2[1].bias, device))
+        self._pk = dict(w_a=pack_w(o1[0].weight, dtype, device, [(cc, cc), (c, c)]), b_a=dev_f32(o1[0].bias, device),
+                        na_g=dev_f32(o1[1].weight, device), na_b=dev_f32(o1[1].bias, device),
+                        w_dw=dev_f32(o1[3].weight.detach().reshape(c, 49).t(), device), b_dw=dev_f32(o1[3].bias, device),
+                        nb_g=dev_f32(o1[4].weight, device), nb_b=dev_f32(o1[4].bias, device),
+                        w_b=pack_w(o1[6].weight, dtype, device), b_b=dev_f32(o1[6].bias, device),
+                        w_2=pack_w(w2, dtype, device, [(c, c)] + ([(pc, pc)] if pc else [])),
+                        b_2=dev_f32(o2[0].bias, device), n2_g=dev_f32(o2[1].weight, device), n2_b=dev_f32(o2[1].bias, device))
 
     def run(self, x_main, inpfeat, previous_offset=None):
         pk, c = self._pk, self.channel
@@ -368,15 +275,15 @@ class TextureWarpingModule(nn.Module):
                                  out=torch.empty((F_, h // r, w // r, inpfeat.shape[3]), dtype=inpfeat.dtype,
                                                  device=inpfeat.device))
         o = ops.conv([inpfeat, x_main], pk["w_a"], pk["b_a"], c, (1, 1, 1))
-        o = _gn(o, pk, "na", A.ACT_SILU)
+        o = gn(o, pk, "na", A.ACT_SILU)
         o = ops.dwconv7(o, pk["w_dw"], pk["b_dw"])
-        o = _gn(o, pk, "nb", A.ACT_SILU)
+        o = gn(o, pk, "nb", A.ACT_SILU)
         o = ops.conv(o, pk["w_b"], pk["b_b"], c, (1, 1, 1))
         xs = [o]
         if previous_offset is not None:
             up = torch.empty((F_, H, W, previous_offset.shape[3]), dtype=o.dtype, device=o.device)
             xs.append(ops.resize(previous_offset, (H, W), ops.RESIZE_BILINEAR, out=up))
-        offset = _gn(ops.conv(xs, pk["w_2"], pk["b_2"], c, (1, 3, 3)), pk, "n2", A.ACT_SILU)
+        offset = gn(ops.conv(xs, pk["w_2"], pk["b_2"], c, (1, 3, 3)), pk, "n2", A.ACT_SILU)
         return self.dcn.run(x_main, offset), offset
 
 
@@ -398,7 +305,7 @@ class MainDecoder(nn.Module):
             if i != self.num_levels - 1:
                 self.pre_upsample_dict["Level_%d" % 2 ** i] = nn.Sequential(
                     nn.UpsamplingNearest2d(scale_factor=2),
-                    nn.Conv2d(channels_prev, channels, kernel_size=3, padding=1),
+                    HeadConv(channels_prev, channels, kernel_size=3, padding=1),
                 )
             previous_offset_channel = 0 if i == self.num_levels - 1 else channels_prev
             self.align_func_dict["Level_%d" % (2 ** i)] = TextureWarpingModule(
@@ -411,10 +318,6 @@ class MainDecoder(nn.Module):
             if i != self.num_levels - 1:
                 self.decoder_dict["Level_%d" % 2 ** i] = ResnetBlock(2 * channels, channels)
 
-    def pack(self, dtype, device):
-        self._pk = {key: dict(w=_pack(seq[1].weight, dtype, device), b=_dev(seq[1].bias, device), c=seq[1].out_channels)
-                    for key, seq in self.pre_upsample_dict.items()}
-
     def run(self, dec_res, inpfeat, fidelity_ratio=1.0, trace=None):
         top = "Level_%d" % 2 ** (self.num_levels - 1)
         x, offset = self.align_func_dict[top].run(dec_res[top], inpfeat)
@@ -422,9 +325,8 @@ class MainDecoder(nn.Module):
             trace["twm." + top] = (x, offset)
         for scale in reversed(range(self.num_levels - 1)):
             key = "Level_%d" % 2 ** scale
-            pk = self._pk[key]
             up = ops.resize(x, (2 * x.shape[1], 2 * x.shape[2]), ops.RESIZE_NEAREST)
-            x = ops.conv(up, pk["w"], pk["b"], pk["c"], (1, 3, 3))
+            x = self.pre_upsample_dict[key][1].run(up)
             warp_feat, offset = self.align_func_dict[key].run(dec_res[key], inpfeat, previous_offset=offset)
             if trace is not None:
                 trace["twm." + key] = (warp_feat, offset)
@@ -457,7 +359,7 @@ def _check_config(base_channels, channel_multipliers, code_dim, inpfeat_dim, cod
                                       f"{DCN_GROUPS} with a power-of-two group width >= 8 and <= 1024 channels")
 
 
-class VQFRv2(nn.Module):
+class VQFRv2(PackedModel, nn.Module):
     """vqfr.py:490-586 (VQFR v2)."""
 
     def __init__(self, base_channels, channel_multipliers, num_enc_blocks, use_enc_attention, num_dec_blocks,
@@ -474,12 +376,10 @@ class VQFRv2(nn.Module):
                                     num_blocks=num_dec_blocks, use_dec_attention=use_dec_attention, code_dim=code_dim)
         self.main_branch = MainDecoder(base_channels=base_channels, channel_multipliers=channel_multipliers,
                                        align_opt=align_opt)
-        self.inpfeat_extraction = nn.Conv2d(3, inpfeat_dim, 3, padding=1)
+        self.inpfeat_extraction = HeadConv(3, inpfeat_dim, 3, padding=1)
         self.quantizer = L2VectorQuantizer(num_code=1024, code_dim=256, spatial_size=(16, 16))
         self.apply(self._init_weights)
         self.code_selection_mode, self.inpfeat_dim, self.code_dim = code_selection_mode, inpfeat_dim, code_dim
-        self.dtype = torch.float32
-        self._packed_key = None
 
     @torch.no_grad()
     def _init_weights(self, m):
@@ -492,36 +392,20 @@ class VQFRv2(nn.Module):
             nn.init.constant_(m.bias, 0)
             nn.init.constant_(m.weight, 1.0)
 
-    def convert_to_bf16(self):
-        self.dtype = torch.bfloat16
-        self._packed_key = None
-        return self
-
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         """A bare state dict, or a BasicSR checkpoint holding it under ``params_ema`` (preferred) or ``params``."""
         for key in ("params_ema", "params"):
             if key in state_dict and isinstance(state_dict[key], Mapping):
                 state_dict = state_dict[key]
                 break
-        out = super().load_state_dict(state_dict, strict=strict, **kwargs)
-        self._packed_key = None                 # kernel-native weight copies are rebuilt on the next forward
-        return out
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key == key:
-            return
-        dt = self.dtype
-        for m in self.modules():
-            if hasattr(m, "pack") and m is not self:
-                m.pack(dt, device)
-        self._pk = dict(w_inp=_pack(self.inpfeat_extraction.weight, dt, device),
-                        b_inp=_dev(self.inpfeat_extraction.bias, device))
+    def pack(self, dtype, device):
+        self._pk = {}
         if self.feat2index is not None:
             ln, lin = self.feat2index
-            self._pk.update(ln_g=_dev(ln.weight, device), ln_b=_dev(ln.bias, device), ln_eps=ln.eps,
-                            w_lin=_pack(lin.weight, dt, device), b_lin=_dev(lin.bias, device))
-        self._packed_key = key
+            self._pk = dict(ln_g=dev_f32(ln.weight, device), ln_b=dev_f32(ln.bias, device),
+                            w_lin=pack_w(lin.weight, dtype, device), b_lin=dev_f32(lin.bias, device))
 
     @torch.no_grad()
     def forward(self, x_lq, fidelity_ratio=1.0, *, code_idx=None, texture=False, trace=None):
@@ -539,12 +423,12 @@ class VQFRv2(nn.Module):
         x = torch.zeros((B, r, r, ops.pad_channels(3, dt)), dtype=dt, device=dev)
         ops.nchw_to_clip(x_lq.float().contiguous(), x, 0)
         pk = self._pk
-        inp_feat = ops.conv(x, pk["w_inp"], pk["b_inp"], self.inpfeat_dim, (1, 3, 3))
+        inp_feat = self.inpfeat_extraction.run(x)
         enc = self.encoder.run(x)                                           # (B, 16, 16, 256)
         res = {"enc_feat": ops.clip_to_nchw(enc, self.code_dim)}
         forced = None if code_idx is None else code_idx.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
         if self.feat2index is not None:
-            t = ops.layer_norm(enc, pk["ln_g"], pk["ln_b"], eps=pk["ln_eps"])
+            t = ops.layer_norm(enc, pk["ln_g"], pk["ln_b"], eps=self.feat2index[0].eps)
             logits = ops.conv(t, pk["w_lin"], pk["b_lin"], 1024, (1, 1, 1))
             res["quant_logit"] = logits.float().reshape(B, 256, 1024)
             quant, idx = ops.argmax_codebook(logits, 1024, self.quantizer._pk["codebook"], forced_idx=forced)
@@ -553,7 +437,7 @@ class VQFRv2(nn.Module):
         res["quant_index"] = idx.long().reshape(B, -1)
         dec_res = self.decoder.run(quant)
         if texture:
-            res["texture_dec"] = ops.clip_to_nchw(_run_conv_out(self.decoder._pk["out"], dec_res["Level_1"]), 3)
+            res["texture_dec"] = ops.clip_to_nchw(_run_conv_out(self.decoder.conv_out, dec_res["Level_1"]), 3)
         main = self.main_branch.run(dec_res, inp_feat, fidelity_ratio=fidelity_ratio, trace=trace)
-        res["main_dec"] = ops.clip_to_nchw(_run_conv_out(self.decoder._pk["out"], main), 3)
+        res["main_dec"] = ops.clip_to_nchw(_run_conv_out(self.decoder.conv_out, main), 3)
         return res

@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from .. import _lib, ops
 from .. import ops as A
-from .retinaface import _conv, _fold, _fold_bn
+from .packing import PackedModel, fold_bn, packed_conv, run_conv
 
 # ---------------------------------------------------------------------------------------------- configurations
 # models/yolov5n.yaml, models/yolov5l.yaml: (from, number, kind, args) per layer; "nc" / "anchors" in Detect's args stand for
@@ -130,11 +130,11 @@ class Conv(nn.Module):
         self.act = nn.SiLU()
 
     def pack(self, dtype, device):
-        self._p = _fold(self.conv, self.bn, dtype, device)
+        self._pk = packed_conv(self.conv, self.bn, dtype, device)
 
     def run(self, x, out=None, res0=None):
         """x: a clip tensor or a list of them (the segments of a torch.cat); out: optional channel-slice view."""
-        return _conv(x, self._p, self.conv, A.ACT_SILU, out=out, res0=res0)
+        return run_conv(x, self._pk, self.conv, A.ACT_SILU, out=out, res0=res0)
 
 
 class StemBlock(nn.Module):
@@ -148,10 +148,6 @@ class StemBlock(nn.Module):
         self.stem_2p = nn.MaxPool2d(kernel_size=2, stride=2, ceil_mode=True)
         self.stem_3 = Conv(c2 * 2, c2, 1, 1, 0)
         self.c2 = c2
-
-    def pack(self, dtype, device):
-        for m in (self.stem_1, self.stem_2a, self.stem_2b, self.stem_3):
-            m.pack(dtype, device)
 
     def run(self, x):
         c2 = self.c2
@@ -173,10 +169,6 @@ class Bottleneck(nn.Module):
         self.cv2 = Conv(c_, c2, 3, 1, g=g)
         self.add = shortcut and c1 == c2
 
-    def pack(self, dtype, device):
-        self.cv1.pack(dtype, device)
-        self.cv2.pack(dtype, device)
-
     def run(self, x, out=None):
         return self.cv2.run(self.cv1.run(x), out=out, res0=x if self.add else None)
 
@@ -193,10 +185,6 @@ class C3(nn.Module):
         self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
         self.c_ = c_
 
-    def pack(self, dtype, device):
-        for m in (self.cv1, self.cv2, self.cv3, *self.m):
-            m.pack(dtype, device)
-
     def run(self, x):
         c_ = self.c_
         x0 = x[0] if isinstance(x, (list, tuple)) else x
@@ -210,21 +198,15 @@ class C3(nn.Module):
         return self.cv3.run(cat)
 
 
-class _DW:
-    """Packed form of ShuffleV2Block's depthwise 3x3 + BatchNorm (no activation): flair_dwconv_nhwc without its 1x1 stage.
-    Not a module: it refers to the block's own Conv2d / BatchNorm2d and holds no parameter."""
+def _pack_dw(conv, bn, dtype, device):
+    """ShuffleV2Block's depthwise 3x3 + BatchNorm (no activation) for flair_dwconv_nhwc without its 1x1 stage: (w (9, c), b)."""
+    assert dtype == torch.float32
+    w, b = fold_bn(conv, bn)                                                # (c, 1, 3, 3)
+    return w.reshape(conv.out_channels, 9).t().contiguous().to(device), b.contiguous().to(device)
 
-    def __init__(self, conv, bn):
-        self._conv, self._bn = conv, bn
 
-    def pack(self, dtype, device):
-        assert dtype == torch.float32
-        c = self._conv.out_channels
-        w, b = _fold_bn(self._conv, self._bn)                               # (c, 1, 3, 3)
-        self._p = (w.reshape(c, 9).t().contiguous().to(device), b.contiguous().to(device))
-
-    def run(self, x):
-        return ops.dwconv(x, self._p[0], self._p[1], stride=self._conv.stride[0], act=A.ACT_NONE)
+def _run_dw(x, wb, conv):
+    return ops.dwconv(x, wb[0], wb[1], stride=conv.stride[0], act=A.ACT_NONE)
 
 
 class ShuffleV2Block(nn.Module):
@@ -257,23 +239,19 @@ class ShuffleV2Block(nn.Module):
 
     def pack(self, dtype, device):
         b1, b2 = self.branch1, self.branch2
+        self._pk = dict(pw2a=packed_conv(b2[0], b2[1], dtype, device), dw2=_pack_dw(b2[3], b2[4], dtype, device),
+                        pw2b=packed_conv(b2[5], b2[6], dtype, device))
         if self.stride > 1:
-            self._dw1 = _DW(b1[0], b1[1])
-            self._dw1.pack(dtype, device)
-            self._pw1 = _fold(b1[2], b1[3], dtype, device)
-        self._pw2a = _fold(b2[0], b2[1], dtype, device)
-        self._dw2 = _DW(b2[3], b2[4])
-        self._dw2.pack(dtype, device)
-        self._pw2b = _fold(b2[5], b2[6], dtype, device)
+            self._pk.update(dw1=_pack_dw(b1[0], b1[1], dtype, device), pw1=packed_conv(b1[2], b1[3], dtype, device))
 
     def run(self, x):
-        b1, b2, bf = self.branch1, self.branch2, self.bf
+        pk, b1, b2, bf = self._pk, self.branch1, self.branch2, self.bf
         if self.stride == 1:
             a, x2 = x[..., :bf], x[..., bf:]                          # x.chunk(2, dim=1)
         else:
-            a, x2 = _conv(self._dw1.run(x), self._pw1, b1[2], A.ACT_SILU), x
-        h = _conv(x2, self._pw2a, b2[0], A.ACT_SILU)
-        h = _conv(self._dw2.run(h), self._pw2b, b2[5], A.ACT_SILU)
+            a, x2 = run_conv(_run_dw(x, pk["dw1"], b1[0]), pk["pw1"], b1[2], A.ACT_SILU), x
+        h = run_conv(x2, pk["pw2a"], b2[0], A.ACT_SILU)
+        h = run_conv(_run_dw(h, pk["dw2"], b2[3]), pk["pw2b"], b2[5], A.ACT_SILU)
         return ops.channel_interleave(a, h)
 
 
@@ -291,10 +269,6 @@ class SPP(nn.Module):
         self.cv2 = Conv(c_ * (len(k) + 1), c2, 1, 1)
         self.m = nn.ModuleList([nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in k])
         self.k, self.c_ = k, c_
-
-    def pack(self, dtype, device):
-        self.cv1.pack(dtype, device)
-        self.cv2.pack(dtype, device)
 
     def run(self, x):
         x0 = x[0] if isinstance(x, (list, tuple)) else x
@@ -351,19 +325,19 @@ class Detect(nn.Module):
         self.m = nn.ModuleList(nn.Conv2d(x, self.no * self.na, 1) for x in ch)
 
     def pack(self, dtype, device):
-        self._p = [_fold(m, None, dtype, device) for m in self.m]
-        self._ag = self.anchor_grid.detach().float().cpu().view(self.nl, self.na, 2).tolist()
-        self._strides = [float(s) for s in self.stride]
+        self._pk = dict(heads=[packed_conv(m, None, dtype, device) for m in self.m],
+                        anchor_grid=self.anchor_grid.detach().float().cpu().view(self.nl, self.na, 2).tolist())
 
     def run(self, xs):
         """-> (z (B, N, 16), [raw head outputs (B, ny, nx, na * 16)])."""
-        raw = [_conv(x, self._p[i], self.m[i], A.ACT_NONE) for i, x in enumerate(xs)]
+        pk = self._pk
+        raw = [run_conv(x, pk["heads"][i], self.m[i]) for i, x in enumerate(xs)]
         B = raw[0].shape[0]
         rows = [self.na * r.shape[1] * r.shape[2] for r in raw]
         z = torch.empty((B, sum(rows), self.no), dtype=torch.float32, device=raw[0].device)
         row0 = 0
         for i, r in enumerate(raw):
-            ops.yolo_face_decode(r, self.na, self._strides[i], self._ag[i], z, row0, no=self.no)
+            ops.yolo_face_decode(r, self.na, self.strides[i], pk["anchor_grid"][i], z, row0, no=self.no)
             row0 += rows[i]
         return z, raw
 
@@ -437,7 +411,7 @@ def _table(cfg):
     raise ValueError(f"flair_amd: cfg={cfg!r}: 'yolov5n', 'yolov5l', or a path whose file name is yolov5n.yaml / yolov5l.yaml")
 
 
-class Model(nn.Module):
+class Model(PackedModel, nn.Module):
     """yolo.py:95-132.  ``cfg``: "yolov5n" / "yolov5l", a path whose file name is ``yolov5n.yaml`` / ``yolov5l.yaml`` (what
     the reference passes; the file is not read), or a table of this module's form."""
 
@@ -452,14 +426,13 @@ class Model(nn.Module):
         self.names = [str(i) for i in range(self.yaml["nc"])]
         m = self.model[-1]
         if isinstance(m, Detect):
-            m.stride = torch.tensor([float(s) for s in strides[-1]])
+            m.strides = [float(s) for s in strides[-1]]                          # what run hands to the decode kernel
+            m.stride = torch.tensor(m.strides)
             m.anchors /= m.stride.view(-1, 1, 1)                                 # yolo.py:114-115
             a = m.anchor_grid.prod(-1).view(-1)                                  # check_anchor_order: the shipped tables ascend
             assert (a[-1] - a[0]).sign() == (m.stride[-1] - m.stride[0]).sign(), "anchors must ascend with the strides"
             self.stride = m.stride
             self._initialize_biases()
-        self.dtype = torch.float32
-        self._packed_key = None
         self._loaded = False
         self.eval()
 
@@ -474,19 +447,9 @@ class Model(nn.Module):
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         out = super().load_state_dict(state_dict, *args, **kwargs)
-        self._packed_key = None
         if not out.missing_keys:                        # a non-strict load that leaves tensors unset does not count as loaded
             self._loaded = True
         return out
-
-    def _ensure_packed(self, device):
-        key = (self.dtype, device)
-        if self._packed_key != key:
-            for layer in self.model:
-                for m in (layer if type(layer) is nn.Sequential else [layer]):      # n > 1 layers are a Sequential of blocks
-                    if hasattr(m, "pack"):
-                        m.pack(self.dtype, device)
-            self._packed_key = key
 
     def run_clip(self, x, taps=None):
         """x: (B, H, W, 16) float32 clip tensor (channels 0-2 the image in [0, 1], the rest zero) -> (z (B, N, 16), raw head

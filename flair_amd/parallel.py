@@ -15,6 +15,8 @@ import time
 import torch
 import torch.distributed as dist
 
+from .guided_diffusion.packing import invalidate_packed
+
 
 def clips_for_rank(num_clips, rank, world_size):
     """Round-robin partition of independent clips (no clip is split across GPUs)."""
@@ -48,8 +50,7 @@ def broadcast_weights(model, src=0, bucket_bytes=256 << 20):
                 size += t.numel() * t.element_size()
     if tensors and tensors[0].is_cuda:
         torch.cuda.synchronize()
-    if hasattr(model, "_packed_key"):
-        model._packed_key = None      # kernel-native weight copies must be rebuilt
+    invalidate_packed(model)          # kernel-native weight copies must be rebuilt
     return time.perf_counter() - t0
 
 

@@ -106,7 +106,7 @@ def main():
             net.convert_to_bf16()
         res[name] = prior_alone(net, x, a.iters)
         print(name, json.dumps(res[name]), flush=True)
-    net.dtype, net._packed_key = torch.float32, None
+    net.convert_to_fp32()
     cf = name_seeded_weights(CodeFormer()).to(dev).eval()
     res["step_ms"] = step_times(dev, a.frames, {"restoreformer_f32": wl.restoreformer_aux(net),
                                                 "codeformer_f32": wl.codeformer_aux(cf), "none": wl.identity_aux},

@@ -97,7 +97,7 @@ def main():
         r["achieved_tflops_from_shapes"] = fl * a.frames / (r["ms_per_call"] * 1e-3) / 1e12
         res[name] = r
         print(name, json.dumps(r), flush=True)
-    net.dtype, net._packed_key = torch.float32, None
+    net.convert_to_fp32()
     if not a.no_steps:
         from flair_amd.guided_diffusion.codeformer import CodeFormer
         from flair_amd.guided_diffusion.restoreformer import VQVAEGANMultiHeadTransformer
