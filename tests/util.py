@@ -141,3 +141,50 @@ def assert_flat_untouched(buf, before, view=None, what=""):
         i = int(changed.nonzero()[0].item())
         where = "outside the tensor" if view is not None else "in a read-only buffer"
         raise AssertionError(f"{what}: {n} element(s) changed {where}, first at {i}: {before[i].item()!r} -> {buf[i].item()!r}")
+
+
+# Exact arithmetic (tests/test_gpu_exact.py, tests/test_exact_cpu.py): on integer-valued data every product and every
+# partial sum of a convolution is an integer below 2^24, hence exact in f32 in ANY accumulation order, tile shape, split
+# or matrix instruction; the one correct output is the exact value (f32) or its round-to-nearest-even (bf16).
+def int_tensor(shape, lo, hi, g):
+    """Uniform integers in [lo, hi] as float32 (exact in bf16 for |v| <= 256)."""
+    return torch.randint(lo, hi + 1, tuple(shape), generator=g).float()
+
+
+def assert_exact_headroom(abs_sum):
+    """abs_sum: the float64 tensor conv(|x|, |w|) + |bias| + |frame_bias| + sum |res| -- a bound on every partial sum in
+    every order.  Below 2^24 all of them are integers (or multiples of the data's power-of-two step) that f32 holds exactly."""
+    assert abs_sum.dtype == torch.float64
+    m = abs_sum.max().item()
+    assert m < 2 ** 24, f"partial sums up to {m:.0f} >= 2^24: not exact in f32"
+    return m
+
+
+def assert_bits_equal(got, ref, what="", tile=None):
+    """got and ref (same shape and dtype, (T, H, W, C) clip layout when `tile` is given) are equal bit for bit, compared
+    through bits().  The sign of a zero is left open: it is no part of the arithmetic contract, and the kernels' two
+    spellings of ReLU differ in it (`v > 0 ? v : 0` gives +0, `fmaxf(v, v * 0)` gives -0 for v < 0).
+    tile = (rows, cols, couts): also counts the differing elements by (h % rows, w % cols, c % couts), so that a failure
+    names the lane, the row or the store group at fault."""
+    assert got.shape == ref.shape and got.dtype == ref.dtype, (what, got.shape, ref.shape, got.dtype, ref.dtype)
+    got, ref = got.detach().cpu().contiguous(), ref.detach().cpu().contiguous()
+    ne = (bits(got) != bits(ref)) & ~((got == 0) & (ref == 0))
+    n = int(ne.sum().item())
+    if not n:
+        return
+    idx = ne.nonzero()
+    first = tuple(idx[0].tolist())
+    d = (got.double() - ref.double()).abs()
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+    msg = (f"{what}: {n} of {ne.numel()} element(s) differ in bits; first at {list(first)}: got {got[first].item()!r}, "
+           f"expected {ref[first].item()!r}; largest |difference| {d[ne].max().item():.6g}")
+    if tile is not None and got.dim() == 4:
+        rows, cols, couts = tile
+        key = (idx[:, 1] % rows) * (cols * couts) + (idx[:, 2] % cols) * couts + idx[:, 3] % couts
+        cnt = torch.bincount(key, minlength=rows * cols * couts).view(rows, cols, couts)
+        msg += (f"\n  by h % {rows}: {cnt.sum((1, 2)).tolist()}\n  by w % {cols}: {cnt.sum((0, 2)).tolist()}"
+                f"\n  by c % {couts}: {cnt.sum((0, 1)).tolist()}")
+        top = cnt.flatten().argsort(descending=True)[:8].tolist()
+        msg += "\n  most hit (h % rows, w % cols, c % couts): " + ", ".join(
+            f"({k // (cols * couts)}, {k // couts % cols}, {k % couts}): {int(cnt.flatten()[k])}" for k in top if cnt.flatten()[k] > 0)
+    raise AssertionError(msg)
