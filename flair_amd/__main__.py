@@ -2,7 +2,7 @@
 
 The options of the reference's ``main()`` keep their names and defaults (``scripts/video_sample.py:249-263``); the
 presets are its ``x8_bicubic_demo`` ... ``jpeg_demo`` commands (:500-556).  Several videos go through one call with
-``--output-root DIR`` (each to ``DIR/<video dir name>``); under ``torch.distributed.run`` the videos are split over the
+``--output-root DIR`` (each to ``DIR/<video dir name>``); ``--frame-size HxW`` (or ``auto``) restores rectangular frames; under ``torch.distributed.run`` the videos are split over the
 ranks (flair_amd.pipeline.restore_many) and rank 0 reads the checkpoints once and ships them to the others.
 """
 import argparse
@@ -21,6 +21,10 @@ def _add_common(p):
                    help="the blur kernels .mat file (MATLAB v5) of the gaussian and jpeg tasks")
     p.add_argument("--device", default=None, help="default: cuda (cuda:LOCAL_RANK under torch.distributed.run)")
     p.add_argument("--size", type=int, default=512, help="frame side of the restored video")
+    p.add_argument("--frame-size", default=None, metavar="HxW|auto",
+                   help="rectangular frames of height H and width W (multiples of the task's frame multiple); the degraded "
+                        "frames must be exactly H/f x W/f and are not resized; auto: the first frame's size times the "
+                        "task's factor f.  Excludes a non-default --size")
     p.add_argument("--steps", type=int, default=100, help="sampler steps (respacing of the diffusion)")
     p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
     p.add_argument("--det-model", choices=tuple(pl.DETECTOR_FILES), default="retinaface_resnet50")
@@ -108,11 +112,28 @@ def faces_of(args):
     return dict(faces="all", max_faces=args.max_faces)
 
 
+def size_of(args, task, jobs):
+    """The ``size`` argument of build_pipeline for a parsed command line: --size S (an int, the reference's square
+    frames) or --frame-size HxW / auto (a pair; auto reads the first frame of the first video)."""
+    if args.frame_size is None:
+        return args.size
+    if args.size != 512:
+        raise SystemExit("restore: --frame-size and --size exclude each other")
+    try:
+        size = pl.parse_frame_size(args.frame_size)
+        if size == "auto":
+            size = pl.auto_frame_size(task, jobs[0][0])
+        return pl.check_frame_size(task, size)
+    except ValueError as exc:
+        raise SystemExit(f"restore: {exc}")
+
+
 def main(argv=None):
     args = make_parser().parse_args(argv)
     task, jobs = jobs_of(args)
     prior = prior_of(args)
     faces = faces_of(args)
+    size = size_of(args, task, jobs)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -126,7 +147,7 @@ def main(argv=None):
         device = args.device or "cuda"
     try:
         torch.set_grad_enabled(False)
-        p = pl.build_pipeline(task, args.weights, device=device, size=args.size, dtype=args.dtype, steps=args.steps,
+        p = pl.build_pipeline(task, args.weights, device=device, size=size, dtype=args.dtype, steps=args.steps,
                               kernels_path=args.kernels, prior=prior, det_model=args.det_model,
                               model_kwargs=json.loads(args.model_kwargs) if args.model_kwargs else None,
                               graph=not args.no_graph,

@@ -13,6 +13,8 @@
 //  * flair_jpeg_roundtrip   : jpeg_decode(jpeg_encode(x, qf), qf) of guided_diffusion/jpeg.py:72-167
 //    fused into one kernel per 16x16 macro-block: RGB->YCbCr, 4:2:0, 8x8 ortho DCT-II,
 //    quantise + round-half-even, dequantise, IDCT, chroma replication, YCbCr->RGB.
+//  * flair_jpeg_roundtrip_hw: the same round trip on (N,3,H,W), H and W multiples of 16: one launch, the YCbCr planes of
+//    ten MCUs per wave in LDS instead of a workspace in HBM; shares the colour transforms and the block codec above.
 //  * flair_matmul_f32       : small dense C = A.B (SRConv's separable operators,
 //    restore_util.py:102-227) -- tiled through LDS, f32.
 // All are tiny next to the UNet (<0.1 % of a step); they are written for coalesced plane
@@ -139,6 +141,25 @@ __device__ __forceinline__ void codec8x8(const JpegTables& t, const float* q, fl
     dct8x8(t.D, c, blk, true);
 }
 
+// The two colour transforms (torch_rgb2ycbcr / torch_ycbcr2rgb, jpeg.py:7-32), shared by the three-launch square
+// entry and the one-launch rectangular one.  The matrix rows are spelt out as the fused multiply-add chains the compiler
+// made of "a*r + b*g + c*bl" in the square kernels (the g product first, rounded; then r, then bl): -ffp-contract=fast
+// leaves it free to fuse such a sum differently in every kernel it is inlined into, and the two entries must agree
+// bit for bit.
+__device__ __forceinline__ void jpeg_rgb_to_ycc(float x0, float x1, float x2, float& Y, float& Cb, float& Cr) {
+    const float r = (x0 + 1.f) / 2.f * 255.f, g = (x1 + 1.f) / 2.f * 255.f, bl = (x2 + 1.f) / 2.f * 255.f;
+    Y = fmaf(0.114f, bl, fmaf(0.299f, r, 0.587f * g));
+    Cb = fmaf(0.5f, bl, fmaf(-0.1687f, r, -0.3313f * g)) + 128.f;
+    Cr = fmaf(-0.0813f, bl, fmaf(0.5f, r, -0.4187f * g)) + 128.f;
+}
+
+__device__ __forceinline__ void jpeg_ycc_to_rgb(float Y, float Cb, float Cr, float& o0, float& o1, float& o2) {
+    const float cb = Cb - 128.f, cr = Cr - 128.f;
+    o0 = fmaf(fmaf(1.40198758f, cr, fmaf(-3.68199903e-05f, cb, Y)) / 255.f, 2.f, -1.f);
+    o1 = fmaf(fmaf(-7.14103821e-01f, cr, fmaf(-3.44113281e-01f, cb, Y)) / 255.f, 2.f, -1.f);
+    o2 = fmaf(fmaf(-1.34583413e-04f, cr, fmaf(1.77197812f, cb, Y)) / 255.f, 2.f, -1.f);
+}
+
 // one thread per 8x8 luma block / per 8x8 chroma block (two launches' worth of work in one
 // kernel: blockIdx.y selects luma (0) or chroma plane (1,2)); planes staged in a YCbCr buffer.
 __global__ void jpeg_to_ycbcr_kernel(const float* x, int N, int S, float* ycc) {
@@ -146,12 +167,8 @@ __global__ void jpeg_to_ycbcr_kernel(const float* x, int N, int S, float* ycc) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long n = i / ((long)S * S), p = i % ((long)S * S);
         const float* b = x + n * 3 * S * S + p;
-        const float r = (b[0] + 1.f) / 2.f * 255.f, g = (b[(long)S * S] + 1.f) / 2.f * 255.f,
-                    bl = (b[2L * S * S] + 1.f) / 2.f * 255.f;
         float* o = ycc + n * 3 * S * S + p;
-        o[0] = 0.299f * r + 0.587f * g + 0.114f * bl;
-        o[(long)S * S] = -0.1687f * r + -0.3313f * g + 0.5f * bl + 128.f;
-        o[2L * S * S] = 0.5f * r + -0.4187f * g + -0.0813f * bl + 128.f;
+        jpeg_rgb_to_ycc(b[0], b[(long)S * S], b[2L * S * S], o[0], o[(long)S * S], o[2L * S * S]);
     }
 }
 
@@ -196,11 +213,89 @@ __global__ void jpeg_to_rgb_kernel(const float* ycc, int N, int S, float* y) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long n = i / ((long)S * S), p = i % ((long)S * S);
         const float* b = ycc + n * 3 * S * S + p;
-        const float Y = b[0], cb = b[(long)S * S] - 128.f, cr = b[2L * S * S] - 128.f;
         float* o = y + n * 3 * S * S + p;
-        o[0] = (1.f * Y + -3.68199903e-05f * cb + 1.40198758f * cr) / 255.f * 2.f - 1.f;
-        o[(long)S * S] = (1.f * Y + -3.44113281e-01f * cb + -7.14103821e-01f * cr) / 255.f * 2.f - 1.f;
-        o[2L * S * S] = (1.f * Y + 1.77197812f * cb + -1.34583413e-04f * cr) / 255.f * 2.f - 1.f;
+        jpeg_ycc_to_rgb(b[0], b[(long)S * S], b[2L * S * S], o[0], o[(long)S * S], o[2L * S * S]);
+    }
+}
+
+// One launch, no workspace, any H x W of whole 16x16 MCUs (flair_jpeg_roundtrip_hw).  A one-wave workgroup owns JPEG_MCUS
+// consecutive MCUs (x fastest, so they are mostly horizontal neighbours and a wave reads 256 contiguous bytes per row).
+// The YCbCr planes never leave the CU: each MCU is six 8x8 blocks in LDS (four luma, Cb, Cr -- chroma only at the even
+// pixels, the 4:2:0 samples), one block per lane for the DCT / quantise / IDCT.  The pitch of a block is 65 floats: lane l
+// reading element i of its own block addresses dword 65 l + i, so consecutive lanes fall into consecutive banks and the
+// codec phase is conflict-free.  The load and store phases touch the two column halves of a row (c and c + 8: neighbouring
+// blocks, one bank apart) in one instruction, a 2-way conflict on 80 cheap accesses per lane that is left as it is.  The
+// codec lane holds its block in registers exactly as jpeg_blocks_kernel does (same codec8x8), and every value is stored to
+// and re-read from LDS where the three-launch form stores it to and re-reads it from the workspace, so both forms round
+// at the same places.  The ten MCUs' image offsets (the only 64-bit divisions) are formed once, by ten lanes.
+constexpr int JPEG_MCUS = 10, JPEG_PITCH = 65;
+
+__global__ __launch_bounds__(64) void jpeg_mcu_kernel(const float* x, int N, int H, int W, JpegTables t, float* y,
+                                                      float* lumaQ, float* chromaQ) {
+    __shared__ float sm[JPEG_MCUS * 6 * JPEG_PITCH];
+    __shared__ long mcuPix[JPEG_MCUS];      // offset of the MCU's first pixel in an (N,3,H,W) image, -1 past the end
+    __shared__ int mcuAt[JPEG_MCUS][3];     // its image, MCU row and MCU column
+    const int mw = W / 16, mh = H / 16;
+    const long total = (long)N * mh * mw, g0 = (long)blockIdx.x * JPEG_MCUS;
+    const long plane = (long)H * W;
+    if (threadIdx.x < JPEG_MCUS) {
+        const long g = g0 + threadIdx.x;
+        long pix = -1;
+        if (g < total) {
+            const long n = g / ((long)mh * mw);
+            const int rest = (int)(g - n * ((long)mh * mw)), my = rest / mw, mx = rest - my * mw;
+            mcuAt[threadIdx.x][0] = (int)n; mcuAt[threadIdx.x][1] = my; mcuAt[threadIdx.x][2] = mx;
+            pix = n * 3 * plane + (long)my * 16 * W + mx * 16;
+        }
+        mcuPix[threadIdx.x] = pix;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < JPEG_MCUS * 256; idx += 64) {
+        const int r = idx / (JPEG_MCUS * 16), q = idx % (JPEG_MCUS * 16), m = q / 16, c = q % 16;
+        const long pix = mcuPix[m];
+        if (pix < 0) continue;
+        const float* b = x + pix + (long)r * W + c;
+        float Y, Cb, Cr;
+        jpeg_rgb_to_ycc(b[0], b[plane], b[2 * plane], Y, Cb, Cr);
+        float* s = sm + m * 6 * JPEG_PITCH;
+        s[((r >> 3) * 2 + (c >> 3)) * JPEG_PITCH + (r & 7) * 8 + (c & 7)] = Y;
+        if (!(r & 1) && !(c & 1)) {   // 4:2:0 keeps the [::2, ::2] samples
+            s[4 * JPEG_PITCH + (r >> 1) * 8 + (c >> 1)] = Cb;
+            s[5 * JPEG_PITCH + (r >> 1) * 8 + (c >> 1)] = Cr;
+        }
+    }
+    __syncthreads();
+    {
+        const int m = threadIdx.x / 6, k = threadIdx.x % 6;
+        if (threadIdx.x < JPEG_MCUS * 6 && mcuPix[m] >= 0) {
+            const long n = mcuAt[m][0];
+            const int my = mcuAt[m][1], mx = mcuAt[m][2];
+            float* s = sm + threadIdx.x * JPEG_PITCH;
+            float blk[8][8];
+            for (int i = 0; i < 8; ++i)
+                for (int j = 0; j < 8; ++j) blk[i][j] = s[i * 8 + j] - 128.f;
+            if (k < 4) {
+                codec8x8(t, t.q1, blk,
+                         lumaQ ? lumaQ + n * plane + (long)(my * 16 + (k >> 1) * 8) * W + mx * 16 + (k & 1) * 8 : nullptr, W);
+            } else {
+                const int hw = W / 2;
+                codec8x8(t, t.q2, blk,
+                         chromaQ ? chromaQ + ((n * 2 + (k - 4)) * (H / 2) + my * 8) * (long)hw + mx * 8 : nullptr, hw);
+            }
+            for (int i = 0; i < 8; ++i)
+                for (int j = 0; j < 8; ++j) s[i * 8 + j] = blk[i][j] + 128.f;
+        }
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < JPEG_MCUS * 256; idx += 64) {
+        const int r = idx / (JPEG_MCUS * 16), q = idx % (JPEG_MCUS * 16), m = q / 16, c = q % 16;
+        const long pix = mcuPix[m];
+        if (pix < 0) continue;
+        const float* s = sm + m * 6 * JPEG_PITCH;
+        float* o = y + pix + (long)r * W + c;
+        jpeg_ycc_to_rgb(s[((r >> 3) * 2 + (c >> 3)) * JPEG_PITCH + (r & 7) * 8 + (c & 7)],
+                        s[4 * JPEG_PITCH + (r >> 1) * 8 + (c >> 1)], s[5 * JPEG_PITCH + (r >> 1) * 8 + (c >> 1)],
+                        o[0], o[plane], o[2 * plane]);
     }
 }
 
@@ -287,6 +382,24 @@ extern "C" int flair_jpeg_roundtrip(const float* x, int N, int S, const float* q
     hipLaunchKernelGGL(jpeg_blocks_kernel, dim3(grid_for(blocks)), dim3(64), 0, stream, workspace, N, S, t, luma_q, chroma_q);
     FLAIR_LAUNCH_CHECK();
     hipLaunchKernelGGL(jpeg_to_rgb_kernel, dim3(grid_for((long)N * S * S)), dim3(256), 0, stream, workspace, N, S, y);
+    FLAIR_LAUNCH_CHECK();
+    return FLAIR_OK;
+}
+
+extern "C" int flair_jpeg_roundtrip_hw(const float* x, int N, int H, int W, const float* q_luma, const float* q_chroma,
+                                       const float* dct8, float* y, float* luma_q, float* chroma_q, hipStream_t stream) {
+    FLAIR_CHECK(x && q_luma && q_chroma && dct8 && y && N > 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0,
+                "flair_jpeg_roundtrip_hw: bad argument (H and W must be multiples of 16)");
+    FLAIR_CHECK(!luma_q == !chroma_q, "flair_jpeg_roundtrip_hw: give both level planes or neither");
+    const long mcus = (long)N * (H / 16) * (W / 16), groups = (mcus + JPEG_MCUS - 1) / JPEG_MCUS;
+    FLAIR_CHECK(groups <= 0x7fffffffL, "flair_jpeg_roundtrip_hw: more than 2^31 workgroups");
+    JpegTables t;
+    for (int i = 0; i < 64; ++i) {
+        t.q1[i] = q_luma[i];
+        t.q2[i] = q_chroma[i];
+        t.D[i] = dct8[i];
+    }
+    hipLaunchKernelGGL(jpeg_mcu_kernel, dim3((unsigned)groups), dim3(64), 0, stream, x, N, H, W, t, y, luma_q, chroma_q);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }

@@ -4,7 +4,8 @@
 inside the data-consistency operator, so the two halves are fused: ``jpeg_encode`` returns a
 token that remembers its input, and ``jpeg_decode`` runs the whole round trip (colour
 transform, 4:2:0, 8x8 ortho DCT-II, quantise + round-half-even, dequantise, IDCT, chroma
-replication, inverse colour transform) in ``flair_jpeg_roundtrip``.
+replication, inverse colour transform) in ``flair_jpeg_roundtrip_hw``: one launch on (N,3,H,W) for any H and W
+that are multiples of the 16-pixel MCU (the square three-launch ``flair_jpeg_roundtrip`` gives the same bits).
 """
 import math
 
@@ -50,7 +51,7 @@ def dct8_matrix():
 class EncodedJpeg:
     """Result of ``jpeg_encode``: consumed by ``jpeg_decode`` (which runs the whole round trip in one pass).
     Iterating or indexing it yields what the reference's ``jpeg_encode`` returns -- the quantised integer levels
-    ``[luma (N,1,S,S), chroma (N,2,S/2,S/2)]`` as float tensors (jpeg.py:108-114) -- materialised on demand."""
+    ``[luma (N,1,H,W), chroma (N,2,H/2,W/2)]`` as float tensors (jpeg.py:108-114) -- materialised on demand."""
 
     def __init__(self, image, qf):
         self.image, self.qf = image, qf
@@ -74,7 +75,7 @@ class EncodedJpeg:
 
 
 def jpeg_encode(x, qf):
-    """jpeg.py:72-114 (deferred; see module docstring).  x: (N,3,S,S) f32 in [-1,1], S % 16 == 0."""
+    """jpeg.py:72-114 (deferred; see module docstring).  x: (N,3,H,W) f32 in [-1,1], H % 16 == W % 16 == 0."""
     return EncodedJpeg(x, qf)
 
 

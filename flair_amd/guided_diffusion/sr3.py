@@ -57,11 +57,12 @@ def aa_bilinear_table(n_in, n_out):
 
 
 def aa_resize(x, size):
-    """(N,C,H,W) f32 device tensor -> (N,C,size,size) with antialiased bilinear filtering."""
+    """(N,C,H,W) f32 device tensor -> (N,C,*size) with antialiased bilinear filtering; size: a side or (h, w)."""
     N, C, H, W = x.shape
     dev = x.device
     out = x.float().contiguous()
-    for dim, n_in in ((2, H), (3, W)):
+    sizes = (size, size) if isinstance(size, int) else tuple(size)
+    for dim, n_in, size in ((2, H, sizes[0]), (3, W, sizes[1])):
         idx, wt = aa_bilinear_table(n_in, size)
         shape = list(out.shape)
         outer = int(np.prod(shape[:dim]))
@@ -409,15 +410,15 @@ class UNet(PackedModel, nn.Module):
 
     # ---- flows: once per (clip, resolution) ----------------------------------------------
     def _flows_for(self, rnn_clip, resolutions):
-        key = (rnn_clip.data_ptr(), rnn_clip._version, tuple(rnn_clip.shape))
+        key = (rnn_clip.data_ptr(), rnn_clip._version, tuple(rnn_clip.shape), tuple(resolutions))
         hit = self._flow_cache.get(key)
         if hit is None:
             sp = self._shared_spynet[0]
             flows = {}
-            for r in resolutions:
-                src = rnn_clip if rnn_clip.shape[-1] == r else aa_resize(rnn_clip, r)
+            for rh, r in resolutions:                         # (height, width) of a level, stored under its width
+                src = rnn_clip if tuple(rnn_clip.shape[-2:]) == (rh, r) else aa_resize(rnn_clip, (rh, r))
                 T = src.shape[0]
-                raw = torch.zeros((T, r, r, 4), dtype=torch.float32, device=src.device)
+                raw = torch.zeros((T, rh, r, 4), dtype=torch.float32, device=src.device)
                 ops.nchw_to_clip(src.contiguous(), raw, 0)
                 norm = torch.zeros_like(raw)
                 ops.affine_channels(raw, 3, 0.5, 0.5, 0.0, 1.0, sp._pk["mean"], sp._pk["istd"], norm)
@@ -466,8 +467,7 @@ class UNet(PackedModel, nn.Module):
         if ent is None:
             st = dict(x=x.clone(), level=level.clone(), lr=low_res.clone(), rnn=rnn.clone(),
                       vw=vw_t.clone() if vw_t is not None else vsrpp_weights)
-            H = x.shape[2]
-            res_needed = sorted({r for r, _ in self._vsrpp_levels(H)}) if enable_cross_frames else []
+            res_needed = self._flow_resolutions(*x.shape[2:]) if enable_cross_frames else []
             flows = self._flows_for(st["rnn"], res_needed) if res_needed else {}      # SPyNet runs eagerly, before capture
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
@@ -493,7 +493,7 @@ class UNet(PackedModel, nn.Module):
         ctx = Ctx(dt, dev, T)
         ctx.enable_cross_frames = enable_cross_frames
         ctx.vsrpp_weights = vsrpp_weights
-        res_needed = sorted({r for r, _ in self._vsrpp_levels(H)}) if enable_cross_frames else []
+        res_needed = self._flow_resolutions(H, W) if enable_cross_frames else []
         if flows is not None:
             ctx.flows = flows
         else:
@@ -523,6 +523,12 @@ class UNet(PackedModel, nn.Module):
         h = ops.group_norm(h, pk["fin_g"], pk["fin_b"], groups=fc.groups, eps=fc.block[0].wrapped_module.eps, act=A.ACT_SILU)
         y = run_conv(h, pk["fin"], fc.block[3].wrapped_module)
         return ops.clip_to_nchw(y, fc.block[3].wrapped_module.out_channels)
+
+    def _flow_resolutions(self, H, W):
+        """(h, w) of every level that carries a BasicVSRPP for an H x W clip, by ascending width: the flow input is
+        resized to the level's own shape (the reference resizes to ``hidden.shape[-2:]``)."""
+        hs, ws = ([r for r, _ in self._vsrpp_levels(n)] for n in (H, W))
+        return sorted(set(zip(hs, ws)), key=lambda p: p[1])
 
     def _vsrpp_levels(self, size):
         """(resolution, module) of every BasicVSRPP in the network for an input of side `size`."""

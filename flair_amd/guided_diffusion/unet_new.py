@@ -737,21 +737,28 @@ class UNetModel(PackedModel, nn.Module):
         flows_forward = self.spynet.run(b, a)
         return flows_forward, flows_backward
 
-    def _flows_for(self, rnn_clip):
-        """rnn_clip: (T,3,S,S) f32 device tensor.  Flows are a pure function of it, so they are
-        cached across the denoising steps of a clip (keyed on storage + version)."""
-        key = (rnn_clip.data_ptr(), rnn_clip._version, tuple(rnn_clip.shape))
+    def _flows_for(self, rnn_clip, hw=None):
+        """rnn_clip: (T,3,h,w) f32 device tensor; hw: the (H, W) of the clip the network denoises (default: the
+        conditioning clip's own).  The level at down-sampling s gets the flows of the conditioning clip resized
+        bicubically to (H/s, W/s), stored under W/s -- the key BasicVSRPP.run looks up.  For a square clip of side
+        image_size these are the reference's (res, res) of need_flows_res.  Flows are a pure function of the clip, so
+        they are cached across the denoising steps (keyed on storage + version)."""
+        T, _, h, w = rnn_clip.shape
+        H, W = (h, w) if hw is None else hw
+        key = (rnn_clip.data_ptr(), rnn_clip._version, tuple(rnn_clip.shape), (H, W))
         hit = self._flow_cache.get(key)
         if hit is None:
-            T, _, h, w = rnn_clip.shape
             raw = torch.zeros((T, h, w, 4), dtype=torch.float32, device=rnn_clip.device)
             ops.nchw_to_clip(rnn_clip.contiguous(), raw, 0)
             flows = {}
-            for r in self.need_flows_res:
+            for s in self.rnn_resolutions:
+                if H % s or W % s:
+                    raise ValueError(f"flair_amd.UNetModel: a {H}x{W} clip has no level at down-sampling {s}")
+                rh, rw = H // s, W // s
                 src = raw
-                if w != r:
-                    src = ops.resize(raw, (r, r), ops.RESIZE_BICUBIC, channels=3)
-                flows[r] = self._flows_from_clip(src)
+                if (h, w) != (rh, rw):
+                    src = ops.resize(raw, (rh, rw), ops.RESIZE_BICUBIC, channels=3)
+                flows[rw] = self._flows_from_clip(src)
             flows["_prop"] = {}              # per-clip store of composed second-order flows (BasicVSRPP._propagate)
             if len(self._flow_cache) >= 16:
                 self._flow_cache.clear()
@@ -800,7 +807,7 @@ class UNetModel(PackedModel, nn.Module):
             ent = None
         if ent is None:
             st = dict(x=x.clone(), t=t.clone(), lr=low_res.clone(), rnn=rnn.clone())
-            flows = self._flows_for(st["rnn"])               # SPyNet runs eagerly, before capture
+            flows = self._flows_for(st["rnn"], tuple(x.shape[-2:]))   # SPyNet runs eagerly, before capture
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
             side.wait_stream(cur)
@@ -829,7 +836,7 @@ class UNetModel(PackedModel, nn.Module):
         ctx = Ctx(dt, dev, T)
         ctx.enable_cross_frames = enable_cross_frames
         ctx.vsrpp_weights = vsrpp_weights
-        ctx.flows = flows if flows is not None else self._flows_for(rnn)
+        ctx.flows = flows if flows is not None else self._flows_for(rnn, (H, W))
         # timestep embedding MLP and every emb_layers linear of the network (f32)
         temb = ops.timestep_embedding(t.float().contiguous(), self.model_channels)
         pk = self._pk

@@ -21,6 +21,7 @@ import torch.distributed as dist
 from . import io as fio
 from . import ops
 from . import parallel
+from . import video
 from . import workload as wl
 from .guided_diffusion import gaussian_diffusion as gd
 
@@ -93,11 +94,96 @@ def _check_task(task):
         raise ValueError(f"unknown task {task!r}: one of {', '.join(TASK_NAMES)}")
 
 
+# the face parsers run on whole frames for the bicubic tasks' propagation weights: ParseNet(in_size=512) halves the frame
+# four times, BiSeNet's ResNet-18 five times
+PARSER_MULTIPLE = {"parsenet": 16, "bisenet": 32}
+JPEG_MCU = 16                       # the codec works on whole 16 x 16 MCUs of the degraded (low-resolution) frames
+SR3_MIN_FLOW_SIDE = 64              # sr3's propagation levels estimate flows on frames of at least 64 pixels a side
+
+
+def frame_multiple(task):
+    """What H and W of a rectangular frame must be multiples of: the least common multiple of the network's deepest
+    level (one halving per entry of channel_mult(s) after the first: the layout is the checkpoint's, whatever the
+    frame), the operator's factor, and -- for the blur tasks, whose operator may run the codec -- the 16-pixel MCU on the
+    low-resolution grid.  64 for gaussian / jpeg, 16 for the bicubic tasks with the shipped configurations."""
+    import math
+    _check_task(task)
+    cfg = MODEL_CONFIG[task]
+    factor = wl.TASKS[task]["factor"]
+    if "bicubic" in task:
+        return math.lcm(2 ** (len(cfg["channel_mults"]) - 1), factor)
+    return math.lcm(2 ** (len(cfg["channel_mult"]) - 1), factor, JPEG_MCU * factor)
+
+
+def frame_minimum(task):
+    """The smallest side of a rectangular frame: sr3's coarsest propagation level (image_size / vsrpp_res halvings)
+    still needs SR3_MIN_FLOW_SIDE pixels; the blur tasks need one multiple."""
+    m = frame_multiple(task)
+    if "bicubic" in task:
+        cfg = MODEL_CONFIG[task]
+        deepest = max(cfg["image_size"] // r for r in cfg["vsrpp_res"])
+        return -(-SR3_MIN_FLOW_SIDE * deepest // m) * m
+    return m
+
+
+def parse_frame_size(text):
+    """``"HxW"`` (also ``H,W``) -> (H, W); ``"auto"`` -> ``"auto"`` (the first frame's (h*f, w*f), resolved by
+    auto_frame_size)."""
+    t = str(text).strip().lower()
+    if t == "auto":
+        return "auto"
+    parts = t.replace(",", "x").split("x")
+    if len(parts) != 2 or not all(p.strip().isdigit() for p in parts) or min(int(p) for p in parts) <= 0:
+        raise ValueError(f"frame size {text!r}: HxW with positive integers (height first), or auto")
+    return int(parts[0]), int(parts[1])
+
+
+def auto_frame_size(task, video_path):
+    """--frame-size auto: (h*f, w*f) of the first frame file of ``video_path`` (only its header is read)."""
+    from PIL import Image
+    _check_task(task)
+    paths = fio.list_frames(video_path)
+    if not paths:
+        raise ValueError(f"{video_path}: no frame files to take the frame size from")
+    with Image.open(paths[0]) as im:
+        w, h = im.size
+    f = wl.TASKS[task]["factor"]
+    return h * f, w * f
+
+
+def check_frame_size(task, size, frames=None, parser=None, dtype="bf16"):
+    """Refuse a rectangular frame size the task cannot restore: not a multiple of frame_multiple(task) (the two
+    nearest valid sizes are named), below frame_minimum(task), not a multiple of the parser's own stride (bicubic
+    tasks: the parser sees whole frames), or -- given the window length ``frames`` -- beyond the kernels' 32-bit
+    offsets (video.check_clip_elements)."""
+    _check_task(task)
+    H, W = video.frame_hw(size)
+    m, lo = frame_multiple(task), frame_minimum(task)
+    bad = [(n, v) for n, v in (("H", H), ("W", W)) if v % m or v < lo]
+    if bad:
+        near = lambda v: (max(lo, v // m * m), max(lo, -(-v // m) * m))                    # noqa: E731
+        (h0, h1), (w0, w1) = near(H), near(W)
+        raise ValueError(f"{task}: frame size {H}x{W} is not valid: H and W must be multiples of {m} and at least {lo}; "
+                         f"the nearest valid sizes are {h0}x{w0} and {h1}x{w1} (frames are not padded or cropped for you)")
+    if parser is not None and "bicubic" in task:
+        pm = PARSER_MULTIPLE[parser]
+        if H % pm or W % pm:
+            raise ValueError(f"{task}: the {parser} parser reads whole frames for the propagation weights and needs H and W "
+                             f"to be multiples of {pm}; {H}x{W} is not")
+    if frames is not None:
+        video.check_clip_elements(frames, H, W, torch.float32 if dtype == "fp32" else torch.bfloat16)
+    return H, W
+
+
 def model_config(task, size=512):
     """MODEL_CONFIG[task] for clips of ``size`` x ``size``: the attention / propagation resolutions scale with the size
-    as in workload.sr3_config / script_util.blur_unet_config (at 512 this is the reference's table)."""
+    as in workload.sr3_config / script_util.blur_unet_config (at 512 this is the reference's table).  A pair (H, W)
+    returns the literal 512 layout: which levels carry attention and BasicVSR++ is a property of the checkpoint, not of
+    the frame, and both networks take their flow resolutions from the clip at run time."""
     _check_task(task)
     cfg = dict(MODEL_CONFIG[task])
+    if video.is_pair(size):
+        return cfg
     cfg["image_size"] = size
     if "bicubic" in task:
         cfg["attn_res"] = (size // 8, size // 16)
@@ -167,10 +253,19 @@ class Pipeline:
     """One task's networks and operators on one device; ``restore_video_files`` runs the reference's window loop over a
     directory of frames (flair_amd.io.restore_video_files)."""
 
-    def __init__(self, task, model, diffusion, A_func, face_helper, aux_model, vsrpp_weights_fn, size, device):
+    def __init__(self, task, model, diffusion, A_func, face_helper, aux_model, vsrpp_weights_fn, size, device, prior=None):
         self.task, self.model, self.diffusion, self.A_func = task, model, diffusion, A_func
         self.face_helper, self.aux_model, self.vsrpp_weights_fn = face_helper, aux_model, vsrpp_weights_fn
-        self.size, self.device = size, torch.device(device)
+        self.size, self.device, self.prior = size, torch.device(device), prior
+
+    def check_aligned(self, aligned):
+        """aligned=True hands whole frames to the prior, which restores 512 x 512 faces: with a size pair and a prior the
+        frames must be exactly that."""
+        if aligned and self.prior is not None and video.is_pair(self.size) and video.frame_hw(self.size) != (512, 512):
+            H, W = video.frame_hw(self.size)
+            raise ValueError(f"aligned=True runs the {PRIOR_LABELS[self.prior]} prior on whole frames, which must be 512x512 "
+                             f"aligned faces; frames of {H}x{W} need aligned=False (faces are detected and cropped) or "
+                             "prior=False")
 
     def restore_fn_for(self, jpeg_qf=-1):
         """RESTORE_FUNC[task] bound to the window's normalised degraded frames (video_sample.py:174-199, :455-459).
@@ -199,6 +294,7 @@ class Pipeline:
         torch's generators first (the reference does not seed).  ``faces="all"`` (aligned=False only): the prior runs on
         every detected face, at most ``max_faces`` per frame, and frames may have none (video.restore_window).  Returns
         the number of frames written."""
+        self.check_aligned(aligned)
         if seed is not None:
             torch.manual_seed(int(seed))
         hp = dict(w=w, rho=rho, noise_level=noise_level, zeta=zeta)
@@ -214,7 +310,11 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     the detector's ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` / ``yolov5l-face.pth`` /
     ``yolov5n-face.pth`` (``det_model``: the RetinaFace bodies or the YOLOv5-face detectors) and the parser's
     ``parsing_parsenet.pth`` (``parser="parsenet"``, the default) or ``parsing_bisenet.pth`` (``parser="bisenet"``),
-    all loaded strictly with ``weights_only=True``.  ``model_kwargs`` overrides entries of MODEL_CONFIG[task]
+    all loaded strictly with ``weights_only=True``.  ``size``: an int S restores S x S frames as the reference does (every
+    input is resized to S x S; a prior needs S = 512); a pair (H, W) restores rectangular frames: H and W multiples of
+    frame_multiple(task), degraded frames of exactly (H/f, W/f), the network in its literal 512 layout, and the face
+    helper at face size 512 whenever a prior is configured, whatever the frame size (check_frame_size holds the
+    refusals).  ``model_kwargs`` overrides entries of MODEL_CONFIG[task]
     (checkpoints of other widths).  ``kernels_path``: the reference's ``miscs/kernels_12.mat`` (gaussian and jpeg tasks).
 
     ``prior``: ``"codeformer"`` (or True, the default) reads ``codeformer.pth`` (its ``params_ema``);
@@ -240,7 +340,10 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     if dtype not in ("bf16", "fp32"):
         raise ValueError(f"dtype={dtype!r}: 'bf16' or 'fp32'")
     prior = prior_name(prior)
-    if prior is not None and size != 512:
+    pair = video.is_pair(size)
+    if pair:
+        size = check_frame_size(task, size, frames=video.FRAME_SLICE_LEN, parser=parser, dtype=dtype)
+    if prior is not None and not pair and size != 512:
         raise ValueError(f"the {PRIOR_LABELS[prior]} prior restores 512 x 512 faces (its code grid is 16 x 16): size={size} needs "
                          "prior=False")
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -320,7 +423,8 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         conf.input_range = np.array(None)
         A_func = psr.pseudoSR(conf, upscale_kernel=kernel, kernel_indx=10).WrapArchitecture_PyTorch().to(device)
         weights_fn = None
-    helper = FaceRestoreHelper(face_size=size, det_model=det_model, device=device, face_det=det, face_parse=parser)
+    # with a size pair the face size is the prior's 512, not the frame's
+    helper = FaceRestoreHelper(face_size=512 if pair else size, det_model=det_model, device=device, face_det=det, face_parse=parser)
     aux = wl.identity_aux
     if prior == "codeformer":
         aux = wl.codeformer_aux(gan)
@@ -329,7 +433,7 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     elif prior == "vqfrv2":
         aux = wl.vqfr_aux(gan, fidelity_ratio)
     diffusion = create_diffusion(task, steps)
-    return Pipeline(task, model, diffusion, A_func, helper, aux, weights_fn, size, device)
+    return Pipeline(task, model, diffusion, A_func, helper, aux, weights_fn, size, device, prior=prior)
 
 
 def restore_many(jobs, restore_one, *, log=print):

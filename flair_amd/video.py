@@ -12,6 +12,8 @@ Everything tensor-valued runs through the HIP kernels (resize / clamp / sampler)
 weights and the CodeFormer prior are passed in as callables (``vsrpp_weights_fn`` / ``aux_model``; the HIP
 versions are ``workload.parsenet_weights_fn(ParseNet(...), task)`` and ``workload.codeformer_aux(CodeFormer(...))``).
 """
+import numbers
+
 import torch
 
 from . import ops
@@ -58,18 +60,93 @@ def _affine(clip, a, b, lo, hi, sub=0.0, mul=1.0):
     return ops.clip_to_nchw(out, 3)
 
 
+def is_pair(size):
+    """A frame size is an int S (the reference's square frames: every input is resized to S x S) or a pair (H, W)
+    (rectangular mode: degraded frames must be exactly (H/f, W/f); nothing is resized on the user's behalf)."""
+    return not isinstance(size, numbers.Integral)
+
+
+def frame_hw(size):
+    """(H, W) of a frame size given as an int or a pair."""
+    if not is_pair(size):
+        return int(size), int(size)
+    hw = tuple(int(v) for v in size)
+    if len(hw) != 2 or min(hw) <= 0:
+        raise ValueError(f"size={size!r}: an int or a pair (H, W) of positive ints")
+    return hw
+
+
+def check_degraded(task, degraded_hw, size):
+    """Pair mode: data consistency needs y = A(x) on the pixel grid, so the degraded frames must be exactly
+    (H/f, W/f) for the task's factor f.  Raised before anything is launched, naming both sizes."""
+    H, W = frame_hw(size)
+    f = wl.TASKS[task]["factor"]
+    h, w = (int(v) for v in degraded_hw)
+    if H % f or W % f or (h, w) != (H // f, W // f):
+        raise ValueError(f"{task} restores {H}x{W} frames from degraded frames of {H // f}x{W // f} (factor {f}), got "
+                         f"{h}x{w}: with a size pair nothing is resized; give size=({h * f}, {w * f}) or frames of the right size")
+
+
+# Size limits of a window (DESIGN section 7, "Rectangular frames").  The element-wise kernels index with 64 bits; the
+# convolution, chain, alignment and warp entries address single frames (or SPyNet's small clips) through buffer
+# descriptors with 32-bit byte offsets and refuse what does not fit.  Two of those checks bound a window:
+#   * one frame of the alignment branch's offset / mask tensor (27 * deform_groups = 432 channels) must stay below the
+#     convolution entry's 1 GiB per frame: H * W * 432 * bytes-per-element < 2^30;
+#   * SPyNet warps the T - 1 frame pairs of a clip in one call over a 4-channel f32 clip that must stay below 2 GiB:
+#     (T - 1) * H * W * 16 < 2^31.
+# The Python layer refuses a window beyond either before anything is launched, so no entry is ever asked to wrap.
+OFFSET_CHANNELS = 27 * 16           # deform_groups = 16: the shipped layouts; offset_channels(model) reads a network's own
+FRAME_BYTES_LIMIT = 2 ** 30
+FLOW_CLIP_BYTES_LIMIT = 2 ** 31
+
+
+def offset_channels(model):
+    """27 * deform_groups of the widest alignment module of ``model`` (a network built with other groups through
+    model_kwargs has another per-frame limit); OFFSET_CHANNELS for an object without such modules (test stand-ins)."""
+    mods = model.modules() if hasattr(model, "modules") else ()
+    groups = [int(m.deform_groups) for m in mods if hasattr(m, "deform_groups")]
+    return 27 * max(groups) if groups else OFFSET_CHANNELS
+
+
+def max_frame_pixels(dtype=torch.bfloat16, channels=OFFSET_CHANNELS):
+    """Largest H*W of one frame: with the shipped 432 offset channels 1 242 756 pixels in bf16 (e.g. 960 x 1280),
+    621 378 in f32 (e.g. 640 x 960)."""
+    esz = 4 if dtype == torch.float32 else 2
+    return (FRAME_BYTES_LIMIT - 1) // (channels * esz)
+
+
+def max_clip_pixels():
+    """Largest (T - 1) * H * W of one window (SPyNet's flow clip), whatever the network's dtype."""
+    return (FLOW_CLIP_BYTES_LIMIT - 1) // 16
+
+
+def check_clip_elements(T, H, W, dtype=torch.bfloat16, channels=OFFSET_CHANNELS):
+    name = "f32" if dtype == torch.float32 else "bf16"
+    if H * W > max_frame_pixels(dtype, channels):
+        raise ValueError(f"frames of {H}x{W} are {H * W} pixels; the {name} kernels address one frame of the alignment "
+                         f"offsets ({channels} channels) with 32-bit byte offsets below 1 GiB: at most "
+                         f"{max_frame_pixels(dtype, channels)} pixels a frame")
+    if (T - 1) * H * W > max_clip_pixels():
+        raise ValueError(f"a window of {T} frames of {H}x{W} gives SPyNet a clip of {(T - 1) * H * W} pixels; its warp "
+                         f"addresses at most {max_clip_pixels()} (2 GiB): use shorter windows")
+
+
 def init_frames(task, degraded01, size):
     """INIT_FUNC (video_sample.py:158-163) followed by the (x - 0.5) / 0.5 of :372-373: bicubic for the
     bicubic tasks, ``area`` (= block replication when upscaling by an integer factor) for the blur tasks,
-    clamped to [0, 1], returned in [-1, 1]."""
+    clamped to [0, 1], returned in [-1, 1].  ``size``: an int S -> (S, S), or a pair (H, W) with degraded frames of
+    exactly (H/f, W/f): the same resize modes, the blur tasks' replication being by exactly f."""
+    H, W = frame_hw(size)
+    if is_pair(size):
+        check_degraded(task, degraded01.shape[-2:], size)
     clip = _to_clip(degraded01)
     if "bicubic" in task:
         mode = ops.RESIZE_BICUBIC
     else:
-        if size % degraded01.shape[-1] or size % degraded01.shape[-2]:
+        if W % degraded01.shape[-1] or H % degraded01.shape[-2]:
             raise ValueError("area initialisation needs an integer upscaling factor")
         mode = ops.RESIZE_NEAREST
-    big = ops.resize(clip, (size, size), mode, channels=3)
+    big = ops.resize(clip, (H, W), mode, channels=3)
     return _affine(big, 1.0, 0.0, 0.0, 1.0, sub=0.5, mul=2.0)
 
 
@@ -84,26 +161,29 @@ def normalise(degraded01):
 
 def rnn_input(degraded_norm_clip, size):
     """The flow-network input of the blur tasks (video_sample.py:406-425): the two ``VF.normalize`` calls
-    cancel around the bicubic resize, what remains is resize + clamp to [-1, 1]."""
-    big = ops.resize(degraded_norm_clip, (size, size), ops.RESIZE_BICUBIC, channels=3)
+    cancel around the bicubic resize, what remains is resize + clamp to [-1, 1].  ``size``: an int or a pair (H, W)."""
+    big = ops.resize(degraded_norm_clip, frame_hw(size), ops.RESIZE_BICUBIC, channels=3)
     return _affine(big, 1.0, 0.0, -1.0, 1.0)
 
 
 FACES = ("largest", "all")
 
 
-def window_faces(face_helper, init_n, window_index=0, frame_indices=None, faces="largest", max_faces=None):
+def window_faces(face_helper, init_n, window_index=0, frame_indices=None, faces="largest", max_faces=None,
+                 any_frame_size=False):
     """Affine matrices of the window's faces (video_sample.py:446-448): one per frame, estimated on the normalised init
     frames ((T, 3, S, S) in [-1, 1]) with the largest face of every frame kept.  A frame without a face is a
     ValueError naming the window and the frame's index in the video (the reference fails later, inside the sampler).
     ``faces="all"`` (extension) returns (matrices, face_frames) instead: every face of every frame, largest first and at
     most ``max_faces`` per frame, face k in frame face_frames[k] of the window; frames without a face are simply absent
-    from the list, and a window without any gives ([], [])."""
+    from the list, and a window without any gives ([], []).
+    ``any_frame_size`` (the pair mode of restore_window): the frames need not have the helper's face size -- the faces
+    are cropped to it and pasted back through FaceRestoreHelper.paste_faces, for which the caller passes face_frames."""
     if faces not in FACES:
         raise ValueError(f"faces={faces!r}: one of {', '.join(FACES)}")
     T = init_n.shape[0]
     frames = list(frame_indices) if frame_indices is not None else list(range(T))
-    if init_n.shape[-1] != face_helper.face_size[0] or init_n.shape[-2] != face_helper.face_size[1]:
+    if not any_frame_size and (init_n.shape[-1] != face_helper.face_size[0] or init_n.shape[-2] != face_helper.face_size[1]):
         raise ValueError(f"aligned=False pastes faces at the helper's face size {face_helper.face_size}: frames of "
                          f"{tuple(init_n.shape[-2:])} must match it (video_sample.py restores 512 x 512 frames)")
     if faces == "all":
@@ -131,10 +211,18 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
     ``face_helper`` before the first step (:446-448) and runs the prior on their crops (:460-479); frame_indices
     (the window's frames in the video) only name frames in its errors.  ``faces="all"`` (with aligned=False) runs the
     prior on every detected face, at most ``max_faces`` per frame, and lets frames -- or the whole window -- have none.
-    Returns (frames01 of the frames this window contributes, (T', 3, S, S) in [0, 1]; next prev_recon)."""
+    ``size``: an int S (every frame is resized to S x S, as in the reference) or a pair (H, W): the degraded frames must
+    be exactly (H/f, W/f), and aligned=False crops the faces to the helper's face size -- which is then independent of
+    the frame size -- and pastes them back with paste_faces (faces="largest" passes face_frames = 0..T-1 itself).
+    Returns (frames01 of the frames this window contributes, (T', 3, H, W) in [0, 1]; next prev_recon)."""
     hp = hp or wl.TASKS[task]
     dev = degraded01.device
     wi = window_index
+    pair = is_pair(size)
+    if pair:                                                                      # refusals come before the first launch
+        check_degraded(task, degraded01.shape[-2:], size)
+        check_clip_elements(degraded01.shape[1], *frame_hw(size), dtype=getattr(model, "dtype", torch.bfloat16),
+                            channels=offset_channels(model))
     deg = degraded01[0].float().contiguous()                                      # (T,3,h,w) in [0,1]
     T = deg.shape[0]
     init_n = init_frames(task, deg, size)[None]                                   # (1,T,3,S,S) in [-1,1]
@@ -145,9 +233,12 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
         if face_helper is None:
             raise ValueError("aligned=False needs face_helper (a FaceRestoreHelper with a detector and a face parser)")
         if faces == "all":
-            mats, face_frames = window_faces(face_helper, init_n[0], wi, frame_indices, faces="all", max_faces=max_faces)
+            mats, face_frames = window_faces(face_helper, init_n[0], wi, frame_indices, faces="all", max_faces=max_faces,
+                                             any_frame_size=pair)
         else:
-            mats = window_faces(face_helper, init_n[0], wi, frame_indices)
+            mats = window_faces(face_helper, init_n[0], wi, frame_indices, any_frame_size=pair)
+            if pair:
+                face_frames = list(range(T))
     deg_n, deg_n_clip = normalise(deg)
     deg_n = deg_n[None]
     t0 = diffusion.num_timesteps - 1 if t_start == -1 else t_start
@@ -174,7 +265,8 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
 def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, aux_model=wl.identity_aux,
                   vsrpp_weights_fn=None, hp=None, tau=5, t_start=-1, length=FRAME_SLICE_LEN, overlap=OVERLAP,
                   noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, faces="largest", max_faces=None):
-    """degraded01: (1, N, 3, h, w) frames in [0, 1] on the GPU.  Returns (N, 3, size, size) in [0, 1].
+    """degraded01: (1, N, 3, h, w) frames in [0, 1] on the GPU.  Returns (N, 3, H, W) in [0, 1] for ``size`` = an int
+    S (H = W = S) or a pair (H, W) (see restore_window).
 
     restore_fn_for(degraded_norm_window (1,T,3,h,w)) -> restore_fn(x0) is the data-consistency
     operator of the window (video_sample.py:455-459); vsrpp_weights_fn(init_norm (1,T,3,S,S)) supplies
@@ -185,7 +277,9 @@ def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, a
     dev = degraded01.device
     n_frames = degraded01.shape[1]
     prev_recon = None
-    out = torch.empty((n_frames, 3, size, size), dtype=torch.float32, device=dev)
+    if is_pair(size):
+        check_degraded(task, degraded01.shape[-2:], size)
+    out = torch.empty((n_frames, 3, *frame_hw(size)), dtype=torch.float32, device=dev)
     filled = 0
     for wi, idx in enumerate(window_indices(n_frames, length, overlap)):
         frames01, prev_recon = restore_window(

@@ -427,6 +427,14 @@ int flair_depthwise_filter(const float* x, int planes, int Hin, int Win, const f
 int flair_jpeg_roundtrip(const float* x, int N, int S, const float* q_luma, const float* q_chroma,
                          const float* dct8, float* workspace, float* y, float* luma_q, float* chroma_q,
                          hipStream_t stream);
+/* The same round trip on rectangular images (N,3,H,W), H % 16 == 0 and W % 16 == 0 (H == W allowed): the codec is
+ * independent per 16x16 MCU, so nothing but the indexing knows the frame's shape.  One launch and no workspace: a
+ * wave owns ten MCUs, keeps their YCbCr blocks in LDS and gives each 8x8 block (four luma, Cb, Cr per MCU) to one
+ * lane.  Every value goes through the expressions of flair_jpeg_roundtrip (shared device functions), so on square
+ * input the two entries agree bit for bit, level planes included.  Tables and level planes as above: luma_q
+ * (N,1,H,W), chroma_q (N,2,H/2,W/2), both or neither.  Offsets are 64-bit; N*(H/16)*(W/16)/10 must stay below 2^31. */
+int flair_jpeg_roundtrip_hw(const float* x, int N, int H, int W, const float* q_luma, const float* q_chroma,
+                            const float* dct8, float* y, float* luma_q, float* chroma_q, hipStream_t stream);
 /* C[b] = A[b] (MxK) * B[b] (KxN), row-major f32; a stride of 0 shares the matrix across the
  * batch.  SRConv's separable U/V products (restore_util.py:102-227). */
 int flair_matmul_f32(const float* A, long a_batch_stride, const float* B, long b_batch_stride,
