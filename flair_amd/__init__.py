@@ -5,6 +5,8 @@ Layout:
   _lib.py, ops.py     ctypes binding and tensor-level wrappers
   guided_diffusion/   host-side mirror of the reference's Python interface
   parallel.py         clip-parallel multi-GPU helpers (RCCL weight broadcast)
+  degrade.py          clean frames -> a task's degraded frames, with the operator restore assumes
+  metrics.py          PSNR / SSIM of written frames on the GPU (csrc/metrics.hip)
 """
 import os
 import sys

@@ -1,4 +1,7 @@
-"""Command line: ``python -m flair_amd restore TASK VIDEO_DIR OUTPUT_DIR [options]`` and the four demo presets.
+"""Command line: ``python -m flair_amd restore TASK VIDEO_DIR OUTPUT_DIR [options]`` and the four demo presets, plus the two
+ends of the loop around it: ``degrade TASK CLEAN_DIR OUT_DIR`` makes a task's degraded frames from clean ones with the exact
+operator the restoration assumes (flair_amd.degrade), and ``evaluate RESTORED_DIR TRUTH_DIR`` scores written frames with PSNR
+and SSIM (flair_amd.metrics); ``restore --ground-truth DIR`` scores every video as soon as it is written.
 
 The options of the reference's ``main()`` keep their names and defaults (``scripts/video_sample.py:249-263``); the
 presets are its ``x8_bicubic_demo`` ... ``jpeg_demo`` commands (:500-556).  Several videos go through one call with
@@ -65,13 +68,96 @@ def make_parser():
     r.add_argument("task", choices=pl.TASK_NAMES)
     r.add_argument("paths", nargs="+", metavar="PATH", help="VIDEO_DIR OUTPUT_DIR, or VIDEO_DIR... with --output-root")
     r.add_argument("--output-root", default=None, metavar="DIR", help="write every VIDEO_DIR to DIR/<its name>")
+    r.add_argument("--ground-truth", default=None, metavar="DIR",
+                   help="clean frames of the video (with --output-root: a root holding one directory per video name): "
+                        "after a video is written, log its mean PSNR / SSIM and write metrics.json next to the frames")
     _add_hparams(r, pl.MAIN_DEFAULTS)
     _add_common(r)
     for name, demo in pl.DEMOS.items():
         d = sub.add_parser(name, help=f"{demo['task']}: {demo['video_path']} -> {demo['output_path']}")
         _add_hparams(d, dict(pl.MAIN_DEFAULTS, **{k: v for k, v in demo.items() if k in pl.MAIN_DEFAULTS}))
         _add_common(d)
+    g = sub.add_parser("degrade", help="clean frames -> the task's degraded frames, with the operator restore assumes")
+    g.add_argument("task", choices=pl.TASK_NAMES)
+    g.add_argument("clean_dir", metavar="CLEAN_DIR", help="clean frames of one size valid for the task (--frame-size's rule)")
+    g.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png at 1/f of the size")
+    g.add_argument("--kernels", default=pl.DEFAULT_KERNELS, metavar="PATH",
+                   help="the blur kernels .mat file (MATLAB v5) of the gaussian and jpeg tasks")
+    g.add_argument("--jpeg-qf", type=int, default=None, metavar="Q", help="jpeg only: the codec's quality factor (default 60)")
+    g.add_argument("--noise-sigma", type=float, default=0.0, metavar="S",
+                   help="add white Gaussian noise of standard deviation S on the 0..255 scale before quantisation")
+    g.add_argument("--seed", type=int, default=None, help="seed of the noise")
+    g.add_argument("--device", default=None, help="default: cuda")
+    e = sub.add_parser("evaluate", help="PSNR / SSIM of written frames against ground truth")
+    e.add_argument("restored_dir", metavar="RESTORED_DIR")
+    e.add_argument("truth_dir", metavar="TRUTH_DIR", help="frames are paired with RESTORED_DIR's in natural order")
+    e.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the means as JSON")
+    e.add_argument("--device", default=None, help="default: cuda")
     return ap
+
+
+def degrade_of(args):
+    """The keyword arguments of degrade_video_files for a parsed ``degrade`` command line (refusals before any GPU work)."""
+    if args.jpeg_qf is not None and args.task != "jpeg":
+        raise SystemExit(f"degrade: --jpeg-qf belongs to the jpeg task, not {args.task}")
+    if args.jpeg_qf is not None and not 1 <= args.jpeg_qf <= 100:
+        raise SystemExit("degrade: --jpeg-qf is a quality factor in 1..100")
+    if not args.noise_sigma >= 0:
+        raise SystemExit("degrade: --noise-sigma must not be negative")
+    if not os.path.isdir(args.clean_dir):
+        raise SystemExit(f"degrade: {args.clean_dir} is not a directory")
+    return dict(jpeg_qf=args.jpeg_qf, noise_sigma=args.noise_sigma, seed=args.seed)
+
+
+def truth_of(args, jobs):
+    """{output_dir: ground-truth directory} for the jobs of a parsed ``restore`` command line (with --output-root the
+    directory of the video's name under --ground-truth), or None without --ground-truth."""
+    root = getattr(args, "ground_truth", None)
+    if root is None:
+        return None
+    if args.output_root is None:
+        truth = [root]
+    else:
+        truth = [os.path.join(root, os.path.basename(os.path.normpath(v))) for v, _ in jobs]
+    for t in truth:
+        if not os.path.isdir(t):
+            raise SystemExit(f"restore: ground truth {t} is not a directory")
+    return {o: t for (_, o), t in zip(jobs, truth)}
+
+
+def _degrade(args):
+    kw = degrade_of(args)
+    import torch
+    from . import degrade as dg
+    torch.set_grad_enabled(False)
+    kernel = pl.load_blur_kernel(args.kernels) if "bicubic" not in args.task else None
+    try:
+        n = dg.degrade_video_files(args.task, args.clean_dir, args.out_dir, device=args.device or "cuda", kernel=kernel, **kw)
+    except ValueError as exc:
+        raise SystemExit(f"degrade: {exc}")
+    print(f"degraded {n} frames of {args.clean_dir} ({args.task}) to {args.out_dir}")
+    return 0
+
+
+def write_json(path, result):
+    with open(path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
+def _evaluate(args):
+    import torch
+    from . import metrics as fm
+    torch.set_grad_enabled(False)
+    try:
+        result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda")
+    except ValueError as exc:
+        raise SystemExit(str(exc))
+    for line in fm.format_report(result):
+        print(line)
+    if args.json:
+        write_json(args.json, result)
+    return 0
 
 
 def jobs_of(args):
@@ -130,7 +216,12 @@ def size_of(args, task, jobs):
 
 def main(argv=None):
     args = make_parser().parse_args(argv)
+    if args.command == "degrade":
+        return _degrade(args)
+    if args.command == "evaluate":
+        return _evaluate(args)
     task, jobs = jobs_of(args)
+    truth = truth_of(args, jobs)
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
@@ -156,7 +247,17 @@ def main(argv=None):
         hp = dict(aligned=args.aligned, t_start=args.t_start, jpeg_qf=args.jpeg_qf, w=args.w, tau=args.tau,
                   rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
         hp.update(faces)
-        pl.restore_many(jobs, lambda v, o: p.restore_video_files(v, o, **hp))
+
+        def restore_one(v, o):
+            n = p.restore_video_files(v, o, **hp)
+            if truth is not None:
+                from . import metrics as fm
+                result = fm.evaluate_dirs(o, truth[o], device)
+                print(f"{o}: mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  "
+                      f"ssim {result['mean']['ssim']:.4f}")
+                write_json(os.path.join(o, "metrics.json"), result)
+            return n
+        pl.restore_many(jobs, restore_one)
     finally:
         if dist.is_available() and dist.is_initialized():
             dist.destroy_process_group()

@@ -82,3 +82,15 @@ def ptr(t):
 
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def image_metrics_workspace(N, H, W):
+    """flair_image_metrics_workspace(N, H, W): bytes of workspace flair_image_metrics needs (0 for a shape it refuses)."""
+    f = lib().flair_image_metrics_workspace
+    f.restype = ctypes.c_size_t
+    return int(f(int(N), int(H), int(W)))
+
+
+def image_metrics(a, b, N, H, W, out, ws, ws_bytes):
+    """flair_image_metrics on torch's current stream; a, b, out, ws: ctypes pointers (ptr()).  Returns the status."""
+    return lib().flair_image_metrics(a, b, int(N), int(H), int(W), out, ws, ctypes.c_size_t(ws_bytes), stream())

@@ -40,12 +40,16 @@ def list_frames(video_path):
     return [os.path.join(str(video_path), n) for n in sorted(names, key=natural_key)]
 
 
-def decode_frame(path):
-    """One frame file -> (3, h, w) uint8 RGB (what ``cv2.cvtColor(cv2.imread(p), COLOR_BGR2RGB)`` yields)."""
+def decode_frame_hwc(path):
+    """One frame file -> dense (h, w, 3) uint8 RGB, the layout of the files and of to_bytes."""
     from PIL import Image
     with Image.open(path) as im:
-        arr = np.asarray(im.convert("RGB"), dtype=np.uint8)
-    return np.ascontiguousarray(arr.transpose(2, 0, 1))
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
+
+
+def decode_frame(path):
+    """One frame file -> (3, h, w) uint8 RGB (what ``cv2.cvtColor(cv2.imread(p), COLOR_BGR2RGB)`` yields)."""
+    return np.ascontiguousarray(decode_frame_hwc(path).transpose(2, 0, 1))
 
 
 def read_frames(paths, pin=False):
@@ -94,7 +98,10 @@ class _Writer(threading.Thread):
 
     def submit(self, first, frames01_dev):
         """frames01_dev: (n, 3, H, W) float on the GPU (or host)."""
-        u8 = to_bytes(frames01_dev)
+        self.submit_bytes(first, to_bytes(frames01_dev))
+
+    def submit_bytes(self, first, u8):
+        """u8: (n, H, W, 3) uint8 on the GPU (or host), written as they are."""
         if u8.is_cuda:
             host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(u8, non_blocking=True)
@@ -155,6 +162,57 @@ def iter_windows(paths, device, length=video.FRAME_SLICE_LEN, overlap=video.OVER
             cur.wait_event(ev)
             u8.record_stream(cur)        # allocated on the side stream, read here: keep the block until this read is done
         yield idx, (u8.float() / 255.0).unsqueeze(0)
+
+
+def iter_frame_batches(path_lists, groups, device):
+    """Yield ``(first, [u8, ...])`` per group ``(first, n)`` of ``groups``: ``u8[k]`` = (n, h, w, 3) uint8 on ``device``,
+    frames ``first .. first + n - 1`` of ``path_lists[k]`` (the frames of one group share one size per list).  As in
+    iter_windows the NEXT group is decoded into pinned memory and uploaded on a side stream while the caller works on the
+    current one."""
+    q = queue.Queue(maxsize=2)
+    on_gpu = torch.device(device).type == "cuda"
+    side = torch.cuda.Stream(device=device) if on_gpu else None
+
+    def produce():
+        try:
+            for first, n in groups:
+                hosts = [torch.from_numpy(np.stack([decode_frame_hwc(p) for p in paths[first:first + n]]))
+                         for paths in path_lists]
+                if on_gpu:
+                    hosts = [h.pin_memory() for h in hosts]
+                    with torch.cuda.stream(side):
+                        devs = [h.to(device, non_blocking=True) for h in hosts]
+                        ev = torch.cuda.Event()
+                        ev.record(side)
+                    q.put((first, devs, ev, hosts))
+                else:
+                    q.put((first, hosts, None, hosts))
+            q.put(None)
+        except Exception as exc:
+            q.put(exc)
+
+    threading.Thread(target=produce, daemon=True).start()
+    while True:
+        item = q.get()
+        if item is None:
+            return
+        if isinstance(item, Exception):
+            raise item
+        first, devs, ev, _keep = item
+        if ev is not None:
+            cur = torch.cuda.current_stream(device)
+            cur.wait_event(ev)
+            for d in devs:
+                d.record_stream(cur)     # allocated on the side stream, read here
+        yield first, devs
+
+
+def frame_size(path):
+    """(h, w) of a frame file; only its header is read."""
+    from PIL import Image
+    with Image.open(path) as im:
+        w, h = im.size
+    return h, w
 
 
 def restore_video_files(task, video_path, output_path, model, diffusion, restore_fn_for, *, size, device,

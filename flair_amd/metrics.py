@@ -1,0 +1,91 @@
+"""PSNR and SSIM of written frames against ground truth, on the GPU (``flair_image_metrics``, csrc/metrics.hip).
+
+The reference ships no scoring tool; this is the restoration literature's usual pair, on the bytes that get written
+(float images go through ``io.to_bytes`` first, so a metric always describes the files):
+
+  * ``psnr = 10 log10(255^2 * 3 H W / sse)`` over the three channels of a frame together, ``inf`` where the frames agree;
+  * ``ssim``: Wang et al.'s index as BasicSR computes it on RGB -- 11 x 11 Gaussian window, sigma 1.5, valid region only
+    ((H - 10) x (W - 10), no padding), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, the mean over the map and the three
+    channels.
+
+Not measured: the Y-channel and border-cropped variants, perceptual (LPIPS), identity and temporal metrics.
+"""
+import math
+import os
+
+import torch
+
+from . import io as fio
+from . import ops
+
+SSIM_WINDOW = 11
+TILE_H, TILE_W = 32, 64         # the SSIM-map tile of one workgroup (MT_TH, MT_TW of csrc/metrics.hip): the tests size their shapes by it
+
+
+def psnr_ssim(a_u8, b_u8):
+    """a_u8, b_u8: (N, H, W, 3) uint8 on the GPU -> dict(psnr=[N floats], ssim=[N floats], sse=[N ints])."""
+    N, H, W, _ = a_u8.shape
+    rows = ops.image_metrics(a_u8, b_u8).cpu().tolist()
+    sse = [int(round(r[0])) for r in rows]
+    peak = 255.0 ** 2 * 3 * H * W
+    psnr = [10.0 * math.log10(peak / e) if e else math.inf for e in sse]
+    valid = 3.0 * (H - SSIM_WINDOW + 1) * (W - SSIM_WINDOW + 1)
+    ssim = [(r[1] + r[2] + r[3]) / valid for r in rows]
+    return dict(psnr=psnr, ssim=ssim, sse=sse)
+
+
+def _pairs(restored_dir, truth_dir):
+    """The (restored, truth) file pairs in list_frames order with their common (h, w); every refusal of evaluate_dirs."""
+    ra, rb = fio.list_frames(restored_dir), fio.list_frames(truth_dir)
+    for d, paths in ((restored_dir, ra), (truth_dir, rb)):
+        if not paths:
+            raise ValueError(f"evaluate: no frame files in {d}")
+    if len(ra) != len(rb):
+        raise ValueError(f"evaluate: {restored_dir} holds {len(ra)} frames and {truth_dir} holds {len(rb)}; "
+                         "frames are paired in order and the counts must agree")
+    sizes = []
+    for pa, pb in zip(ra, rb):
+        sa, sb = fio.frame_size(pa), fio.frame_size(pb)
+        if sa != sb:
+            raise ValueError(f"evaluate: {pa} is {sa[0]}x{sa[1]} and {pb} is {sb[0]}x{sb[1]}; paired frames must share one size")
+        if min(sa) < SSIM_WINDOW:
+            raise ValueError(f"evaluate: {pa} and {pb} are {sa[0]}x{sa[1]}; SSIM's {SSIM_WINDOW}x{SSIM_WINDOW} window needs "
+                             f"frames of at least {SSIM_WINDOW} pixels a side")
+        sizes.append(sa)
+    return ra, rb, sizes
+
+
+def _groups(sizes, batch):
+    """Runs of at most ``batch`` consecutive frames of one size as (first, n)."""
+    groups, first = [], 0
+    while first < len(sizes):
+        n = 1
+        while n < batch and first + n < len(sizes) and sizes[first + n] == sizes[first]:
+            n += 1
+        groups.append((first, n))
+        first += n
+    return groups
+
+
+def evaluate_dirs(restored_dir, truth_dir, device, batch=8):
+    """Score the frames of ``restored_dir`` against those of ``truth_dir``, paired in ``io.list_frames`` order:
+    ``dict(frames=[{name, psnr, ssim}], mean={psnr, ssim}, count)``; the means are those of the per-frame values.
+    ValueError when a directory is empty, the counts differ, a pair differs in size or is smaller than 11 pixels a side
+    (checked on the file headers, before anything is decoded).  The next batch is decoded and uploaded while the current
+    one is measured (io.iter_frame_batches)."""
+    ra, rb, sizes = _pairs(restored_dir, truth_dir)
+    frames = []
+    for first, (a, b) in fio.iter_frame_batches([ra, rb], _groups(sizes, max(1, int(batch))), device):
+        got = psnr_ssim(a, b)
+        for i, (p, s) in enumerate(zip(got["psnr"], got["ssim"])):
+            frames.append(dict(name=os.path.basename(ra[first + i]), psnr=p, ssim=s))
+    n = len(frames)
+    mean = dict(psnr=sum(f["psnr"] for f in frames) / n, ssim=sum(f["ssim"] for f in frames) / n)
+    return dict(frames=frames, mean=mean, count=n)
+
+
+def format_report(result):
+    """One line per frame and the means, four decimals each."""
+    lines = [f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" for f in result["frames"]]
+    lines.append(f"mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  ssim {result['mean']['ssim']:.4f}")
+    return lines

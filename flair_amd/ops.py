@@ -1124,3 +1124,23 @@ def letterbox(src, new_hw, top_left, out_hw, *, pre=(1.0, 0.0, float("-inf"), fl
                                      ctypes.c_float(scale), ctypes.c_float(pad_value), ptr(out), _ld(out), stream()),
           "flair_letterbox_nhwc")
     return out
+
+
+# --------------------------------------------------------------------------- image metrics (metrics.hip)
+def image_metrics(a, b, out=None):
+    """Squared error and SSIM sums of two sets of written frames (flair_image_metrics): a, b (N, H, W, 3) uint8 dense RGB
+    on the GPU, H, W >= 11 -> (N, 4) float64 device tensor, row n = [sum of squared byte differences (the exact integer),
+    sum of the SSIM map of R, of G, of B over its (H - 10) x (W - 10) valid region].  flair_amd.metrics turns the rows into
+    PSNR and mean SSIM.  The workspace comes from the library's size query."""
+    _refuse(a.dim() == 4 and a.shape[3] == 3 and tuple(a.shape) == tuple(b.shape),
+            f"image_metrics: two (N, H, W, 3) frame sets of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    _refuse(a.dtype == torch.uint8 and b.dtype == torch.uint8, f"image_metrics: uint8 frames, got {a.dtype} and {b.dtype}")
+    _refuse(a.is_contiguous() and b.is_contiguous(), "image_metrics: dense (contiguous) frames")
+    N, H, W, _ = a.shape
+    if out is None:
+        out = torch.empty((N, 4), dtype=torch.float64, device=a.device)
+    _refuse(out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (N, 4), "image_metrics: out is a dense (N, 4) float64 tensor")
+    nbytes = _lib.image_metrics_workspace(N, H, W)
+    ws = _workspace(max(nbytes, 8), a.device, tag="metrics")
+    check(_lib.image_metrics(ptr(a), ptr(b), N, H, W, ptr(out), ptr(ws), nbytes), "flair_image_metrics")
+    return out

@@ -140,13 +140,11 @@ def parse_frame_size(text):
 
 def auto_frame_size(task, video_path):
     """--frame-size auto: (h*f, w*f) of the first frame file of ``video_path`` (only its header is read)."""
-    from PIL import Image
     _check_task(task)
     paths = fio.list_frames(video_path)
     if not paths:
         raise ValueError(f"{video_path}: no frame files to take the frame size from")
-    with Image.open(paths[0]) as im:
-        w, h = im.size
+    h, w = fio.frame_size(paths[0])
     f = wl.TASKS[task]["factor"]
     return h * f, w * f
 
@@ -304,6 +302,25 @@ class Pipeline:
             vsrpp_weights_fn=self.vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, faces=faces, max_faces=max_faces)
 
 
+def build_operator(task, size, device, kernel=None):
+    """The task operator (get_A_func, video_sample.py:190-247) on ``device``: SRConv with the 4f-tap bicubic kernel and
+    reflect padding for the bicubic tasks (``size``: an int or a pair (H, W)); the pseudoSR operator of ``kernel`` (the
+    25 x 25 blur array of load_blur_kernel) at factor 4 for gaussian and jpeg.  build_pipeline's data-consistency step and
+    flair_amd.degrade.Degrader apply the same object."""
+    _check_task(task)
+    if "bicubic" in task:
+        from .guided_diffusion.restore_util import SRConv
+        factor = wl.TASKS[task]["factor"]
+        return SRConv(wl.bicubic_taps(factor), 3, size, device, stride=factor)
+    from .guided_diffusion import pseudoSR as psr
+    if kernel is None:
+        raise ValueError(f"{task}: the blur operator needs the 25 x 25 blur kernel (load_blur_kernel)")
+    conf = psr.Get_pseudoSR_Conf(4)
+    conf.sigmoid_range_limit = False
+    conf.input_range = np.array(None)
+    return psr.pseudoSR(conf, upscale_kernel=kernel, kernel_indx=10).WrapArchitecture_PyTorch().to(device)
+
+
 def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=100, kernels_path=None, prior=True,
                    det_model="retinaface_resnet50", model_kwargs=None, graph=True, prior_kwargs=None, parser="parsenet"):
     """Build ``task``'s Pipeline from the checkpoints in ``weights_dir``: ``flair_{task}.pt``, the prior's checkpoint,
@@ -410,19 +427,8 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
                 parallel.broadcast_weights(net, src=0)
     if graph and hasattr(model, "enable_hip_graph") and device.type == "cuda":
         model.enable_hip_graph()
-    # the task operator (get_A_func, video_sample.py:190-247)
-    if "bicubic" in task:
-        from .guided_diffusion.restore_util import SRConv
-        factor = wl.TASKS[task]["factor"]
-        A_func = SRConv(wl.bicubic_taps(factor), 3, size, device, stride=factor)
-        weights_fn = wl.parsenet_weights_fn(parser, task)
-    else:
-        from .guided_diffusion import pseudoSR as psr
-        conf = psr.Get_pseudoSR_Conf(4)
-        conf.sigmoid_range_limit = False
-        conf.input_range = np.array(None)
-        A_func = psr.pseudoSR(conf, upscale_kernel=kernel, kernel_indx=10).WrapArchitecture_PyTorch().to(device)
-        weights_fn = None
+    A_func = build_operator(task, size, device, kernel)
+    weights_fn = wl.parsenet_weights_fn(parser, task) if "bicubic" in task else None
     # with a size pair the face size is the prior's 512, not the frame's
     helper = FaceRestoreHelper(face_size=512 if pair else size, det_model=det_model, device=device, face_det=det, face_parse=parser)
     aux = wl.identity_aux

@@ -65,7 +65,8 @@ const char* flair_last_error(void);
  * 11: + flair_global_avgpool_nhwc, flair_channel_gate_nhwc, flair_upsample_argmax_nhwc (BiSeNet face parsing);
  * 12: + flair_warp_affine_cubic_indexed, flair_face_paste (several faces per frame, frames without a face);
  * 13: + flair_maxpool2x2s2_nhwc, flair_spp_maxpool_nhwc, flair_channel_interleave_nhwc, flair_yolo_face_decode,
- *     flair_letterbox_nhwc (the YOLOv5-face detectors)).
+ *     flair_letterbox_nhwc (the YOLOv5-face detectors); 14: + flair_jpeg_roundtrip_hw (rectangular frames);
+ * 15: + flair_image_metrics_workspace, flair_image_metrics (PSNR / SSIM of written frames)).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -602,6 +603,24 @@ int flair_letterbox_nhwc(const float* src, int B, int H, int W, int new_h, int n
  * one broadcast per parameter).  librccl is bound with dlopen at the first call.  Clips are independent after that: no
  * data-path collective exists. */
 int flair_bcast_weights(void* blob, size_t bytes, int root, void* rccl_comm, hipStream_t stream);
+
+/* ------------------------------------------------------------- image metrics (python -m flair_amd evaluate)
+ * No counterpart in the reference, which ships no scoring tool: squared error and SSIM of two sets of WRITTEN frames.
+ * a, b: dense [N][H][W][3] uint8 RGB (what flair_amd.io.decode_frame yields after the HWC transpose and io.to_bytes produces).
+ * out: [N][4] doubles per frame n: out[4n] = sum of (a - b)^2 over the 3 H W byte values, the exact integer (32-bit integer
+ * partials, summed in double: exact below 2^53); out[4n + 1 .. 4n + 3] = sums of the SSIM map of R, G, B over its
+ * (H - 10) x (W - 10) valid region: the restoration definition (Wang et al. 2004, as BasicSR computes it on RGB) on the 0..255
+ * scale: 11 x 11 Gaussian window, sigma 1.5, normalised to sum 1, applied separably without padding; mu_x, mu_y,
+ * var_x = E[x^2] - mu_x^2, var_y, cov_xy; C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2;
+ * ssim = (2 mu_x mu_y + C1)(2 cov_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(var_x + var_y + C2)), moments in f32 on values shifted by
+ * -128.  PSNR = 10 log10(255^2 * 3 H W / out[4n]) and the mean SSIM = (out[4n+1] + out[4n+2] + out[4n+3]) / (3 (H-10)(W-10)) are
+ * the caller's arithmetic (flair_amd.metrics).  One workgroup per 32 x 64 tile of one (frame, channel) writes one partial into
+ * ws; a second launch sums each frame's partials in a fixed order: no floating-point atomics, so a frame's four values are the
+ * same bits in every run and for every N.  ws: flair_image_metrics_workspace(N, H, W) bytes (0 for a shape the entry refuses),
+ * 8-byte aligned, contents irrelevant.  H, W >= 11, N >= 1; offsets are 64-bit (N H W 3 may exceed 2^31). */
+size_t flair_image_metrics_workspace(int N, int H, int W);
+int flair_image_metrics(const uint8_t* a, const uint8_t* b, int N, int H, int W, double* out, void* ws, size_t ws_bytes,
+                        hipStream_t stream);
 
 /* ------------------------------------------------------------- calibration launches (measurement only)
  * No counterpart in the reference: they exist so that bench.py can print, beside every roofline fraction against the data-sheet
