@@ -38,6 +38,18 @@ struct AttnArgs {
     float scale;                        // applied to q.k
 };
 
+// The scaled score of the f32 paths, rounded on its own.  Written as `d *= scale`, the later `d - mn` contracts to
+// fma(d, scale, -mn) (-ffp-contract=fast), which for the key that holds the running maximum (mn = round(d * scale))
+// returns the product's rounding error instead of 0: its p is exp(eps) instead of 1, l and acc pick up one rounding per
+// key, and a one-hot or uniform softmax no longer returns the V row / the mean of the V rows to the last bit (1 ulp and up
+// to 38 ulp at L = 130 were measured wherever scale or the dot product is no power of two).  The empty asm keeps the
+// product in a register of its own.
+__device__ __forceinline__ float scaled_score(float d, float scale) {
+    float s = d * scale;
+    asm volatile("" : "+v"(s));
+    return s;
+}
+
 // ------------------------------------------------------------------ f32 / generic path
 template <typename E, int D>
 __global__ void attn_rowwise_kernel(AttnArgs a) {
@@ -63,7 +75,7 @@ __global__ void attn_rowwise_kernel(AttnArgs a) {
         for (int j = 1; j < CPL; ++j) d = fmaf(qv[j], ET<E>::ld(base + (long)s * a.ld + a.kOff + cl + LPQ * j), d);
 #pragma unroll
         for (int off = LPQ / 2; off > 0; off >>= 1) d += __shfl_xor(d, off);
-        d *= a.scale;
+        d = scaled_score(d, a.scale);
         const float mn = fmaxf(m, d);
         const float alpha = __expf(m - mn);
         const float p = __expf(d - mn);
@@ -515,7 +527,7 @@ __global__ void attn_rowwise_wide_kernel(AttnArgs a, int nc) {
             if (j < nc) d = fmaf(qv[j], kr[64 * j], d);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off);
-        d *= a.scale;
+        d = scaled_score(d, a.scale);
         const float mn = fmaxf(m, d);
         const float alpha = __expf(m - mn);
         const float p = __expf(d - mn);
@@ -610,7 +622,7 @@ __global__ void temporal_attn_kernel(TAttnArgs a) {
         if (!on) d = 0.f;
 #pragma unroll
         for (int off = 1; off < G; off <<= 1) d += __shfl_xor(d, off);
-        d *= a.scale;
+        d = scaled_score(d, a.scale);
         const float mn = fmaxf(m, d);
         const float alpha = __expf(m - mn), p = __expf(d - mn);
         l = l * alpha + p;

@@ -70,8 +70,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const E* x, int xLd, lon
 
 // ---- attention with wide heads (AttnBlock.forward, codeformer.py:217-241: one head of width C = 512 over the 256
 // pixels of the 16x16 level).  A workgroup owns QT = 16 queries of one (frame, head): scores for every key in LDS
-// (thread per key, the query tile broadcast from LDS), row softmax by one wave per 4 queries, then P.V with a
-// thread per output channel (coalesced V rows).  ~0.27 GFLOP per 16x16 frame: not worth MFMA tiles.
+// (thread per key, the query tile broadcast from LDS), row maximum, exponentials and row sum by one wave per 4 queries,
+// then P.V with a thread per output channel (coalesced V rows), scaled by 1 / (row sum).  ~0.27 GFLOP per 16x16 frame: not worth MFMA tiles.
 struct WideAttn {
     const void* qkv; void* out;
     int ld, outLd, L, heads, d;
@@ -131,8 +131,11 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(WideAttn a) {
                 sc[q * a.L + k] = e;
                 s += e;
             }
-            const float inv = 1.f / wave_sum(s);
-            for (int k = lane; k < a.L; k += 64) sc[q * a.L + k] *= inv;
+            // P stays unnormalised and P.V is scaled by 1 / (row sum) once: two roundings per output instead of one per
+            // key (a uniform softmax over integer V rows gives their mean within 1 ulp).  The reciprocal goes to qs, the
+            // query tile, which nobody reads after the score pass.
+            s = wave_sum(s);
+            if (lane == 0) qs[q] = 1.f / s;
         }
     }
     __syncthreads();
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(WideAttn a) {
         }
 #pragma unroll
         for (int q = 0; q < QT; ++q)
-            if (q0 + q < a.L) ET<E>::st(ob + (long)(q0 + q) * a.outLd + c, acc[q]);
+            if (q0 + q < a.L) ET<E>::st(ob + (long)(q0 + q) * a.outLd + c, acc[q] * qs[q]);
     }
 }
 

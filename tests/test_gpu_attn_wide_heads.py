@@ -2,7 +2,9 @@
 channel-split MFMA kernel (bf16) and the row kernel (f32) behind flair_qkv_attention, the blocks at their default one
 head per layer, and a UNetModel whose widest level has d = 192 at 4096 tokens (d + L > 2048: refused before these
 kernels).  Measured errors go to parity_log; bf16 bounds are about 1.5x the largest error measured on an MI355X for
-the group of cases (relative to max|ref|), f32 bounds sit at the accumulation-order floor."""
+the group of cases (relative to max|ref|), f32 bounds sit at the accumulation-order floor.  Row clamping to L - 1, the
+masked last tile, the cross-wave exchange and the online rescale of these kernels are checked bit for bit, within 1 ulp
+and per element on inputs with a known softmax in test_gpu_attn_exact.py (all three (NW, CPW) builds)."""
 import functools
 
 import pytest

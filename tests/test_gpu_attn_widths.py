@@ -3,7 +3,9 @@
 built on them and the two models whose configurations use them (sr3.UNet's default head_dim=32, UNetModel with
 num_head_channels=32).  Measured errors go to parity_log; every bound is about 1.5x the largest error measured on an
 MI355X for its group of cases (relative to max|ref|), except the f32 spatial blocks (at the f32 accumulation floor)
-and the models (the bounds of test_gpu_sr3 / test_gpu_unet)."""
+and the models (the bounds of test_gpu_sr3 / test_gpu_unet).  These are max-norm bounds on randn data: the masked tail of
+the last KV tile, the odd and even tile counts, the online rescale and the clamped windows are checked bit for bit, within
+1 ulp and per element on inputs with a known softmax in test_gpu_attn_exact.py."""
 import pytest
 import torch
 

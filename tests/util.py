@@ -1,4 +1,6 @@
 """Helpers shared by the parity tests."""
+import math
+
 import pytest
 import torch
 
@@ -188,3 +190,312 @@ def assert_bits_equal(got, ref, what="", tile=None):
         msg += "\n  most hit (h % rows, w % cols, c % couts): " + ", ".join(
             f"({k // (cols * couts)}, {k // couts % cols}, {k % couts}): {int(cnt.flatten()[k])}" for k in top if cnt.flatten()[k] > 0)
     raise AssertionError(msg)
+
+
+# Attention with a known softmax (tests/test_gpu_attn_exact.py, tests/test_attn_exact_cpu.py).  q, k, v are float32 CPU
+# tensors of shape (frames, heads, L, d).  Three families of inputs:
+#   selection: the softmax is one-hot (every other probability is below 2^-149: nothing in f32 or bf16), so the one
+#              correct output row is a V row, bit for bit;
+#   tie:       all real keys of a query score the same bit for bit, so the output is the mean of the V rows (integers:
+#              every partial sum is exact) within one unit in the last place;
+#   staircase: the running maximum moves (or never moves) from one 32-key tile to the next; compared per element with
+#              S = sum_j p_j |v_j|, the magnitude that the roundings of p and of the accumulator act on.
+SIGNIFICAND = {torch.float32: 24, torch.bfloat16: 8, torch.float16: 11}
+MIN_NORMAL = {torch.float32: 2.0 ** -126, torch.bfloat16: 2.0 ** -126, torch.float16: 2.0 ** -14}
+
+
+def round_to(x64, dtype):
+    """float64 -> the nearest value of `dtype` (ties to even), still as float64.  One rounding: a cast through float32
+    would round twice.  Normal range only."""
+    assert x64.dtype == torch.float64
+    fin = x64[~torch.isnan(x64)].abs()
+    assert bool(((fin == 0) | ((fin >= MIN_NORMAL[dtype]) & (fin <= torch.finfo(dtype).max))).all()), "outside the normal range"
+    m, e = torch.frexp(x64)
+    p = SIGNIFICAND[dtype]
+    return torch.ldexp(torch.round(m * 2.0 ** p), e - p)
+
+
+def ordered_bits(t):
+    """The bits of a float tensor as int64 in the order of the values (sign-magnitude -> two's complement; +0 = -0 = 0):
+    neighbouring values differ by 1."""
+    b = bits(t).to(torch.int64)
+    mag = b & ((1 << (8 * t.element_size() - 1)) - 1)
+    return torch.where(b < 0, -mag, mag)
+
+
+def _hist_32_64(bad):
+    """Failing positions of a (F, 1, L, C) clip tensor by query % 32 and channel % 64."""
+    if bad.dim() != 4:
+        return ""
+    idx = bad.nonzero()
+    return (f"\n  by query % 32: {torch.bincount(idx[:, 2] % 32, minlength=32).tolist()}"
+            f"\n  by channel % 64: {torch.bincount(idx[:, 3] % 64, minlength=64).tolist()}"
+            f"\n  by frame: {torch.bincount(idx[:, 0], minlength=bad.shape[0]).tolist()}")
+
+
+def assert_within_ulps(got, ref64, n, what=""):
+    """got (float32, bfloat16 or float16) is within n units in the last place of ref64 rounded to got's type: the distance
+    is taken on the ordered integer view of the bits.  NaN on either side fails.  -> the largest distance."""
+    assert ref64.dtype == torch.float64 and got.shape == ref64.shape, (what, got.dtype, ref64.dtype, got.shape, ref64.shape)
+    got = got.detach().cpu().contiguous()
+    want = round_to(ref64.contiguous(), got.dtype).to(got.dtype)
+    nan = torch.isnan(got) | torch.isnan(want)
+    dist = (ordered_bits(got) - ordered_bits(want)).abs()
+    dist = torch.where(nan, torch.full_like(dist, 1 << 40), dist)
+    bad = dist > n
+    if bool(bad.any()):
+        first = tuple(bad.nonzero()[0].tolist())
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} element(s) more than {n} ulp from the reference "
+                             f"({int(nan.sum())} NaN); first at {list(first)}: got {got[first].item()!r}, expected "
+                             f"{want[first].item()!r} ({ref64[first].item()!r}); largest distance "
+                             f"{int(dist[~nan].max()) if bool((~nan).any()) else 'NaN'} ulp" + _hist_32_64(bad))
+    return int(dist.max())
+
+
+def assert_attn_close(got, ref64, S, bound_rel, what="", ab=0.0):
+    """|got - ref64| <= bound_rel * S (+ ab, an absolute rounding floor of the output type) for every element, S =
+    sum_j p_j |v_j| of that element (float64).  NaN fails.  -> max((err - ab) / S) / bound_rel."""
+    assert ref64.dtype == torch.float64 and S.dtype == torch.float64 and got.shape == ref64.shape == S.shape, what
+    err = (got.detach().cpu().double() - ref64).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), (err - ab).clamp_min(0.0))
+    bad = err > bound_rel * S
+    ratio = (err / S.clamp_min(1e-300)).max().item() / bound_rel
+    if bool(bad.any()):
+        worst = tuple((err / S.clamp_min(1e-300)).flatten().argmax().unsqueeze(0).tolist())
+        first = tuple(bad.nonzero()[0].tolist())
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} element(s) beyond {bound_rel:.3e} * S; largest "
+                             f"err / (bound_rel * S) = {ratio:.3f} (flat index {worst[0]}); first at {list(first)}: got "
+                             f"{got[first].item()!r}, expected {ref64[first].item()!r}, S {S[first].item():.6g}"
+                             + _hist_32_64(bad))
+    return ratio
+
+
+def sign_code(n, d):
+    """(n, d) of +-1: the bits of the row index (0 -> -1, 1 -> +1), each repeated d // ceil(log2 n) times, the remaining
+    channels +1.  Two rows differ in at least d // ceil(log2 n) channels."""
+    nb = max(1, math.ceil(math.log2(n))) if n > 1 else 1
+    rep = d // nb
+    assert rep >= 1, (n, d)
+    code = torch.ones(n, d)
+    j = torch.arange(n)
+    for b in range(nb):
+        code[:, b * rep:(b + 1) * rep] = (((j >> b) & 1).float() * 2 - 1)[:, None]
+    return code
+
+
+MARGIN = 110.0      # natural-log units: exp(-110) < 2^-149, the smallest f32 (and bf16) denormal
+
+
+def selection_strength(n, d):
+    """The smallest power of two A <= 256 at which q = A * code separates the codes of sign_code(n, d) by >= MARGIN after
+    the 1/sqrt(d) scale: rows differ in >= rep channels, each worth 2A."""
+    if n == 1:
+        return 1
+    nb = max(1, math.ceil(math.log2(n)))
+    for A in (1, 2, 4, 8, 16, 32, 64, 128, 256):
+        if 2 * A * (d // nb) / math.sqrt(d) >= MARGIN:
+            return A
+    raise AssertionError(f"no A <= 256 separates {n} codes of width {d} by {MARGIN}: shorten L")
+
+
+def _signs(shape, g):
+    return torch.randint(0, 2, tuple(shape), generator=g).float() * 2 - 1
+
+
+def attn_selection(frames, heads, L, d, g, last=False):
+    """-> q, k, v, sel: query i of every (frame, head) selects key sel[i] (a seeded permutation, or L - 1 for all with
+    `last`).  k = code * u with a sign vector u per (frame, head), q = A * code[sel] * u, v integers in [-256, 256]."""
+    u = _signs((frames, heads, 1, d), g)
+    code = sign_code(L, d)
+    if last:
+        sel = torch.full((frames, heads, L), L - 1, dtype=torch.long)
+    else:
+        sel = torch.stack([torch.randperm(L, generator=g) for _ in range(frames * heads)]).view(frames, heads, L)
+    A = selection_strength(L, d)
+    return A * code[sel] * u, (code * u).contiguous(), int_tensor((frames, heads, L, d), -256, 256, g), sel
+
+
+def attn_tie(frames, heads, L, d, g):
+    """-> q, k, v, a: every key of a (frame, head) is the sign vector u, query i is a_i * u with integer levels a_i in
+    [-64, 64] (the first three are -64, 0, 64), v integers in [0, 256].  All keys of a query tie at a_i * sqrt(d)."""
+    u = _signs((frames, heads, 1, d), g)
+    a = torch.randint(-64, 65, (frames, heads, L), generator=g).float()
+    a[..., :3] = torch.tensor([-64.0, 0.0, 64.0])[:L]
+    return a[..., None] * u, u.expand(frames, heads, L, d).contiguous(), int_tensor((frames, heads, L, d), 0, 256, g), a
+
+
+STAIRS = ("up", "down", "alt")
+
+
+def stair_levels(n, d, variant, jitter):
+    """g_j = s * step(j // 32) + jitter_j / 8 for n keys, s = round(32 * 3 / sqrt(d)) / 32 (about 3 nats per 32-key tile
+    at a = 1).  up: step = tile; down: the reverse (the maximum never moves after tile 0); alt: up on even tiles, down on
+    odd ones.  Every level is a multiple of 1/32 below 8: exact in bf16 and fp16."""
+    s32 = max(1, round(32 * 3 / math.sqrt(d)))
+    tile = torch.arange(n) // 32
+    nt = (n + 31) // 32
+    step = {"up": tile, "down": nt - 1 - tile, "alt": torch.where(tile % 2 == 0, tile, nt - 1 - tile)}[variant]
+    num = s32 * step + 4 * jitter
+    assert int(num.max()) < 256, (n, d, int(num.max()))
+    return num.float() / 32
+
+
+def attn_staircase(frames, heads, L, d, g, variant, dtype):
+    """-> q, k, v rounded through `dtype`: k_j = g_j * u, q_i = a_i * u with a_i in {1, 2}, v randn."""
+    u = _signs((frames, heads, 1, d), g)
+    jitter = torch.randint(0, 4, (frames, heads, L), generator=g)
+    lev = stair_levels(L, d, variant, jitter)
+    a = torch.randint(1, 3, (frames, heads, L), generator=g).float()
+    v = torch.randn(frames, heads, L, d, generator=g)
+    return rb(a[..., None] * u, dtype), rb(lev[..., None] * u, dtype), rb(v, dtype)
+
+
+def attn_scores64(q, k, d):
+    return q.double() @ k.double().transpose(-1, -2) / math.sqrt(d)
+
+
+def attn_ref64(q, k, v, extra_key_score=None, scale_error=0.0):
+    """float64 softmax attention of (..., L, d) tensors -> (out, S, R): S = sum_j p_j |v_j| per output element, R the
+    largest spread of one query's scores in log2 units.  The two arguments emulate kernel faults for the written record of
+    tests/test_attn_exact_cpu.py: a phantom key with this score and v = 0, a relative error of the softmax scale."""
+    s = attn_scores64(q, k, q.shape[-1]) * (1.0 + scale_error)
+    R = (s.max(-1).values - s.min(-1).values).max().item() / math.log(2.0)
+    vv = v.double()
+    if extra_key_score is not None:
+        s = torch.cat([s, torch.full_like(s[..., :1], extra_key_score)], dim=-1)
+        vv = torch.cat([vv, torch.zeros_like(vv[..., :1, :])], dim=-2)
+    p = torch.softmax(s, dim=-1)
+    return p @ vv, p @ vv.abs(), R
+
+
+def selection_margin(scores, hit):
+    """scores (..., n) float64, hit (..., n) bool (the keys a query selects; they must tie exactly): the smallest lead of
+    a selected key over the best other key, inf where there is no other."""
+    top = torch.where(hit, scores, torch.full_like(scores, float("inf"))).min(-1).values
+    assert torch.equal(top, torch.where(hit, scores, torch.full_like(scores, float("-inf"))).max(-1).values), "selected keys differ"
+    rest = torch.where(hit, torch.full_like(scores, float("-inf")), scores).max(-1).values
+    return (top - rest).min().item()
+
+
+QKV_LAYOUTS = ("legacy", "new", "vqk")
+
+
+def pack_qkv(q, k, v, layout, fill=float("nan")):
+    """(frames, heads, L, d) x 3 -> ((frames, 1, L, ld) float32, offsets): legacy = per head q | k | v, new = all q | all k |
+    all v (the two orders of qkv_attention), vqk = per head v | q | k | 8 channels of `fill` (attention_wide only)."""
+    Fr, heads, L, d = q.shape
+    if layout == "new":
+        x = torch.stack([q, k, v], dim=1)                               # Fr, 3, heads, L, d
+        x = x.permute(0, 3, 1, 2, 4).reshape(Fr, 1, L, 3 * heads * d)
+        return x.contiguous(), dict(q_off=0, k_off=heads * d, v_off=2 * heads * d, head_stride=d)
+    parts = [q, k, v] if layout == "legacy" else [v, q, k, torch.full((Fr, heads, L, 8), fill)]
+    x = torch.cat(parts, dim=-1)                                        # Fr, heads, L, 3d (+ 8)
+    hs = x.shape[-1]
+    x = x.permute(0, 2, 1, 3).reshape(Fr, 1, L, heads * hs)
+    off = dict(q_off=0, k_off=d, v_off=2 * d) if layout == "legacy" else dict(q_off=d, k_off=2 * d, v_off=0)
+    return x.contiguous(), dict(off, head_stride=hs)
+
+
+def heads_to_clip(o):
+    """(frames, heads, L, d) -> (frames, 1, L, heads * d), the layout of the attention output."""
+    Fr, heads, L, d = o.shape
+    return o.permute(0, 2, 1, 3).reshape(Fr, 1, L, heads * d).contiguous()
+
+
+# Temporal window attention: q, k, v (T, P, heads, d) over P pixels, kpos (window - 1, heads, d); slot j of frame t reads
+# frame clamp(t + off_j), off = -half .. half without 0.
+def window_frames(T, window):
+    half = window // 2
+    offs = torch.tensor([j for j in range(-half, half + 1) if j != 0])
+    return (torch.arange(T).view(T, 1) + offs.view(1, -1)).clamp(0, T - 1)       # (T, n)
+
+
+def temporal_windows(q, k, v, kpos, window, round_fp16):
+    """-> q (T, P, heads, d), kw and vw (T, n, P, heads, d) as the kernel sees them: k + kpos added in f32, then q, k + kpos
+    and v rounded through fp16 when round_fp16."""
+    idx = window_frames(q.shape[0], window)
+    kw = k[idx] + kpos[None, :, None]
+    vw = v[idx]
+    if round_fp16:
+        q, kw, vw = rb(q, torch.float16), rb(kw, torch.float16), rb(vw, torch.float16)
+    return q, kw, vw
+
+
+def temporal_scores64(q, kw):
+    return torch.einsum("tphd,tnphd->tphn", q.double(), kw.double()) / math.sqrt(q.shape[-1])
+
+
+def temporal_ref64(q, k, v, kpos, window, round_fp16=False):
+    """float64 reference of the temporal window attention -> (out, S, R) as attn_ref64."""
+    q, kw, vw = temporal_windows(q, k, v, kpos, window, round_fp16)
+    s = temporal_scores64(q, kw)
+    R = (s.max(-1).values - s.min(-1).values).max().item() / math.log(2.0)
+    p = torch.softmax(s, dim=-1)
+    return (torch.einsum("tphn,tnphd->tphd", p, vw.double()), torch.einsum("tphn,tnphd->tphd", p, vw.double().abs()), R)
+
+
+def pack_temporal(q, k, v, H, W):
+    """(T, P, heads, d) x 3 -> (T, H, W, 3C) float32: q | k | v, channel = head * d + c."""
+    T, P, heads, d = q.shape
+    assert P == H * W
+    return torch.cat([z.reshape(T, H, W, heads * d) for z in (q, k, v)], dim=-1).contiguous()
+
+
+def temporal_slot_selection(T, P, heads, d, window, g):
+    """k = 0, kpos[slot] = the sign code of the slot (rotated by the head), q = A * kpos[sigma] for a seeded slot sigma per
+    (t, pixel, head) -> q, k, v, kpos, hit (T, P, heads, n) bool, expected (T, P, heads, d) = v[clamp(t + off_sigma)]."""
+    n = window - 1
+    code = sign_code(n, d)
+    kpos = torch.stack([code[(torch.arange(n) + h) % n] for h in range(heads)], dim=1)      # n, heads, d
+    sigma = torch.randint(0, n, (T, P, heads), generator=g)
+    q = selection_strength(n, d) * kpos[sigma, torch.arange(heads).view(1, 1, heads)]
+    v = int_tensor((T, P, heads, d), -256, 256, g)
+    idx = window_frames(T, window)                                                          # T, n
+    src = idx.gather(1, sigma.reshape(T, -1)).view(T, P, heads)
+    want = v[src, torch.arange(P).view(1, P, 1), torch.arange(heads).view(1, 1, heads)]
+    hit = torch.arange(n).view(1, 1, 1, n) == sigma[..., None]
+    return q, torch.zeros_like(v), v, kpos, hit, want
+
+
+def temporal_frame_selection(T, P, heads, d, window, g):
+    """kpos = 0, k[t] = the sign code of frame t (times a sign vector per pixel and head), q selects the frame of a seeded
+    slot of its window -> q, k, v, kpos, hit (every slot that the clamp sends to that frame), expected = v[that frame]."""
+    n = window - 1
+    u = _signs((1, P, heads, d), g)
+    code = sign_code(T, d)
+    k = (code.view(T, 1, 1, d) * u).contiguous()
+    sigma = torch.randint(0, n, (T, P, heads), generator=g)
+    idx = window_frames(T, window)
+    src = idx.gather(1, sigma.reshape(T, -1)).view(T, P, heads)
+    q = selection_strength(T, d) * code[src] * u
+    v = int_tensor((T, P, heads, d), -256, 256, g)
+    want = v[src, torch.arange(P).view(1, P, 1), torch.arange(heads).view(1, 1, heads)]
+    hit = idx.view(T, 1, 1, n) == src[..., None]
+    return q, k, v, torch.zeros(n, heads, d), hit, want
+
+
+def temporal_tie(T, P, heads, d, window, g):
+    """k = u in every frame, kpos = 0, q = a * u with integer levels a in [-64, 64], v integers in [0, 256] -> q, k, v,
+    kpos, the float64 mean over the window's slots of the clamped V rows."""
+    n = window - 1
+    u = _signs((1, P, heads, d), g)
+    a = torch.randint(-64, 65, (T, P, heads), generator=g).float()
+    a.view(-1)[:3] = torch.tensor([-64.0, 0.0, 64.0])
+    v = int_tensor((T, P, heads, d), 0, 256, g)
+    want = v[window_frames(T, window)].double().sum(1) / n
+    return a[..., None] * u, u.expand(T, P, heads, d).contiguous(), v, torch.zeros(n, heads, d), want
+
+
+def temporal_staircase(T, P, heads, d, window, g, dtype):
+    """kpos[slot] = g_slot * u with g rising to the middle slots and falling again (about 3 nats per slot at a = 1),
+    k = (0, 1 or 2) / 8 * u, q = a * u with a in {1, 2}, v randn; q, k, v rounded through `dtype` (kpos stays f32)."""
+    n = window - 1
+    u = _signs((1, 1, heads, d), g)
+    s32 = max(1, round(32 * 3 / math.sqrt(d)))
+    slot = torch.arange(n)
+    lev = (s32 * torch.minimum(slot, n - 1 - slot) + 4 * torch.randint(0, 4, (n,), generator=g)).float() / 32
+    kpos = lev.view(n, 1, 1) * u[0]
+    k = torch.randint(0, 3, (T, P, heads, 1), generator=g).float() / 8 * u
+    a = torch.randint(1, 3, (T, P, heads, 1), generator=g).float()
+    v = torch.randn(T, P, heads, d, generator=g)
+    return rb(a * u, dtype), rb(k, dtype), rb(v, dtype), kpos.contiguous()
