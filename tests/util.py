@@ -499,3 +499,173 @@ def temporal_staircase(T, P, heads, d, window, g, dtype):
     a = torch.randint(1, 3, (T, P, heads, 1), generator=g).float()
     v = torch.randn(T, P, heads, d, generator=g)
     return rb(a * u, dtype), rb(k, dtype), rb(v, dtype), kpos.contiguous()
+
+
+# Normalisation kernels on inputs whose statistics are known (tests/test_gpu_norm_exact.py, tests/test_norm_exact_cpu.py).
+# x is a float32 CPU clip tensor (T, H, W, C); a statistic spans `fps` consecutive frames and the C / groups channels of a
+# group, so the (statistic, group) sets are the [:, :, g, :] slices of x.reshape(T / fps, fps * H * W, groups, C / groups).
+U24 = 2.0 ** -24            # unit roundoff of f32
+ACT_NONE, ACT_RELU, ACT_LRELU01, ACT_SILU, ACT_LRELU02, ACT_GELU = 0, 1, 2, 3, 5, 6
+ACT_LIPSCHITZ = {ACT_NONE: 1.0, ACT_RELU: 1.0, ACT_LRELU01: 1.0, ACT_LRELU02: 1.0, ACT_SILU: 1.1, ACT_GELU: 1.13}
+
+
+
+def out_rounding(ref64, dtype):
+    """What rounding a value near ref64 to `dtype` may add: nothing for f32 (its roundings are counted in units of 2^-24
+    by the callers), half a unit in the last place of ref64 for bf16 -- 2^(e - 8) for 2^e <= |ref| < 2^(e + 1), between
+    2^-9 |ref| at the top of a binade and 2^-8 |ref| at its bottom.  (2^-9 |ref| alone is not a bound: the correctly
+    rounded 1.1275 is 1.125, off by 2.3 * 2^-9.)"""
+    if dtype != torch.bfloat16:
+        return torch.zeros_like(ref64)
+    _, e = torch.frexp(ref64)                       # |ref| = m * 2^e, 0.5 <= m < 1
+    return torch.ldexp(torch.ones_like(ref64), torch.where(ref64 == 0, torch.full_like(e, -125), e).clamp_min(-125) - 9)
+
+
+assert_elem_close = assert_attn_close       # |got - ref| <= rel * S (+ ab) per element: nothing in it is about attention
+
+
+def gn_sets(x, fps, groups):
+    """(T, H, W, C) -> (T / fps, fps * H * W, groups, C / groups): a view for contiguous x."""
+    T, H, W, C = x.shape
+    assert T % fps == 0 and C % groups == 0, (x.shape, fps, groups)
+    return x.reshape(T // fps, fps * H * W, groups, C // groups)
+
+
+def gn_from_sets(s, T, H, W):
+    return s.reshape(T, H, W, s.shape[2] * s.shape[3])
+
+
+def balanced_signs(T, H, W, C, fps, groups, g):
+    """+-1, exactly half of each in every (statistic, group), placed by a seeded random permutation per set: mean 0 and
+    variance 1 in any summation order, while every proper contiguous sub-range is (almost surely) unbalanced."""
+    ns, n, cpg = T // fps, fps * H * W, C // groups
+    cnt = n * cpg
+    assert cnt % 2 == 0, (T, H, W, C, fps, groups)
+    order = torch.rand(ns, groups, cnt, generator=g).argsort(-1)
+    s = torch.ones(ns, groups, cnt)
+    s.scatter_(-1, order[..., :cnt // 2], -1.0)
+    return gn_from_sets(s.view(ns, groups, n, cpg).permute(0, 2, 1, 3), T, H, W).contiguous()
+
+
+def pow2_affine(C, g):
+    """gamma = +-1, +-2 or +-4; beta = -gamma on even channels and +gamma on odd ones: gamma * (+-1) + beta is 0 or
+    +-2 gamma."""
+    gamma = (torch.randint(0, 2, (C,), generator=g).float() * 2 - 1) * 2.0 ** torch.randint(0, 3, (C,), generator=g).float()
+    return gamma, torch.where(torch.arange(C) % 2 == 0, -gamma, gamma)
+
+
+def exact_film(T, C, ld, g):
+    """(T, ld) float32 rows scale[C] | shift[C] | NaN padding: scale in {0, 1, -0.5, 3}, shift an integer in [-3, 3]."""
+    assert ld >= 2 * C
+    film = torch.full((T, ld), float("nan"))
+    film[:, :C] = torch.tensor([0.0, 1.0, -0.5, 3.0])[torch.randint(0, 4, (T, C), generator=g)]
+    film[:, C:2 * C] = torch.randint(-3, 4, (T, C), generator=g).float()
+    return film
+
+
+def spiked_ints(T, H, W, C, fps, groups, g):
+    """Integers in [-3, 3] and, in every (statistic, group), one element of 64 at a pixel, channel and frame of its own:
+    the first and the last pixel of the statistic for the first two groups, the last pixel of the first frame and the first
+    pixel of the last frame for the next two, seeded positions for the rest.  -> x, positions (ns, groups) in the set."""
+    ns, n, cpg = T // fps, fps * H * W, C // groups
+    s = torch.randint(-3, 4, (ns, n, groups, cpg), generator=g).float()
+    pix = torch.randint(0, n, (ns, groups), generator=g)
+    edge = [0, n - 1, H * W - 1, n - H * W]
+    for j in range(min(groups, 4)):
+        pix[:, j] = edge[j]
+    ch = torch.randint(0, cpg, (ns, groups), generator=g)
+    s[torch.arange(ns)[:, None], pix, torch.arange(groups)[None, :], ch] = 64.0
+    return gn_from_sets(s, T, H, W).contiguous(), pix * cpg + ch
+
+
+def act64(v, act):
+    """The activations of apply_act in float64 (the leaky slopes are the f32 constants of the kernels)."""
+    if act == ACT_NONE:
+        return v
+    if act == ACT_RELU:
+        return v.clamp_min(0.0)
+    if act in (ACT_LRELU01, ACT_LRELU02):
+        slope = torch.tensor(0.1 if act == ACT_LRELU01 else 0.2, dtype=torch.float32).double().item()
+        return torch.where(v > 0, v, slope * v)
+    if act == ACT_SILU:
+        return v / (1.0 + torch.exp(-v))
+    if act == ACT_GELU:
+        return 0.5 * v * (1.0 + torch.erf(v * 0.7071067811865476))
+    raise ValueError(act)
+
+
+def gn_ref64(x, gamma, beta, fps, groups, eps, film=None):
+    """GroupNorm (+ FiLM) before the activation, written out in float64 -> dict of (T, H, W, C) float64 tensors:
+      pre   ((x - mean) * rstd * gamma + beta) * (1 + scale) + shift
+      S     ((|x| + |mean|) * rstd * |gamma| + |beta|) * |1 + scale| + |shift|: what the f32 roundings of the fold act on
+      slope (x - mean) * rstd * gamma * (1 + scale): the part of pre that is proportional to rstd
+    and mean, var, rstd, ex2 = E[x^2] of the element's (statistic, group)."""
+    T, H, W, C = x.shape
+    s = gn_sets(x.double(), fps, groups)
+    mean = s.mean((1, 3), keepdim=True)
+    var = (s - mean).pow(2).mean((1, 3), keepdim=True)
+    ex2 = s.pow(2).mean((1, 3), keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    full = lambda t: gn_from_sets(t.expand_as(s), T, H, W)
+    mean, var, ex2, rstd = full(mean), full(var), full(ex2), full(rstd)
+    ga, be = gamma.double(), beta.double()
+    if film is not None:
+        m = 1.0 + film[:, None, None, :C].double()
+        sh = film[:, None, None, C:2 * C].double()
+    else:
+        m, sh = torch.ones(1, 1, 1, 1, dtype=torch.float64), torch.zeros(1, 1, 1, 1, dtype=torch.float64)
+    xd = x.double()
+    slope = (xd - mean) * rstd * ga * m
+    return dict(pre=slope + be * m + sh, S=((xd.abs() + mean.abs()) * rstd * ga.abs() + be.abs()) * m.abs() + sh.abs(),
+                slope=slope, mean=mean, var=var, rstd=rstd, ex2=ex2)
+
+
+def pool2(t):
+    """2x2 mean of a (T, H, W, C) tensor."""
+    T, H, W, C = t.shape
+    return t.reshape(T, H // 2, 2, W // 2, 2, C).mean((2, 4))
+
+
+def up2(t):
+    """Nearest x2 of a (T, H, W, C) tensor."""
+    return t.repeat_interleave(2, 1).repeat_interleave(2, 2)
+
+
+def resample_ref(t, mode):
+    return t if mode == 0 else (pool2(t) if mode == 1 else up2(t))
+
+
+def layernorm_ref64(x, gamma, beta, eps):
+    """nn.LayerNorm over the last axis in float64 -> (y, S), S = (|x| + |mean|) * rstd * |gamma| + |beta|."""
+    xd = x.double()
+    mean = xd.mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt((xd - mean).pow(2).mean(-1, keepdim=True) + eps)
+    return ((xd - mean) * rstd * gamma.double() + beta.double(),
+            (xd.abs() + mean.abs()) * rstd * gamma.double().abs() + beta.double().abs())
+
+
+def adain_ref64(content, style, eps):
+    """adaptive_instance_normalization on (F, H, W, C) in float64 with the unbiased variance + eps -> (y, S),
+    S = (|c| + |mean_c|) * std_s / std_c + |mean_s|."""
+    c, s = content.double(), style.double()
+    mc, ms = c.mean((1, 2), keepdim=True), s.mean((1, 2), keepdim=True)
+    sc = torch.sqrt(c.var((1, 2), unbiased=True, keepdim=True) + eps)
+    ss = torch.sqrt(s.var((1, 2), unbiased=True, keepdim=True) + eps)
+    return (c - mc) / sc * ss + ms, (c.abs() + mc.abs()) / sc * ss + ms.abs()
+
+
+def gn_fold_f32(x, mean64, var64, gamma, beta, eps, film=None):
+    """The arithmetic of the GroupNorm kernels after their f64 statistics, step by step in float32 on the CPU: mean and
+    1 / sqrt(var + eps) cast to f32, A = gamma * rstd, B = beta - mean * A, the FiLM step, y = fma(x, A, B).  mean64 and
+    var64 are (T, H, W, C)-broadcastable float64 tensors, so a test can hand in faulty statistics.  -> float32 (T, H, W, C)
+    before the activation (the fma is emulated in float64 and rounded once)."""
+    C = x.shape[3]
+    mean = mean64.float()
+    rstd = (1.0 / torch.sqrt(var64.clamp_min(0.0) + eps)).float()
+    A = gamma.float() * rstd
+    B = beta.float() - mean * A
+    if film is not None:
+        m = 1.0 + film[:, None, None, :C]
+        A = A * m
+        B = (B.double() * m.double() + film[:, None, None, C:2 * C].double()).float()
+    return (x.double() * A.double() + B.double()).float()
