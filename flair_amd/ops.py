@@ -1144,3 +1144,45 @@ def image_metrics(a, b, out=None):
     ws = _workspace(max(nbytes, 8), a.device, tag="metrics")
     check(_lib.image_metrics(ptr(a), ptr(b), N, H, W, ptr(out), ptr(ws), nbytes), "flair_image_metrics")
     return out
+
+
+# --------------------------------------------------------------------------- SuperSloMo frame interpolation (slomo.hip)
+SLOMO_MEAN = (0.429, 0.431, 0.397)          # superslomo.py:250: the channel means of normalize()
+
+
+def slomo_coefficients(k, factor):
+    """t = k / factor and co_eff of superslomo.py:260-262 as Python doubles -> (t, [c0, c1, c2, c3])."""
+    t = k / factor
+    temp = -t * (1 - t)
+    return t, [temp, t * t, (1 - t) * (1 - t), temp]
+
+
+def slomo_warp_pack(pair, flow, coef, out=None):
+    """Stage A of one intermediate frame (flair_slomo_warp_pack): pair (B, H, W, >= 6) normalised i0 | i1, flow (B, H, W, >= 4)
+    f01 | f10, coef the four doubles of slomo_coefficients -> the interpolation UNet's input, (B, H, W, pad_channels(20))
+    with zeros in the pad channels; out: optional view of that shape."""
+    B, H, W, _ = pair.shape
+    assert flow.dtype == pair.dtype and tuple(flow.shape[:3]) == (B, H, W)
+    oc = pad_channels(20, pair.dtype)
+    if out is None:
+        out = torch.empty((B, H, W, oc), dtype=pair.dtype, device=pair.device)
+    assert tuple(out.shape) == (B, H, W, oc) and out.dtype == pair.dtype
+    c = [ctypes.c_float(v) for v in coef]
+    check(lib().flair_slomo_warp_pack(ptr(pair), _ld(pair), ptr(flow), _ld(flow), dtype_code(pair), B, H, W, *c, ptr(out),
+                                      _ld(out), oc, stream()), "flair_slomo_warp_pack")
+    return out
+
+
+def slomo_blend(pair, flow, io, coef, t, out, mean=SLOMO_MEAN):
+    """Stage B of one intermediate frame (flair_slomo_blend): io (B, H, W, >= 5) is the interpolation UNet's output; out: a
+    (B, 3, H, W) f32 view whose frames are dense, e.g. slot [:, k] of the (B, factor - 1, 3, H, W) result."""
+    B, H, W, _ = pair.shape
+    assert flow.dtype == pair.dtype and io.dtype == pair.dtype
+    assert tuple(flow.shape[:3]) == (B, H, W) and tuple(io.shape[:3]) == (B, H, W)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out[0].is_contiguous()
+    c = [ctypes.c_float(v) for v in coef]
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    check(lib().flair_slomo_blend(ptr(pair), _ld(pair), ptr(flow), _ld(flow), ptr(io), _ld(io), dtype_code(pair), B, H, W, *c,
+                                  ctypes.c_double(t), m, ptr(out), ctypes.c_long(out.stride(0) if B > 1 else 3 * H * W),
+                                  stream()), "flair_slomo_blend")
+    return out

@@ -74,6 +74,8 @@ CODEFORMER_FILE = "codeformer.pth"
 # project's release name; guided_diffusion/restoreformer.py of the reference)
 PRIOR_FILES = {"codeformer": CODEFORMER_FILE, "restoreformer": "RestoreFormer.ckpt", "vqfrv2": "VQFR_v2.pth"}
 PRIOR_LABELS = {"codeformer": "CodeFormer", "restoreformer": "RestoreFormer", "vqfrv2": "VQFR"}
+# frame interpolation (flair_amd.interpolate): the published SuperSloMo checkpoint, or the flat state dict of the reference module
+INTERPOLATOR_FILES = {"superslomo": "SuperSloMo.ckpt"}
 # VQFRv2's constructor arguments in the VQFR project's published v2 release configuration (its options file for VQFR v2:
 # base_channels 64, channel_multipliers [1, 2, 2, 4, 4, 8], two encoder and two decoder blocks with attention, code_dim
 # 256, inpfeat_dim 32, align_opt cond_channels 32 / deformable_groups 4, "Predict" code selection).  The reference tree

@@ -596,6 +596,32 @@ int flair_letterbox_nhwc(const float* src, int B, int H, int W, int new_h, int n
                          float a, float b, float lo, float hi, float s, float pad_value, float* y, int y_ld,
                          hipStream_t stream);
 
+/* ------------------------------------------------------------- SuperSloMo frame interpolation (guided_diffusion/superslomo.py)
+ * The per-timestep tail of SuperSloMo.forward around the interpolation UNet; everything else of the network is
+ * flair_conv_nhwc (FLAIR_ACT_LRELU01) and flair_resize_nhwc (modes 0 and 3).  Both entries use the reference's back_warp
+ * (superslomo.py:225-247), which is NOT flair_flow_warp's convention: x = w + u, gx = 2 (x / W - 0.5), then F.grid_sample with
+ * its defaults (bilinear, zeros padding, align_corners=False), i.e. ix = ((gx + 1) W - 1) / 2: the sample sits half a pixel
+ * up-left of w + u, and corners outside the frame contribute zero.  f32 arithmetic in the reference's order of operations.
+ * Clip tensors [B][H][W][ld] in the activation dtype (F32 / BF16), any H, W >= 1:
+ *   pair: the normalised frames ((frame + 1) / 2 - mean), i0 in channels 0-2, i1 in 3-5;
+ *   flow: the flow UNet's output, f01 in channels 0-1, f10 in 2-3, each (u, v) in pixels;
+ *   strides: every *_ld at least the channels named and a multiple of 16 bytes, every pointer 16-byte aligned (FLAIR_ERR_ARG
+ *            naming the argument otherwise); a clip of B H W ld elements spans < 2 GiB.
+ *
+ * flair_slomo_warp_pack, stage A (:260-270): ft0 = c0 f01 + c1 f10, ft1 = c2 f01 + c3 f10 and
+ *   out[p] = (i0, i1, f01, f10, ft1, ft0, back_warp(i1, ft1), back_warp(i0, ft0)), 20 channels in the reference's torch.cat
+ *   order, zeros in channels 20 .. out_c - 1 (out_c: 20 .. 32, a multiple of 16 bytes: the padded input of interp.conv1). */
+int flair_slomo_warp_pack(const void* pair, int pair_ld, const void* flow, int flow_ld, int dtype, int B, int H, int W,
+                          float c0, float c1, float c2, float c3, void* out, int out_ld, int out_c, hipStream_t stream);
+/* flair_slomo_blend, stage B (:273-287): io is the interpolation UNet's output (>= 5 channels); ft0 and ft1 are recomputed
+ *   from the flows; ft0f = io[0:2] + ft0, ft1f = io[2:4] + ft1, v0 = sigmoid(io[4]), v1 = 1 - v0, g0 = back_warp(i0, ft0f),
+ *   g1 = back_warp(i1, ft1f), out = (((1 - t) v0 g0 + t v1 g1) / ((1 - t) v0 + t v1) + mean[c]) * 2 - 1 with 1 - t taken in
+ *   double (0 < t < 1).  mean: HOST array of 3 floats.  out: f32 NCHW, frame b at out + b * out_batch_stride (>= 3 H W
+ *   floats), so a call fills slot [:, k] of a (B, factor - 1, 3, H, W) tensor. */
+int flair_slomo_blend(const void* pair, int pair_ld, const void* flow, int flow_ld, const void* io, int io_ld, int dtype,
+                      int B, int H, int W, float c0, float c1, float c2, float c3, double t, const float* mean, float* out,
+                      long out_batch_stride, hipStream_t stream);
+
 /* ------------------------------------------------------------- multi-GPU start-up
  * The only collective of the path: in-place RCCL broadcast of the kernel-native weight blob (flair_amd.checkpoint.export_packed:
  * bf16 [Cout][taps][Cin] conv weights, batched embedding matrix, f32 biases ...) from `root` to every rank of `rccl_comm`
