@@ -2,7 +2,7 @@
 ends of the loop around it: ``degrade TASK CLEAN_DIR OUT_DIR`` makes a task's degraded frames from clean ones with the exact
 operator the restoration assumes (flair_amd.degrade), and ``evaluate RESTORED_DIR TRUTH_DIR`` scores written frames with PSNR
 and SSIM (flair_amd.metrics); ``restore --ground-truth DIR`` scores every video as soon as it is written.
-``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo (flair_amd.interpolate).
+``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo or AMT-G (flair_amd.interpolate).
 
 The options of the reference's ``main()`` keep their names and defaults (``scripts/video_sample.py:249-263``); the
 presets are its ``x8_bicubic_demo`` ... ``jpeg_demo`` commands (:500-556).  Several videos go through one call with
@@ -94,12 +94,15 @@ def make_parser():
     e.add_argument("truth_dir", metavar="TRUTH_DIR", help="frames are paired with RESTORED_DIR's in natural order")
     e.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the means as JSON")
     e.add_argument("--device", default=None, help="default: cuda")
-    i = sub.add_parser("interpolate", help="factor - 1 new frames between every two frames of a video (SuperSloMo)")
+    i = sub.add_parser("interpolate", help="factor - 1 new frames between every two frames of a video (SuperSloMo or AMT-G)")
     i.add_argument("src_dir", metavar="SRC_DIR", help="frames of one size")
     i.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png, factor * (T - 1) + 1 of them")
     i.add_argument("--factor", type=int, required=True, metavar="N", help="frame-rate multiplier, >= 2")
-    i.add_argument("--weights", default="./checkpoints", metavar="DIR", help="directory with SuperSloMo.ckpt")
-    i.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
+    i.add_argument("--interpolator", choices=("superslomo", "amt-g"), default="superslomo",
+                   help="the network: SuperSloMo (default) or AMT-G (fp32 only; frames whose coarsest correlation level is "
+                        "at least 2x2 or exactly 1x1)")
+    i.add_argument("--weights", default="./checkpoints", metavar="DIR", help="directory with SuperSloMo.ckpt / amt-g.pth")
+    i.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="bf16: SuperSloMo only")
     i.add_argument("--device", default=None, help="default: cuda")
     i.add_argument("--ground-truth", default=None, metavar="DIR",
                    help="frames at the new rate: score the written frames against them (PSNR / SSIM)")
@@ -111,7 +114,8 @@ def interpolate_of(args):
     """The refusals of a parsed ``interpolate`` command line, before any GPU work -> the frame paths."""
     from . import interpolate as fi
     try:
-        paths, _ = fi.check_source(args.src_dir, args.factor)
+        paths, size = fi.check_source(args.src_dir, args.factor)
+        fi.check_interpolator(args.interpolator, args.dtype, size)
     except ValueError as exc:
         raise SystemExit(f"interpolate: {exc}")
     if args.json and not args.ground_truth:
@@ -128,7 +132,7 @@ def _interpolate(args):
     torch.set_grad_enabled(False)
     device = args.device or "cuda"
     try:
-        net = fi.load_interpolator(args.weights, device, args.dtype)
+        net = fi.load_interpolator(args.weights, device, args.dtype, name=args.interpolator)
         n = fi.interpolate_video_files(args.src_dir, args.out_dir, args.factor, net=net, device=device)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"interpolate: {exc}")

@@ -1,11 +1,12 @@
 """Change the frame rate of a video: ``python -m flair_amd interpolate SRC_DIR OUT_DIR --factor N``.
 
-The reference ships the network (``guided_diffusion/superslomo.py``) and no driver for it; this is the driver.  Every pair of
-neighbouring frames gets ``factor - 1`` frames between them from ``SuperSloMo`` on the HIP kernels, so ``T`` frames become
-``factor * (T - 1) + 1``.  The original frames pass through untouched: files are written from their decoded bytes.
+The reference ships the networks (``guided_diffusion/superslomo.py``, ``guided_diffusion/amt.py``) and no driver for them;
+this is the driver.  Every pair of neighbouring frames gets ``factor - 1`` frames between them from ``SuperSloMo`` (the
+default) or ``AMT`` (``--interpolator amt-g``) on the HIP kernels, so ``T`` frames become ``factor * (T - 1) + 1``.  The
+original frames pass through untouched: files are written from their decoded bytes.
 
-The interface leaves room for a second interpolator: ``load_interpolator`` returns any module with
-``forward(frame0, frame1, factor) -> (B, factor - 1, 3, H, W)`` on frames in [-1, 1] and a ``MULTIPLE`` attribute.
+``load_interpolator`` returns a module with ``forward(frame0, frame1, factor) -> (B, factor - 1, 3, H, W)`` on frames in
+[-1, 1] and a ``MULTIPLE`` attribute (32 for SuperSloMo; 1 for AMT, which pads to multiples of 16 itself, centred).
 """
 import os
 
@@ -16,6 +17,36 @@ from . import io as fio
 from . import pipeline as pl
 
 _PARTS = (("state_dictFC", "flow_estimator."), ("state_dictAT", "interp."))
+# name -> checkpoint file under the weights directory
+INTERPOLATORS = {**pl.INTERPOLATOR_FILES, **pl.AMT_INTERPOLATOR_FILES}
+
+
+def amt_state_dict(obj, what="checkpoint"):
+    """The two forms of an AMT checkpoint -> the flat state dict of the module: the published file's {"state_dict": ...}
+    (what the reference's ``AMT(pretrained=...)`` loads), or the flat dict itself."""
+    if not isinstance(obj, dict):
+        raise ValueError(f"{what}: not a state dict")
+    if "state_dict" in obj:
+        obj = obj["state_dict"]
+        if not isinstance(obj, dict):
+            raise ValueError(f"{what}: holds no state dict under state_dict")
+    if not all(isinstance(v, torch.Tensor) for v in obj.values()):
+        raise ValueError(f"{what}: not a tensor state dict")
+    return obj
+
+
+def check_interpolator(name, dtype="fp32", size=None):
+    """What an interpolator refuses, before any GPU work: its name, its dtype and (AMT) the frame size (h, w)."""
+    if name not in INTERPOLATORS:
+        raise ValueError(f"interpolator={name!r}: one of {', '.join(INTERPOLATORS)}")
+    if dtype not in ("fp32", "bf16"):
+        raise ValueError(f"dtype={dtype!r}: fp32 or bf16")
+    if name == "amt-g":
+        from .guided_diffusion import amt
+        if dtype != "fp32":
+            raise ValueError("interpolator='amt-g' runs in fp32 only (--dtype bf16 is SuperSloMo's)")
+        if size is not None and not amt.supported_size(*size)[0]:
+            raise ValueError(amt.size_error(*size))
 
 
 def superslomo_state_dict(obj, what="checkpoint"):
@@ -44,22 +75,23 @@ def load_state(net, sd, what="checkpoint"):
     if unexpected or missing or shapes:
         parts = [f"{name}: {', '.join(keys)}" for name, keys in (("unexpected keys", unexpected), ("missing keys", missing),
                                                                 ("shapes", shapes)) if keys]
-        raise ValueError(f"{what} does not fit SuperSloMo; " + "; ".join(parts))
+        raise ValueError(f"{what} does not fit {type(net).__name__}; " + "; ".join(parts))
     net.load_state_dict(sd, strict=True)
     return net
 
 
 def load_interpolator(weights_dir, device, dtype="fp32", name="superslomo"):
-    """SuperSloMo with ``weights_dir/SuperSloMo.ckpt`` on ``device``; dtype "fp32" (default) or "bf16"."""
-    from .guided_diffusion.superslomo import SuperSloMo
-    if name not in pl.INTERPOLATOR_FILES:
-        raise ValueError(f"interpolator={name!r}: one of {', '.join(pl.INTERPOLATOR_FILES)}")
-    if dtype not in ("fp32", "bf16"):
-        raise ValueError(f"dtype={dtype!r}: fp32 or bf16")
-    path = os.path.join(str(weights_dir), pl.INTERPOLATOR_FILES[name])
+    """``name`` "superslomo": SuperSloMo with ``weights_dir/SuperSloMo.ckpt``, dtype "fp32" (default) or "bf16";
+    "amt-g": AMT with ``weights_dir/amt-g.pth``, fp32 only.  On ``device``, eval mode."""
+    check_interpolator(name, dtype)
+    path = os.path.join(str(weights_dir), INTERPOLATORS[name])
     if not os.path.isfile(path):
         raise FileNotFoundError(f"{path} not found")
     obj = torch.load(path, map_location="cpu", weights_only=True)
+    if name == "amt-g":
+        from .guided_diffusion.amt import AMT
+        return load_state(AMT(), amt_state_dict(obj, path), path).eval().to(device)
+    from .guided_diffusion.superslomo import SuperSloMo
     net = load_state(SuperSloMo(), superslomo_state_dict(obj, path), path).eval().to(device)
     return net.convert_to_bf16() if dtype == "bf16" else net
 

@@ -1186,3 +1186,162 @@ def slomo_blend(pair, flow, io, coef, t, out, mean=SLOMO_MEAN):
                                   ctypes.c_double(t), m, ptr(out), ctypes.c_long(out.stride(0) if B > 1 else 3 * H * W),
                                   stream()), "flair_slomo_blend")
     return out
+
+
+# --------------------------------------------------------------------------- AMT-G frame interpolation (amt.hip)
+CORR_TAPS = 49                              # (2 * 3 + 1) ** 2: AMT's lookup radius
+
+
+def corr_volume(fa, fb_nchw, out=None):
+    """BidirCorrBlock.corr (raft.py:201-209): fa (B, h, w, D) NHWC features of one frame, fb_nchw (B, D, h, w) the other
+    frame's features channel-major -> (B * h * w, h, w) planes of fa^T fb / sqrt(D): flair_matmul_f32, then the division
+    in place (flair_corr_scale)."""
+    B, h, w, D = fa.shape
+    assert tuple(fb_nchw.shape) == (B, D, h, w)
+    vol = matmul(fa.reshape(B, h * w, D), fb_nchw.reshape(B, D, h * w), out=None if out is None else out.view(B, h * w, h * w))
+    div = float(torch.sqrt(torch.tensor(D).float()))
+    check(lib().flair_corr_scale(ptr(vol), ctypes.c_long(vol.numel()), ctypes.c_float(div), stream()), "flair_corr_scale")
+    return vol.view(B * h * w, h, w)
+
+
+def corr_pool(vol, out=None):
+    """F.avg_pool2d(vol, 2, stride=2) of (planes, h, w) f32 planes (flair_corr_pool); odd sizes floor."""
+    P, h, w = vol.shape
+    assert vol.dtype == torch.float32 and vol.is_contiguous()
+    if h < 2 or w < 2:
+        raise ValueError(f"corr_pool: planes of {h}x{w} hold no 2x2 window")
+    if out is None:
+        out = torch.empty((P, h // 2, w // 2), dtype=torch.float32, device=vol.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (P, h // 2, w // 2)
+    check(lib().flair_corr_pool(ptr(vol), ctypes.c_long(P), h, w, ptr(out), stream()), "flair_corr_pool")
+    return out
+
+
+def corr_lookup(pyramid, pyramid_t, flow, scale_corr, scale_corr_t, out):
+    """BidirCorrBlock.__call__ on coord + flow1 * scale_corr (pyramid) and coord + flow0 * scale_corr_t (pyramid_t)
+    (flair_corr_lookup): the pyramids are lists of (B * h * w, lh, lw) f32 volumes, flow (B, h, w, >= 4) f32 flow0 | flow1,
+    out a (B, h, w, >= 98 * levels) f32 clip view whose first 98 * levels channels are written: corr | corr_T."""
+    B, h, w, _ = flow.shape
+    n = len(pyramid)
+    assert len(pyramid_t) == n and flow.dtype == torch.float32 and out.dtype == torch.float32
+    assert tuple(out.shape[:3]) == (B, h, w) and out.shape[3] >= 2 * CORR_TAPS * n
+    for v in list(pyramid) + list(pyramid_t):
+        assert v.dtype == torch.float32 and v.is_contiguous() and v.dim() == 3 and v.shape[0] == B * h * w, tuple(v.shape)
+    for a, b in zip(pyramid, pyramid_t):
+        assert a.shape == b.shape
+    pa = (ctypes.c_void_p * n)(*[v.data_ptr() for v in pyramid])
+    pb = (ctypes.c_void_p * n)(*[v.data_ptr() for v in pyramid_t])
+    lh = (ctypes.c_int * n)(*[v.shape[1] for v in pyramid])
+    lw = (ctypes.c_int * n)(*[v.shape[2] for v in pyramid])
+    e0 = _prof_begin()
+
+    def launch(_keep=(pyramid, pyramid_t)):
+        check(lib().flair_corr_lookup(pa, pb, lh, lw, n, ptr(flow), _ld(flow), B, h, w, ctypes.c_float(scale_corr),
+                                      ctypes.c_float(scale_corr_t), ptr(out), _ld(out), stream()), "flair_corr_lookup")
+    launch()
+    if e0 is not None:      # algorithmic bytes: an 8 x 8 patch per level and direction read, 98 floats per level written
+        _prof_end(e0, ("corr_lookup",), torch.float32, 2.0 * 7 * B * h * w * 2 * n * CORR_TAPS,
+                  4.0 * B * h * w * (2 * n * (64 + CORR_TAPS) + 4), launch, ("corr_lookup", B, h, w, n))
+    return out
+
+
+def prelu(x0, slope, x1=None, out=None):
+    """prelu(x0 (+ x1), slope[c]) on f32 clip tensors (flair_prelu_nhwc); slope: (>= C,) f32; out may be x0."""
+    T, H, W, C = x0.shape
+    assert x0.dtype == torch.float32 and slope.dtype == torch.float32 and slope.is_contiguous() and slope.numel() >= C
+    assert x1 is None or (x1.dtype == torch.float32 and x1.shape == x0.shape)
+    if out is None:
+        out = torch.empty((T, H, W, C), dtype=torch.float32, device=x0.device)
+    assert out.dtype == torch.float32 and out.shape == x0.shape
+    check(lib().flair_prelu_nhwc(ptr(x0), _ld(x0), ptr(x1), _ld(x1) if x1 is not None else 0, ptr(slope), C,
+                                 ctypes.c_long(T * H * W), ptr(out), _ld(out), stream()), "flair_prelu_nhwc")
+    return out
+
+
+def depth_to_space2(x, C, out=None):
+    """(F, H, W, >= 4 C) f32, channels parity-major -> (F, 2 H, 2 W, C) (flair_depth_to_space2_nhwc)."""
+    F_, H, W, Cx = x.shape
+    assert x.dtype == torch.float32 and Cx >= 4 * C
+    if out is None:
+        out = torch.empty((F_, 2 * H, 2 * W, C), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape[:3]) == (F_, 2 * H, 2 * W) and out.shape[3] >= C
+    check(lib().flair_depth_to_space2_nhwc(ptr(x), _ld(x), F_, H, W, C, ptr(out), _ld(out), stream()),
+          "flair_depth_to_space2_nhwc")
+    return out
+
+
+def deconv_as_conv3x3(w, b, cpad=None):
+    """nn.ConvTranspose2d(Cin, Cout, 4, 2, 1) as a 3x3 convolution with 4 * cpad outputs (host-side, once per load).
+    Output pixel (2 m + py, 2 n + px) sums input pixels (m + dy, n + dx), dy in {py - 1, py}, dx in {px - 1, px}, through
+    kernel tap (py + 1 - 2 dy, px + 1 - 2 dx); parity (py, px) takes output channels [(2 py + px) cpad, ... + Cout) and the 3x3
+    taps it does not use are zero (9/4 of the products; depth_to_space2 undoes the channel layout).
+    w: (Cin, Cout, 4, 4), b: (Cout,) or None -> (4 cpad, Cin, 3, 3), (4 cpad,); cpad: Cout rounded up to a multiple of 4."""
+    cin, cout, kh, kw = w.shape
+    assert (kh, kw) == (4, 4), "deconv_as_conv3x3 restates ConvTranspose2d(kernel 4, stride 2, padding 1) only"
+    cpad = cpad or (cout + 3) // 4 * 4
+    w3 = w.new_zeros(4 * cpad, cin, 3, 3)
+    b3 = w.new_zeros(4 * cpad)
+    for py in (0, 1):
+        for px in (0, 1):
+            o = (2 * py + px) * cpad
+            for dy in (py - 1, py):
+                for dx in (px - 1, px):
+                    w3[o:o + cout, :, dy + 1, dx + 1] = w[:, :, py + 1 - 2 * dy, px + 1 - 2 * dx].t()
+            if b is not None:
+                b3[o:o + cout] = b
+    return w3, b3
+
+
+def axpby_nhwc(x0, a, x1=None, b=0.0, out=None):
+    """a * x0 + b * x1 on f32 clip views (flair_axpby_nhwc), products rounded before the sum; out may be x0 or x1."""
+    T, H, W, C = x0.shape
+    assert x0.dtype == torch.float32 and (x1 is None or (x1.dtype == torch.float32 and x1.shape == x0.shape))
+    if out is None:
+        out = torch.empty((T, H, W, C), dtype=torch.float32, device=x0.device)
+    assert out.dtype == torch.float32 and out.shape == x0.shape
+    check(lib().flair_axpby_nhwc(ptr(x0), _ld(x0), ctypes.c_float(a), ptr(x1), _ld(x1) if x1 is not None else 0,
+                                 ctypes.c_float(b), C, ctypes.c_long(T * H * W), ptr(out), _ld(out), stream()), "flair_axpby_nhwc")
+    return out
+
+
+def amt_multiflow_prepare(dec, up, out=None):
+    """MultiFlowDecoder.forward behind its convblock (flair_amt_multiflow_prepare): dec (B, H, W, >= 40), up (B, H, W, >= 4)
+    -> (B, H, W, 40) final flows | sigmoid mask | img_res."""
+    B, H, W, _ = dec.shape
+    assert dec.dtype == torch.float32 and up.dtype == torch.float32 and tuple(up.shape[:3]) == (B, H, W)
+    if out is None:
+        out = torch.empty((B, H, W, 40), dtype=torch.float32, device=dec.device)
+    check(lib().flair_amt_multiflow_prepare(ptr(dec), _ld(dec), ptr(up), _ld(up), ctypes.c_long(B * H * W), ptr(out), _ld(out),
+                                            stream()), "flair_amt_multiflow_prepare")
+    return out
+
+
+def amt_multiflow_combine(pair, prep, neg_mean, x=None, avg=None):
+    """multi_flow_combine up to comb_block (flair_amt_multiflow_combine): pair (B, H, W, >= 6) mean-free frames, prep
+    (B, H, W, >= 40), neg_mean (B, >= 1) f32 -> x (B, H, W, 16) comb_block's input, avg (B, H, W, 4) the mean prediction."""
+    B, H, W, _ = pair.shape
+    assert pair.dtype == torch.float32 and prep.dtype == torch.float32 and tuple(prep.shape[:3]) == (B, H, W)
+    assert neg_mean.dtype == torch.float32 and neg_mean.shape[0] == B and neg_mean.stride(1) == 1
+    if x is None:
+        x = torch.empty((B, H, W, 16), dtype=torch.float32, device=pair.device)
+    if avg is None:
+        avg = torch.empty((B, H, W, 4), dtype=torch.float32, device=pair.device)
+    check(lib().flair_amt_multiflow_combine(ptr(pair), _ld(pair), ptr(prep), _ld(prep), ptr(neg_mean), neg_mean.stride(0), B, H, W,
+                                            ptr(x), _ld(x), ptr(avg), _ld(avg), stream()), "flair_amt_multiflow_combine")
+    return x, avg
+
+
+def instance_norm(x, act=ACT_NONE, eps=1e-5, out=None):
+    """nn.InstanceNorm2d (no affine) + activation (none or ReLU) on an f32 clip tensor (flair_instnorm_nhwc)."""
+    F_, H, W, C = x.shape
+    assert x.dtype == torch.float32
+    if out is None:
+        out = torch.empty((F_, H, W, C), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape == x.shape
+    f = lib().flair_instnorm_workspace_bytes
+    f.restype = ctypes.c_size_t
+    nbytes = int(f(F_, H, W, C))
+    ws = _workspace(nbytes, x.device, "instnorm")
+    check(lib().flair_instnorm_nhwc(ptr(x), _ld(x), F_, H, W, C, ctypes.c_double(eps), act, ptr(out), _ld(out), ptr(ws),
+                                    ctypes.c_size_t(nbytes), stream()), "flair_instnorm_nhwc")
+    return out

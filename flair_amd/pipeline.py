@@ -76,6 +76,8 @@ PRIOR_FILES = {"codeformer": CODEFORMER_FILE, "restoreformer": "RestoreFormer.ck
 PRIOR_LABELS = {"codeformer": "CodeFormer", "restoreformer": "RestoreFormer", "vqfrv2": "VQFR"}
 # frame interpolation (flair_amd.interpolate): the published SuperSloMo checkpoint, or the flat state dict of the reference module
 INTERPOLATOR_FILES = {"superslomo": "SuperSloMo.ckpt"}
+# the second interpolator, AMT-G: the file the reference's authors load, {"state_dict": ...} (or the flat state dict)
+AMT_INTERPOLATOR_FILES = {"amt-g": "amt-g.pth"}
 # VQFRv2's constructor arguments in the VQFR project's published v2 release configuration (its options file for VQFR v2:
 # base_channels 64, channel_multipliers [1, 2, 2, 4, 4, 8], two encoder and two decoder blocks with attention, code_dim
 # 256, inpfeat_dim 32, align_opt cond_channels 32 / deformable_groups 4, "Predict" code selection).  The reference tree

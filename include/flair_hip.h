@@ -66,7 +66,10 @@ const char* flair_last_error(void);
  * 12: + flair_warp_affine_cubic_indexed, flair_face_paste (several faces per frame, frames without a face);
  * 13: + flair_maxpool2x2s2_nhwc, flair_spp_maxpool_nhwc, flair_channel_interleave_nhwc, flair_yolo_face_decode,
  *     flair_letterbox_nhwc (the YOLOv5-face detectors); 14: + flair_jpeg_roundtrip_hw (rectangular frames);
- * 15: + flair_image_metrics_workspace, flair_image_metrics (PSNR / SSIM of written frames)).
+ * 15: + flair_image_metrics_workspace, flair_image_metrics (PSNR / SSIM of written frames);
+ * 16: + flair_slomo_warp_pack, flair_slomo_blend (SuperSloMo); 17: + flair_corr_scale, flair_corr_pool, flair_corr_lookup,
+ *     flair_prelu_nhwc, flair_depth_to_space2_nhwc, flair_axpby_nhwc,
+ *     flair_amt_multiflow_prepare, flair_amt_multiflow_combine, flair_instnorm_workspace_bytes, flair_instnorm_nhwc (AMT-G)).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -622,6 +625,80 @@ int flair_slomo_blend(const void* pair, int pair_ld, const void* flow, int flow_
                       int B, int H, int W, float c0, float c1, float c2, float c3, double t, const float* mean, float* out,
                       long out_batch_stride, hipStream_t stream);
 
+/* ------------------------------------------------------------- AMT-G frame interpolation (amt.hip)
+ * What guided_diffusion/amt.py and amt_blocks/ need beyond convolutions, resizes and flair_flow_warp (border).  All f32.
+ *
+ * The correlation volume (raft.py:142-163, :201-209).  BidirCorrBlock.corr is fmap1^T fmap2 / sqrt(dim): the product is
+ * flair_matmul_f32 on the NHWC feature map of one frame and the NCHW copy of the other (corr), and once more with the two
+ * frames swapped (corr_T: no permuted copy), each followed by flair_corr_scale, a true division in place (n floats at x,
+ * 16-byte aligned; divisor positive and finite).  A volume is B h w planes of h x w floats, dense; flair_corr_pool makes the
+ * next pyramid level, F.avg_pool2d(., 2, stride=2) per plane: dst is planes x (h / 2) x (w / 2), odd sizes floor, h, w >= 2;
+ * ((a + b) + c) + d in row-major order, times 1/4.  64-bit offsets; src, dst 4-byte aligned. */
+int flair_corr_scale(float* x, long n, float divisor, hipStream_t stream);
+int flair_corr_pool(const float* src, long planes, int h, int w, float* dst, hipStream_t stream);
+/* BidirCorrBlock.__call__ (raft.py:165-199) on the coordinates of AMT._corr_scale_lookup (amt.py:98-111), radius 3.
+ *   corr, corr_t : HOST arrays of `levels` (1 .. 4) device pointers, level l of each direction: B h w planes of
+ *                  level_h[l] x level_w[l] floats (HOST int arrays), plane q belonging to query pixel q of the [B][h][w] grid.
+ *                  A level is either >= 2 on both sides (sampled) or 1 x 1 (its value goes to all 49 taps, raft.py:186-188);
+ *                  FLAIR_ERR_ARG on any other size, where the reference raises.
+ *   flow         : [B][h][w] pixels of (flow0.x, flow0.y, flow1.x, flow1.y), flow_ld floats apart.
+ *   out          : [B][h][w] pixels, out_ld floats apart; channels [0, 49 levels) receive corr sampled around
+ *                  (x, y) + flow1 * scale_corr, channels [49 levels, 98 levels) corr_t around (x, y) + flow0 * scale_corr_t
+ *                  (scale_corr = 1 / t, scale_corr_t = 1 / (1 - t) in the reference), level-major, tap 7 a + b of a level at
+ *                  centre / 2^l + (a - 3, b - 3): the first tap axis moves x (raft.py:177-184).  Nothing else is written,
+ *                  so out may be the 392-channel head of convc1's zero-padded 400-channel input segment.
+ *   Bilinear, align_corners=True, zeros outside the plane; each coordinate step rounded to f32 as in the reference; the
+ *   pixel -> [-1, 1] -> pixel round trip of bilinear_sampler is the identity and is not repeated (integer coordinates return
+ *   volume entries bit for bit).  Coordinates must be finite.
+ *   strides: flow_ld >= 4 and a multiple of 4 floats, flow 16-byte aligned; out_ld >= 98 levels, out and the planes 4-byte
+ *            aligned (the results leave as 4-byte stores, 49 consecutive ones per wave and level); FLAIR_ERR_ARG naming the
+ *            argument otherwise; 64-bit offsets, at most 2^31 workgroups of two queries. */
+int flair_corr_lookup(const float* const* corr, const float* const* corr_t, const int* level_h, const int* level_w, int levels,
+                      const float* flow, int flow_ld, int B, int h, int w, float scale_corr, float scale_corr_t, float* out,
+                      int out_ld, hipStream_t stream);
+/* y = prelu(x0 (+ x1), slope[c]) = v > 0 ? v : slope[c] v on P pixels of C channels: nn.PReLU(C) behind a convolution
+ * (ifrnet.py:10-14) and ResBlock's prelu(x + out) (:52).  x1 may be NULL; y may be x0 or x1 (each thread reads what it
+ * writes).  A separate launch on purpose: the convolution epilogues stay as they are.
+ *   strides: C a multiple of 4; x0_ld / x1_ld / y_ld at least C and multiples of 4 floats; x0, x1, y, slope 16-byte aligned. */
+int flair_prelu_nhwc(const float* x0, int x0_ld, const float* x1, int x1_ld, const float* slope, int C, long P, float* y,
+                     int y_ld, hipStream_t stream);
+/* x [F][H][W][4 C] -> y [F][2 H][2 W][C]: y(2 m + py, 2 n + px, c) = x(m, n, (2 py + px) C + c).  With the host-side repack
+ * of a ConvTranspose2d(4, 2, 1) weight into a 3 x 3 convolution of 4 C outputs (flair_amd.ops.
+ * deconv_as_conv3x3) this is nn.ConvTranspose2d(Cin, C, 4, 2, 1) of ifrnet.py:84, :100 and multi_flow.py:65.
+ *   strides: C a multiple of 4; x_ld >= 4 C, y_ld >= C, multiples of 4 floats; x, y 16-byte aligned. */
+int flair_depth_to_space2_nhwc(const float* x, int x_ld, int F, int H, int W, int C, float* y, int y_ld, hipStream_t stream);
+
+/* y = a x0 + b x1 on P pixels of C channels (x1 may be NULL: y = a x0), each product rounded before the sum, as ATen does
+ * `delta + 2.0 * resize(flow, 2.0)` (ifrnet.py:109-110) and `flow + scale_factor * resize(delta_flow, scale_factor)`
+ * (raft.py:138 with amt.py:161-162).  y may be x0 or x1.  strides as flair_prelu_nhwc. */
+int flair_axpby_nhwc(const float* x0, int x0_ld, float a, const float* x1, int x1_ld, float b, int C, long P, float* y, int y_ld,
+                     hipStream_t stream);
+/* The tail of one timestep for num_flows = 5 (multi_flow.py).  flair_amt_multiflow_prepare is MultiFlowDecoder.forward behind
+ * its convblock (:73-83): dec holds the 40 channels delta_flow0 (10) | delta_flow1 (10) | mask (5) | img_res (15), up the
+ * 4 channels resize(flow0 | flow1, 2.0); out = (delta_flow0 + 2 up[0:2] five times | delta_flow1 + 2 up[2:4] five times |
+ * sigmoid(mask) | img_res).  flair_amt_multiflow_combine is multi_flow_combine up to comb_block (:27-54): pair holds the
+ * mean-free frames (img0 in channels 0-2, img1 in 3-5), prep the 40 channels above at the frames' size, neg_mean[f *
+ * neg_mean_ld] minus the pair's mean (device); per flow i, x[3 i + c] = mask_i warp(img0, flow0_i) + (1 - mask_i)
+ * warp(img1, flow1_i) + mean + img_res_i with flow_utils.warp (bilinear, border, align_corners=True), x[15] = 0 (the padded
+ * input of comb_block[0]), avg[c] = the mean of x[3 i + c] over i, avg[3] = 0.
+ *   strides: every *_ld at least the channels named (pair 6, prep / dec / out 40, up 4, x 16, avg 4) and a multiple of 4
+ *            floats, every pointer 16-byte aligned (FLAIR_ERR_ARG naming the argument otherwise); 64-bit offsets. */
+int flair_amt_multiflow_prepare(const float* dec, int dec_ld, const float* up, int up_ld, long P, float* out, int out_ld,
+                                hipStream_t stream);
+int flair_amt_multiflow_combine(const float* pair, int pair_ld, const float* prep, int prep_ld, const float* neg_mean,
+                                int neg_mean_ld, int B, int H, int W, float* x, int x_ld, float* avg, int avg_ld,
+                                hipStream_t stream);
+
+/* nn.InstanceNorm2d(C) (no affine, biased variance) + activation (FLAIR_ACT_NONE or FLAIR_ACT_RELU) on [F][H][W] pixels of C
+ * channels: feat_enc.py:86-114 with norm_fn='instance'.  Two-pass: the mean, then the variance of the centred values, summed
+ * in double over fixed pixel ranges in a fixed order (bitwise reproducible), y = act((x - mean) * rstd) in f32.
+ * (flair_groupnorm_nhwc with groups = C is the one-pass var = E[x^2] - mean^2 and misses the f32 ATen deviation on planes
+ * whose mean is a few standard deviations.)  y must not alias x.
+ *   workspace: flair_instnorm_workspace_bytes(F, H, W, C) bytes, 16-byte aligned, contents irrelevant.
+ *   strides: C a multiple of 4; x_ld / y_ld at least C and multiples of 4 floats; x, y 16-byte aligned; F <= 65535. */
+size_t flair_instnorm_workspace_bytes(int F, int H, int W, int C);
+int flair_instnorm_nhwc(const float* x, int x_ld, int F, int H, int W, int C, double eps, int act, float* y, int y_ld,
+                        void* workspace, size_t workspace_bytes, hipStream_t stream);
 /* ------------------------------------------------------------- multi-GPU start-up
  * The only collective of the path: in-place RCCL broadcast of the kernel-native weight blob (flair_amd.checkpoint.export_packed:
  * bf16 [Cout][taps][Cin] conv weights, batched embedding matrix, f32 biases ...) from `root` to every rank of `rccl_comm`
