@@ -3,6 +3,8 @@ ends of the loop around it: ``degrade TASK CLEAN_DIR OUT_DIR`` makes a task's de
 operator the restoration assumes (flair_amd.degrade), and ``evaluate RESTORED_DIR TRUTH_DIR`` scores written frames with PSNR
 and SSIM (flair_amd.metrics); ``restore --ground-truth DIR`` scores every video as soon as it is written.
 ``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo or AMT-G (flair_amd.interpolate).
+``scenes SRC_DIR --json PATH`` finds the hard cuts of a video (flair_amd.scenes); ``restore`` / ``interpolate --scene-cuts
+auto|PATH`` then treat every shot on its own.
 
 The options of the reference's ``main()`` keep their names and defaults (``scripts/video_sample.py:249-263``); the
 presets are its ``x8_bicubic_demo`` ... ``jpeg_demo`` commands (:500-556).  Several videos go through one call with
@@ -15,6 +17,7 @@ import os
 import sys
 
 from . import pipeline as pl
+from . import scenes
 
 
 def _add_common(p):
@@ -43,6 +46,27 @@ def _add_common(p):
     p.add_argument("--model-kwargs", default=None, metavar="JSON", help="overrides of the task's model configuration")
     p.add_argument("--no-graph", action="store_true", help="run the network eagerly instead of replaying hipGraphs")
     p.add_argument("--seed", type=int, default=None, help="seed torch's generators before every video")
+    _add_cut_options(p, "restore every shot on its own: no window spans a cut and a shot's first window is not pinned to "
+                        "the shot before it")
+
+
+def _add_cut_rule(p):
+    d = scenes.RULE_DEFAULTS
+    p.add_argument("--cut-threshold", type=float, default=d["threshold"], metavar="D",
+                   help="a cut needs a block-luma distance d of at least D between its two frames (0..255 scale)")
+    p.add_argument("--cut-ratio", type=float, default=d["ratio"], metavar="R",
+                   help="... and of at least R times the median d of the neighbouring pairs (rejects motion, noise and fades)")
+    p.add_argument("--cut-radius", type=int, default=d["radius"], metavar="K", help="pairs on either side in that median")
+    p.add_argument("--min-shot", type=int, default=d["min_shot"], metavar="N",
+                   help="shortest shot in frames; flash frames are folded into a neighbouring shot")
+
+
+def _add_cut_options(p, what):
+    p.add_argument("--scene-cuts", default="off", metavar="off|auto|PATH",
+                   help=f"{what}.  off (default): the frames are one shot; auto: detect the cuts first (hard cuts only, no "
+                        "fades or dissolves; the rule's defaults are heuristics chosen on synthetic sequences and have NOT "
+                        "been validated on real footage); PATH: a cuts file written by the scenes command or by hand")
+    _add_cut_rule(p)
 
 
 def _add_hparams(p, d):
@@ -107,7 +131,76 @@ def make_parser():
     i.add_argument("--ground-truth", default=None, metavar="DIR",
                    help="frames at the new rate: score the written frames against them (PSNR / SSIM)")
     i.add_argument("--json", default=None, metavar="PATH", help="with --ground-truth: also write the values as JSON")
+    _add_cut_options(i, "synthesise nothing between the two frames of a cut: the in-betweens there are copies of the nearer "
+                        "frame (--min-shot keeps its default of 4 here too)")
+    s = sub.add_parser("scenes", help="find the hard cuts of a video (block-luma distances; heuristic defaults, not validated "
+                                      "on real footage) and write the cuts file restore / interpolate --scene-cuts PATH read",
+                       description="Print one line per shot and, with --json, write the cuts file that restore / interpolate "
+                                   "--scene-cuts PATH read.  Hard cuts only: fades and dissolves are not detected.  The rule's "
+                                   "defaults are heuristics chosen on synthetic sequences; they have NOT been validated on real "
+                                   "footage, so check the shots it prints, tune the options below, or edit the cuts file.")
+    s.add_argument("src_dir", metavar="SRC_DIR", help="frames of one size, at least 8 pixels a side")
+    s.add_argument("--json", default=None, metavar="PATH", help='write {"cuts": [...], "distances": [...], "frames": n}')
+    _add_cut_rule(s)
+    s.add_argument("--device", default=None, help="default: cuda")
     return ap
+
+
+def rule_of(args, command):
+    """find_cuts' keywords of a parsed command line (refused before any GPU work)."""
+    rule = dict(threshold=args.cut_threshold, ratio=args.cut_ratio, radius=args.cut_radius, min_shot=args.min_shot)
+    try:
+        scenes.check_rule(**rule)
+    except ValueError as exc:
+        raise SystemExit(f"{command}: {exc}")
+    return rule
+
+
+def cuts_of(args, command, video_dirs):
+    """The ``scene_cuts`` / ``cut_rule`` arguments of the drivers for a parsed command line: "off", "auto", or the checked
+    cuts of --scene-cuts PATH (one file describes one video).  Refusals come before any GPU work."""
+    rule = rule_of(args, command)
+    mode = args.scene_cuts
+    if mode in ("off", "auto"):
+        return dict(scene_cuts=mode, cut_rule=rule)
+    if len(video_dirs) != 1:
+        raise SystemExit(f"{command}: --scene-cuts {mode} is the cuts file of one video; with --output-root and "
+                         f"{len(video_dirs)} videos use --scene-cuts auto, or restore them one by one")
+    from . import io as fio
+    try:
+        cuts = scenes.read_cuts(mode, len(fio.list_frames(video_dirs[0])))
+    except (ValueError, OSError) as exc:
+        raise SystemExit(f"{command}: {exc}")
+    return dict(scene_cuts=cuts, cut_rule=rule)
+
+
+def scenes_of(args):
+    """The refusals of a parsed ``scenes`` command line, before any GPU work -> (frame paths, rule)."""
+    rule = rule_of(args, "scenes")
+    if not os.path.isdir(args.src_dir):
+        raise SystemExit(f"scenes: {args.src_dir} is not a directory")
+    from . import io as fio
+    paths = fio.list_frames(args.src_dir)
+    try:
+        scenes.check_frames(paths)
+    except ValueError as exc:
+        raise SystemExit(f"scenes: {args.src_dir}: {exc}")
+    return paths, rule
+
+
+def _scenes(args):
+    paths, rule = scenes_of(args)
+    import torch
+    torch.set_grad_enabled(False)
+    try:
+        result = scenes.detect_cuts_files(paths, args.device or "cuda", **rule)
+    except ValueError as exc:
+        raise SystemExit(f"scenes: {exc}")
+    for line in scenes.describe(result):
+        print(line)
+    if args.json:
+        scenes.write_cuts(args.json, result)
+    return 0
 
 
 def interpolate_of(args):
@@ -126,14 +219,19 @@ def interpolate_of(args):
 
 
 def _interpolate(args):
-    interpolate_of(args)
+    paths = interpolate_of(args)
+    how = cuts_of(args, "interpolate", [args.src_dir])
     import torch
     from . import interpolate as fi
     torch.set_grad_enabled(False)
     device = args.device or "cuda"
     try:
+        cuts, _ = scenes.resolve(how["scene_cuts"], paths, device, **how["cut_rule"])
+        if cuts is not None:
+            found = scenes.shots(len(paths), cuts)
+            print(f"{args.src_dir}: {len(found)} shot{'s' if len(found) != 1 else ''} " + ", ".join(f"{a}..{b - 1}" for a, b in found))
         net = fi.load_interpolator(args.weights, device, args.dtype, name=args.interpolator)
-        n = fi.interpolate_video_files(args.src_dir, args.out_dir, args.factor, net=net, device=device)
+        n = fi.interpolate_video_files(args.src_dir, args.out_dir, args.factor, net=net, device=device, cuts=cuts)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"interpolate: {exc}")
     print(f"wrote {n} frames to {args.out_dir} ({args.factor}x the rate of {args.src_dir})")
@@ -276,11 +374,14 @@ def main(argv=None):
         return _evaluate(args)
     if args.command == "interpolate":
         return _interpolate(args)
+    if args.command == "scenes":
+        return _scenes(args)
     task, jobs = jobs_of(args)
     truth = truth_of(args, jobs)
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
+    how = cuts_of(args, "restore", [v for v, _ in jobs])
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -303,6 +404,7 @@ def main(argv=None):
         hp = dict(aligned=args.aligned, t_start=args.t_start, jpeg_qf=args.jpeg_qf, w=args.w, tau=args.tau,
                   rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
         hp.update(faces)
+        hp.update(how)
 
         def restore_one(v, o):
             n = p.restore_video_files(v, o, **hp)

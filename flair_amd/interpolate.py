@@ -3,7 +3,8 @@
 The reference ships the networks (``guided_diffusion/superslomo.py``, ``guided_diffusion/amt.py``) and no driver for them;
 this is the driver.  Every pair of neighbouring frames gets ``factor - 1`` frames between them from ``SuperSloMo`` (the
 default) or ``AMT`` (``--interpolator amt-g``) on the HIP kernels, so ``T`` frames become ``factor * (T - 1) + 1``.  The
-original frames pass through untouched: files are written from their decoded bytes.
+original frames pass through untouched: files are written from their decoded bytes.  With ``cuts`` (flair_amd.scenes,
+``--scene-cuts``) nothing is synthesised between the two frames of a cut: the in-betweens there are copies of the nearer one.
 
 ``load_interpolator`` returns a module with ``forward(frame0, frame1, factor) -> (B, factor - 1, 3, H, W)`` on frames in
 [-1, 1] and a ``MULTIPLE`` attribute (32 for SuperSloMo; 1 for AMT, which pads to multiples of 16 itself, centred).
@@ -15,6 +16,7 @@ import torch.nn.functional as F
 
 from . import io as fio
 from . import pipeline as pl
+from . import scenes
 
 _PARTS = (("state_dictFC", "flow_estimator."), ("state_dictAT", "interp."))
 # name -> checkpoint file under the weights directory
@@ -130,9 +132,29 @@ def interpolate_pairs(net, first01, second01, factor):
     return ((mid[..., :h, :w] + 1) / 2).clamp(0, 1)
 
 
-def interpolate_frames(net, frames01, factor, batch=4):
+def nearest_original(k, factor):
+    """Across a cut nothing is synthesised: in-between k (at t = (k + 1) / factor) of a pair (p, p + 1) is a copy of frame
+    p + nearest_original(k, factor), i.e. of p where t < 0.5 and of p + 1 otherwise (2 (k + 1) < factor, in integers)."""
+    return 0 if 2 * (k + 1) < factor else 1
+
+
+def _pairs_of_group(p, q, cutset):
+    """Pairs p .. q - 1 split into those the network interpolates and those that straddle a cut."""
+    keep = [i for i in range(p, q) if i + 1 not in cutset]
+    return keep, [i for i in range(p, q) if i + 1 in cutset]
+
+
+def _run_pairs(net, frames01, keep, base, factor):
+    """interpolate_pairs on the pairs ``keep`` (video indices; frames01[i - base] is frame i) of a group with a cut in it."""
+    idx = torch.tensor([i - base for i in keep], device=frames01.device)
+    return interpolate_pairs(net, frames01[idx], frames01[idx + 1], factor)
+
+
+def interpolate_frames(net, frames01, factor, batch=4, cuts=None):
     """(T, 3, H, W) in [0, 1] -> (factor * (T - 1) + 1, 3, H, W): originals (untouched) and intermediates interleaved in
-    time order.  Pairs go through the network ``batch`` at a time."""
+    time order.  Pairs go through the network ``batch`` at a time.  ``cuts`` (flair_amd.scenes: frames that start a new
+    shot): the network is not called for a pair (p, p + 1) with p + 1 in cuts; its in-betweens are copies of the nearer
+    original (nearest_original), so the count and the timing of the result stay the same."""
     if frames01.dim() != 4 or frames01.shape[1] != 3:
         raise ValueError(f"interpolate: (T, 3, H, W) frames, got {tuple(frames01.shape)}")
     T = frames01.shape[0]
@@ -141,13 +163,24 @@ def interpolate_frames(net, frames01, factor, batch=4):
     if isinstance(factor, bool) or int(factor) != factor or factor < 2:
         raise ValueError(f"interpolate: factor={factor!r}; an integer >= 2")
     factor = int(factor)
+    cutset = set(scenes.check_cuts(cuts or [], T))
     out = frames01.new_empty((factor * (T - 1) + 1, *frames01.shape[1:]), dtype=torch.float32)
     out[::factor] = frames01
     for p in range(0, T - 1, max(1, int(batch))):
         q = min(T - 1, p + max(1, int(batch)))
-        mid = interpolate_pairs(net, frames01[p:q], frames01[p + 1:q + 1], factor)
-        for k in range(factor - 1):
-            out[p * factor + 1 + k:q * factor:factor] = mid[:, k]
+        keep, across = _pairs_of_group(p, q, cutset)
+        if not across:
+            mid = interpolate_pairs(net, frames01[p:q], frames01[p + 1:q + 1], factor)
+            for k in range(factor - 1):
+                out[p * factor + 1 + k:q * factor:factor] = mid[:, k]
+            continue
+        if keep:
+            mid = _run_pairs(net, frames01[p:q + 1], keep, p, factor)
+            for j, i in enumerate(keep):
+                out[i * factor + 1:(i + 1) * factor] = mid[j]
+        for i in across:
+            for k in range(factor - 1):
+                out[i * factor + 1 + k] = frames01[i + nearest_original(k, factor)]
     return out
 
 
@@ -168,28 +201,41 @@ def check_source(src_dir, factor):
     return paths, sizes[0]
 
 
-def interpolate_video_files(src_dir, out_dir, factor, *, net, device, batch=4):
+def interpolate_video_files(src_dir, out_dir, factor, *, net, device, batch=4, cuts=None):
     """Frame files of ``src_dir`` (flair_amd.io's listing and order) -> ``out_dir/{i:04d}.png``, factor * (T - 1) + 1 of
     them.  Original frames are written from their decoded bytes (never re-quantised from floats), intermediates through
     ``io.to_bytes``.  At most ``batch`` pairs are on the device at a time; decoding and PNG encoding overlap the network
-    (the reader and writer threads of flair_amd.io).  Returns the number of frames written."""
+    (the reader and writer threads of flair_amd.io).  ``cuts``: as in interpolate_frames; the copies that stand between the
+    two frames of a cut are written from the decoded bytes too.  Returns the number of frames written."""
     paths, _ = check_source(src_dir, factor)
     factor = int(factor)
     T = len(paths)
     batch = max(1, int(batch))
+    cutset = set(scenes.check_cuts(cuts or [], T))
     # group g holds frames first .. first + n - 1: its pairs and the frame that closes the last of them
     groups = [(p, min(batch, T - 1 - p) + 1) for p in range(0, T - 1, batch)]
     writer = fio._Writer(out_dir)
     try:
         for first, (u8,) in fio.iter_frame_batches([paths], groups, device):
             frames01 = u8.permute(0, 3, 1, 2).float() / 255.0
-            mid = fio.to_bytes(interpolate_pairs(net, frames01[:-1], frames01[1:], factor).flatten(0, 1))
             n = u8.shape[0] - 1
+            keep, across = _pairs_of_group(first, first + n, cutset)
             block = torch.empty((n * factor, *u8.shape[1:]), dtype=torch.uint8, device=u8.device)
             block[::factor] = u8[:-1]
-            mid = mid.view(n, factor - 1, *u8.shape[1:])
-            for k in range(factor - 1):
-                block[1 + k::factor] = mid[:, k]
+            if not across:
+                mid = fio.to_bytes(interpolate_pairs(net, frames01[:-1], frames01[1:], factor).flatten(0, 1))
+                mid = mid.view(n, factor - 1, *u8.shape[1:])
+                for k in range(factor - 1):
+                    block[1 + k::factor] = mid[:, k]
+            else:
+                if keep:
+                    mid = fio.to_bytes(_run_pairs(net, frames01, keep, first, factor).flatten(0, 1))
+                    mid = mid.view(len(keep), factor - 1, *u8.shape[1:])
+                    for j, i in enumerate(keep):
+                        block[(i - first) * factor + 1:(i - first + 1) * factor] = mid[j]
+                for i in across:
+                    for k in range(factor - 1):
+                        block[(i - first) * factor + 1 + k] = u8[i - first + nearest_original(k, factor)]
             writer.submit_bytes(first * factor, block)
         last = torch.from_numpy(fio.decode_frame_hwc(paths[-1]).copy())[None]
         writer.submit_bytes((T - 1) * factor, last)

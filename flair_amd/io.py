@@ -118,23 +118,25 @@ class _Writer(threading.Thread):
             raise self.error
 
 
-def iter_windows(paths, device, length=video.FRAME_SLICE_LEN, overlap=video.OVERLAP):
+def iter_windows(paths, device, length=video.FRAME_SLICE_LEN, overlap=video.OVERLAP, cuts=None):
     """Yield ``(indices, degraded01)`` per window with ``degraded01`` = (1, T, 3, h, w) float in [0, 1] on
     ``device``: the frames of the NEXT window are decoded and uploaded (pinned memory, side stream) while the
-    caller works on the current one.  Frames shared by two windows are decoded once."""
-    wins = video.window_indices(len(paths), length, overlap)
+    caller works on the current one.  Frames shared by two windows are decoded once.  ``cuts``: the windows of
+    video.window_plan (no window spans a cut) instead of video.window_indices."""
+    wins = [idx for idx, _ in video.window_plan(len(paths), cuts, length, overlap)]
     cache, q = {}, queue.Queue(maxsize=2)
     on_gpu = torch.device(device).type == "cuda"
     side = torch.cuda.Stream(device=device) if on_gpu else None
 
     def produce():
         try:
-            for idx in wins:
+            for w, idx in enumerate(wins):
                 for i in idx:
                     if i not in cache:
                         cache[i] = decode_frame(paths[i])
                 host = torch.from_numpy(np.stack([cache[i] for i in idx]))
-                for i in [k for k in cache if k < idx[-1] - overlap]:   # older frames are never needed again
+                ahead = set(wins[w + 1]) if w + 1 < len(wins) else ()
+                for i in [k for k in cache if k not in ahead]:          # only the next window's frames are needed again
                     del cache[i]
                 if on_gpu:
                     host = host.pin_memory()
@@ -216,17 +218,21 @@ def frame_size(path):
 
 
 def restore_video_files(task, video_path, output_path, model, diffusion, restore_fn_for, *, size, device,
-                        length=video.FRAME_SLICE_LEN, overlap=video.OVERLAP, aligned=True, face_helper=None, **kw):
+                        length=video.FRAME_SLICE_LEN, overlap=video.OVERLAP, aligned=True, face_helper=None, cuts=None, **kw):
     """``scripts/video_sample.py:334-492`` end to end: frame files in, restored ``{i:04d}.png`` out, with
     decode / upload / sampling / download / encode overlapped.  ``kw`` goes to ``video.restore_window``
     (aux_model, vsrpp_weights_fn, hp, tau, t_start, noise_fn, q_noise_fn, faces, max_faces).  ``aligned=False`` detects every window's
     faces on the main thread before its first step (video.window_faces) while the reader thread decodes the next
-    window.  Returns the number of frames written."""
+    window.  ``cuts`` (None = one shot): frames that start a new shot; every shot is windowed on its own and its first
+    window gets no ``prev_recon`` (video.window_plan).  Returns the number of frames written."""
     paths = list_frames(video_path)
+    plan = video.window_plan(len(paths), cuts, length, overlap)            # refuses bad cuts before anything is decoded
     writer = _Writer(output_path)
     prev_recon, written = None, 0
     try:
-        for wi, (idx, degraded01) in enumerate(iter_windows(paths, device, length, overlap)):
+        for wi, (idx, degraded01) in enumerate(iter_windows(paths, device, length, overlap, cuts=cuts)):
+            if plan[wi][1]:
+                prev_recon = None
             keep, prev_recon = video.restore_window(task, degraded01, model, diffusion, restore_fn_for, size=size,
                                                     prev_recon=prev_recon, overlap=overlap, window_index=wi, aligned=aligned,
                                                     face_helper=face_helper, frame_indices=idx, **kw)

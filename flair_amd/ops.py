@@ -1146,6 +1146,23 @@ def image_metrics(a, b, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- scene cuts (scenes.hip)
+def block_luma_sums(u8, out=None):
+    """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB
+    on the GPU, H, W >= 8 -> (N, 64) int64 device tensor, entry 8 a + b = sum of (77 R + 150 G + 29 B + 128) >> 8 over rows
+    (a H) // 8 .. ((a + 1) H) // 8 and columns (b W) // 8 .. ((b + 1) W) // 8.  flair_amd.scenes turns the rows into distances."""
+    _refuse(u8.dim() == 4 and u8.shape[3] == 3, f"block_luma_sums: (N, H, W, 3) frames, got {tuple(u8.shape)}")
+    _refuse(u8.dtype == torch.uint8, f"block_luma_sums: uint8 frames, got {u8.dtype}")
+    _refuse(u8.is_contiguous(), "block_luma_sums: dense (contiguous) frames")
+    N, H, W, _ = u8.shape
+    if out is None:
+        out = torch.empty((N, 64), dtype=torch.int64, device=u8.device)
+    _refuse(out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (N, 64),
+            "block_luma_sums: out is a dense (N, 64) int64 tensor")
+    check(lib().flair_block_luma_sums(ptr(u8), N, H, W, ptr(out), stream()), "flair_block_luma_sums")
+    return out
+
+
 # --------------------------------------------------------------------------- SuperSloMo frame interpolation (slomo.hip)
 SLOMO_MEAN = (0.429, 0.431, 0.397)          # superslomo.py:250: the channel means of normalize()
 

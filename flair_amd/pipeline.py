@@ -21,6 +21,7 @@ import torch.distributed as dist
 from . import io as fio
 from . import ops
 from . import parallel
+from . import scenes
 from . import video
 from . import workload as wl
 from .guided_diffusion import gaussian_diffusion as gd
@@ -291,19 +292,30 @@ class Pipeline:
     def restore_video_files(self, video_path, output_path, *, aligned=MAIN_DEFAULTS["aligned"], t_start=-1, jpeg_qf=-1,
                             w=MAIN_DEFAULTS["w"], tau=5, rho=MAIN_DEFAULTS["rho"],
                             noise_level=MAIN_DEFAULTS["noise_level"], zeta=MAIN_DEFAULTS["zeta"], seed=None,
-                            faces="largest", max_faces=None):
+                            faces="largest", max_faces=None, scene_cuts="off", cut_rule=None, log=print):
         """Frame files of ``video_path`` -> ``output_path/{i:04d}.png`` (video_sample.py:334-492).  ``seed`` seeds
         torch's generators first (the reference does not seed).  ``faces="all"`` (aligned=False only): the prior runs on
-        every detected face, at most ``max_faces`` per frame, and frames may have none (video.restore_window).  Returns
-        the number of frames written."""
+        every detected face, at most ``max_faces`` per frame, and frames may have none (video.restore_window).
+        ``scene_cuts`` (ours): "off" restores the directory as one shot, like the reference; "auto" finds the cuts of
+        the degraded input frames first (scenes.detect_cuts_files with ``cut_rule``, find_cuts' keywords: heuristic
+        defaults, not validated on real footage); a list of cuts or the path of a cuts file is used as given.  Every
+        shot is then restored on its own (io.restore_video_files' ``cuts``), and one line with the shots is logged.
+        Returns the number of frames written."""
         self.check_aligned(aligned)
+        paths = fio.list_frames(video_path)
+        cuts, _ = scenes.resolve(scene_cuts, paths, self.device, **(cut_rule or {}))
+        if cuts is not None:
+            found = scenes.shots(len(paths), cuts)
+            log(f"{video_path}: {len(found)} shot{'s' if len(found) != 1 else ''} "
+                + ", ".join(f"{a}..{b - 1}" for a, b in found))
         if seed is not None:
             torch.manual_seed(int(seed))
         hp = dict(w=w, rho=rho, noise_level=noise_level, zeta=zeta)
         return fio.restore_video_files(
             self.task, video_path, output_path, self.model, self.diffusion, self.restore_fn_for(jpeg_qf), size=self.size,
             device=self.device, aligned=aligned, face_helper=self.face_helper, aux_model=self.aux_model,
-            vsrpp_weights_fn=self.vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, faces=faces, max_faces=max_faces)
+            vsrpp_weights_fn=self.vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, faces=faces, max_faces=max_faces,
+            cuts=cuts)
 
 
 def build_operator(task, size, device, kernel=None):

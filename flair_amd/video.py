@@ -17,6 +17,7 @@ import numbers
 import torch
 
 from . import ops
+from . import scenes
 from . import workload as wl
 
 FRAME_SLICE_LEN = 10   # scripts/video_sample.py:202
@@ -34,6 +35,20 @@ def window_indices(n_frames, length=FRAME_SLICE_LEN, overlap=OVERLAP):
     if n_frames <= length:
         return [list(range(n_frames))]
     return [list(range(s, min(s + length, n_frames))) for s in range(0, n_frames - length + step, step)]
+
+
+def window_plan(n_frames, cuts=None, length=FRAME_SLICE_LEN, overlap=OVERLAP):
+    """[(indices, starts_shot)] of every window of a video with scene cuts (flair_amd.scenes; ours, the reference restores one
+    continuous clip): ``window_indices`` applied to every shot and shifted to video indices, so that no window spans a
+    cut.  The first window of a shot has ``starts_shot`` True: it gets no ``prev_recon`` and contributes all its frames.
+    Without cuts the plan is window_indices with only the first window starting a shot."""
+    plan = []
+    for start, stop in (scenes.shots(n_frames, cuts) if n_frames > 0 else []):
+        for k, idx in enumerate(window_indices(stop - start, length, overlap)):
+            plan.append(([start + i for i in idx], k == 0))
+    if not plan:
+        window_indices(n_frames, length, overlap)                 # its refusals hold for an empty video too
+    return plan
 
 
 _consts = {}
@@ -264,7 +279,7 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
 
 def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, aux_model=wl.identity_aux,
                   vsrpp_weights_fn=None, hp=None, tau=5, t_start=-1, length=FRAME_SLICE_LEN, overlap=OVERLAP,
-                  noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, faces="largest", max_faces=None):
+                  noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, faces="largest", max_faces=None, cuts=None):
     """degraded01: (1, N, 3, h, w) frames in [0, 1] on the GPU.  Returns (N, 3, H, W) in [0, 1] for ``size`` = an int
     S (H = W = S) or a pair (H, W) (see restore_window).
 
@@ -272,7 +287,9 @@ def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, a
     operator of the window (video_sample.py:455-459); vsrpp_weights_fn(init_norm (1,T,3,S,S)) supplies
     the per-pixel propagation weights of the bicubic tasks (face parsing, :427-444) and defaults to 1.0;
     noise_fn / q_noise_fn(window_index, like) let tests share one noise tape with the oracle; aligned / face_helper /
-    faces / max_faces: see restore_window.
+    faces / max_faces: see restore_window.  ``cuts`` (ours; None = one shot, exactly the reference's loop): frames that start
+    a new shot (flair_amd.scenes).  Every shot is windowed on its own (window_plan): its first window gets no prev_recon and
+    contributes all its frames, while window_index keeps counting over the whole video (noise_fn / q_noise_fn are keyed by it).
     (File-to-file form with decode / upload / encode overlapped: flair_amd.io.restore_video_files.)"""
     dev = degraded01.device
     n_frames = degraded01.shape[1]
@@ -281,10 +298,10 @@ def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, a
         check_degraded(task, degraded01.shape[-2:], size)
     out = torch.empty((n_frames, 3, *frame_hw(size)), dtype=torch.float32, device=dev)
     filled = 0
-    for wi, idx in enumerate(window_indices(n_frames, length, overlap)):
+    for wi, (idx, starts_shot) in enumerate(window_plan(n_frames, cuts, length, overlap)):
         frames01, prev_recon = restore_window(
             task, degraded01[:, idx[0]:idx[-1] + 1], model, diffusion, restore_fn_for, size=size,
-            prev_recon=prev_recon, overlap=overlap, window_index=wi, aux_model=aux_model,
+            prev_recon=None if starts_shot else prev_recon, overlap=overlap, window_index=wi, aux_model=aux_model,
             vsrpp_weights_fn=vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, noise_fn=noise_fn, q_noise_fn=q_noise_fn,
             aligned=aligned, face_helper=face_helper, frame_indices=idx, faces=faces, max_faces=max_faces)
         out[filled:filled + frames01.shape[0]].copy_(frames01)

@@ -69,7 +69,8 @@ const char* flair_last_error(void);
  * 15: + flair_image_metrics_workspace, flair_image_metrics (PSNR / SSIM of written frames);
  * 16: + flair_slomo_warp_pack, flair_slomo_blend (SuperSloMo); 17: + flair_corr_scale, flair_corr_pool, flair_corr_lookup,
  *     flair_prelu_nhwc, flair_depth_to_space2_nhwc, flair_axpby_nhwc,
- *     flair_amt_multiflow_prepare, flair_amt_multiflow_combine, flair_instnorm_workspace_bytes, flair_instnorm_nhwc (AMT-G)).
+ *     flair_amt_multiflow_prepare, flair_amt_multiflow_combine, flair_instnorm_workspace_bytes, flair_instnorm_nhwc (AMT-G);
+ * 18: + flair_block_luma_sums (scene cuts).
  * The library may be used from several devices of one process: per-kernel launch attributes and
  * CU counts are cached per device. */
 int flair_abi_version(void);
@@ -724,6 +725,19 @@ int flair_bcast_weights(void* blob, size_t bytes, int root, void* rccl_comm, hip
 size_t flair_image_metrics_workspace(int N, int H, int W);
 int flair_image_metrics(const uint8_t* a, const uint8_t* b, int N, int H, int W, double* out, void* ws, size_t ws_bytes,
                         hipStream_t stream);
+
+/* ------------------------------------------------------------- scene cuts (python -m flair_amd scenes, --scene-cuts auto)
+ * No counterpart in the reference, whose script restores one continuous clip: the per-block mean brightness that
+ * flair_amd.scenes compares between neighbouring frames to find the cuts of a video.
+ * frames: dense [N][H][W][3] uint8 RGB (what flair_amd.io.iter_frame_batches yields), at an address of any alignment.
+ * out: [N][64] 64-bit integers; out[64 n + 8 a + b] = the sum of the integer luma Y = (77 R + 150 G + 29 B + 128) >> 8 over the
+ * pixels (y, x) of frame n with (a H) / 8 <= y < ((a + 1) H) / 8 and (b W) / 8 <= x < ((b + 1) W) / 8 (integer divisions: an
+ * 8 x 8 grid of blocks whose sizes differ by at most one row and one column).  Integer arithmetic only, so the sums are exact
+ * and the same in every run, for every N and every position of a frame in the batch.  Every byte of the frames is read once:
+ * one workgroup per (block, 32 rows) reads each row segment as an unaligned head, aligned 12-byte pieces and a tail, and adds
+ * ONE 64-bit integer atomic to its entry; the entry zeroes `out` on `stream` first.  No allocation, no workspace, asynchronous
+ * on `stream`.  H, W >= 8, W <= 2^24, N >= 1, out 8-byte aligned; offsets are 64-bit (N H W 3 may exceed 2^31). */
+int flair_block_luma_sums(const uint8_t* frames, int N, int H, int W, long long* out, hipStream_t stream);
 
 /* ------------------------------------------------------------- calibration launches (measurement only)
  * No counterpart in the reference: they exist so that bench.py can print, beside every roofline fraction against the data-sheet
