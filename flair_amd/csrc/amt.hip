@@ -42,8 +42,6 @@ namespace {
 constexpr int CORR_TAPS = 49;           // (2 r + 1)^2 at the radius 3 AMT uses
 constexpr int CORR_MAX_LEVELS = 4;
 
-inline int amt_grid(long n) { return (int)((n + 255) / 256); }
-
 __global__ void corr_scale_kernel(float* x, long n4, long n, float d) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n4) {
@@ -313,7 +311,7 @@ extern "C" int flair_corr_scale(float* x, long n, float divisor, hipStream_t str
     FLAIR_CHECK(divisor > 0.f && divisor < INFINITY, "flair_corr_scale: divisor = %g must be positive and finite", divisor);
     const long n4 = n / 4, threads = n4 + (n - 4 * n4);
     FLAIR_CHECK(threads <= 0x7fffffffL * 256, "flair_corr_scale: n = %ld needs more than 2^31 workgroups", n);
-    hipLaunchKernelGGL(corr_scale_kernel, dim3(amt_grid(threads)), dim3(256), 0, stream, x, n4, n, divisor);
+    hipLaunchKernelGGL(corr_scale_kernel, dim3(grid_for(threads, 256, GRID_NO_CAP)), dim3(256), 0, stream, x, n4, n, divisor);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -326,7 +324,7 @@ extern "C" int flair_corr_pool(const float* src, long planes, int h, int w, floa
                 "flair_corr_pool: src = %p and dst = %p must be 4-byte aligned", (const void*)src, (const void*)dst);
     const long total = planes * (h / 2) * (w / 2);
     FLAIR_CHECK(total <= 0x7fffffffL * 256, "flair_corr_pool: %ld outputs need more than 2^31 workgroups", total);
-    hipLaunchKernelGGL(corr_pool_kernel, dim3(amt_grid(total)), dim3(256), 0, stream, src, planes, h, w, dst);
+    hipLaunchKernelGGL(corr_pool_kernel, dim3(grid_for(total, 256, GRID_NO_CAP)), dim3(256), 0, stream, src, planes, h, w, dst);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -377,7 +375,7 @@ extern "C" int flair_prelu_nhwc(const float* x0, int x0_ld, const float* x1, int
                 (const void*)slope);
     const long n = P * (C / 4);
     FLAIR_CHECK(n <= 0x7fffffffL * 256, "flair_prelu_nhwc: P = %ld pixels of %d channels need more than 2^31 workgroups", P, C);
-    hipLaunchKernelGGL(prelu_kernel, dim3(amt_grid(n)), dim3(256), 0, stream, x0, x0_ld, x1, x1_ld, slope, C, P, y, y_ld);
+    hipLaunchKernelGGL(prelu_kernel, dim3(grid_for(n, 256, GRID_NO_CAP)), dim3(256), 0, stream, x0, x0_ld, x1, x1_ld, slope, C, P, y, y_ld);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -390,7 +388,7 @@ extern "C" int flair_depth_to_space2_nhwc(const float* x, int x_ld, int F, int H
     FLAIR_CHECK_VIEW("flair_depth_to_space2_nhwc", "y", y, y_ld, C, 4);
     const long n = (long)F * 4 * H * W * (C / 4);
     FLAIR_CHECK(n <= 0x7fffffffL * 256, "flair_depth_to_space2_nhwc: more than 2^31 workgroups");
-    hipLaunchKernelGGL(depth_to_space2_kernel, dim3(amt_grid(n)), dim3(256), 0, stream, x, x_ld, (long)F, H, W, C, y, y_ld);
+    hipLaunchKernelGGL(depth_to_space2_kernel, dim3(grid_for(n, 256, GRID_NO_CAP)), dim3(256), 0, stream, x, x_ld, (long)F, H, W, C, y, y_ld);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -404,7 +402,7 @@ extern "C" int flair_axpby_nhwc(const float* x0, int x0_ld, float a, const float
     FLAIR_CHECK_VIEW("flair_axpby_nhwc", "y", y, y_ld, C, 4);
     const long n = P * (C / 4);
     FLAIR_CHECK(n <= 0x7fffffffL * 256, "flair_axpby_nhwc: more than 2^31 workgroups");
-    hipLaunchKernelGGL(axpby_nhwc_kernel, dim3(amt_grid(n)), dim3(256), 0, stream, x0, x0_ld, a, x1, x1_ld, b, C, P, y, y_ld);
+    hipLaunchKernelGGL(axpby_nhwc_kernel, dim3(grid_for(n, 256, GRID_NO_CAP)), dim3(256), 0, stream, x0, x0_ld, a, x1, x1_ld, b, C, P, y, y_ld);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -416,7 +414,7 @@ extern "C" int flair_amt_multiflow_prepare(const float* dec, int dec_ld, const f
     FLAIR_CHECK_VIEW("flair_amt_multiflow_prepare", "up", up, up_ld, 4, 4);
     FLAIR_CHECK_VIEW("flair_amt_multiflow_prepare", "out", out, out_ld, MF_C, 4);
     FLAIR_CHECK(P <= 0x7fffffffL * 256, "flair_amt_multiflow_prepare: more than 2^31 workgroups");
-    hipLaunchKernelGGL(multiflow_prepare_kernel, dim3(amt_grid(P)), dim3(256), 0, stream, dec, dec_ld, up, up_ld, P, out, out_ld);
+    hipLaunchKernelGGL(multiflow_prepare_kernel, dim3(grid_for(P, 256, GRID_NO_CAP)), dim3(256), 0, stream, dec, dec_ld, up, up_ld, P, out, out_ld);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -432,7 +430,7 @@ extern "C" int flair_amt_multiflow_combine(const float* pair, int pair_ld, const
     FLAIR_CHECK_VIEW("flair_amt_multiflow_combine", "avg", avg, avg_ld, 4, 4);
     const long P = (long)B * H * W;
     FLAIR_CHECK(P <= 0x7fffffffL * 256, "flair_amt_multiflow_combine: more than 2^31 workgroups");
-    hipLaunchKernelGGL(multiflow_combine_kernel, dim3(amt_grid(P)), dim3(256), 0, stream, pair, pair_ld, prep, prep_ld, neg_mean,
+    hipLaunchKernelGGL(multiflow_combine_kernel, dim3(grid_for(P, 256, GRID_NO_CAP)), dim3(256), 0, stream, pair, pair_ld, prep, prep_ld, neg_mean,
                        neg_mean_ld, B, H, W, x, x_ld, avg, avg_ld);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
@@ -465,10 +463,10 @@ extern "C" int flair_instnorm_nhwc(const float* x, int x_ld, int F, int H, int W
     const long n = (long)F * HW * (C / 4);
     FLAIR_CHECK(n <= 0x7fffffffL * 256, "flair_instnorm_nhwc: more than 2^31 workgroups");
     hipLaunchKernelGGL(in_partial_kernel, grid, dim3(256), 0, stream, x, x_ld, HW, C, S, (const float*)nullptr, partial);
-    hipLaunchKernelGGL(in_finish_kernel, dim3(amt_grid((long)F * C)), dim3(256), 0, stream, partial, (long)F, C, S, HW, eps, 0, mean);
+    hipLaunchKernelGGL(in_finish_kernel, dim3(grid_for((long)F * C, 256, GRID_NO_CAP)), dim3(256), 0, stream, partial, (long)F, C, S, HW, eps, 0, mean);
     hipLaunchKernelGGL(in_partial_kernel, grid, dim3(256), 0, stream, x, x_ld, HW, C, S, (const float*)mean, partial);
-    hipLaunchKernelGGL(in_finish_kernel, dim3(amt_grid((long)F * C)), dim3(256), 0, stream, partial, (long)F, C, S, HW, eps, 1, rstd);
-    hipLaunchKernelGGL(in_apply_kernel, dim3(amt_grid(n)), dim3(256), 0, stream, x, x_ld, (long)F, HW, C, mean, rstd,
+    hipLaunchKernelGGL(in_finish_kernel, dim3(grid_for((long)F * C, 256, GRID_NO_CAP)), dim3(256), 0, stream, partial, (long)F, C, S, HW, eps, 1, rstd);
+    hipLaunchKernelGGL(in_apply_kernel, dim3(grid_for(n, 256, GRID_NO_CAP)), dim3(256), 0, stream, x, x_ld, (long)F, HW, C, mean, rstd,
                        act == FLAIR_ACT_RELU ? 1 : 0, y, y_ld);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;

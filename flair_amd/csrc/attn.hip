@@ -708,6 +708,7 @@ constexpr int kWideHeadMin = 192, kWideHeadMax = 1024;
 
 extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, void* out, hipStream_t stream) {
     FLAIR_CHECK(p && qkv && out, "flair_qkv_attention: null argument");
+    FLAIR_CHECK_DTYPE("flair_qkv_attention", p->dtype);
     FLAIR_CHECK(p->frames > 0 && p->L > 0 && p->heads > 0, "flair_qkv_attention: empty shape");
     const int d = p->head_dim;
     const bool native = d == 32 || d == 64 || d == 128;
@@ -738,7 +739,7 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
             launch_qkv_bf16<128>(p, a, stream);
         else
             launch_qkv_bf16<64>(p, a, stream);
-    } else if (p->dtype == FLAIR_F32) {
+    } else {
         if (wide)
             hipLaunchKernelGGL(attn_rowwise_wide_kernel, dim3((p->L + 3) / 4, p->frames * p->heads), dim3(256), 0, stream,
                                a, d / 64);
@@ -748,8 +749,6 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
             launch_qkv_f32<128>(p, a, stream);
         else
             launch_qkv_f32<64>(p, a, stream);
-    } else {
-        FLAIR_CHECK(false, "flair_qkv_attention: bad dtype");
     }
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
@@ -758,6 +757,7 @@ extern "C" int flair_qkv_attention(const flair_attn_params* p, const void* qkv, 
 extern "C" int flair_temporal_attention(const flair_tattn_params* p, const void* qkv, const float* kpos, void* out,
                                         hipStream_t stream) {
     FLAIR_CHECK(p && qkv && kpos && out, "flair_temporal_attention: null argument");
+    FLAIR_CHECK_DTYPE("flair_temporal_attention", p->dtype);
     const int d = p->head_dim ? p->head_dim : 64;   // 0: the width-64 default of ABI version <= 6
     FLAIR_CHECK(d % 8 == 0 && d >= 8 && d <= 256,
                 "flair_temporal_attention: head width %d unsupported (multiples of 8 from 8 to 256)", d);
@@ -770,10 +770,8 @@ extern "C" int flair_temporal_attention(const flair_tattn_params* p, const void*
     a.headDim = d;
     if (p->dtype == FLAIR_BF16)
         launch_temporal<bf16_t>(a, stream);
-    else if (p->dtype == FLAIR_F32)
-        launch_temporal<float>(a, stream);
     else
-        FLAIR_CHECK(false, "flair_temporal_attention: bad dtype");
+        launch_temporal<float>(a, stream);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }

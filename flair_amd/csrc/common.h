@@ -29,6 +29,26 @@ void flair_set_error(const char* fmt, ...);
     FLAIR_CHECK((ld) >= (C) && (ld) % (vec) == 0 && reinterpret_cast<uintptr_t>(ptr) % 16 == 0,                        \
                 fn ": " name " stride/alignment: " name "_ld = %d must be >= C = %d and a multiple of %d elements, " \
                 name " = %p 16-byte aligned", (int)(ld), (int)(C), (int)(vec), (const void*)(ptr))
+// The element type code of an entry.  Refuse a bad one before anything derives `vec` or an element size from it.
+#define FLAIR_CHECK_DTYPE(fn, dtype) \
+    FLAIR_CHECK((dtype) == FLAIR_BF16 || (dtype) == FLAIR_F32, "%s: bad dtype = %d (FLAIR_F32 = %d or FLAIR_BF16 = %d)", fn, (int)(dtype), FLAIR_F32, FLAIR_BF16)
+// One launch for both element types: f(bf16_t{}) or f(float{}), with the refusal above for any other code.  `f` is a generic
+// lambda `[&](auto e) -> int` (the explicit int: FLAIR_OK and FLAIR_CHECK's FLAIR_ERR_ARG are enumerators); inside,
+// `using E = decltype(e)`, `ET<E>::VEC`, `(const E*)x`, the checks that need VEC, the launch, FLAIR_LAUNCH_CHECK, return FLAIR_OK.
+template <typename F>
+static inline int flair_by_dtype(const char* fn, int dtype, F&& f) {
+    FLAIR_CHECK_DTYPE(fn, dtype);
+    return dtype == FLAIR_BF16 ? f(bf16_t{}) : f(float{});
+}
+// Blocks of `block` threads for n work items, at most `cap` (grid-stride kernels) and at least one.  A kernel that
+// indexes with `if (i < n)` needs every block: its launch passes GRID_NO_CAP.  Block and cap stand at the call site.
+constexpr int GRID_NO_CAP = 0x7fffffff;
+static inline int grid_for(long n, int block, int cap) {
+    long g = (n + block - 1) / block;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
 #define FLAIR_LAUNCH_CHECK()                                                  \
     do {                                                                      \
         hipError_t e_ = hipGetLastError();                                    \

@@ -285,10 +285,11 @@ __device__ __forceinline__ void igemm_epilogue(const ConvArgs& a, const f32x16 (
 // 64 couts = two A fragments.  Pixel pitch 80 B and weight row pitch 80 B make every
 // ds_read_b128 conflict-free (odd multiples of 16 B).  Loads of chunk k+1 are issued before
 // the MFMAs of chunk k (register staging), written after a barrier.
-template <typename E, int TH, int RPW, int PF>
-__global__ __launch_bounds__(64 * TH / RPW, (2 * 64 * TH / RPW + 255) / 256)  // two workgroups per CU
+template <typename E, int TH>
+__global__ __launch_bounds__(64 * TH, (2 * 64 * TH + 255) / 256)  // two workgroups per CU
 void conv3x3_halo_kernel(ConvArgs a) {
     prefetch_kernargs<sizeof(ConvArgs)>();
+    constexpr int RPW = 1, PF = 1;                 // image rows per wavefront; register sets = prefetch depth in chunks
     constexpr int BKE = Mma<E>::BKE;
     constexpr int VEC = ET<E>::VEC;
     constexpr int NT = 64 * TH / RPW;              // one wavefront per RPW image rows
@@ -563,13 +564,13 @@ void conv3x3_halo_kernel(ConvArgs a) {
     }
 }
 
-template <typename E, int TH, int RPW, int PF>
+template <typename E, int TH>
 int launch_halo(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     a.nCoTiles = cdiv(a.Cout, 64);
     const int grid = a.T * cdiv(a.H, TH) * (a.W / 32) * a.nCoTiles;
     const size_t lds = (size_t)(TH + 2) * 34 * 80 + 64 * 9 * 80;
-    hipLaunchKernelGGL((conv3x3_halo_kernel<E, TH, RPW, PF>), dim3(grid), dim3(64 * TH / RPW), lds, s, a);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<E, TH>), dim3(grid), dim3(64 * TH), lds, s, a);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -584,9 +585,9 @@ int launch_halo(const ConvArgs& a0, hipStream_t s) {
 // matter, tools/probes/lds_mfma_probe.hip).  The two k-halves of a tile are summed through the
 // LDS staging tile of the epilogue.  Two LDS stages (one barrier per chunk), one workgroup per CU (up to 146 KB of LDS,
 // 256 VGPRs).  Needs Cout % 8 == 0.
-template <typename E, int TH, int RPW, int CF>
-__global__ __launch_bounds__(256 * TH / RPW / CF, (256 * TH / RPW / CF) / 256) void conv3x3_halo_ks_kernel(ConvArgs a) {
-    static_assert(RPW == 1 && CF == 2, "one image row and both 32-cout fragments per wave");
+template <typename E, int TH>
+__global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_kernel(ConvArgs a) {
+    constexpr int RPW = 1, CF = 2;                 // one image row and both 32-cout fragments per wave
     prefetch_kernargs<sizeof(ConvArgs)>();
     constexpr int NRG = TH / RPW;                  // row groups
     constexpr int NCG = 2 / CF;                    // cout-fragment groups (CF fragments of 32 couts per wave)
@@ -849,7 +850,7 @@ __global__ __launch_bounds__(256 * TH / RPW / CF, (256 * TH / RPW / CF) / 256) v
     }
 }
 
-template <typename E, int TH, int RPW, int CF>
+template <typename E, int TH>
 int launch_halo_ks(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     a.nCoTiles = cdiv(a.Cout, 64);
@@ -857,10 +858,10 @@ int launch_halo_ks(const ConvArgs& a0, hipStream_t s) {
     const size_t lds = 2 * ((size_t)(TH + 2) * 34 * 80 + 64 * 9 * 80);
     static LdsAttrOnce attr;
     {
-        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv3x3_halo_ks_kernel<E, TH, RPW, CF>));
+        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv3x3_halo_ks_kernel<E, TH>));
         FLAIR_CHECK(e == hipSuccess, "flair_conv_nhwc: hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL((conv3x3_halo_ks_kernel<E, TH, RPW, CF>), dim3(grid), dim3(256 * TH / RPW / CF), lds, s, a);
+    hipLaunchKernelGGL((conv3x3_halo_ks_kernel<E, TH>), dim3(grid), dim3(128 * TH), lds, s, a);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -891,15 +892,16 @@ struct DmaTile {
     int t, h0, w0, co0;
 };
 
-// NW wavefronts per workgroup, RPW image rows per wavefront (tile = NW * RPW rows x 32 pixels x 64 couts), NSTAGE LDS stages:
-//   <8, 2, 2> clip-level launches (the shape described above);
-//   <8, 1, 2> single-round launches of 256 tiles of 8 rows = the per-frame convolutions of the BasicVSR++ recurrence at 256^2
+// Eight wavefronts per workgroup, RPW image rows per wavefront (tile = 8 RPW rows x 32 pixels x 64 couts), two LDS stages:
+//   <2> clip-level launches (the shape described above);
+//   <1> single-round launches of 256 tiles of 8 rows = the per-frame convolutions of the BasicVSR++ recurrence at 256^2
 //   (c = 64) that conv_frame_kernel does not take: one tile per workgroup, where the gain is the short prologue (DMA instead
 //   of load -> ds_write -> barrier) and the register epilogue (no LDS transposition, no k-half reduction barriers).
-template <int NW, int RPW, int NSTAGE>
+template <int RPW>
 __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, int tilesPerXcd) {
     using E = bf16_t;
-    static_assert((RPW == 1 || RPW == 2) && NSTAGE == 2, "the clip-level and one-tile forms (two stages)");
+    static_assert(RPW == 1 || RPW == 2, "the clip-level and one-tile forms");
+    constexpr int NW = 8, NSTAGE = 2;
     constexpr int KSTEPS = 2;                              // 16-channel k-steps of a chunk
     constexpr int TH = NW * RPW, HWP = 34;                 // tile rows, halo pitch in pixels
     constexpr int HALO_ROWS = (TH + 2) * HWP;              // staged pixels
@@ -1372,15 +1374,15 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     }
 }
 
-template <int NW, int RPW, int NSTAGE>
-__global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void conv3x3_dma_kernel(ConvArgs a, int nTiles, int tilesPerXcd) {
+template <int RPW>
+__global__ __launch_bounds__(512, 2) void conv3x3_dma_kernel(ConvArgs a, int nTiles, int tilesPerXcd) {
     prefetch_kernargs<sizeof(ConvArgs) + 8>();
-    conv3x3_dma_body<NW, RPW, NSTAGE>(a, nTiles, tilesPerXcd);
+    conv3x3_dma_body<RPW>(a, nTiles, tilesPerXcd);
 }
 
-template <int NW, int RPW, int NSTAGE>
+template <int RPW>
 int launch_dma(const ConvArgs& a0, hipStream_t s) {
-    constexpr int TH = NW * RPW;
+    constexpr int NW = 8, NSTAGE = 2, TH = NW * RPW;
     ConvArgs a = a0;
     a.nCoTiles = cdiv(a.Cout, 64);
     a.tFast = a.KT == 3 && a.T > 1;
@@ -1393,18 +1395,17 @@ int launch_dma(const ConvArgs& a0, hipStream_t s) {
     const size_t lds = NSTAGE * (size_t)(HALO_INSTR + 36) * 1024 + NW * 1024 + 512;  // stages + idle DMA slots' scratch + two bias slots
     static LdsAttrOnce attr;
     {
-        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv3x3_dma_kernel<NW, RPW, NSTAGE>));
+        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv3x3_dma_kernel<RPW>));
         FLAIR_CHECK(e == hipSuccess, "flair_conv_nhwc: hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL((conv3x3_dma_kernel<NW, RPW, NSTAGE>), dim3(grid), dim3(64 * NW), lds, s, a, nTiles, tilesPerXcd);
-
+    hipLaunchKernelGGL(conv3x3_dma_kernel<RPW>, dim3(grid), dim3(64 * NW), lds, s, a, nTiles, tilesPerXcd);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One-tile 3x3 convolution with a THREE-deep halo ring (round 4): the per-frame convolutions of the 256^2 level (Cout <= 64, one
-// 8 x 32 tile per workgroup, 4-7 K chunks).  conv3x3_dma_kernel<8, 1, 2> stages halo + weights of a chunk together in two 58 KB stages:
+// 8 x 32 tile per workgroup, 4-7 K chunks).  conv3x3_dma_kernel<1> stages halo + weights of a chunk together in two 58 KB stages:
 // chunk n + 1 is requested when chunk n starts to be multiplied and must have landed 2 304 MFMA cycles later -- it has not (measured
 // ~2.2 us per chunk against 1.15 us of matrix work).  Three such stages do not fit the LDS; here the 22 KB halo images go through a
 // ring of three (requested TWO chunks ahead) and the 36 KB weight images through a ring of two, 138 KB together, every wave issuing
@@ -1414,9 +1415,7 @@ int launch_dma(const ConvArgs& a0, hipStream_t s) {
 // are requested at the head of the last chunk.
 
 // bf16, stride 1, KT = 1, W % 32 == 0, H % 8 == 0, segments multiples of 32 channels, activations none / ReLU / LeakyReLU(0.1 | 0.2).
-template <bool HALO3>       // true: the halo ring of three
-__global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {
-    static_assert(HALO3, "halo ring of three, weight ring of two");
+__global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {      // halo ring of three, weight ring of two
     prefetch_kernargs<sizeof(ConvArgs)>();
     using E = bf16_t;
     constexpr int NW = 8, HWP = 34;
@@ -1616,9 +1615,9 @@ static bool frame_kernel_ok(const ConvArgs& a) {
 static int launch_frame(const ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = (3 * 22 + 2 * 36) * 1024 + 1024;
     static LdsAttrOnce attr;
-    const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv_frame_kernel<true>));
+    const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&conv_frame_kernel));
     FLAIR_CHECK(e == hipSuccess, "flair_conv_nhwc: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(conv_frame_kernel<true>, dim3(a.T * (a.H / 8) * (a.W / 32)), dim3(512), lds, s, a);
+    hipLaunchKernelGGL(conv_frame_kernel, dim3(a.T * (a.H / 8) * (a.W / 32)), dim3(512), lds, s, a);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -1905,9 +1904,7 @@ int launch_pd(const ConvArgs& a0, hipStream_t s) {
     hipLaunchKernelGGL((conv_igemm_kernel<E, TC, TP, WC, WP, PD, KWID>), dim3(grid, a.splitK), dim3(256), lds, s, a);
     FLAIR_LAUNCH_CHECK();
     if (a.splitK > 1) {
-        long g = (a.P * (a.Cout / 4) + 255) / 256;
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel<E>, dim3((int)g), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(conv_splitk_reduce_kernel<E>, dim3(grid_for(a.P * (a.Cout / 4), 256, 2048)), dim3(256), 0, s, a);
         FLAIR_LAUNCH_CHECK();
     }
     return FLAIR_OK;
@@ -1925,12 +1922,26 @@ int launch(const ConvArgs& a, hipStream_t s) {
     return launch_pd<E, TC, TP, WC, WP, 4, 1>(a, s);
 }
 
+// The kernel forms.  The values are what flair_conv_variant() reports (benchmarks and ops.conv_variant read them): keep them.
+enum ConvVariant {
+    IGEMM_128x128 = 0,      // im2col tiles, couts x pixels
+    IGEMM_64x128 = 1,
+    IGEMM_64x64 = 2,
+    HALO_8 = 3,             // halo kernel, 8 / 4 / 2 image rows per workgroup
+    HALO_4 = 4,
+    HALO_2 = 5,
+    HALO_KS_8 = 6,          // its K-split form, 8 / 4 rows
+    HALO_KS_4 = 7,
+    DMA_CLIP = 8,           // persistent LDS-DMA kernel, 16-row tiles
+    DMA_FRAME = 9,          // one 8-row tile per workgroup: conv_frame_kernel where it applies, else the LDS-DMA kernel
+};
+
 // Split-K factor for the im2col path: deep-K convolutions on few pixels (the 16x16 .. 4x4
 // levels: K up to 13,824, <= 256 tiles) would otherwise run one long serial K loop per CU.
-int choose_split(const ConvArgs& a, int variant) {
-    if (variant > 2) return 1;
-    const int maxBlocks = variant == 0 ? 512 : 1024, maxSplit = 16;
-    const int tc = variant == 0 ? 128 : 64, tp = variant == 2 ? 64 : 128;
+int choose_split(const ConvArgs& a, ConvVariant variant) {
+    if (variant > IGEMM_64x64) return 1;
+    const int maxBlocks = variant == IGEMM_128x128 ? 512 : 1024, maxSplit = 16;
+    const int tc = variant == IGEMM_128x128 ? 128 : 64, tp = variant == IGEMM_64x64 ? 64 : 128;
     const int bke = 64 / (a.wBytes && a.CinTot ? (int)(a.wBytes / ((unsigned long long)a.Cout * a.KT * a.KH * a.KW * a.CinTot)) : 2);
     const long nk = (long)a.KT * a.KH * a.KW * (a.CinTot / bke);
     const long tiles = (long)cdiv(a.P, tp) * cdiv(a.Cout, tc);
@@ -1941,60 +1952,60 @@ int choose_split(const ConvArgs& a, int variant) {
     return s < 1 ? 1 : (int)s;
 }
 
-// Kernel choice.  3..5: halo kernel with 8/4/2 image rows per workgroup (3x3 spatial taps,
-// W a multiple of 32); 6/7: its K-split form (8/4 rows) when the launch is exactly one round of
-// 256 workgroups; 0..2: im2col tiles 128 couts x 128 pixels, 64 x 128, 64 x 64.
+// Kernel choice.  The halo kernel with 8/4/2 image rows per workgroup (3x3 spatial taps, W a multiple of 32); its
+// K-split form (8/4 rows) when the launch is exactly one round of 256 workgroups; else the im2col tiles.
 // Either way keep >= ~2 workgroups per CU when the problem allows it.
-int choose_variant(const ConvArgs& a) {
+ConvVariant choose_variant(const ConvArgs& a) {
     if (!a.reflect && a.stride == 1 && a.KH == 3 && a.KW == 3 && a.W % 32 == 0 && a.H >= 2) {
         const long per = (long)a.T * (a.W / 32) * cdiv(a.Cout, 64);
         // single-round launches (<= one workgroup per CU): K-split kernel, twice the wavefronts
         const bool ks = a.Cout % 8 == 0;
         // persistent LDS-DMA kernel (bf16): launches of more than one round of 8-row tiles whose 16-row tiles fill most CUs
-        if (a.esz == 2 && ks && a.act != FLAIR_ACT_GELU && a.H % 16 == 0 && per * cdiv(a.H, 8) > 256 && per * (a.H / 16) >= 192) return 8;
+        if (a.esz == 2 && ks && a.act != FLAIR_ACT_GELU && a.H % 16 == 0 && per * cdiv(a.H, 8) > 256 && per * (a.H / 16) >= 192) return DMA_CLIP;
         // single-round launches (per-frame convolutions): the one-tile-per-workgroup LDS-DMA form (bf16) at the 256^2 level,
         // the register-staged K-split kernel at the 128^2 level.  Measured (profiles/r03_dma_switches.txt): <8 rows> 12.6 vs
         // 13.6 us on 64->64; <4 rows> LDS-DMA forms lost to the K-split kernel (one wave per SIMD: 14.3 vs 11.9 us; eight
         // waves, K split: +0.5 ms per step).
         const bool dmaOk = a.esz == 2 && ks && a.act != FLAIR_ACT_GELU;
-        if (per * cdiv(a.H, 8) >= 256) return ks && per * cdiv(a.H, 8) <= 256 ? (dmaOk && a.H % 8 == 0 ? 9 : 6) : 3;
-        if (per * cdiv(a.H, 4) >= 256) return ks && per * cdiv(a.H, 4) <= 256 ? 7 : 4;
-        return 5;
+        if (per * cdiv(a.H, 8) >= 256) return ks && per * cdiv(a.H, 8) <= 256 ? (dmaOk && a.H % 8 == 0 ? DMA_FRAME : HALO_KS_8) : HALO_8;
+        if (per * cdiv(a.H, 4) >= 256) return ks && per * cdiv(a.H, 4) <= 256 ? HALO_KS_4 : HALO_4;
+        return HALO_2;
     }
     const long tiles128 = (long)cdiv(a.P, 128) * cdiv(a.Cout, 128);
-    if (a.Cout > 64 && tiles128 >= 512) return 0;
+    if (a.Cout > 64 && tiles128 >= 512) return IGEMM_128x128;
     // deep-K convolutions on few pixels (16x16 / 8x8 levels, K = 2304 .. 13,824): 128x128 tiles with split-K move half
     // the L2->LDS bytes of 64x64 tiles per flop; hipGraph-timed 256->256 3x3x3 at 16x16^2: 57.7 -> 43.4 us,
     // 512->512 at 16x8^2: 58.1 -> 45.2 us (4x4 stays on 64x64: 29.6 vs 34.0 us).
-    if (a.Cout >= 128 && a.P >= 1024 && tiles128 <= 64 && (long)a.KT * a.KH * a.KW * a.CinTot >= 2304) return 0;
+    if (a.Cout >= 128 && a.P >= 1024 && tiles128 <= 64 && (long)a.KT * a.KH * a.KW * a.CinTot >= 2304) return IGEMM_128x128;
     const long tiles64x128 = (long)cdiv(a.P, 128) * cdiv(a.Cout, 64);
-    if (tiles64x128 >= 512) return 1;
-    return 2;
+    if (tiles64x128 >= 512) return IGEMM_64x128;
+    return IGEMM_64x64;
 }
 
 template <typename E>
 int dispatch(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
-    const int variant = choose_variant(a);
+    const ConvVariant variant = choose_variant(a);
     a.splitK = a.part ? choose_split(a, variant) : 1;
     switch (variant) {
-        case 0: return launch<E, 128, 128, 2, 2>(a, s);
-        case 1: return launch<E, 64, 128, 1, 4>(a, s);
-        case 2: return launch<E, 64, 64, 2, 2>(a, s);
-        case 3: return launch_halo<E, 8, 1, 1>(a, s);
-        case 4: return launch_halo<E, 4, 1, 1>(a, s);
+        case IGEMM_128x128: return launch<E, 128, 128, 2, 2>(a, s);
+        case IGEMM_64x128: return launch<E, 64, 128, 1, 4>(a, s);
+        case IGEMM_64x64: return launch<E, 64, 64, 2, 2>(a, s);
+        case HALO_8: return launch_halo<E, 8>(a, s);
+        case HALO_4: return launch_halo<E, 4>(a, s);
         // one row per wave: two rows per wave were neutral end to end (90.95 vs 90.84 ms/step) and slower per call (26.1 vs 22.9 us)
-        case 6: return launch_halo_ks<E, 8, 1, 2>(a, s);
+        case HALO_KS_8: return launch_halo_ks<E, 8>(a, s);
         // two rows per wave leave 4 waves per CU here: +3.5 ms/step
-        case 7: return launch_halo_ks<E, 4, 1, 2>(a, s);
-        case 8: return launch_dma<8, 2, 2>(a, s);
-        case 9:
+        case HALO_KS_4: return launch_halo_ks<E, 4>(a, s);
+        case DMA_CLIP: return launch_dma<2>(a, s);
+        case DMA_FRAME:
             // conv_frame_kernel for the shapes it takes (same box: per-frame family 19.59 / 19.55 ms per step on
-            // conv3x3_dma_kernel<8, 1, 2>, 19.03 / 19.09 ms on conv_frame_kernel), conv3x3_dma_kernel<8, 1, 2> for the rest
+            // conv3x3_dma_kernel<1>, 19.03 / 19.09 ms on conv_frame_kernel), conv3x3_dma_kernel<1> for the rest
             if (frame_kernel_ok(a)) return launch_frame(a, s);
-            return launch_dma<8, 1, 2>(a, s);
-        default: return launch_halo<E, 2, 1, 1>(a, s);
+            return launch_dma<1>(a, s);
+        case HALO_2: break;
     }
+    return launch_halo<E, 2>(a, s);
 }
 
 }  // namespace
@@ -2029,7 +2040,7 @@ extern "C" int flair_conv_nhwc(const flair_conv_params* p, const void* const* x,
                                const float* bias, const float* frame_bias, const void* res0, const void* res1,
                                void* y, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     FLAIR_CHECK(p && x && w && y, "flair_conv_nhwc: null argument");
-    FLAIR_CHECK(p->dtype == FLAIR_F32 || p->dtype == FLAIR_BF16, "flair_conv_nhwc: bad dtype %d", p->dtype);
+    FLAIR_CHECK_DTYPE("flair_conv_nhwc", p->dtype);
     FLAIR_CHECK(p->nseg >= 1 && p->nseg <= 4, "flair_conv_nhwc: nseg %d not in 1..4", p->nseg);
     FLAIR_CHECK(p->T > 0 && p->H > 0 && p->W > 0 && p->Cout > 0, "flair_conv_nhwc: empty shape");
     FLAIR_CHECK((p->KT & 1) && (p->KH & 1) && (p->KW & 1), "flair_conv_nhwc: kernel taps must be odd");
@@ -2037,7 +2048,7 @@ extern "C" int flair_conv_nhwc(const flair_conv_params* p, const void* const* x,
     const int bke = p->dtype == FLAIR_BF16 ? 32 : 16;
     const int esz = p->dtype == FLAIR_BF16 ? 2 : 4;
     ConvArgs a{};
-    a.CinTot = 0;
+    fill_geometry(a, p);            // shape, taps, stride, CinTot, esz, wBytes, act, reflect
     for (int i = 0; i < p->nseg; ++i) {
         FLAIR_CHECK(x[i], "flair_conv_nhwc: segment %d is null", i);
         FLAIR_CHECK(p->seg_c[i] > 0 && p->seg_c[i] % bke == 0,
@@ -2048,7 +2059,6 @@ extern "C" int flair_conv_nhwc(const flair_conv_params* p, const void* const* x,
         a.x[i] = x[i];
         a.segC[i] = p->seg_c[i];
         a.segLd[i] = p->seg_ld[i];
-        a.CinTot += p->seg_c[i];
         // buffer resources cover single frames (halo kernels) or the few frames a pixel tile spans
         // (im2col kernels: at most 2 frames of this size), never the whole clip: only ONE FRAME has to
         // stay below 1 GiB
@@ -2057,14 +2067,14 @@ extern "C" int flair_conv_nhwc(const flair_conv_params* p, const void* const* x,
                     i, bytes);
         a.segBytes[i] = (unsigned)bytes;
     }
-    {
+    {   // a.wBytes is this value in 32 bits
         const unsigned long long wb = (unsigned long long)p->Cout * p->KT * p->KH * p->KW * a.CinTot * esz;
         FLAIR_CHECK(wb < 0x80000000ull, "flair_conv_nhwc: weights span %llu bytes (limit 2 GiB)", wb);
-        a.wBytes = (unsigned)wb;
     }
     // The epilogues move 8 couts of a pixel as 16-byte pieces of y / res0 / res1 whenever Cout % 8 == 0 (halo, K-split and
     // LDS-DMA kernels unconditionally), and f32 quads as 16 bytes in store_quad; only bf16 outputs with Cout % 8 == 4 are
-    // written and read in 8-byte quads everywhere.  So strides and residual pointers are 16-byte granular, except there.
+    // written and read in 8-byte quads everywhere.  So strides and residual pointers are 16-byte granular, except there
+    // (which is why these three are not FLAIR_CHECK_VIEW: its rule is the 16-byte one alone).
     const int gran = (p->dtype == FLAIR_BF16 && p->Cout % 8 != 0) ? 8 : 16;
     FLAIR_CHECK(p->y_ld >= p->Cout && (p->y_ld * esz) % gran == 0 && ((uintptr_t)y) % 16 == 0,
                 "flair_conv_nhwc: output stride/alignment (y_ld = %d: >= Cout = %d, a multiple of %d bytes; y 16-byte aligned)",
@@ -2094,30 +2104,23 @@ extern "C" int flair_conv_nhwc(const flair_conv_params* p, const void* const* x,
     a.res1Ld = p->res_ld[1];
     a.y = y;
     a.yLd = p->y_ld;
-    a.act = p->act;
     a.actParam = p->act_param;
     a.actPeriod = p->act_period;
     FLAIR_CHECK(p->act != FLAIR_ACT_DCN_OFFSETS || (p->act_period > 0 && p->act_period % 24 == 0),
                 "flair_conv_nhwc: FLAIR_ACT_DCN_OFFSETS needs act_period = 3 * deform_groups (multiple of 24), got %d",
                 p->act_period);
     a.outScale = p->out_scale;
-    {
-        ConvArgs g{};
-        fill_geometry(g, p);
-        a.stride = g.stride; a.Hin = g.Hin; a.Win = g.Win; a.T = g.T; a.H = g.H; a.W = g.W; a.P = g.P;
-        a.KT = g.KT; a.KH = g.KH; a.KW = g.KW; a.Cout = g.Cout; a.esz = g.esz;
-    }
     FLAIR_CHECK(a.stride == 1 || a.stride == 2, "flair_conv_nhwc: stride %d unsupported", p->stride);
     FLAIR_CHECK(!p->asym_pad || (a.stride == 2 && a.KH == a.KW && a.KT == 1 && p->H % 2 == 0 && p->W % 2 == 0),
                 "flair_conv_nhwc: asym_pad needs a square 2-D stride-2 kernel on even frames");
     a.tapShift = p->asym_pad ? a.KH / 2 : 0;
     FLAIR_CHECK(!p->reflect_pad || (!p->asym_pad && a.KT == 1 && p->H > a.KH / 2 && p->W > a.KW / 2),
                 "flair_conv_nhwc: reflect_pad needs a 2-D kernel smaller than the frame");
-    a.reflect = p->reflect_pad ? 1 : 0;
     a.part = nullptr;
     a.splitK = 1;
 
-    if (workspace && workspace_bytes >= flair_conv_workspace_bytes(p) && flair_conv_workspace_bytes(p) > 0) {
+    const size_t need = flair_conv_workspace_bytes(p);
+    if (workspace && need > 0 && workspace_bytes >= need) {
         FLAIR_CHECK(((uintptr_t)workspace) % 16 == 0, "flair_conv_nhwc: workspace alignment");
         a.part = reinterpret_cast<float*>(workspace);
     }

@@ -123,9 +123,21 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // PFD = gather register sets in flight (2: the loads of step k+1 fly while step k is blended; 3: also step k+2 --
 // for the c = 128 tiles, where only 8 wavefronts per CU exist to hide the gather round trip; 1 (round 4, the c = 64 per-frame form): the
 // loads of a step are waited for in the same step, at 64 VGPRs, and a SECOND workgroup on the CU hides them).
-template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME, int PFD, bool DOT2>
-__global__ __launch_bounds__(32 * NPF * TPP, (PFD == 1 ? 8 : NCF >= 4 ? 32 * NPF * TPP / 256 : 4)) void dcn_kernel(DcnArgs a) {
-    static_assert(DOT2 == (sizeof(E) == 2 && OFFS == 1 && ONEFRAME), "the dot2 blend exactly for the bf16 per-frame activated forms");
+// Both follow from the tile: they are no template parameters of their own.
+constexpr bool dcn_dot2(int esz, int offs, bool oneframe) { return esz == 2 && offs == 1 && oneframe; }
+constexpr int dcn_pfd(int esz, int ncf, int npf, int tpp, int offs, bool oneframe) {
+    // The 128-pixel c = 64 dot2 tile takes ONE gather register set (64 VGPRs instead of 106) so that TWO 16-wave workgroups share a CU (2 x 78 KB
+    // of LDS, 8 waves per SIMD): at 106 VGPRs a 256^2 frame's 512 workgroups ran as two rounds of one workgroup per CU, every barrier idling the CU
+    // for the skew of its 16 waves; now the other workgroup's waves fill the barrier skew and the gather round trips that the second register set
+    // hid.  Alignment family 7.86 / 7.98 -> 7.03 / 7.10 ms per step, step 78.07 / 77.61 -> 77.13 / 77.00 ms (same box).
+    return dcn_dot2(esz, offs, oneframe) && ncf == 2 && npf == 4 ? 1 : ncf >= 4 && tpp <= 8 ? 3 : 2;
+}
+
+template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME>
+__global__ __launch_bounds__(32 * NPF * TPP, (dcn_pfd(sizeof(E), NCF, NPF, TPP, OFFS, ONEFRAME) == 1 ? 8 : NCF >= 4 ? 32 * NPF * TPP / 256 : 4))
+void dcn_kernel(DcnArgs a) {
+    constexpr int PFD = dcn_pfd(sizeof(E), NCF, NPF, TPP, OFFS, ONEFRAME);
+    constexpr bool DOT2 = dcn_dot2(sizeof(E), OFFS, ONEFRAME);
     static_assert(OFFS != 2 || !ONEFRAME, "raw offsets: the general (batched) form only");
     prefetch_kernargs<sizeof(DcnArgs)>();
     constexpr int NT = 32 * NPF * TPP, NW = NT / 64;
@@ -545,9 +557,8 @@ __global__ __launch_bounds__(32 * NPF * TPP, (PFD == 1 ? 8 : NCF >= 4 ? 32 * NPF
 
 }  // namespace
 
-template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME, bool DOT2, int PFDSEL = 0>
-static int launch_dcn_v2(const DcnArgs& a0, hipStream_t stream) {
-    constexpr int PFD = PFDSEL > 0 ? PFDSEL : NCF >= 4 && TPP <= 8 ? 3 : 2;
+template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME>
+static int launch_dcn_v(const DcnArgs& a0, hipStream_t stream) {
     DcnArgs a = a0;
     if (ONEFRAME) {      // resources cover one frame: rows outside the image fall outside the resource
         const unsigned long long half = a.Cin / 2, hw = (unsigned long long)a.H * a.W;
@@ -559,30 +570,12 @@ static int launch_dcn_v2(const DcnArgs& a0, hipStream_t stream) {
     const size_t lds = (size_t)2 * TP * rawPitch + 2 * (TC + TP) * TPP * 16;
     static LdsAttrOnce attr;
     {
-        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&dcn_kernel<E, NCF, NPF, TPP, OFFS, ONEFRAME, PFD, DOT2>));
+        const hipError_t e = flair_max_lds_once(attr, reinterpret_cast<const void*>(&dcn_kernel<E, NCF, NPF, TPP, OFFS, ONEFRAME>));
         FLAIR_CHECK(e == hipSuccess, "flair_dcn_align: hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL((dcn_kernel<E, NCF, NPF, TPP, OFFS, ONEFRAME, PFD, DOT2>), dim3(cdiv(a.P, TP)), dim3(NT), lds, stream, a);
+    hipLaunchKernelGGL((dcn_kernel<E, NCF, NPF, TPP, OFFS, ONEFRAME>), dim3(cdiv(a.P, TP)), dim3(NT), lds, stream, a);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
-}
-
-// The dot2 blend for the bf16 per-frame activated forms of the recurrence; the f32 blend everywhere else
-template <typename E, int NCF, int NPF, int TPP, int OFFS, bool ONEFRAME>
-static int launch_dcn_v(const DcnArgs& a, hipStream_t stream) {
-    if constexpr (sizeof(E) == 2 && OFFS == 1 && ONEFRAME) {
-        if constexpr (NCF == 2 && NPF == 4) {
-            // ONE gather register set (64 VGPRs instead of 106) so that TWO 16-wave workgroups share a CU (2 x 78 KB of LDS, 8 waves per SIMD): at
-            // 106 VGPRs a 256^2 frame's 512 workgroups ran as two rounds of one workgroup per CU, every barrier idling the CU for the skew of
-            // its 16 waves; now the other workgroup's waves fill the barrier skew and the gather round trips that the second register set hid.
-            // Alignment family 7.86 / 7.98 -> 7.03 / 7.10 ms per step, step 78.07 / 77.61 -> 77.13 / 77.00 ms (same box).
-            return launch_dcn_v2<E, NCF, NPF, TPP, OFFS, ONEFRAME, true, 1>(a, stream);
-        } else {
-            return launch_dcn_v2<E, NCF, NPF, TPP, OFFS, ONEFRAME, true>(a, stream);
-        }
-    } else {
-        return launch_dcn_v2<E, NCF, NPF, TPP, OFFS, ONEFRAME, false>(a, stream);
-    }
 }
 
 template <typename E, int NCF, int NPF, int TPP>
@@ -646,7 +639,7 @@ extern "C" int flair_dcn_align(const flair_dcn_params* p, const void* x0, const 
                                const float* flow1, const float* flow2, const void* w, const float* bias, void* y,
                                hipStream_t stream) {
     FLAIR_CHECK(p && x0 && x1 && raw && w && y, "flair_dcn_align: null argument");
-    FLAIR_CHECK(p->dtype == FLAIR_F32 || p->dtype == FLAIR_BF16, "flair_dcn_align: bad dtype");
+    FLAIR_CHECK_DTYPE("flair_dcn_align", p->dtype);
     FLAIR_CHECK(p->raw_activated >= 0 && p->raw_activated <= 2, "flair_dcn_align: raw_activated = %d (0, 1 or 2)", p->raw_activated);
     const bool vqfr = p->raw_activated == 2;
     FLAIR_CHECK(!vqfr || (!flow1 && !flow2), "flair_dcn_align: raw_activated = 2 takes no flows");

@@ -335,13 +335,6 @@ __global__ void gather_mac_kernel(const float* x, long outer, int Lin, long inne
     }
 }
 
-inline int grid_for(long n) {
-    long g = (n + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
 extern "C" int flair_depthwise_filter(const float* x, int planes, int Hin, int Win, const float* filt, int kh, int kw,
@@ -357,7 +350,7 @@ extern "C" int flair_depthwise_filter(const float* x, int planes, int Hin, int W
         FLAIR_LAUNCH_CHECK();
         return FLAIR_OK;
     }
-    hipLaunchKernelGGL(depthwise_filter_kernel, dim3(grid_for((long)planes * Hout * Wout)), dim3(256),
+    hipLaunchKernelGGL(depthwise_filter_kernel, dim3(grid_for((long)planes * Hout * Wout, 256, 4096)), dim3(256),
                        (size_t)kh * kw * sizeof(float), stream, x, planes, Hin, Win, filt, kh, kw, pad, out_stride,
                        out_offset, stuff, stuff_offset, Hout, Wout, reflect, y);
     FLAIR_LAUNCH_CHECK();
@@ -375,13 +368,14 @@ extern "C" int flair_jpeg_roundtrip(const float* x, int N, int S, const float* q
         t.q2[i] = q_chroma[i];
         t.D[i] = dct8[i];
     }
-    hipLaunchKernelGGL(jpeg_to_ycbcr_kernel, dim3(grid_for((long)N * S * S)), dim3(256), 0, stream, x, N, S, workspace);
+    hipLaunchKernelGGL(jpeg_to_ycbcr_kernel, dim3(grid_for((long)N * S * S, 256, 4096)), dim3(256), 0, stream, x, N, S, workspace);
     FLAIR_LAUNCH_CHECK();
     const long blocks = (long)N * (S / 8) * (S / 8) + (long)N * 2 * (S / 16) * (S / 16);
     FLAIR_CHECK(!luma_q == !chroma_q, "flair_jpeg_roundtrip: give both level planes or neither");
-    hipLaunchKernelGGL(jpeg_blocks_kernel, dim3(grid_for(blocks)), dim3(64), 0, stream, workspace, N, S, t, luma_q, chroma_q);
+    // one 8x8 block per thread and grid-stride step; a 64-thread workgroup per 256 blocks
+    hipLaunchKernelGGL(jpeg_blocks_kernel, dim3(grid_for(blocks, 256, 4096)), dim3(64), 0, stream, workspace, N, S, t, luma_q, chroma_q);
     FLAIR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(jpeg_to_rgb_kernel, dim3(grid_for((long)N * S * S)), dim3(256), 0, stream, workspace, N, S, y);
+    hipLaunchKernelGGL(jpeg_to_rgb_kernel, dim3(grid_for((long)N * S * S, 256, 4096)), dim3(256), 0, stream, workspace, N, S, y);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -417,8 +411,8 @@ extern "C" int flair_gather_mac_f32(const float* x, long outer, int Lin, long in
                                     int taps, int Lout, float* y, hipStream_t stream) {
     FLAIR_CHECK(x && fov && w && y && outer > 0 && Lin > 0 && inner > 0 && taps > 0 && Lout > 0,
                 "flair_gather_mac_f32: bad argument");
-    hipLaunchKernelGGL(gather_mac_kernel, dim3(grid_for(outer * Lout * inner)), dim3(256), 0, stream, x, outer, Lin,
-                       inner, fov, w, taps, Lout, y);
+    hipLaunchKernelGGL(gather_mac_kernel, dim3(grid_for(outer * Lout * inner, 256, 4096)), dim3(256), 0, stream, x, outer,
+                       Lin, inner, fov, w, taps, Lout, y);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }

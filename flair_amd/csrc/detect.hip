@@ -8,18 +8,9 @@
 
 namespace {
 
-constexpr int DET_THREADS = 256;
-
-int det_grid(long n) {
-    long g = (n + DET_THREADS - 1) / DET_THREADS;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // nn.MaxPool2d(2, 2, ceil_mode=True): windows clipped at the bottom / right edge
 template <typename E>
-__global__ __launch_bounds__(DET_THREADS) void maxpool2s2_kernel(const E* __restrict__ x, int xLd, int F, int H, int W, int C,
+__global__ __launch_bounds__(256) void maxpool2s2_kernel(const E* __restrict__ x, int xLd, int F, int H, int W, int C,
                                                                  E* __restrict__ y, int yLd) {
     constexpr int VEC = ET<E>::VEC;
     const int cv = C / VEC, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
@@ -50,7 +41,7 @@ __global__ __launch_bounds__(DET_THREADS) void maxpool2s2_kernel(const E* __rest
 // and commutative, so the ring order gives the same bits as three separate pools).  Positions outside the frame do not take
 // part (-inf padding).  Slice 0 is only read, slices 1..3 only written: no thread reads what another writes.
 template <typename E>
-__global__ __launch_bounds__(DET_THREADS) void spp_pool_kernel(E* __restrict__ buf, int ld, int F, int H, int W, int C, int r0, int r1,
+__global__ __launch_bounds__(256) void spp_pool_kernel(E* __restrict__ buf, int ld, int F, int H, int W, int C, int r0, int r1,
                                                                int r2) {
     constexpr int VEC = ET<E>::VEC;
     const int cv = C / VEC;
@@ -90,7 +81,7 @@ __global__ __launch_bounds__(DET_THREADS) void spp_pool_kernel(E* __restrict__ b
 // y[p][2i] = a[p][i], y[p][2i + 1] = b[p][i]: torch.cat((a, b), 1) + channel_shuffle(., 2).  One thread: VEC channels of
 // a and of b -> 2 VEC consecutive channels of y (two 16-byte stores).
 template <typename E>
-__global__ __launch_bounds__(DET_THREADS) void interleave_kernel(const E* __restrict__ a, int aLd, const E* __restrict__ b, int bLd, int C,
+__global__ __launch_bounds__(256) void interleave_kernel(const E* __restrict__ a, int aLd, const E* __restrict__ b, int bLd, int C,
                                                                  long P, E* __restrict__ y, int yLd) {
     constexpr int VEC = ET<E>::VEC;
     const int cv = C / VEC;
@@ -122,7 +113,7 @@ struct AnchorArgs {
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + expf(-v)); }
 
 // Detect.forward, inference branch, one level (yolo.py:52-86).  One thread: the 16 values of (frame b, anchor a, cell y, x).
-__global__ __launch_bounds__(DET_THREADS) void yolo_decode_kernel(const float* __restrict__ x, int xLd, int B, int ny, int nx, int na,
+__global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restrict__ x, int xLd, int B, int ny, int nx, int na,
                                                                   float stride, AnchorArgs an, float* __restrict__ z, long N, long row0) {
     const long total = (long)B * na * ny * nx;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -161,7 +152,7 @@ struct LetterboxArgs {
 };
 
 // One thread: one output pixel, 16 channels (3 image channels, 13 zeros).
-__global__ __launch_bounds__(DET_THREADS) void letterbox_kernel(const float* __restrict__ src, LetterboxArgs p, float* __restrict__ y) {
+__global__ __launch_bounds__(256) void letterbox_kernel(const float* __restrict__ src, LetterboxArgs p, float* __restrict__ y) {
     const long total = (long)p.B * p.Ho * p.Wo, plane = (long)p.H * p.W;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int ox = (int)(i % p.Wo);
@@ -206,70 +197,62 @@ __global__ __launch_bounds__(DET_THREADS) void letterbox_kernel(const float* __r
 
 }  // namespace
 
-#define DET_CHECK_DTYPE(fn, dtype) FLAIR_CHECK((dtype) == FLAIR_BF16 || (dtype) == FLAIR_F32, fn ": dtype = %d (FLAIR_F32 or FLAIR_BF16)", (int)(dtype))
-
 extern "C" int flair_maxpool2x2s2_nhwc(const void* x, int x_ld, int dtype, int F, int H, int W, int C, void* y, int y_ld,
                                        hipStream_t stream) {
     FLAIR_CHECK(x && y, "flair_maxpool2x2s2_nhwc: x / y is null");
     FLAIR_CHECK(F > 0 && H > 0 && W > 0, "flair_maxpool2x2s2_nhwc: F = %d, H = %d, W = %d must be positive", F, H, W);
-    DET_CHECK_DTYPE("flair_maxpool2x2s2_nhwc", dtype);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(C > 0 && C % vec == 0, "flair_maxpool2x2s2_nhwc: C = %d is not a positive multiple of %d", C, vec);
-    FLAIR_CHECK_VIEW("flair_maxpool2x2s2_nhwc", "x", x, x_ld, C, vec);
-    FLAIR_CHECK_VIEW("flair_maxpool2x2s2_nhwc", "y", y, y_ld, C, vec);
-    const long n = (long)F * ((H + 1) / 2) * ((W + 1) / 2) * (C / vec);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(maxpool2s2_kernel<bf16_t>, dim3(det_grid(n)), dim3(DET_THREADS), 0, stream, (const bf16_t*)x, x_ld, F, H, W, C,
-                           (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(maxpool2s2_kernel<float>, dim3(det_grid(n)), dim3(DET_THREADS), 0, stream, (const float*)x, x_ld, F, H, W, C,
-                           (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_maxpool2x2s2_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(C > 0 && C % VEC == 0, "flair_maxpool2x2s2_nhwc: C = %d is not a positive multiple of %d", C, VEC);
+        FLAIR_CHECK_VIEW("flair_maxpool2x2s2_nhwc", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_maxpool2x2s2_nhwc", "y", y, y_ld, C, VEC);
+        const long n = (long)F * ((H + 1) / 2) * ((W + 1) / 2) * (C / VEC);
+        hipLaunchKernelGGL(maxpool2s2_kernel<E>, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, (const E*)x, x_ld, F, H, W, C,
+                           (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_spp_maxpool_nhwc(void* buf, int ld, int dtype, int F, int H, int W, int C, int k0, int k1, int k2,
                                       hipStream_t stream) {
     FLAIR_CHECK(buf, "flair_spp_maxpool_nhwc: buf is null");
     FLAIR_CHECK(F > 0 && H > 0 && W > 0, "flair_spp_maxpool_nhwc: F = %d, H = %d, W = %d must be positive", F, H, W);
-    DET_CHECK_DTYPE("flair_spp_maxpool_nhwc", dtype);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(C > 0 && C % vec == 0, "flair_spp_maxpool_nhwc: C = %d is not a positive multiple of %d", C, vec);
-    FLAIR_CHECK(k0 % 2 == 1 && k1 % 2 == 1 && k2 % 2 == 1 && 3 <= k0 && k0 < k1 && k1 < k2 && k2 <= 13,
-                "flair_spp_maxpool_nhwc: k = (%d, %d, %d) must be odd, strictly increasing, from 3 to 13", k0, k1, k2);
-    FLAIR_CHECK((long)ld >= 4L * C && ld % vec == 0 && reinterpret_cast<uintptr_t>(buf) % 16 == 0,
-                "flair_spp_maxpool_nhwc: buf stride/alignment: ld = %d must be >= 4 C = %ld and a multiple of %d elements, buf = %p 16-byte "
-                "aligned", ld, 4L * C, vec, (const void*)buf);
-    const long n = (long)F * H * W * (C / vec);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(spp_pool_kernel<bf16_t>, dim3(det_grid(n)), dim3(DET_THREADS), 0, stream, (bf16_t*)buf, ld, F, H, W, C, k0 / 2,
+    return flair_by_dtype("flair_spp_maxpool_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(C > 0 && C % VEC == 0, "flair_spp_maxpool_nhwc: C = %d is not a positive multiple of %d", C, VEC);
+        FLAIR_CHECK(k0 % 2 == 1 && k1 % 2 == 1 && k2 % 2 == 1 && 3 <= k0 && k0 < k1 && k1 < k2 && k2 <= 13,
+                    "flair_spp_maxpool_nhwc: k = (%d, %d, %d) must be odd, strictly increasing, from 3 to 13", k0, k1, k2);
+        // not FLAIR_CHECK_VIEW: the buffer holds the input and the three pooled copies side by side, ld >= 4 C (in long: 4 C may overflow)
+        FLAIR_CHECK((long)ld >= 4L * C && ld % VEC == 0 && reinterpret_cast<uintptr_t>(buf) % 16 == 0,
+                    "flair_spp_maxpool_nhwc: buf stride/alignment: ld = %d must be >= 4 C = %ld and a multiple of %d elements, buf = %p "
+                    "16-byte aligned", ld, 4L * C, VEC, (const void*)buf);
+        const long n = (long)F * H * W * (C / VEC);
+        hipLaunchKernelGGL(spp_pool_kernel<E>, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, (E*)buf, ld, F, H, W, C, k0 / 2,
                            k1 / 2, k2 / 2);
-    else
-        hipLaunchKernelGGL(spp_pool_kernel<float>, dim3(det_grid(n)), dim3(DET_THREADS), 0, stream, (float*)buf, ld, F, H, W, C, k0 / 2, k1 / 2,
-                           k2 / 2);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_channel_interleave_nhwc(const void* a, int a_ld, const void* b, int b_ld, int dtype, int C, long P, void* y,
                                              int y_ld, hipStream_t stream) {
     FLAIR_CHECK(a && b && y, "flair_channel_interleave_nhwc: a / b / y is null");
     FLAIR_CHECK(P > 0, "flair_channel_interleave_nhwc: P = %ld must be positive", P);
-    DET_CHECK_DTYPE("flair_channel_interleave_nhwc", dtype);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(C > 0 && C % vec == 0, "flair_channel_interleave_nhwc: C = %d is not a positive multiple of %d", C, vec);
-    FLAIR_CHECK_VIEW("flair_channel_interleave_nhwc", "a", a, a_ld, C, vec);
-    FLAIR_CHECK_VIEW("flair_channel_interleave_nhwc", "b", b, b_ld, C, vec);
-    FLAIR_CHECK_VIEW("flair_channel_interleave_nhwc", "y", y, y_ld, 2 * C, vec);
-    const long n = P * (C / vec);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(interleave_kernel<bf16_t>, dim3(det_grid(n)), dim3(DET_THREADS), 0, stream, (const bf16_t*)a, a_ld,
-                           (const bf16_t*)b, b_ld, C, P, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(interleave_kernel<float>, dim3(det_grid(n)), dim3(DET_THREADS), 0, stream, (const float*)a, a_ld, (const float*)b,
-                           b_ld, C, P, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_channel_interleave_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(C > 0 && C % VEC == 0, "flair_channel_interleave_nhwc: C = %d is not a positive multiple of %d", C, VEC);
+        FLAIR_CHECK_VIEW("flair_channel_interleave_nhwc", "a", a, a_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_channel_interleave_nhwc", "b", b, b_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_channel_interleave_nhwc", "y", y, y_ld, 2 * C, VEC);
+        hipLaunchKernelGGL(interleave_kernel<E>, dim3(grid_for(P * (C / VEC), 256, 4096)), dim3(256), 0, stream, (const E*)a, a_ld,
+                           (const E*)b, b_ld, C, P, (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_yolo_face_decode(const float* x, int x_ld, int B, int ny, int nx, int na, int no, float stride,
@@ -288,8 +271,8 @@ extern "C" int flair_yolo_face_decode(const float* x, int x_ld, int B, int ny, i
         an.w[a] = anchor_grid[2 * a];
         an.h[a] = anchor_grid[2 * a + 1];
     }
-    hipLaunchKernelGGL(yolo_decode_kernel, dim3(det_grid((long)B * na * ny * nx)), dim3(DET_THREADS), 0, stream, x, x_ld, B, ny, nx, na,
-                       stride, an, z, N, row0);
+    hipLaunchKernelGGL(yolo_decode_kernel, dim3(grid_for((long)B * na * ny * nx, 256, 4096)), dim3(256), 0, stream, x, x_ld, B, ny,
+                       nx, na, stride, an, z, N, row0);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -306,7 +289,7 @@ extern "C" int flair_letterbox_nhwc(const float* src, int B, int H, int W, int n
     FLAIR_CHECK(lo <= hi, "flair_letterbox_nhwc: lo = %g > hi = %g", (double)lo, (double)hi);
     FLAIR_CHECK_VIEW("flair_letterbox_nhwc", "y", y, y_ld, 16, 4);
     LetterboxArgs p = {B, H, W, new_h, new_w, top, left, Ho, Wo, y_ld, a, b, lo, hi, s, pad_value};
-    hipLaunchKernelGGL(letterbox_kernel, dim3(det_grid((long)B * Ho * Wo)), dim3(DET_THREADS), 0, stream, src, p, y);
+    hipLaunchKernelGGL(letterbox_kernel, dim3(grid_for((long)B * Ho * Wo, 256, 4096)), dim3(256), 0, stream, src, p, y);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }

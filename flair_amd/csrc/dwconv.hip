@@ -112,13 +112,6 @@ __global__ __launch_bounds__(DW_THREADS) void dwpw_kernel(const float* __restric
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int grid_for(long n) {
-    long g = (n + DW_THREADS - 1) / DW_THREADS;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
 extern "C" int flair_dwconv_nhwc(const float* x, int x_ld, int T, int H, int W, int C, int stride, const float* w_dw, const float* b_dw,
@@ -132,15 +125,15 @@ extern "C" int flair_dwconv_nhwc(const float* x, int x_ld, int T, int H, int W, 
         FLAIR_CHECK(Cout > 0 && Cout % 4 == 0, "flair_dwconv_nhwc: Cout = %d is not a positive multiple of 4", Cout);
         FLAIR_CHECK(C <= 512, "flair_dwconv_nhwc: C = %d > 512 with the 1x1 stage", C);
     }
-    FLAIR_CHECK(x_ld >= C && x_ld % 4 == 0, "flair_dwconv_nhwc: x_ld = %d (>= C = %d, multiple of 4)", x_ld, C);
-    FLAIR_CHECK(y_ld >= cy && y_ld % 4 == 0, "flair_dwconv_nhwc: y_ld = %d (>= %d, multiple of 4)", y_ld, cy);
-    FLAIR_CHECK(aligned16(x) && aligned16(y) && aligned16(w_dw) && aligned16(b_dw) && aligned16(w_pw) && aligned16(b_pw),
-                "flair_dwconv_nhwc: pointers must be 16-byte aligned");
+    FLAIR_CHECK_VIEW("flair_dwconv_nhwc", "x", x, x_ld, C, 4);
+    FLAIR_CHECK_VIEW("flair_dwconv_nhwc", "y", y, y_ld, cy, 4);
+    FLAIR_CHECK(aligned16(w_dw) && aligned16(b_dw) && aligned16(w_pw) && aligned16(b_pw),
+                "flair_dwconv_nhwc: weights and biases must be 16-byte aligned");
     const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
     const long total = (long)T * Ho * Wo;
     if (!w_pw) {
-        hipLaunchKernelGGL(dw3x3_kernel, dim3(grid_for(total * (C / 4))), dim3(DW_THREADS), 0, stream, x, x_ld, H, W, Ho, Wo, C, stride,
-                           w_dw, b_dw, act, total, y, y_ld);
+        hipLaunchKernelGGL(dw3x3_kernel, dim3(grid_for(total * (C / 4), DW_THREADS, 4096)), dim3(DW_THREADS), 0, stream, x, x_ld, H, W, Ho, Wo,
+                           C, stride, w_dw, b_dw, act, total, y, y_ld);
     } else {
         int tp = 256;                                            // pixels per workgroup: LDS of at most ~33 KiB
         while (tp > 16 && tp * C > 8192) tp /= 2;

@@ -10,13 +10,12 @@
 
 namespace {
 
-constexpr int DW7_THREADS = 256;
 constexpr int DW7_R = 4;          // output pixels per thread (along W)
 
 template <typename E>
-__global__ __launch_bounds__(DW7_THREADS) void dw7_kernel(const E* __restrict__ x, int xLd, int H, int W, int C,
-                                                          const float* __restrict__ w, const float* __restrict__ bias,
-                                                          long strips, E* __restrict__ y, int yLd) {
+__global__ __launch_bounds__(256) void dw7_kernel(const E* __restrict__ x, int xLd, int H, int W, int C,
+                                                  const float* __restrict__ w, const float* __restrict__ bias, long strips,
+                                                  E* __restrict__ y, int yLd) {
     constexpr int VEC = ET<E>::VEC;
     const int cv = C / VEC;
     const int ws = (W + DW7_R - 1) / DW7_R;                  // strips per row
@@ -84,22 +83,17 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 extern "C" int flair_dwconv7_nhwc(const void* x, int x_ld, int dtype, int T, int H, int W, int C, const float* w,
                                   const float* bias, void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(x && y && w && T > 0 && H > 0 && W > 0 && C > 0, "flair_dwconv7_nhwc: bad argument (x, y, w, T, H, W, C)");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_dwconv7_nhwc: bad dtype");
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(C % vec == 0, "flair_dwconv7_nhwc: C = %d is not a multiple of %d", C, vec);
-    FLAIR_CHECK(x_ld >= C && x_ld % vec == 0 && y_ld >= C && y_ld % vec == 0,
-                "flair_dwconv7_nhwc: x_ld = %d / y_ld = %d (>= C = %d, multiples of %d)", x_ld, y_ld, C, vec);
-    FLAIR_CHECK(aligned16(x) && aligned16(y) && aligned16(w) && aligned16(bias),
-                "flair_dwconv7_nhwc: pointers must be 16-byte aligned");
-    const long strips = (long)T * H * ((W + DW7_R - 1) / DW7_R);
-    long g = (strips * (C / vec) + DW7_THREADS - 1) / DW7_THREADS;
-    if (g > 8192) g = 8192;
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(dw7_kernel<bf16_t>, dim3((unsigned)g), dim3(DW7_THREADS), 0, stream, (const bf16_t*)x, x_ld, H, W, C, w,
-                           bias, strips, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(dw7_kernel<float>, dim3((unsigned)g), dim3(DW7_THREADS), 0, stream, (const float*)x, x_ld, H, W, C, w,
-                           bias, strips, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    FLAIR_CHECK(aligned16(w) && aligned16(bias), "flair_dwconv7_nhwc: w / bias must be 16-byte aligned");
+    return flair_by_dtype("flair_dwconv7_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(C % VEC == 0, "flair_dwconv7_nhwc: C = %d is not a multiple of %d", C, VEC);
+        FLAIR_CHECK_VIEW("flair_dwconv7_nhwc", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_dwconv7_nhwc", "y", y, y_ld, C, VEC);
+        const long strips = (long)T * H * ((W + DW7_R - 1) / DW7_R);
+        hipLaunchKernelGGL(dw7_kernel<E>, dim3(grid_for(strips * (C / VEC), 256, 8192)), dim3(256), 0, stream, (const E*)x, x_ld, H,
+                           W, C, w, bias, strips, (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

@@ -271,13 +271,6 @@ __global__ void maxpool3s2_kernel(const E* x, int xLd, int F, int H, int W, int 
     }
 }
 
-inline int grid_for(long n, int block = 256, int cap = 2048) {
-    long g = (n + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
 extern "C" int flair_nchw_f32_to_nhwc(const float* src, int N, int C, int H, int W, void* dst, int dtype,
@@ -285,16 +278,13 @@ extern "C" int flair_nchw_f32_to_nhwc(const float* src, int N, int C, int H, int
     FLAIR_CHECK(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && dst_coff >= 0 && dst_coff + C <= dst_ld,
                 "flair_nchw_f32_to_nhwc: bad argument");
     const long HW = (long)H * W;
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(grid_for(N * HW)), dim3(256), 0, stream, src, N, C, HW,
-                           (bf16_t*)dst, dst_ld, dst_coff);
-    else if (dtype == FLAIR_F32)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(N * HW)), dim3(256), 0, stream, src, N, C, HW,
-                           (float*)dst, dst_ld, dst_coff);
-    else
-        FLAIR_CHECK(false, "flair_nchw_f32_to_nhwc: bad dtype");
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_nchw_f32_to_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<E>, dim3(grid_for(N * HW, 256, 2048)), dim3(256), 0, stream, src, N, C, HW,
+                           (E*)dst, dst_ld, dst_coff);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_nhwc_to_nchw_f32(const void* src, int dtype, int src_ld, int src_coff, int N, int C, int H,
@@ -302,16 +292,13 @@ extern "C" int flair_nhwc_to_nchw_f32(const void* src, int dtype, int src_ld, in
     FLAIR_CHECK(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && src_coff >= 0 && src_coff + C <= src_ld,
                 "flair_nhwc_to_nchw_f32: bad argument");
     const long HW = (long)H * W;
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(grid_for(N * HW)), dim3(256), 0, stream,
-                           (const bf16_t*)src, src_ld, src_coff, N, C, HW, dst);
-    else if (dtype == FLAIR_F32)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for(N * HW)), dim3(256), 0, stream,
-                           (const float*)src, src_ld, src_coff, N, C, HW, dst);
-    else
-        FLAIR_CHECK(false, "flair_nhwc_to_nchw_f32: bad dtype");
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_nhwc_to_nchw_f32", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<E>, dim3(grid_for(N * HW, 256, 2048)), dim3(256), 0, stream,
+                           (const E*)src, src_ld, src_coff, N, C, HW, dst);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_timestep_embedding(const float* t, int N, int dim, float max_period, int sin_first,
@@ -349,7 +336,7 @@ extern "C" int flair_predict_xstart(const float* x, const float* model_out, int 
                                     float c_recip, float c_recipm1, int clip, float* x0, hipStream_t stream) {
     FLAIR_CHECK(x && model_out && x0 && N > 0 && C > 0 && Cm >= C, "flair_predict_xstart: bad argument");
     const long HW = (long)H * W;
-    hipLaunchKernelGGL(predict_xstart_kernel, dim3(grid_for((long)N * C * HW)), dim3(256), 0, stream, x, model_out, N,
+    hipLaunchKernelGGL(predict_xstart_kernel, dim3(grid_for((long)N * C * HW, 256, 2048)), dim3(256), 0, stream, x, model_out, N,
                        C, Cm, HW, c_recip, c_recipm1, clip, x0);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
@@ -363,7 +350,7 @@ extern "C" int flair_sampler_update(const flair_sampler_coefs* c, const float* x
     FLAIR_CHECK(!prev_recon || (c->frame_elems > 0 && c->frames > 0 && c->prev_frames > 0 &&
                                 c->prev_frames <= c->frames && n % (c->frame_elems * c->frames) == 0),
                 "flair_sampler_update: prev_recon geometry");
-    hipLaunchKernelGGL(sampler_update_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, x0, restored, aux, z,
+    hipLaunchKernelGGL(sampler_update_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, stream, x, x0, restored, aux, z,
                        prev_recon, (long)c->frame_elems, c->frames, c->prev_frames, n,
                        c->gamma, c->w_aux, c->sqrt_recip_alphas_cumprod, c->sqrt_recipm1_alphas_cumprod,
                        c->sqrt_alphas_cumprod_prev, c->sqrt_one_minus_alphas_cumprod_prev, c->sqrt_one_minus_rho,
@@ -375,33 +362,30 @@ extern "C" int flair_sampler_update(const flair_sampler_coefs* c, const float* x
 extern "C" int flair_axpby_f32(const float* x, const float* y, float a, float b, float lo, float hi, long n,
                                float* out, hipStream_t stream) {
     FLAIR_CHECK(x && out && n > 0, "flair_axpby_f32: bad argument");
-    hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, y, a, b, lo, hi, n, out);
+    hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, stream, x, y, a, b, lo, hi, n, out);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
 
 extern "C" int flair_scale_pixels(void* x, int dtype, int ld, int C, long P, const float* wmap, hipStream_t stream) {
     FLAIR_CHECK(x && wmap && P > 0 && C > 0, "flair_scale_pixels: bad argument");
-    FLAIR_CHECK(ld >= C && ld % (dtype == FLAIR_BF16 ? 8 : 4) == 0 && ((uintptr_t)x) % 16 == 0,
-                "flair_scale_pixels: ld = %d (>= C = %d, 16-byte granular) / x alignment", ld, C);
-    if (dtype == FLAIR_BF16) {
-        FLAIR_CHECK(C % 8 == 0, "flair_scale_pixels: C %% 8");
-        hipLaunchKernelGGL(scale_pixels_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(256), 0, stream,
-                           (bf16_t*)x, ld, C, P, wmap);
-    } else {
-        FLAIR_CHECK(C % 4 == 0, "flair_scale_pixels: C %% 4");
-        hipLaunchKernelGGL(scale_pixels_kernel<float>, dim3(grid_for(P * (C / 4))), dim3(256), 0, stream, (float*)x,
-                           ld, C, P, wmap);
-    }
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_scale_pixels", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK_VIEW("flair_scale_pixels", "x", x, ld, C, VEC);
+        FLAIR_CHECK(C % VEC == 0, "flair_scale_pixels: C %% %d", VEC);
+        hipLaunchKernelGGL(scale_pixels_kernel<E>, dim3(grid_for(P * (C / VEC), 256, 2048)), dim3(256), 0, stream, (E*)x, ld, C, P,
+                           wmap);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_affine_channels_f32(const float* x, int x_ld, int C, long P, float a, float b, float lo,
                                          float hi, const float* sub, const float* mul, float* y, int y_ld,
                                          hipStream_t stream) {
     FLAIR_CHECK(x && y && C > 0 && P > 0 && x_ld >= C && y_ld >= C, "flair_affine_channels_f32: bad argument");
-    hipLaunchKernelGGL(affine_channels_kernel, dim3(grid_for(P * C)), dim3(256), 0, stream, x, x_ld, C, P, a, b, lo,
+    hipLaunchKernelGGL(affine_channels_kernel, dim3(grid_for(P * C, 256, 2048)), dim3(256), 0, stream, x, x_ld, C, P, a, b, lo,
                        hi, sub, mul, y, y_ld);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
@@ -410,32 +394,26 @@ extern "C" int flair_affine_channels_f32(const float* x, int x_ld, int C, long P
 extern "C" int flair_add_frame_bias(void* x, int dtype, int ld, int C, int F, long HW, const float* bias,
                                     int bias_ld, hipStream_t stream) {
     FLAIR_CHECK(x && bias && C > 0 && F > 0 && HW > 0 && ld >= C && bias_ld >= C, "flair_add_frame_bias: bad argument");
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(add_frame_bias_kernel<bf16_t>, dim3(grid_for(F * HW * C)), dim3(256), 0, stream,
-                           (bf16_t*)x, ld, C, F, HW, bias, bias_ld);
-    else if (dtype == FLAIR_F32)
-        hipLaunchKernelGGL(add_frame_bias_kernel<float>, dim3(grid_for(F * HW * C)), dim3(256), 0, stream, (float*)x,
-                           ld, C, F, HW, bias, bias_ld);
-    else
-        FLAIR_CHECK(false, "flair_add_frame_bias: bad dtype");
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_add_frame_bias", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(add_frame_bias_kernel<E>, dim3(grid_for(F * HW * C, 256, 2048)), dim3(256), 0, stream, (E*)x, ld, C, F,
+                           HW, bias, bias_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_cast_channels(const float* src, int src_ld, int C, long P, void* dst, int dtype, int dst_ld,
                                    int dst_coff, hipStream_t stream) {
     FLAIR_CHECK(src && dst && C > 0 && P > 0 && src_ld >= C && dst_coff >= 0 && dst_coff + C <= dst_ld,
                 "flair_cast_channels: bad argument");
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(cast_channels_kernel<bf16_t>, dim3(grid_for(P * C)), dim3(256), 0, stream, src, src_ld, C,
-                           P, (bf16_t*)dst, dst_ld, dst_coff);
-    else if (dtype == FLAIR_F32)
-        hipLaunchKernelGGL(cast_channels_kernel<float>, dim3(grid_for(P * C)), dim3(256), 0, stream, src, src_ld, C, P,
-                           (float*)dst, dst_ld, dst_coff);
-    else
-        FLAIR_CHECK(false, "flair_cast_channels: bad dtype");
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_cast_channels", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(cast_channels_kernel<E>, dim3(grid_for(P * C, 256, 2048)), dim3(256), 0, stream, src, src_ld, C, P,
+                           (E*)dst, dst_ld, dst_coff);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 namespace {
@@ -460,7 +438,7 @@ extern "C" int flair_learned_range_variance(const float* model_out, int N, int C
                                             hipStream_t stream) {
     FLAIR_CHECK(model_out && variance && log_variance && N > 0 && C > 0, "flair_learned_range_variance: bad argument");
     const long HW = (long)H * W;
-    hipLaunchKernelGGL(learned_range_kernel, dim3(grid_for((long)N * C * HW)), dim3(256), 0, stream, model_out, N, C,
+    hipLaunchKernelGGL(learned_range_kernel, dim3(grid_for((long)N * C * HW, 256, 2048)), dim3(256), 0, stream, model_out, N, C,
                        HW, min_log, max_log, variance, log_variance);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
@@ -469,57 +447,51 @@ extern "C" int flair_learned_range_variance(const float* model_out, int N, int C
 extern "C" int flair_gated_blend(const void* x, int x_ld, const void* m, int m_ld, const float* gate, int gate_ld,
                                  int dtype, int C, int F, long HW, void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(x && m && gate && y && C > 0 && F > 0 && HW > 0 && gate_ld >= C, "flair_gated_blend: bad argument");
-    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_gated_blend: bad dtype");
-    {
-        const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-        FLAIR_CHECK_VIEW("flair_gated_blend", "x", x, x_ld, C, vec);
-        FLAIR_CHECK_VIEW("flair_gated_blend", "m", m, m_ld, C, vec);
-        FLAIR_CHECK_VIEW("flair_gated_blend", "y", y, y_ld, C, vec);
-    }
-    if (dtype == FLAIR_BF16) {
-        FLAIR_CHECK(C % 8 == 0, "flair_gated_blend: C %% 8");
-        hipLaunchKernelGGL(gated_blend_kernel<bf16_t>, dim3(grid_for(F * HW * (C / 8))), dim3(256), 0, stream,
-                           (const bf16_t*)x, x_ld, (const bf16_t*)m, m_ld, gate, gate_ld, C, F, HW, (bf16_t*)y, y_ld);
-    } else {
-        FLAIR_CHECK(C % 4 == 0, "flair_gated_blend: C %% 4");
-        hipLaunchKernelGGL(gated_blend_kernel<float>, dim3(grid_for(F * HW * (C / 4))), dim3(256), 0, stream,
-                           (const float*)x, x_ld, (const float*)m, m_ld, gate, gate_ld, C, F, HW, (float*)y, y_ld);
-    }
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_gated_blend", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK_VIEW("flair_gated_blend", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_gated_blend", "m", m, m_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_gated_blend", "y", y, y_ld, C, VEC);
+        FLAIR_CHECK(C % VEC == 0, "flair_gated_blend: C %% %d", VEC);
+        hipLaunchKernelGGL(gated_blend_kernel<E>, dim3(grid_for(F * HW * (C / VEC), 256, 2048)), dim3(256), 0, stream,
+                           (const E*)x, x_ld, (const E*)m, m_ld, gate, gate_ld, C, F, HW, (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_add_act_nhwc(const void* x0, int x0_ld, const void* x1, int x1_ld, int dtype, int C, long P, int act, void* y,
                                   int y_ld, hipStream_t stream) {
-    FLAIR_CHECK(x0 && y && C > 0 && P > 0 && x0_ld >= C && y_ld >= C && (!x1 || x1_ld >= C), "flair_add_act_nhwc: bad argument");
+    FLAIR_CHECK(x0 && y && C > 0 && P > 0, "flair_add_act_nhwc: bad argument");
     FLAIR_CHECK(act >= FLAIR_ACT_NONE && act <= FLAIR_ACT_GELU && act != FLAIR_ACT_DCN_OFFSETS, "flair_add_act_nhwc: activation %d", act);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4, esz = dtype == FLAIR_BF16 ? 2 : 4;
-    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_add_act_nhwc: bad dtype");
-    FLAIR_CHECK(C % vec == 0 && (x0_ld * esz) % 16 == 0 && (y_ld * esz) % 16 == 0 && (!x1 || (x1_ld * esz) % 16 == 0) &&
-                    ((uintptr_t)x0) % 16 == 0 && ((uintptr_t)y) % 16 == 0 && ((uintptr_t)x1) % 16 == 0,
-                "flair_add_act_nhwc: C %% %d, 16-byte aligned rows", vec);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(add_act_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(256), 0, stream, (const bf16_t*)x0, x0_ld,
-                           (const bf16_t*)x1, x1_ld, C, P, act, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(add_act_kernel<float>, dim3(grid_for(P * (C / 4))), dim3(256), 0, stream, (const float*)x0, x0_ld,
-                           (const float*)x1, x1_ld, C, P, act, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_add_act_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK_VIEW("flair_add_act_nhwc", "x0", x0, x0_ld, C, VEC);
+        if (x1) FLAIR_CHECK_VIEW("flair_add_act_nhwc", "x1", x1, x1_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_add_act_nhwc", "y", y, y_ld, C, VEC);
+        FLAIR_CHECK(C % VEC == 0, "flair_add_act_nhwc: C %% %d", VEC);
+        hipLaunchKernelGGL(add_act_kernel<E>, dim3(grid_for(P * (C / VEC), 256, 2048)), dim3(256), 0, stream, (const E*)x0, x0_ld,
+                           (const E*)x1, x1_ld, C, P, act, (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_maxpool3x3s2_nhwc(const void* x, int x_ld, int dtype, int F, int H, int W, int C, void* y, int y_ld,
                                        hipStream_t stream) {
-    FLAIR_CHECK(x && y && F > 0 && H > 0 && W > 0 && C > 0 && x_ld >= C && y_ld >= C, "flair_maxpool3x3s2_nhwc: bad argument");
-    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_maxpool3x3s2_nhwc: bad dtype");
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4, esz = dtype == FLAIR_BF16 ? 2 : 4;
-    FLAIR_CHECK(C % vec == 0 && (x_ld * esz) % 16 == 0 && (y_ld * esz) % 16 == 0 && ((uintptr_t)x) % 16 == 0 && ((uintptr_t)y) % 16 == 0,
-                "flair_maxpool3x3s2_nhwc: C %% %d, 16-byte aligned rows", vec);
-    const long n = (long)F * ((H + 1) / 2) * ((W + 1) / 2) * (C / vec);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(maxpool3s2_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, stream, (const bf16_t*)x, x_ld, F, H, W, C, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(maxpool3s2_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, (const float*)x, x_ld, F, H, W, C, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    FLAIR_CHECK(x && y && F > 0 && H > 0 && W > 0 && C > 0, "flair_maxpool3x3s2_nhwc: bad argument");
+    return flair_by_dtype("flair_maxpool3x3s2_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK_VIEW("flair_maxpool3x3s2_nhwc", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_maxpool3x3s2_nhwc", "y", y, y_ld, C, VEC);
+        FLAIR_CHECK(C % VEC == 0, "flair_maxpool3x3s2_nhwc: C %% %d", VEC);
+        const long n = (long)F * ((H + 1) / 2) * ((W + 1) / 2) * (C / VEC);
+        hipLaunchKernelGGL(maxpool3s2_kernel<E>, dim3(grid_for(n, 256, 2048)), dim3(256), 0, stream, (const E*)x, x_ld, F, H, W, C,
+                           (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

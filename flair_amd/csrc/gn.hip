@@ -502,7 +502,7 @@ extern "C" int flair_groupnorm_nhwc(const flair_gn_params* p, const void* x0, co
                                     const float* gamma, const float* beta, const float* film,
                                     void* y, void* raw, void* workspace, hipStream_t stream) {
     FLAIR_CHECK(p && x0 && gamma && beta && y && workspace, "flair_groupnorm_nhwc: null argument");
-    FLAIR_CHECK(p->dtype == FLAIR_F32 || p->dtype == FLAIR_BF16, "flair_groupnorm_nhwc: bad dtype");
+    FLAIR_CHECK_DTYPE("flair_groupnorm_nhwc", p->dtype);
     const int vec = p->dtype == FLAIR_BF16 ? 8 : 4;
     const int C = p->C;
     FLAIR_CHECK(C > 0 && C % vec == 0 && C % p->groups == 0, "flair_groupnorm_nhwc: C=%d groups=%d", C, p->groups);
@@ -549,29 +549,26 @@ extern "C" int flair_groupnorm_nhwc(const flair_gn_params* p, const void* x0, co
             a.act = p->act; a.resample = 0;
             a.y = y; a.yLd = p->y_ld; a.raw = nullptr; a.rawLd = 0; a.blocksPerFrame = 0;
             a.filmVec = film && p->film_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(film) & 15) == 0;
-            static LdsAttrOnce attr0, attr1;
-            {
-                const hipError_t e0 = flair_max_lds_once(attr0, reinterpret_cast<const void*>(&gn_group_kernel<bf16_t>), 128 * 1024);
-                const hipError_t e1 = flair_max_lds_once(attr1, reinterpret_cast<const void*>(&gn_group_kernel<float>), 128 * 1024);
-                FLAIR_CHECK(e0 == hipSuccess && e1 == hipSuccess, "flair_groupnorm_nhwc: hipFuncSetAttribute failed");
-            }
             const int grid = nstat * p->groups;
-            if (p->dtype == FLAIR_BF16)
-                hipLaunchKernelGGL(gn_group_kernel<bf16_t>, dim3(grid), dim3(1024), (size_t)groupBytes, stream, a, p->eps);
-            else
-                hipLaunchKernelGGL(gn_group_kernel<float>, dim3(grid), dim3(1024), (size_t)groupBytes, stream, a, p->eps);
-            FLAIR_LAUNCH_CHECK();
-            return FLAIR_OK;
+            return flair_by_dtype("flair_groupnorm_nhwc", p->dtype, [&](auto e) -> int {
+                using E = decltype(e);
+                static LdsAttrOnce attr;                              // one per element type: the lambda is instantiated for each
+                FLAIR_CHECK(flair_max_lds_once(attr, reinterpret_cast<const void*>(&gn_group_kernel<E>), 128 * 1024) == hipSuccess,
+                            "flair_groupnorm_nhwc: hipFuncSetAttribute failed");
+                hipLaunchKernelGGL(gn_group_kernel<E>, dim3(grid), dim3(1024), (size_t)groupBytes, stream, a, p->eps);
+                FLAIR_LAUNCH_CHECK();
+                return FLAIR_OK;
+            });
         }
     }
     const size_t lds = (size_t)2 * rows * C * sizeof(float);
-    if (p->dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(gn_partial_kernel<bf16_t>, dim3(nstat * bps), dim3(threads), lds, stream, s, C, p->groups, pix, bps,
+    const int rc = flair_by_dtype("flair_groupnorm_nhwc", p->dtype, [&](auto e) -> int {
+        hipLaunchKernelGGL(gn_partial_kernel<decltype(e)>, dim3(nstat * bps), dim3(threads), lds, stream, s, C, p->groups, pix, bps,
                            part);
-    else
-        hipLaunchKernelGGL(gn_partial_kernel<float>, dim3(nstat * bps), dim3(threads), lds, stream, s, C, p->groups, pix, bps,
-                           part);
-    FLAIR_LAUNCH_CHECK();
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
+    if (rc != FLAIR_OK) return rc;
     const int sg = nstat * p->groups;
     FLAIR_CHECK(sg % 4 == 0 || sg < 4, "flair_groupnorm_nhwc: groups");
     const int wavesPerBlock = sg >= 4 ? 4 : sg;
@@ -597,10 +594,9 @@ extern "C" int flair_groupnorm_nhwc(const flair_gn_params* p, const void* x0, co
     if (bpf > maxBpf) bpf = maxBpf;
     if (bpf < 1) bpf = 1;
     a.blocksPerFrame = bpf;
-    if (p->dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, dim3(p->F * bpf), dim3(threads), 0, stream, a);
-    else
-        hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(p->F * bpf), dim3(threads), 0, stream, a);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_groupnorm_nhwc", p->dtype, [&](auto e) -> int {
+        hipLaunchKernelGGL(gn_apply_kernel<decltype(e)>, dim3(p->F * bpf), dim3(threads), 0, stream, a);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

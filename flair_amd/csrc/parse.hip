@@ -204,78 +204,68 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 extern "C" int flair_global_avgpool_nhwc(const void* x, int dtype, int x_ld, int F, int H, int W, int C, float* y, int y_ld,
                                          hipStream_t stream) {
     FLAIR_CHECK(x && y, "flair_global_avgpool_nhwc: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_global_avgpool_nhwc: bad dtype %d", dtype);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
     FLAIR_CHECK(F > 0 && F <= 65535 && H > 0 && W > 0 && C > 0 && (long)H * W <= 0x7fffffffL,
                 "flair_global_avgpool_nhwc: bad shape F=%d H=%d W=%d C=%d", F, H, W, C);
-    FLAIR_CHECK(C % vec == 0 && x_ld % vec == 0 && x_ld >= C && aligned16(x),
-                "flair_global_avgpool_nhwc: C = %d and x_ld = %d must be multiples of %d, x_ld >= C, x 16-byte aligned", C, x_ld,
-                vec);
-    FLAIR_CHECK(y_ld >= C, "flair_global_avgpool_nhwc: y_ld = %d below C = %d", y_ld, C);
-    const dim3 grid(cdiv(C / vec, POOL_CHUNKS), F);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(global_avgpool_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, x_ld, H * W, C, y, y_ld);
-    else
-        hipLaunchKernelGGL(global_avgpool_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, x_ld, H * W, C, y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_global_avgpool_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(C % VEC == 0, "flair_global_avgpool_nhwc: C = %d must be a multiple of %d", C, VEC);
+        FLAIR_CHECK_VIEW("flair_global_avgpool_nhwc", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK(y_ld >= C, "flair_global_avgpool_nhwc: y_ld = %d below C = %d", y_ld, C);      // y: f32 scalars, no pieces
+        const dim3 grid(cdiv(C / VEC, POOL_CHUNKS), F);
+        hipLaunchKernelGGL(global_avgpool_kernel<E>, grid, dim3(256), 0, stream, (const E*)x, x_ld, H * W, C, y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_channel_gate_nhwc(const void* x, int x_ld, int dtype, int F, long HW, int C, const float* gate, int gate_ld,
                                        int gate_is_logit, int add_x, const float* bias, int bias_ld, const void* a, int a_ld,
                                        void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(x && gate && y, "flair_channel_gate_nhwc: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_channel_gate_nhwc: bad dtype %d", dtype);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
     FLAIR_CHECK(F > 0 && F <= 65535 && HW > 0 && HW <= 0x7fffffffL && C > 0, "flair_channel_gate_nhwc: bad shape F=%d HW=%ld C=%d",
                 F, HW, C);
-    FLAIR_CHECK(C % vec == 0 && x_ld % vec == 0 && y_ld % vec == 0 && x_ld >= C && y_ld >= C && aligned16(x) && aligned16(y),
-                "flair_channel_gate_nhwc: C = %d, x_ld = %d, y_ld = %d must be multiples of %d and >= C, x / y 16-byte aligned", C,
-                x_ld, y_ld, vec);
-    FLAIR_CHECK(!a || (a_ld % vec == 0 && a_ld >= C && aligned16(a)),
-                "flair_channel_gate_nhwc: a_ld = %d must be a multiple of %d and >= C, a 16-byte aligned", a_ld, vec);
-    FLAIR_CHECK(gate_ld >= C && (!bias || bias_ld >= C), "flair_channel_gate_nhwc: gate_ld = %d / bias_ld = %d below C = %d",
-                gate_ld, bias_ld, C);
-    long blocks = (HW * (C / vec) + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    const dim3 grid((unsigned)blocks, F);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(channel_gate_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, x_ld, gate, gate_ld,
-                           gate_is_logit, add_x, bias, bias_ld, (const bf16_t*)a, a_ld, (int)HW, C, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(channel_gate_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, x_ld, gate, gate_ld,
-                           gate_is_logit, add_x, bias, bias_ld, (const float*)a, a_ld, (int)HW, C, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_channel_gate_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(C % VEC == 0, "flair_channel_gate_nhwc: C = %d must be a multiple of %d", C, VEC);
+        FLAIR_CHECK_VIEW("flair_channel_gate_nhwc", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_channel_gate_nhwc", "y", y, y_ld, C, VEC);
+        if (a) FLAIR_CHECK_VIEW("flair_channel_gate_nhwc", "a", a, a_ld, C, VEC);
+        FLAIR_CHECK(gate_ld >= C && (!bias || bias_ld >= C), "flair_channel_gate_nhwc: gate_ld = %d / bias_ld = %d below C = %d",
+                    gate_ld, bias_ld, C);
+        const dim3 grid(grid_for(HW * (C / VEC), 256, 1024), F);
+        hipLaunchKernelGGL(channel_gate_kernel<E>, grid, dim3(256), 0, stream, (const E*)x, x_ld, gate, gate_ld, gate_is_logit, add_x,
+                           bias, bias_ld, (const E*)a, a_ld, (int)HW, C, (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_upsample_argmax_nhwc(const void* logits, int dtype, int ld, int F, int h, int w, int N, int H, int W,
                                           const float* table, int D, int* idx, float* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(logits && (idx || y), "flair_upsample_argmax_nhwc: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_upsample_argmax_nhwc: bad dtype %d", dtype);
     FLAIR_CHECK(F > 0 && F <= 65535 && h > 0 && w > 0 && H > 0 && W > 0 && (H + UA_ROWS - 1) / UA_ROWS <= 65535,
                 "flair_upsample_argmax_nhwc: bad shape F=%d h=%d w=%d H=%d W=%d", F, h, w, H, W);
     FLAIR_CHECK(N >= 1 && N <= 32, "flair_upsample_argmax_nhwc: N = %d classes (1 .. 32)", N);
     FLAIR_CHECK(ld >= N, "flair_upsample_argmax_nhwc: ld = %d below N = %d", ld, N);
     FLAIR_CHECK(!y || (table && D > 0 && y_ld >= D), "flair_upsample_argmax_nhwc: y needs a table, D = %d > 0 and y_ld = %d >= D",
                 D, y_ld);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    const int np = (N + 7) / 8 * 8;
-    // 16-byte loads when every pixel's class vector starts on a 16-byte boundary and its last chunk stays inside the
-    // pixel stride; element loads otherwise (same arithmetic)
-    int nload = (N + vec - 1) / vec * vec;
-    if (!(ld % vec == 0 && nload <= ld && aligned16(logits))) nload = 0;
-    const float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    const dim3 grid(cdiv(W, 256), cdiv(H, UA_ROWS), F);
-    int rc;
-    if (dtype == FLAIR_BF16)
-        rc = launch_upsample_argmax<bf16_t>(np, grid, stream, (const bf16_t*)logits, ld, h, w, N, nload, H, W, sy, sx, table, D,
-                                            idx, y, y_ld);
-    else
-        rc = launch_upsample_argmax<float>(np, grid, stream, (const float*)logits, ld, h, w, N, nload, H, W, sy, sx, table, D,
-                                           idx, y, y_ld);
-    FLAIR_CHECK(rc == 0, "flair_upsample_argmax_nhwc: no kernel for %d classes", N);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_upsample_argmax_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        const int np = (N + 7) / 8 * 8;
+        // 16-byte loads when every pixel's class vector starts on a 16-byte boundary and its last chunk stays inside the
+        // pixel stride; element loads otherwise (same arithmetic)
+        int nload = (N + VEC - 1) / VEC * VEC;
+        if (!(ld % VEC == 0 && nload <= ld && aligned16(logits))) nload = 0;
+        const float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
+        const float sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+        const dim3 grid(cdiv(W, 256), cdiv(H, UA_ROWS), F);
+        const int rc = launch_upsample_argmax<E>(np, grid, stream, (const E*)logits, ld, h, w, N, nload, H, W, sy, sx, table, D, idx,
+                                                 y, y_ld);
+        FLAIR_CHECK(rc == 0, "flair_upsample_argmax_nhwc: no kernel for %d classes", N);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

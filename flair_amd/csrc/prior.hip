@@ -257,30 +257,28 @@ extern "C" int flair_layernorm_nhwc(const void* x, int dtype, int x_ld, long row
                                     const float* beta, float eps, void* y, int y_ld, const float* pos, int pos_rows,
                                     void* y2, int y2_ld, hipStream_t stream) {
     FLAIR_CHECK(x && gamma && beta && y, "flair_layernorm_nhwc: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_layernorm_nhwc: bad dtype %d", dtype);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(rows > 0 && C > 0 && C % vec == 0 && C <= 64 * 4 * vec,
-                "flair_layernorm_nhwc: C=%d unsupported (a multiple of %d, at most %d)", C, vec, 64 * 4 * vec);
-    FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "x", x, x_ld, C, vec);
-    FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "y", y, y_ld, C, vec);
-    if (y2) {
-        FLAIR_CHECK(pos && pos_rows > 0, "flair_layernorm_nhwc: y2 needs the positional table");
-        FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "y2", y2, y2_ld, C, vec);
-    }
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL((layernorm_kernel<bf16_t, 4>), grid, dim3(256), 0, stream, (const bf16_t*)x, x_ld, rows, C, gamma,
-                           beta, eps, (bf16_t*)y, y_ld, pos, pos_rows, (bf16_t*)y2, y2_ld);
-    else
-        hipLaunchKernelGGL((layernorm_kernel<float, 4>), grid, dim3(256), 0, stream, (const float*)x, x_ld, rows, C, gamma,
-                           beta, eps, (float*)y, y_ld, pos, pos_rows, (float*)y2, y2_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_layernorm_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(rows > 0 && C > 0 && C % VEC == 0 && C <= 64 * 4 * VEC,
+                    "flair_layernorm_nhwc: C=%d unsupported (a multiple of %d, at most %d)", C, VEC, 64 * 4 * VEC);
+        FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "y", y, y_ld, C, VEC);
+        if (y2) {
+            FLAIR_CHECK(pos && pos_rows > 0, "flair_layernorm_nhwc: y2 needs the positional table");
+            FLAIR_CHECK_VIEW("flair_layernorm_nhwc", "y2", y2, y2_ld, C, VEC);
+        }
+        const dim3 grid((unsigned)((rows + 3) / 4));                 // one wavefront per row, four rows per block
+        hipLaunchKernelGGL((layernorm_kernel<E, 4>), grid, dim3(256), 0, stream, (const E*)x, x_ld, rows, C, gamma, beta, eps,
+                           (E*)y, y_ld, pos, pos_rows, (E*)y2, y2_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_attention_wide(const flair_attn_params* p, const void* qkv, void* out, hipStream_t stream) {
     FLAIR_CHECK(p && qkv && out, "flair_attention_wide: null argument");
-    FLAIR_CHECK(p->dtype == FLAIR_F32 || p->dtype == FLAIR_BF16, "flair_attention_wide: bad dtype %d", p->dtype);
+    FLAIR_CHECK_DTYPE("flair_attention_wide", p->dtype);
     const int vec = p->dtype == FLAIR_BF16 ? 8 : 4;
     FLAIR_CHECK(p->frames > 0 && p->L > 0 && p->heads > 0 && p->head_dim > 0 && p->head_dim % vec == 0,
                 "flair_attention_wide: shape");
@@ -312,65 +310,57 @@ extern "C" int flair_attention_wide(const flair_attn_params* p, const void* qkv,
         FLAIR_CHECK(e0 == hipSuccess && e1 == hipSuccess, "flair_attention_wide: hipFuncSetAttribute failed");
     }
     const dim3 grid((p->L + 15) / 16, p->frames * p->heads);
-    if (p->dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(attn_wide_kernel<bf16_t>, grid, dim3(256), lds, stream, a);
-    else
-        hipLaunchKernelGGL(attn_wide_kernel<float>, grid, dim3(256), lds, stream, a);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_attention_wide", p->dtype, [&](auto e) -> int {
+        hipLaunchKernelGGL(attn_wide_kernel<decltype(e)>, grid, dim3(256), lds, stream, a);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_argmax_codebook(const void* logits, int dtype, int ld, long rows, int N, const float* codebook, int D,
                                      const int* forced_idx, int* idx, void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(logits && codebook && y, "flair_argmax_codebook: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_argmax_codebook: bad dtype %d", dtype);
     FLAIR_CHECK(rows > 0 && N > 0 && D > 0 && ld >= N && y_ld >= D, "flair_argmax_codebook: shape");
     const dim3 grid((unsigned)((rows + 3) / 4));
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(argmax_codebook_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)logits, ld, rows, N,
-                           codebook, D, forced_idx, idx, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(argmax_codebook_kernel<float>, grid, dim3(256), 0, stream, (const float*)logits, ld, rows, N,
-                           codebook, D, forced_idx, idx, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_argmax_codebook", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(argmax_codebook_kernel<E>, grid, dim3(256), 0, stream, (const E*)logits, ld, rows, N, codebook, D,
+                           forced_idx, idx, (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_adain_nhwc(const void* content, int c_ld, const void* style, int s_ld, int dtype, int frames, int HW,
                                 int C, float eps, void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(content && style && y, "flair_adain_nhwc: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_adain_nhwc: bad dtype %d", dtype);
     FLAIR_CHECK(frames > 0 && HW > 1 && C > 0 && c_ld >= C && s_ld >= C && y_ld >= C, "flair_adain_nhwc: shape");
     const dim3 grid((C + 63) / 64, frames);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(adain_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)content, c_ld, (const bf16_t*)style,
-                           s_ld, HW, C, eps, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(adain_kernel<float>, grid, dim3(256), 0, stream, (const float*)content, c_ld, (const float*)style,
-                           s_ld, HW, C, eps, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_adain_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(adain_kernel<E>, grid, dim3(256), 0, stream, (const E*)content, c_ld, (const E*)style, s_ld, HW, C, eps,
+                           (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_sft_fuse(const void* dec, const void* scale, const void* shift, float w, int dtype, long n, void* y,
                               hipStream_t stream) {
     FLAIR_CHECK(dec && scale && shift && y, "flair_sft_fuse: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_sft_fuse: bad dtype %d", dtype);
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(n > 0 && n % vec == 0, "flair_sft_fuse: n=%ld must be a multiple of %d", n, vec);
+    // flat tensors, no stride: only the pointers' alignment
     FLAIR_CHECK(reinterpret_cast<uintptr_t>(dec) % 16 == 0, "flair_sft_fuse: dec = %p must be 16-byte aligned", dec);
     FLAIR_CHECK(reinterpret_cast<uintptr_t>(scale) % 16 == 0, "flair_sft_fuse: scale = %p must be 16-byte aligned", scale);
     FLAIR_CHECK(reinterpret_cast<uintptr_t>(shift) % 16 == 0, "flair_sft_fuse: shift = %p must be 16-byte aligned", shift);
     FLAIR_CHECK(reinterpret_cast<uintptr_t>(y) % 16 == 0, "flair_sft_fuse: y = %p must be 16-byte aligned", (const void*)y);
-    const long nvec = n / vec;
-    long blocks = (nvec + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(sft_fuse_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)dec,
-                           (const bf16_t*)scale, (const bf16_t*)shift, w, (bf16_t*)y, nvec);
-    else
-        hipLaunchKernelGGL(sft_fuse_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)dec,
-                           (const float*)scale, (const float*)shift, w, (float*)y, nvec);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_sft_fuse", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(n > 0 && n % VEC == 0, "flair_sft_fuse: n=%ld must be a multiple of %d", n, VEC);
+        const long nvec = n / VEC;
+        hipLaunchKernelGGL(sft_fuse_kernel<E>, dim3(grid_for(nvec, 256, 4096)), dim3(256), 0, stream, (const E*)dec, (const E*)scale,
+                           (const E*)shift, w, (E*)y, nvec);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

@@ -189,23 +189,14 @@ __global__ void slomo_blend_kernel(const E* pair, int pairLd, const E* flow, int
     for (int c = 0; c < 3; ++c) o[(size_t)c * H * W] = ((a0 * g0[c] + a1 * g1[c]) / den + mean[c]) * 2.f - 1.f;
 }
 
-// shared refusals; -> elements per 16 bytes, or 0 with the message set
-int slomo_check(const char* fn, int dtype, int B, int H, int W, const int* lds, int n) {
-    if (dtype != FLAIR_BF16 && dtype != FLAIR_F32) {
-        flair_set_error("%s: bad dtype", fn);
-        return 0;
-    }
-    if (B <= 0 || H <= 0 || W <= 0) {
-        flair_set_error("%s: bad shape B = %d, H = %d, W = %d", fn, B, H, W);
-        return 0;
-    }
-    const unsigned long long npix = (unsigned long long)B * H * W, esz = dtype == FLAIR_BF16 ? 2 : 4;
+// the size limits both entries share, for elements of esz bytes
+int slomo_check(const char* fn, unsigned long long esz, int B, int H, int W, const int* lds, int n) {
+    FLAIR_CHECK(B > 0 && H > 0 && W > 0, "%s: bad shape B = %d, H = %d, W = %d", fn, B, H, W);
+    const unsigned long long npix = (unsigned long long)B * H * W;
     for (int i = 0; i < n; ++i)
-        if (npix >= 0x80000000ull || (lds[i] > 0 && npix * lds[i] * esz >= 0x80000000ull)) {
-            flair_set_error("%s: a clip spans >= 2 GiB (32-bit gather offsets): call with fewer frames", fn);
-            return 0;
-        }
-    return dtype == FLAIR_BF16 ? 8 : 4;
+        FLAIR_CHECK(npix < 0x80000000ull && (lds[i] <= 0 || npix * lds[i] * esz < 0x80000000ull),
+                    "%s: a clip spans >= 2 GiB (32-bit gather offsets): call with fewer frames", fn);
+    return FLAIR_OK;
 }
 
 }  // namespace
@@ -215,23 +206,22 @@ extern "C" int flair_slomo_warp_pack(const void* pair, int pair_ld, const void* 
                                      hipStream_t stream) {
     FLAIR_CHECK(pair && flow && out, "flair_slomo_warp_pack: null pointer");
     const int lds[3] = {pair_ld, flow_ld, out_ld};
-    const int vec = slomo_check("flair_slomo_warp_pack", dtype, B, H, W, lds, 3);
-    if (!vec) return FLAIR_ERR_ARG;
-    FLAIR_CHECK(out_c >= SLOMO_IN && out_c <= SLOMO_IN_MAX && out_c % vec == 0,
-                "flair_slomo_warp_pack: out_c = %d must be %d .. %d channels and a multiple of %d", out_c, SLOMO_IN,
-                SLOMO_IN_MAX, vec);
-    FLAIR_CHECK_VIEW("flair_slomo_warp_pack", "pair", pair, pair_ld, 6, vec);
-    FLAIR_CHECK_VIEW("flair_slomo_warp_pack", "flow", flow, flow_ld, 4, vec);
-    FLAIR_CHECK_VIEW("flair_slomo_warp_pack", "out", out, out_ld, out_c, vec);
-    const dim3 grid(cdiv((long)B * H * W, 256));
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(slomo_warp_pack_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)pair, pair_ld,
-                           (const bf16_t*)flow, flow_ld, B, H, W, c0, c1, c2, c3, (bf16_t*)out, out_ld, out_c);
-    else
-        hipLaunchKernelGGL(slomo_warp_pack_kernel<float>, grid, dim3(256), 0, stream, (const float*)pair, pair_ld,
-                           (const float*)flow, flow_ld, B, H, W, c0, c1, c2, c3, (float*)out, out_ld, out_c);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_slomo_warp_pack", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        if (const int rc = slomo_check("flair_slomo_warp_pack", sizeof(E), B, H, W, lds, 3)) return rc;
+        FLAIR_CHECK(out_c >= SLOMO_IN && out_c <= SLOMO_IN_MAX && out_c % VEC == 0,
+                    "flair_slomo_warp_pack: out_c = %d must be %d .. %d channels and a multiple of %d", out_c, SLOMO_IN,
+                    SLOMO_IN_MAX, VEC);
+        FLAIR_CHECK_VIEW("flair_slomo_warp_pack", "pair", pair, pair_ld, 6, VEC);
+        FLAIR_CHECK_VIEW("flair_slomo_warp_pack", "flow", flow, flow_ld, 4, VEC);
+        FLAIR_CHECK_VIEW("flair_slomo_warp_pack", "out", out, out_ld, out_c, VEC);
+        // one thread per pixel, no grid-stride loop: every block
+        hipLaunchKernelGGL(slomo_warp_pack_kernel<E>, dim3(grid_for((long)B * H * W, 256, GRID_NO_CAP)), dim3(256), 0, stream,
+                           (const E*)pair, pair_ld, (const E*)flow, flow_ld, B, H, W, c0, c1, c2, c3, (E*)out, out_ld, out_c);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_slomo_blend(const void* pair, int pair_ld, const void* flow, int flow_ld, const void* io, int io_ld,
@@ -239,25 +229,24 @@ extern "C" int flair_slomo_blend(const void* pair, int pair_ld, const void* flow
                                  const float* mean, float* out, long out_batch_stride, hipStream_t stream) {
     FLAIR_CHECK(pair && flow && io && out && mean, "flair_slomo_blend: null pointer");
     const int lds[3] = {pair_ld, flow_ld, io_ld};
-    const int vec = slomo_check("flair_slomo_blend", dtype, B, H, W, lds, 3);
-    if (!vec) return FLAIR_ERR_ARG;
-    FLAIR_CHECK(t > 0.0 && t < 1.0, "flair_slomo_blend: t = %g is not inside (0, 1)", t);
-    FLAIR_CHECK_VIEW("flair_slomo_blend", "pair", pair, pair_ld, 6, vec);
-    FLAIR_CHECK_VIEW("flair_slomo_blend", "flow", flow, flow_ld, 4, vec);
-    FLAIR_CHECK_VIEW("flair_slomo_blend", "io", io, io_ld, 5, vec);
-    FLAIR_CHECK(out_batch_stride >= 3L * H * W && reinterpret_cast<uintptr_t>(out) % 4 == 0,
-                "flair_slomo_blend: out_batch_stride = %ld must be >= 3 H W = %ld floats, out = %p 4-byte aligned",
-                out_batch_stride, 3L * H * W, (const void*)out);
-    const dim3 grid(cdiv((long)B * H * W, 256));
-    const float t0 = (float)(1.0 - t), t1 = (float)t;            // co_eff = [1 - t, t]: Python doubles, cast by the multiply
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(slomo_blend_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)pair, pair_ld,
-                           (const bf16_t*)flow, flow_ld, (const bf16_t*)io, io_ld, B, H, W, c0, c1, c2, c3, t0, t1, mean[0],
-                           mean[1], mean[2], out, out_batch_stride);
-    else
-        hipLaunchKernelGGL(slomo_blend_kernel<float>, grid, dim3(256), 0, stream, (const float*)pair, pair_ld,
-                           (const float*)flow, flow_ld, (const float*)io, io_ld, B, H, W, c0, c1, c2, c3, t0, t1, mean[0],
-                           mean[1], mean[2], out, out_batch_stride);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_slomo_blend", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        if (const int rc = slomo_check("flair_slomo_blend", sizeof(E), B, H, W, lds, 3)) return rc;
+        FLAIR_CHECK(t > 0.0 && t < 1.0, "flair_slomo_blend: t = %g is not inside (0, 1)", t);
+        FLAIR_CHECK_VIEW("flair_slomo_blend", "pair", pair, pair_ld, 6, VEC);
+        FLAIR_CHECK_VIEW("flair_slomo_blend", "flow", flow, flow_ld, 4, VEC);
+        FLAIR_CHECK_VIEW("flair_slomo_blend", "io", io, io_ld, 5, VEC);
+        // not FLAIR_CHECK_VIEW: out is planar f32, written one float at a time
+        FLAIR_CHECK(out_batch_stride >= 3L * H * W && reinterpret_cast<uintptr_t>(out) % 4 == 0,
+                    "flair_slomo_blend: out_batch_stride = %ld must be >= 3 H W = %ld floats, out = %p 4-byte aligned",
+                    out_batch_stride, 3L * H * W, (const void*)out);
+        const float t0 = (float)(1.0 - t), t1 = (float)t;            // co_eff = [1 - t, t]: Python doubles, cast by the multiply
+        // one thread per pixel, no grid-stride loop: every block
+        hipLaunchKernelGGL(slomo_blend_kernel<E>, dim3(grid_for((long)B * H * W, 256, GRID_NO_CAP)), dim3(256), 0, stream,
+                           (const E*)pair, pair_ld, (const E*)flow, flow_ld, (const E*)io, io_ld, B, H, W, c0, c1, c2, c3, t0, t1,
+                           mean[0], mean[1], mean[2], out, out_batch_stride);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

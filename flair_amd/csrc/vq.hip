@@ -125,17 +125,15 @@ __global__ __launch_bounds__(256) void vq_nearest_kernel(const E* z, int ld, lon
 extern "C" int flair_vq_nearest_nhwc(const void* z, int dtype, int ld, long rows, int D, const float* codebook, int N,
                                      const int* forced_idx, int* idx, void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(codebook && y && (z || forced_idx), "flair_vq_nearest_nhwc: null argument");
-    FLAIR_CHECK(dtype == FLAIR_F32 || dtype == FLAIR_BF16, "flair_vq_nearest_nhwc: bad dtype %d", dtype);
     FLAIR_CHECK(rows > 0 && N > 0 && D > 0 && D % 4 == 0 && D <= VQ_MAX_D, "flair_vq_nearest_nhwc: D=%d unsupported", D);
     FLAIR_CHECK(ld >= D && y_ld >= D, "flair_vq_nearest_nhwc: strides");
     FLAIR_CHECK((reinterpret_cast<uintptr_t>(codebook) & 15) == 0, "flair_vq_nearest_nhwc: codebook must be 16-byte aligned");
     const dim3 grid((unsigned)((rows + VQ_TOK - 1) / VQ_TOK));
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(vq_nearest_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)z, ld, rows, D, codebook,
-                           N, forced_idx, idx, (bf16_t*)y, y_ld);
-    else
-        hipLaunchKernelGGL(vq_nearest_kernel<float>, grid, dim3(256), 0, stream, (const float*)z, ld, rows, D, codebook, N,
-                           forced_idx, idx, (float*)y, y_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_vq_nearest_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(vq_nearest_kernel<E>, grid, dim3(256), 0, stream, (const E*)z, ld, rows, D, codebook, N, forced_idx, idx,
+                           (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

@@ -352,45 +352,32 @@ __global__ void resize_kernel(const E* x, int xLd, int F, int Hi, int Wi, int C,
     }
 }
 
-inline int grid_for(long n) {
-    long g = (n + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
 extern "C" int flair_flow_warp(const void* x, int dtype, int x_ld, const float* flow, int flow_ld, int F, int H,
                                int W, int C, int border, void* y, int y_ld, hipStream_t stream) {
     FLAIR_CHECK(x && flow && y && F > 0 && H > 0 && W > 0 && C > 0 && flow_ld >= 2 && flow_ld % 2 == 0,
                 "flair_flow_warp: bad argument");
-    FLAIR_CHECK((unsigned long long)F * H * W * x_ld * (dtype == FLAIR_BF16 ? 2 : 4) < 0x80000000ull,
-                "flair_flow_warp: the source clip spans >= 2 GiB (32-bit gather offsets): call per frame");
-    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_flow_warp: bad dtype");
-    {
-        const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-        FLAIR_CHECK_VIEW("flair_flow_warp", "x", x, x_ld, C, vec);
-        FLAIR_CHECK_VIEW("flair_flow_warp", "y", y, y_ld, C, vec);
-    }
-    if (dtype == FLAIR_BF16) {
-        FLAIR_CHECK(C % 8 == 0, "flair_flow_warp: bf16 needs C %% 8 == 0");
-        hipLaunchKernelGGL(flow_warp_kernel<bf16_t>, dim3(grid_for((long)F * H * W * (C / 8))), dim3(256), 0, stream,
-                           (const bf16_t*)x, x_ld, flow, flow_ld, F, H, W, C, border, (bf16_t*)y, y_ld);
-    } else {
-        FLAIR_CHECK(C % 4 == 0, "flair_flow_warp: f32 needs C %% 4 == 0");
-        hipLaunchKernelGGL(flow_warp_kernel<float>, dim3(grid_for((long)F * H * W * (C / 4))), dim3(256), 0, stream,
-                           (const float*)x, x_ld, flow, flow_ld, F, H, W, C, border, (float*)y, y_ld);
-    }
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_flow_warp", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK((unsigned long long)F * H * W * x_ld * sizeof(E) < 0x80000000ull,
+                    "flair_flow_warp: the source clip spans >= 2 GiB (32-bit gather offsets): call per frame");
+        FLAIR_CHECK_VIEW("flair_flow_warp", "x", x, x_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_flow_warp", "y", y, y_ld, C, VEC);
+        FLAIR_CHECK(C % VEC == 0, "flair_flow_warp: needs C %% %d == 0", VEC);
+        hipLaunchKernelGGL(flow_warp_kernel<E>, dim3(grid_for((long)F * H * W * (C / VEC), 256, 4096)), dim3(256), 0, stream,
+                           (const E*)x, x_ld, flow, flow_ld, F, H, W, C, border, (E*)y, y_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_flow_compose(const float* f1, const float* f2, int F, int H, int W, float* out,
                                   hipStream_t stream) {
     FLAIR_CHECK(f1 && f2 && out && F > 0 && H > 0 && W > 0, "flair_flow_compose: bad argument");
-    hipLaunchKernelGGL(flow_compose_kernel, dim3(grid_for((long)F * H * W)), dim3(256), 0, stream, f1, f2, F, H, W,
-                       out);
+    hipLaunchKernelGGL(flow_compose_kernel, dim3(grid_for((long)F * H * W, 256, 4096)), dim3(256), 0, stream, f1, f2, F, H,
+                       W, out);
     FLAIR_LAUNCH_CHECK();
     return FLAIR_OK;
 }
@@ -402,43 +389,34 @@ extern "C" int flair_resize_nhwc(const void* x, int dtype, int x_ld, int F, int 
     FLAIR_CHECK(mode != 3 || (Hi == 2 * Ho && Wi == 2 * Wo), "flair_resize_nhwc: avg-pool needs exact 2x");
     FLAIR_CHECK(x_ld >= C && y_ld >= C, "flair_resize_nhwc: x_ld = %d / y_ld = %d below C = %d", x_ld, y_ld, C);
     const long n = (long)F * Ho * Wo * C;
-    {
-        const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-        if (mode == 4 && Ho == 2 * Hi && Wo == 2 * Wi && C % vec == 0 && x_ld % vec == 0 && y_ld % vec == 0 &&
-            scale_c0 == 1.f && scale_c1 == 1.f && (dtype == FLAIR_BF16 || dtype == FLAIR_F32)) {
-            if (dtype == FLAIR_BF16)
-                hipLaunchKernelGGL(nearest2x_kernel<bf16_t>, dim3(grid_for(n / vec)), dim3(256), 0, stream, (const bf16_t*)x,
-                                   x_ld, (long)F, Hi, Wi, C, (bf16_t*)y, y_ld);
-            else
-                hipLaunchKernelGGL(nearest2x_kernel<float>, dim3(grid_for(n / vec)), dim3(256), 0, stream, (const float*)x,
-                                   x_ld, (long)F, Hi, Wi, C, (float*)y, y_ld);
+    FLAIR_CHECK_DTYPE("flair_resize_nhwc", dtype);
+    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
+    // whole 16-byte pieces and no per-channel scale: the two vector kernels
+    const bool pieces = C % vec == 0 && x_ld % vec == 0 && y_ld % vec == 0 && scale_c0 == 1.f && scale_c1 == 1.f;
+    if (mode == 4 && Ho == 2 * Hi && Wo == 2 * Wi && pieces)
+        return flair_by_dtype("flair_resize_nhwc", dtype, [&](auto e) -> int {
+            using E = decltype(e);
+            hipLaunchKernelGGL(nearest2x_kernel<E>, dim3(grid_for(n / vec, 256, 4096)), dim3(256), 0, stream, (const E*)x, x_ld,
+                               (long)F, Hi, Wi, C, (E*)y, y_ld);
             FLAIR_LAUNCH_CHECK();
             return FLAIR_OK;
-        }
-        // feature maps (16 channels and more: images and flows keep the scalar kernel)
-        if (mode == 0 && C >= 16 && C % vec == 0 && x_ld % vec == 0 && y_ld % vec == 0 && scale_c0 == 1.f && scale_c1 == 1.f &&
-            ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 &&
-            (dtype == FLAIR_BF16 || dtype == FLAIR_F32)) {
-            if (dtype == FLAIR_BF16)
-                hipLaunchKernelGGL(bilinear_vec_kernel<bf16_t>, dim3(grid_for(n / vec)), dim3(256), 0, stream, (const bf16_t*)x,
-                                   x_ld, (long)F, Hi, Wi, C, Ho, Wo, (bf16_t*)y, y_ld);
-            else
-                hipLaunchKernelGGL(bilinear_vec_kernel<float>, dim3(grid_for(n / vec)), dim3(256), 0, stream, (const float*)x,
-                                   x_ld, (long)F, Hi, Wi, C, Ho, Wo, (float*)y, y_ld);
+        });
+    // feature maps (16 channels and more: images and flows keep the scalar kernel)
+    if (mode == 0 && C >= 16 && pieces && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0)
+        return flair_by_dtype("flair_resize_nhwc", dtype, [&](auto e) -> int {
+            using E = decltype(e);
+            hipLaunchKernelGGL(bilinear_vec_kernel<E>, dim3(grid_for(n / vec, 256, 4096)), dim3(256), 0, stream, (const E*)x, x_ld,
+                               (long)F, Hi, Wi, C, Ho, Wo, (E*)y, y_ld);
             FLAIR_LAUNCH_CHECK();
             return FLAIR_OK;
-        }
-    }
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(resize_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, stream, (const bf16_t*)x, x_ld, F,
-                           Hi, Wi, C, mode, Ho, Wo, (bf16_t*)y, y_ld, scale_c0, scale_c1);
-    else if (dtype == FLAIR_F32)
-        hipLaunchKernelGGL(resize_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, (const float*)x, x_ld, F,
-                           Hi, Wi, C, mode, Ho, Wo, (float*)y, y_ld, scale_c0, scale_c1);
-    else
-        FLAIR_CHECK(false, "flair_resize_nhwc: bad dtype");
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+        });
+    return flair_by_dtype("flair_resize_nhwc", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        hipLaunchKernelGGL(resize_kernel<E>, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, (const E*)x, x_ld, F, Hi, Wi, C, mode,
+                           Ho, Wo, (E*)y, y_ld, scale_c0, scale_c1);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_vsrpp_warp2(const void* prop, int prop_ld, const void* feat2, int feat2_ld, const float* flow1,
@@ -446,29 +424,25 @@ extern "C" int flair_vsrpp_warp2(const void* prop, int prop_ld, const void* feat
                                  void* cond2, int cond2_ld, hipStream_t stream) {
     FLAIR_CHECK(prop && flow1 && cond1 && H > 0 && W > 0 && C > 0, "flair_vsrpp_warp2: bad argument");
     FLAIR_CHECK(!flow2 || (feat2 && cond2), "flair_vsrpp_warp2: second-order inputs incomplete");
-    const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_vsrpp_warp2: bad dtype");
-    FLAIR_CHECK(C % vec == 0, "flair_vsrpp_warp2: C %% %d", vec);
-    FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "prop", prop, prop_ld, C, vec);
-    FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "cond1", cond1, cond1_ld, C, vec);
-    if (flow2) {
-        FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "feat2", feat2, feat2_ld, C, vec);
-        FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "cond2", cond2, cond2_ld, C, vec);
-    }
-    FLAIR_CHECK((unsigned long long)H * W * prop_ld * (16 / vec) < 0x80000000ull &&
-                    (!flow2 || (unsigned long long)H * W * feat2_ld * (16 / vec) < 0x80000000ull),
-                "flair_vsrpp_warp2: a source frame spans >= 2 GiB");
-    const dim3 grid(grid_for((long)H * W * (C / vec)), flow2 ? 2 : 1);
-    if (dtype == FLAIR_BF16)
-        hipLaunchKernelGGL(vsrpp_warp2_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)prop, prop_ld,
-                           (const bf16_t*)feat2, feat2_ld, flow1, flow2, H, W, C, (bf16_t*)cond1, cond1_ld,
-                           (bf16_t*)cond2, cond2_ld);
-    else
-        hipLaunchKernelGGL(vsrpp_warp2_kernel<float>, grid, dim3(256), 0, stream, (const float*)prop, prop_ld,
-                           (const float*)feat2, feat2_ld, flow1, flow2, H, W, C, (float*)cond1, cond1_ld,
-                           (float*)cond2, cond2_ld);
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+    return flair_by_dtype("flair_vsrpp_warp2", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK(C % VEC == 0, "flair_vsrpp_warp2: C %% %d", VEC);
+        FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "prop", prop, prop_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "cond1", cond1, cond1_ld, C, VEC);
+        if (flow2) {
+            FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "feat2", feat2, feat2_ld, C, VEC);
+            FLAIR_CHECK_VIEW("flair_vsrpp_warp2", "cond2", cond2, cond2_ld, C, VEC);
+        }
+        FLAIR_CHECK((unsigned long long)H * W * prop_ld * sizeof(E) < 0x80000000ull &&
+                        (!flow2 || (unsigned long long)H * W * feat2_ld * sizeof(E) < 0x80000000ull),
+                    "flair_vsrpp_warp2: a source frame spans >= 2 GiB");
+        const dim3 grid(grid_for((long)H * W * (C / VEC), 256, 4096), flow2 ? 2 : 1);
+        hipLaunchKernelGGL(vsrpp_warp2_kernel<E>, grid, dim3(256), 0, stream, (const E*)prop, prop_ld, (const E*)feat2, feat2_ld,
+                           flow1, flow2, H, W, C, (E*)cond1, cond1_ld, (E*)cond2, cond2_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }
 
 extern "C" int flair_vsrpp_prep(const void* prop, int prop_ld, const void* feat2, int feat2_ld, const float* flow1,
@@ -477,31 +451,25 @@ extern "C" int flair_vsrpp_prep(const void* prop, int prop_ld, const void* feat2
                                 hipStream_t stream) {
     FLAIR_CHECK(prop && flow1 && cond1 && flowpad && H > 0 && W > 0 && C > 0, "flair_vsrpp_prep: bad argument");
     FLAIR_CHECK(!flow_prev || (feat2 && cond2 && flow2_out), "flair_vsrpp_prep: second-order inputs incomplete");
-    FLAIR_CHECK(dtype == FLAIR_BF16 || dtype == FLAIR_F32, "flair_vsrpp_prep: bad dtype");
-    {
-        const int vec = dtype == FLAIR_BF16 ? 8 : 4;
-        FLAIR_CHECK_VIEW("flair_vsrpp_prep", "prop", prop, prop_ld, C, vec);
-        FLAIR_CHECK_VIEW("flair_vsrpp_prep", "cond1", cond1, cond1_ld, C, vec);
+    return flair_by_dtype("flair_vsrpp_prep", dtype, [&](auto e) -> int {
+        using E = decltype(e);
+        constexpr int VEC = ET<E>::VEC;
+        FLAIR_CHECK_VIEW("flair_vsrpp_prep", "prop", prop, prop_ld, C, VEC);
+        FLAIR_CHECK_VIEW("flair_vsrpp_prep", "cond1", cond1, cond1_ld, C, VEC);
         if (flow_prev) {
-            FLAIR_CHECK_VIEW("flair_vsrpp_prep", "feat2", feat2, feat2_ld, C, vec);
-            FLAIR_CHECK_VIEW("flair_vsrpp_prep", "cond2", cond2, cond2_ld, C, vec);
+            FLAIR_CHECK_VIEW("flair_vsrpp_prep", "feat2", feat2, feat2_ld, C, VEC);
+            FLAIR_CHECK_VIEW("flair_vsrpp_prep", "cond2", cond2, cond2_ld, C, VEC);
         }
-        // flowpad is a convolution input segment (conv_offset[0]'s fourth): that entry's stride / alignment rule
-        FLAIR_CHECK(pad_ld >= 4 && pad_ld % vec == 0 && reinterpret_cast<uintptr_t>(flowpad) % 16 == 0,
+        // not FLAIR_CHECK_VIEW: flowpad is a convolution input segment (conv_offset[0]'s fourth), four channels of it are
+        // written whatever C is: that entry's stride / alignment rule, pad_ld >= 4
+        FLAIR_CHECK(pad_ld >= 4 && pad_ld % VEC == 0 && reinterpret_cast<uintptr_t>(flowpad) % 16 == 0,
                     "flair_vsrpp_prep: flowpad stride/alignment: pad_ld = %d must be >= 4 and a multiple of %d elements, "
-                    "flowpad = %p 16-byte aligned", pad_ld, vec, (const void*)flowpad);
-    }
-    if (dtype == FLAIR_BF16) {
-        FLAIR_CHECK(C % 8 == 0, "flair_vsrpp_prep: C %% 8");
-        hipLaunchKernelGGL(vsrpp_prep_kernel<bf16_t>, dim3(grid_for((long)H * W * (C / 8))), dim3(256), 0, stream,
-                           (const bf16_t*)prop, prop_ld, (const bf16_t*)feat2, feat2_ld, flow1, flow_prev, H, W, C,
-                           (bf16_t*)cond1, cond1_ld, (bf16_t*)cond2, cond2_ld, flow2_out, (bf16_t*)flowpad, pad_ld);
-    } else {
-        FLAIR_CHECK(C % 4 == 0, "flair_vsrpp_prep: C %% 4");
-        hipLaunchKernelGGL(vsrpp_prep_kernel<float>, dim3(grid_for((long)H * W * (C / 4))), dim3(256), 0, stream,
-                           (const float*)prop, prop_ld, (const float*)feat2, feat2_ld, flow1, flow_prev, H, W, C,
-                           (float*)cond1, cond1_ld, (float*)cond2, cond2_ld, flow2_out, (float*)flowpad, pad_ld);
-    }
-    FLAIR_LAUNCH_CHECK();
-    return FLAIR_OK;
+                    "flowpad = %p 16-byte aligned", pad_ld, VEC, (const void*)flowpad);
+        FLAIR_CHECK(C % VEC == 0, "flair_vsrpp_prep: C %% %d", VEC);
+        hipLaunchKernelGGL(vsrpp_prep_kernel<E>, dim3(grid_for((long)H * W * (C / VEC), 256, 4096)), dim3(256), 0, stream,
+                           (const E*)prop, prop_ld, (const E*)feat2, feat2_ld, flow1, flow_prev, H, W, C, (E*)cond1, cond1_ld,
+                           (E*)cond2, cond2_ld, flow2_out, (E*)flowpad, pad_ld);
+        FLAIR_LAUNCH_CHECK();
+        return FLAIR_OK;
+    });
 }

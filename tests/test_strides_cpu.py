@@ -163,12 +163,13 @@ def _chain(p, res0=None, res1=None, y=P16, x=P16):
 @pytest.mark.parametrize("dtype", [0, 1])
 def test_chain_refuses_strides(dtype):
     _refused(_chain(_chain_params(dtype, seg_ld=56)), "segment 0 stride/alignment")
-    _refused(_chain(_chain_params(dtype, y_ld=56)), "output stride/alignment")
-    _refused(_chain(_chain_params(dtype, y_ld=66)), "output stride/alignment")
-    _refused(_chain(_chain_params(dtype), y=P8), "output stride/alignment")
-    _refused(_chain(_chain_params(dtype, res_ld=(56, 0)), res0=P16), "res0 stride/alignment")
-    _refused(_chain(_chain_params(dtype, res_ld=(64, 66)), res0=P16, res1=P16), "res1 stride/alignment")
-    _refused(_chain(_chain_params(dtype, res_ld=(64, 0)), res0=P8), "res0 stride/alignment")
+    _refused(_chain(_chain_params(dtype, y_ld=56)), "flair_conv_chain", "y stride/alignment", "y_ld = 56")
+    _refused(_chain(_chain_params(dtype, y_ld=66)), "flair_conv_chain", "y stride/alignment", "y_ld = 66")
+    _refused(_chain(_chain_params(dtype), y=P8), "flair_conv_chain", "y stride/alignment")
+    _refused(_chain(_chain_params(dtype, res_ld=(56, 0)), res0=P16), "flair_conv_chain", "res0 stride/alignment", "res0_ld = 56")
+    _refused(_chain(_chain_params(dtype, res_ld=(64, 66)), res0=P16, res1=P16), "flair_conv_chain", "res1 stride/alignment",
+             "res1_ld = 66")
+    _refused(_chain(_chain_params(dtype, res_ld=(64, 0)), res0=P8), "flair_conv_chain", "res0 stride/alignment")
 
 
 def _gn(dtype=1, C=64, c0=64, ld0=64, ld1=0, y_ld=64, raw_ld=0, x0=P16, x1=None, y=P16, raw=None):
@@ -195,10 +196,10 @@ def test_group_norm_refuses_strides(dtype):
     _refused(_gn(dtype, raw_ld=64, raw=P8), "strides/alignment")
 
 
-def _attn(ld, out_ld, d=64, q_off=0):
+def _attn(ld, out_ld, d=64, q_off=0, dtype=1):
     from flair_amd import ops
     p = ops.AttnParams()
-    p.dtype, p.frames, p.L, p.heads, p.head_dim = 1, 1, 64, 1, d
+    p.dtype, p.frames, p.L, p.heads, p.head_dim = dtype, 1, 64, 1, d
     p.ld, p.out_ld = ld, out_ld
     p.q_off, p.k_off, p.v_off, p.head_stride = q_off, q_off + d, q_off + 2 * d, 3 * d
     p.scale = 0.125
@@ -214,10 +215,10 @@ def test_qkv_attention_refuses_strides(d):
     _refused(_attn(3 * d + 8, d, d, q_off=4), "multiples of 8")
 
 
-def _tattn(ld, out_ld, C=64):
+def _tattn(ld, out_ld, C=64, dtype=1):
     from flair_amd import ops
     p = ops.TAttnParams()
-    p.dtype, p.T, p.H, p.W, p.C, p.window = 1, 4, 2, 2, C, 5
+    p.dtype, p.T, p.H, p.W, p.C, p.window = dtype, 4, 2, 2, C, 5
     p.ld, p.out_ld, p.scale, p.head_dim = ld, out_ld, 0.125, 64
     return _lib().flair_temporal_attention(ctypes.byref(p), P16, P16, P16, None)
 
@@ -257,17 +258,22 @@ def test_elementwise_entries_refuse_strides(dtype):
     g = 8 if dtype else 4
     P = ctypes.c_long(16)
     # add_act: ld below C, off-granule ld, misaligned pointer
-    _refused(lib.flair_add_act_nhwc(P16, 56, None, 0, dtype, 64, P, 0, P16, 64, None), "bad argument")
-    _refused(lib.flair_add_act_nhwc(P16, 64, P16, 64 + g // 2, dtype, 64, P, 0, P16, 64, None))
-    _refused(lib.flair_add_act_nhwc(P16, 64, None, 0, dtype, 64, P, 0, P8, 64, None))
+    off = 64 + g // 2
+    _refused(lib.flair_add_act_nhwc(P16, 56, None, 0, dtype, 64, P, 0, P16, 64, None), "flair_add_act_nhwc", "x0 stride/alignment",
+             "x0_ld = 56")
+    _refused(lib.flair_add_act_nhwc(P16, 64, P16, off, dtype, 64, P, 0, P16, 64, None), "flair_add_act_nhwc", "x1 stride/alignment",
+             f"x1_ld = {off}")
+    _refused(lib.flair_add_act_nhwc(P16, 64, None, 0, dtype, 64, P, 0, P8, 64, None), "flair_add_act_nhwc", "y stride/alignment")
     # maxpool
-    _refused(lib.flair_maxpool3x3s2_nhwc(P16, 56, dtype, 1, 4, 4, 64, P16, 64, None), "bad argument")
-    _refused(lib.flair_maxpool3x3s2_nhwc(P16, 64, dtype, 1, 4, 4, 64, P16, 64 + g // 2, None))
-    _refused(lib.flair_maxpool3x3s2_nhwc(P8, 64, dtype, 1, 4, 4, 64, P16, 64, None))
+    _refused(lib.flair_maxpool3x3s2_nhwc(P16, 56, dtype, 1, 4, 4, 64, P16, 64, None), "flair_maxpool3x3s2_nhwc", "x stride/alignment",
+             "x_ld = 56")
+    _refused(lib.flair_maxpool3x3s2_nhwc(P16, 64, dtype, 1, 4, 4, 64, P16, off, None), "flair_maxpool3x3s2_nhwc", "y stride/alignment",
+             f"y_ld = {off}")
+    _refused(lib.flair_maxpool3x3s2_nhwc(P8, 64, dtype, 1, 4, 4, 64, P16, 64, None), "flair_maxpool3x3s2_nhwc", "x stride/alignment")
     # scale_pixels
-    _refused(lib.flair_scale_pixels(P16, dtype, 56, 64, P, P16, None), "flair_scale_pixels: ld = 56")
-    _refused(lib.flair_scale_pixels(P16, dtype, 64 + g // 2, 64, P, P16, None), "flair_scale_pixels: ld")
-    _refused(lib.flair_scale_pixels(P8, dtype, 64, 64, P, P16, None), "flair_scale_pixels: ld")
+    _refused(lib.flair_scale_pixels(P16, dtype, 56, 64, P, P16, None), "flair_scale_pixels", "x stride/alignment", "x_ld = 56")
+    _refused(lib.flair_scale_pixels(P16, dtype, off, 64, P, P16, None), "flair_scale_pixels", "x stride/alignment", f"x_ld = {off}")
+    _refused(lib.flair_scale_pixels(P8, dtype, 64, 64, P, P16, None), "flair_scale_pixels", "x stride/alignment")
     # flow_warp: flow_ld < 2 / odd, x / y strides off the vector granule
     _refused(lib.flair_flow_warp(P16, dtype, 64, P16, 1, 1, 4, 4, 64, 0, P16, 64, None), "flair_flow_warp")
     _refused(lib.flair_flow_warp(P16, dtype, 64, P16, 3, 1, 4, 4, 64, 0, P16, 64, None), "flair_flow_warp")
@@ -437,6 +443,90 @@ def test_flow_warp_refuses_strides(dtype):
     _refused(warp(y_ld=64 + g // 2), "flair_flow_warp", "y stride/alignment")
     _refused(warp(x=P8), "flair_flow_warp", "x stride/alignment")
     _refused(warp(y=P8), "flair_flow_warp", "y stride/alignment")
+
+
+# ------------------------------------------------------------------------------------------------ the element type code
+# Every entry that takes a dtype refuses a code that is neither FLAIR_F32 nor FLAIR_BF16, naming itself and the argument.
+# The entries come from the header: a prototype with `int dtype`, or with a params struct that has a dtype field, so an
+# entry added later is covered (a struct entry by failing the set comparison below until it gets a call).
+def _header():
+    import os
+    import re
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "flair_hip.h")
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    protos = {m.group(1): [a.strip() for a in m.group(2).split(",")]
+              for m in re.finditer(r"^int (flair_\w+)\(([^)]*)\);", text, flags=re.M)}
+    structs = {m.group(2) for m in re.finditer(r"typedef struct \{([^}]*)\} (flair_\w+);", text) if re.search(r"\bint dtype;", m.group(1))}
+    return protos, structs
+
+
+def _dtype_entries():
+    protos, structs = _header()
+    direct = sorted(n for n, args in protos.items() if "int dtype" in args)
+    by_struct = sorted(n for n, args in protos.items() if any(a.split("*")[0].replace("const", "").strip() in structs for a in args))
+    by_struct.remove("flair_conv_variant")          # reports the kernel choice for a shape; launches nothing, refuses nothing
+    return direct, by_struct
+
+
+# otherwise valid small arguments by parameter name: 64 channels in pixels 64 elements apart, one frame of 4 x 4 pixels
+_INT_ARGS = {"C": 64, "D": 64, "F": 1, "B": 1, "T": 1, "N": 1, "frames": 1, "H": 4, "W": 4, "h": 4, "w": 4, "Hi": 4, "Wi": 4, "Ho": 8,
+             "Wo": 8, "HW": 16, "mode": 0, "border": 0, "act": 0, "k0": 5, "k1": 9, "k2": 13, "out_c": 64, "pos_rows": 16,
+             "gate_is_logit": 0, "add_x": 0}
+_LONG_ARGS = {"P": 16, "HW": 16, "rows": 16, "n": 64, "out_batch_stride": 4096}
+
+
+def _bad_dtype_call(name, args, code):
+    call = []
+    for a in args:
+        kind, arg = a.rsplit(" ", 1)
+        if "*" in a:
+            call.append(P16)
+        elif kind == "hipStream_t":
+            call.append(None)
+        elif arg == "dtype":
+            call.append(code)
+        elif kind == "long":
+            call.append(ctypes.c_long(_LONG_ARGS[arg]))
+        elif kind == "float":
+            call.append(ctypes.c_float(1.0))
+        elif kind == "double":
+            call.append(ctypes.c_double(0.5))
+        elif arg.endswith("ld"):
+            call.append(64)
+        elif arg.endswith("coff"):
+            call.append(0)
+        else:
+            assert kind == "int", (name, a)
+            call.append(_INT_ARGS[arg])
+    return getattr(_lib(), name)(*call)
+
+
+_STRUCT_CALLS = {
+    "flair_conv_nhwc": lambda code: _conv(_conv_params(code)),
+    "flair_conv_chain": lambda code: _chain(_chain_params(code)),
+    "flair_groupnorm_nhwc": lambda code: _gn(code),
+    "flair_qkv_attention": lambda code: _attn(192, 64, dtype=code),
+    "flair_temporal_attention": lambda code: _tattn(192, 64, dtype=code),
+    "flair_dcn_align": lambda code: _dcn(code),
+    "flair_attention_wide": lambda code: _wide(code),
+}
+
+
+def test_the_header_lists_the_dtype_entries():
+    direct, by_struct = _dtype_entries()
+    assert len(direct) >= 26 and "flair_scale_pixels" in direct and "flair_resize_nhwc" in direct
+    assert set(by_struct) == set(_STRUCT_CALLS)
+
+
+@pytest.mark.parametrize("name", _dtype_entries()[0] + _dtype_entries()[1])
+def test_entries_refuse_an_unknown_dtype(name):
+    if name in _dtype_entries()[1]:
+        assert name in _STRUCT_CALLS, f"{name} takes a params struct with a dtype: give it a call in _STRUCT_CALLS"
+        rc = _STRUCT_CALLS[name](7)
+    else:
+        rc = _bad_dtype_call(name, _header()[0][name], 7)
+    _refused(rc, name, "dtype")
 
 
 # ------------------------------------------------------------------------------------------------ the finite input guard
