@@ -62,6 +62,37 @@ def test_bcast_entry_validates_arguments():
     assert rc == -1 and b"flair_bcast_weights" in lib.flair_last_error()
 
 
+# Functions of flair_amd/ops.py that launch nothing and so need no GPU test of their own: the K granularity of a dtype, the
+# shape test in front of conv_chain, the host-side blend coefficients of SuperSloMo.
+HOST_ONLY = {"k_align", "chain_supported", "slomo_coefficients"}
+
+
+def test_every_ops_wrapper_is_called_by_a_gpu_test():
+    """Every public function of flair_amd/ops.py (each ends in a lib().flair_* call or prepares one) is called, as
+    `ops.<name>(` or `<name>(`, in at least one test file that carries the gpu marker; a private one that calls the library
+    is reached through a public one.  A new entry without a test of its own fails here."""
+    import glob
+    src = open(os.path.join(ROOT, "flair_amd", "ops.py")).read()
+    bodies = dict(zip(re.findall(r"(?m)^def (\w+)\(", src), re.split(r"(?m)^def \w+\(", src)[1:]))
+    launches = {n for n, b in bodies.items() if re.search(r"\blib\(\)\.flair_\w+", b)}
+    assert len(launches) > 60 and {"axpby_nhwc", "amt_multiflow_prepare", "amt_multiflow_combine"} <= launches
+    assert HOST_ONLY <= set(bodies) and not HOST_ONLY & launches
+    tests = [open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "tests", "test_*.py")))]
+    tests = [t for t in tests if re.search(r"\bpytest\.mark\.gpu\b", t)]
+    assert len(tests) > 10
+
+    def called(name, texts):
+        pat = re.compile(r"(?:\bops\.|(?<![\w.]))%s\(" % re.escape(name))
+        return any(pat.search(t) for t in texts)
+
+    public = [n for n in bodies if not n.startswith("_") and n not in HOST_ONLY]
+    missing = [n for n in public if not called(n, tests)]
+    assert not missing, f"no gpu-marked test calls {missing}"
+    private = [n for n in launches if n.startswith("_")]
+    unreached = [n for n in private if not called(n, [b for m, b in bodies.items() if m != n and not m.startswith("_")])]
+    assert not unreached, unreached
+
+
 def test_dispatch_reads_no_environment():
     """Kernel choice depends on the arguments alone: no HIP source reads an environment variable and no model module
     reads os.environ (FLAIR_HIP_LIB, which picks the library file in flair_amd/_lib.py, is not a dispatch switch)."""

@@ -3,7 +3,9 @@ bit for bit at integer coordinates, dyadic coordinates on integer volumes bit fo
 ATen deviation, guarded strided destinations), the pyramid pooling, the volume itself, per-channel PReLU, the transposed
 convolution as a repacked 3x3 convolution plus depth-to-space, and InstanceNorm + ReLU.  The network: the feature encoder,
 one decoder and one update block on the reference's own inputs, the three cases end to end with their intermediate flows
-(tests/golden/g18_amt.npz), batch and factor invariance bit for bit, and the driver on an uneven size."""
+(tests/golden/g18_amt.npz), batch and factor invariance bit for bit, and the driver on an uneven size.  The tail of the
+network (multi-flow prepare and combine, axpby, corr_scale) and the instance norm on planes large enough to be summed in
+chunks have their per-element tests in tests/test_gpu_amt_tail.py."""
 import functools
 
 import numpy as np
