@@ -2,7 +2,8 @@
 
 Layout:
   csrc/               hand-written HIP kernels + the C ABI (include/flair_hip.h)
-  _lib.py, ops.py     ctypes binding and tensor-level wrappers
+  _header.py          the header read into ctypes structs and prototypes
+  _lib.py, ops.py     ctypes binding (derived from the header) and tensor-level wrappers
   guided_diffusion/   host-side mirror of the reference's Python interface
   parallel.py         clip-parallel multi-GPU helpers (RCCL weight broadcast)
   degrade.py          clean frames -> a task's degraded frames, with the operator restore assumes

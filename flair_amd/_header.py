@@ -1,0 +1,96 @@
+"""include/flair_hip.h read into ctypes: the parameter structs and every entry's prototype.
+
+The header is the contract with libflair_hip.so; nothing of it is restated in Python.  ``STRUCTS`` maps a C struct name to
+a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``.  Only the constructs the header uses
+are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
+"""
+import collections
+import ctypes
+import os
+import re
+
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "flair_hip.h")
+
+SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+           "size_t": ctypes.c_size_t}
+RETURNS = dict(SCALARS, **{"char*": ctypes.c_char_p})
+POINTEES = {"void", "float", "double", "int", "uint8_t", "long long", "void*", "float*"}
+
+# name, ctypes type, pointed-to C type (None for a scalar or a stream), e.g. ("bias", c_void_p, "float")
+Param = collections.namedtuple("Param", "name ctype elem")
+
+
+class HeaderError(RuntimeError):
+    pass
+
+
+def _ctype(text):
+    """'const float* const*' -> 'float**': qualifiers dropped, stars attached."""
+    return re.sub(r"\s*\*\s*", "*", " ".join(w for w in re.sub(r"\*", " * ", text).split() if w != "const"))
+
+
+def _struct(name, body):
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        m = re.fullmatch(r"(int|long|float)\s+(.+)", decl, re.S)
+        if not m:
+            raise HeaderError(f"struct {name}: cannot read the field declaration {decl!r}")
+        for item in m.group(2).split(","):
+            f = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", item.strip())
+            if not f:
+                raise HeaderError(f"struct {name}: cannot read the field {item!r} of {decl!r}")
+            t = SCALARS[m.group(1)]
+            fields.append((f.group(1), t * int(f.group(2)) if f.group(2) else t))
+    # no instance __dict__: assigning a name that is not a field raises AttributeError instead of being dropped
+    return type(name, (ctypes.Structure,), {"__slots__": (), "_fields_": fields})
+
+
+def _param(entry, text, structs):
+    m = re.fullmatch(r"(.+?)(\w+)", text.strip(), re.S)
+    if not m:
+        raise HeaderError(f"{entry}: cannot read the parameter {text!r}")
+    t, name = _ctype(m.group(1)), m.group(2)
+    if t in SCALARS:
+        return Param(name, SCALARS[t], None)
+    if t == "hipStream_t":
+        return Param(name, ctypes.c_void_p, None)
+    if t.endswith("*") and t[:-1] in structs:
+        return Param(name, ctypes.POINTER(structs[t[:-1]]), t[:-1])
+    if t.endswith("*") and t[:-1] in POINTEES:
+        return Param(name, ctypes.c_void_p, t[:-1])
+    raise HeaderError(f"{entry}: parameter type {m.group(1).strip()!r} of {text.strip()!r} is not understood")
+
+
+def parse(text):
+    """-> (structs, protos) of a header in the dialect of flair_hip.h."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"(?m)^\s*#.*$", "", text)
+    text, n = re.subn(r'extern\s+"C"\s*\{', "", text)
+    if n != 1 or not text.rstrip().endswith("}"):
+        raise HeaderError('expected one extern "C" { ... } block around the declarations')
+    text = text.rstrip()[:-1]
+    structs, protos, pos = {}, {}, 0
+    for m in re.finditer(r"\s*((?:[^;{}]|\{[^{}]*\})*?)\s*;", text):
+        if m.start() != pos:
+            break
+        pos, stmt = m.end(), m.group(1)
+        s = re.fullmatch(r"typedef\s+struct\s*\{(.*)\}\s*(\w+)", stmt, re.S)
+        p = re.fullmatch(r"([\w\s\*]+?)\b(flair_\w+)\s*\((.*)\)", stmt, re.S)
+        if s:
+            structs[s.group(2)] = _struct(s.group(2), s.group(1))
+        elif p:
+            ret, name, args = _ctype(p.group(1)), p.group(2), p.group(3).strip()
+            if ret not in RETURNS:
+                raise HeaderError(f"{name}: return type {p.group(1).strip()!r} is not understood")
+            if name in protos:
+                raise HeaderError(f"{name} is declared twice")
+            protos[name] = (RETURNS[ret], [] if args == "void" else [_param(name, a, structs) for a in args.split(",")])
+        elif not re.fullmatch(r"typedef\s+enum\s*\{[^{}]*\}\s*\w+|typedef\s+struct\s+ihipStream_t\s*\*\s*hipStream_t", stmt):
+            raise HeaderError(f"cannot read the declaration {' '.join(stmt.split())!r}")
+    if text[pos:].strip():
+        raise HeaderError(f"cannot read the header from {' '.join(text[pos:].split())[:120]!r} on")
+    return structs, protos
+
+
+with open(HEADER_PATH) as _f:
+    STRUCTS, PROTOS = parse(_f.read())

@@ -1,19 +1,25 @@
-"""ctypes binding of libflair_hip.so (the C ABI declared in include/flair_hip.h).
+"""ctypes binding of libflair_hip.so, derived from the C ABI's own header (include/flair_hip.h, read by _header.py).
 
 The library is the product path: there is no CPU or PyTorch fallback.  Loading fails
-loudly (``FlairHipUnavailable``) when the shared object has not been built, and every
-wrapper raises ``FlairHipError`` with the library's message on a non-zero status.
+loudly (``FlairHipUnavailable``) when the shared object has not been built.  ``lib()`` is the
+raw library with every declared entry typed (``argtypes`` / ``restype``); ``call.flair_x(...)`` launches
+an entry on torch tensors and raises ``FlairHipError`` with the library's message on a non-zero status.
 """
 import ctypes
+import functools
 import os
 
 import torch  # noqa: F401  (must be imported first: the library binds to torch's HIP runtime)
+
+from ._header import PROTOS, STRUCTS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libflair_hip.so")
 
 FLAIR_F32, FLAIR_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU01, ACT_SILU, ACT_DCN_OFFSETS, ACT_LRELU02, ACT_GELU = 0, 1, 2, 3, 4, 5, 6
+
+ConvParams = STRUCTS["flair_conv_params"]
 
 
 class FlairHipUnavailable(RuntimeError):
@@ -22,17 +28,6 @@ class FlairHipUnavailable(RuntimeError):
 
 class FlairHipError(RuntimeError):
     pass
-
-
-class ConvParams(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int),
-                ("W", ctypes.c_int), ("KT", ctypes.c_int), ("KH", ctypes.c_int),
-                ("KW", ctypes.c_int), ("Cout", ctypes.c_int), ("nseg", ctypes.c_int),
-                ("seg_c", ctypes.c_int * 4), ("seg_ld", ctypes.c_int * 4),
-                ("y_ld", ctypes.c_int), ("res_ld", ctypes.c_int * 2), ("act", ctypes.c_int),
-                ("out_scale", ctypes.c_float), ("frame_bias_ld", ctypes.c_int), ("stride", ctypes.c_int),
-                ("act_param", ctypes.c_float), ("act_period", ctypes.c_int), ("asym_pad", ctypes.c_int),
-                ("reflect_pad", ctypes.c_int)]
 
 
 _lib = None
@@ -51,7 +46,9 @@ def lib():
                 f"g.build()'` (or `make -C flair_amd/csrc`). The HIP library is required; "
                 f"there is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        l.flair_last_error.restype = ctypes.c_char_p
+        for name, (restype, params) in PROTOS.items():
+            f = getattr(l, name)
+            f.restype, f.argtypes = restype, [p.ctype for p in params]
         _lib = l
     return _lib
 
@@ -70,27 +67,68 @@ def dtype_code(t):
     raise TypeError(f"unsupported activation dtype {t.dtype}")
 
 
-def ptr(t):
-    """Device pointer of a tensor (None -> NULL)."""
-    if t is None:
-        return ctypes.c_void_p(0)
+def _address(t):
     if not t.is_cuda:
         raise FlairHipError("flair_amd ops need tensors resident in HBM (device='cuda'); "
                             "no CPU path exists")
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
+
+
+def ptr(t):
+    """Device pointer of a tensor (None -> NULL)."""
+    return ctypes.c_void_p(0 if t is None else _address(t))
 
 
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# The entries that launch: status returned, `stream` last.  Per entry, the position, name and required tensor dtype (None
+# behind a void*) of every data pointer, worked out once so that a call only walks this list.
+_ELEM_DTYPE = {"float": torch.float32, "double": torch.float64, "int": torch.int32, "uint8_t": torch.uint8,
+               "long long": torch.int64}
+_LAUNCHES = {name: [(i, p.name, _ELEM_DTYPE.get(p.elem)) for i, p in enumerate(params[:-1])
+                    if p.elem is not None and p.ctype is ctypes.c_void_p]
+             for name, (restype, params) in PROTOS.items()
+             if restype is ctypes.c_int and params and params[-1].name == "stream"}
+
+
+def _launch(name, *args):
+    fn = getattr(lib(), name)
+    if len(args) != len(fn.argtypes) - 1:
+        raise TypeError(f"{name} takes {len(fn.argtypes) - 1} arguments and the stream ({len(args)} given)")
+    args = list(args)
+    for i, pname, dtype in _LAUNCHES[name]:
+        t = args[i]
+        if hasattr(t, "data_ptr"):      # a tensor; None, host arrays and byref() go to ctypes as they are
+            args[i] = _address(t)
+            if dtype is not None and t.dtype != dtype:
+                raise FlairHipError(f"{name}: {pname} must be {str(dtype)[6:]}, got {str(t.dtype)[6:]}")
+    check(fn(*args, stream()), name)
+
+
+class _Entries:
+    """``call.flair_x(*args)`` launches entry flair_x of the header on torch's current stream.  ``args`` are the entry's
+    arguments without the stream; a tensor stands for its device pointer (it must live in HBM and, behind a typed pointer
+    such as ``const float*``, have that dtype) and None for NULL; numbers and flags convert through the entry's
+    ``argtypes``.  Raises FlairHipError on a refusal here or a non-zero status of the library.  The entries that return
+    a value instead of a status (size queries, flair_conv_variant, flair_abi_version) are called through ``lib()``.
+    An attribute, not a string, so that a search for ``flair_x(`` finds the header, the C source and the Python callers."""
+
+    def __getattr__(self, name):
+        if name not in _LAUNCHES:
+            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream")
+        return functools.partial(_launch, name)
+
+
+call = _Entries()
+
+
 def image_metrics_workspace(N, H, W):
     """flair_image_metrics_workspace(N, H, W): bytes of workspace flair_image_metrics needs (0 for a shape it refuses)."""
-    f = lib().flair_image_metrics_workspace
-    f.restype = ctypes.c_size_t
-    return int(f(int(N), int(H), int(W)))
+    return lib().flair_image_metrics_workspace(N, H, W)
 
 
 def image_metrics(a, b, N, H, W, out, ws, ws_bytes):
     """flair_image_metrics on torch's current stream; a, b, out, ws: ctypes pointers (ptr()).  Returns the status."""
-    return lib().flair_image_metrics(a, b, int(N), int(H), int(W), out, ws, ctypes.c_size_t(ws_bytes), stream())
+    return lib().flair_image_metrics(a, b, N, H, W, out, ws, ws_bytes, stream())

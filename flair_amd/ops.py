@@ -9,9 +9,9 @@ import ctypes
 
 import torch
 
-from . import _lib
-from ._lib import (ACT_DCN_OFFSETS, ACT_GELU, ACT_LRELU01, ACT_LRELU02, ACT_NONE, ACT_RELU, ACT_SILU, ConvParams, check, dtype_code, lib,
-                   ptr, stream)
+from ._header import STRUCTS
+from ._lib import ACT_DCN_OFFSETS, ACT_GELU, ACT_LRELU01, ACT_LRELU02, ACT_NONE, ACT_RELU, ACT_SILU, ConvParams, call, dtype_code, lib
+from ._lib import check, ptr, stream  # noqa: F401  (for callers that drive lib() themselves)
 
 __all__ = ["conv", "conv_chain", "group_norm", "nchw_to_clip", "clip_to_nchw", "timestep_embedding", "linear",
            "qkv_attention", "temporal_attention", "flow_warp", "flow_compose", "resize",
@@ -19,46 +19,9 @@ __all__ = ["conv", "conv_chain", "group_norm", "nchw_to_clip", "clip_to_nchw", "
            "ACT_NONE", "ACT_RELU", "ACT_LRELU01", "ACT_SILU", "ACT_DCN_OFFSETS", "ACT_LRELU02", "ACT_GELU"]
 
 
-class GnParams(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int), ("C", ctypes.c_int), ("c0", ctypes.c_int),
-                ("ld0", ctypes.c_int), ("ld1", ctypes.c_int), ("groups", ctypes.c_int),
-                ("F", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("frames_per_stat", ctypes.c_int), ("eps", ctypes.c_float), ("act", ctypes.c_int),
-                ("resample", ctypes.c_int), ("y_ld", ctypes.c_int), ("raw_ld", ctypes.c_int),
-                ("film_ld", ctypes.c_int)]
-
-
-class SamplerCoefs(ctypes.Structure):
-    _fields_ = [("gamma", ctypes.c_float), ("w_aux", ctypes.c_float),
-                ("sqrt_recip_alphas_cumprod", ctypes.c_float),
-                ("sqrt_recipm1_alphas_cumprod", ctypes.c_float),
-                ("sqrt_alphas_cumprod_prev", ctypes.c_float),
-                ("sqrt_one_minus_alphas_cumprod_prev", ctypes.c_float),
-                ("sqrt_one_minus_rho", ctypes.c_float), ("sqrt_rho", ctypes.c_float),
-                ("clip_denoised", ctypes.c_int), ("nonzero", ctypes.c_int),
-                ("frame_elems", ctypes.c_long), ("frames", ctypes.c_int),
-                ("prev_frames", ctypes.c_int)]
-
-
-class AttnParams(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int), ("frames", ctypes.c_int), ("L", ctypes.c_int),
-                ("heads", ctypes.c_int), ("head_dim", ctypes.c_int), ("ld", ctypes.c_int),
-                ("out_ld", ctypes.c_int), ("q_off", ctypes.c_int), ("k_off", ctypes.c_int),
-                ("v_off", ctypes.c_int), ("head_stride", ctypes.c_int), ("scale", ctypes.c_float)]
-
-
-class TAttnParams(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int),
-                ("W", ctypes.c_int), ("C", ctypes.c_int), ("window", ctypes.c_int),
-                ("ld", ctypes.c_int), ("out_ld", ctypes.c_int), ("round_fp16", ctypes.c_int),
-                ("scale", ctypes.c_float), ("head_dim", ctypes.c_int)]
-
-
-class DcnParams(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int), ("F", ctypes.c_int), ("H", ctypes.c_int),
-                ("W", ctypes.c_int), ("Cin", ctypes.c_int), ("Cout", ctypes.c_int),
-                ("G", ctypes.c_int), ("x_ld", ctypes.c_int * 2), ("raw_ld", ctypes.c_int),
-                ("y_ld", ctypes.c_int), ("max_residue_magnitude", ctypes.c_float), ("raw_activated", ctypes.c_int)]
+# the parameter structs of the header (their layouts are derived from it: _header.py)
+GnParams, SamplerCoefs, AttnParams = STRUCTS["flair_gn_params"], STRUCTS["flair_sampler_coefs"], STRUCTS["flair_attn_params"]
+TAttnParams, DcnParams, ChainParams = STRUCTS["flair_tattn_params"], STRUCTS["flair_dcn_params"], STRUCTS["flair_chain_params"]
 
 
 def _ld(t):
@@ -70,8 +33,9 @@ def _ld(t):
     return ld
 
 
-def _f32(t):
-    assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+def _dense(t):
+    """A per-channel parameter (bias, norm scale, flow): contiguous; that it is float32 is for the call to refuse, by name."""
+    assert t is None or t.is_contiguous()
     return t
 
 
@@ -111,8 +75,8 @@ def conv(xs, weight, bias, cout, kernel, *, out=None, act=ACT_NONE, res0=None, r
         p.seg_ld[i] = _ld(x)
         arr[i] = x.data_ptr()
     p.stride = stride
-    p.asym_pad = int(asym_pad)
-    p.reflect_pad = int(reflect_pad)
+    p.asym_pad = asym_pad
+    p.reflect_pad = reflect_pad
     p.frame_bias_ld = frame_bias.stride(0) if frame_bias is not None else 0
     if frame_bias is not None:
         assert frame_bias.dtype == torch.float32 and frame_bias.stride(1) == 1 and frame_bias.shape[0] == T
@@ -132,8 +96,7 @@ def conv(xs, weight, bias, cout, kernel, *, out=None, act=ACT_NONE, res0=None, r
     ws = _workspace(wsb, x0.device, "conv") if wsb else None
 
     def launch(_keep=xs):       # the segment tensors reach the library as raw pointers: keep them alive with the closure
-        check(lib().flair_conv_nhwc(ctypes.byref(p), arr, ptr(weight), ptr(_f32(bias)), ptr(frame_bias), ptr(res0),
-                                    ptr(res1), ptr(out), ptr(ws), ctypes.c_size_t(wsb), stream()), "flair_conv_nhwc")
+        call.flair_conv_nhwc(ctypes.byref(p), arr, weight, _dense(bias), frame_bias, res0, res1, out, ws, wsb)
     launch()
     if e0 is not None:
         cin = sum(x.shape[3] for x in xs)
@@ -187,9 +150,7 @@ def conv_variant(T, H, W, cins, cout, kernel, dtype=torch.bfloat16, stride=1):
 
 
 def _conv_ws_bytes(p):
-    f = lib().flair_conv_workspace_bytes
-    f.restype = ctypes.c_size_t
-    return f(ctypes.byref(p))
+    return lib().flair_conv_workspace_bytes(ctypes.byref(p))
 
 
 def pack_conv_weight(w, seg_channels, dtype, cout_pad=None):
@@ -218,14 +179,6 @@ def pack_conv_weight(w, seg_channels, dtype, cout_pad=None):
 
 
 # ---------------------------------------------------------------- fused conv chains
-class ChainParams(ctypes.Structure):
-    _fields_ = [("dtype", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("C", ctypes.c_int), ("CoutB", ctypes.c_int), ("nseg", ctypes.c_int),
-                ("seg_c", ctypes.c_int * 4), ("seg_ld", ctypes.c_int * 4), ("y_ld", ctypes.c_int),
-                ("res_ld", ctypes.c_int * 2), ("actA", ctypes.c_int), ("actB", ctypes.c_int),
-                ("out_scale", ctypes.c_float), ("act_param", ctypes.c_float), ("act_period", ctypes.c_int)]
-
-
 def chain_supported(xs, c_mid):
     """Where the fused chain kernel is used: the geometry flair_conv_chain covers (W a multiple of 8, 64 or 128
     mid channels) AND a launch of at most ~2 workgroups per CU (per-frame calls of the recurrence).  Clip-level
@@ -270,8 +223,7 @@ def conv_chain(xs, wA, bA, actA, wB, bB, actB, c_mid, coutB, *, res0=None, res1=
     e0 = _prof_begin()
 
     def launch(_keep=xs):
-        check(lib().flair_conv_chain(ctypes.byref(p), arr, ptr(wA), ptr(_f32(bA)), ptr(wB), ptr(_f32(bB)), ptr(res0),
-                                     ptr(res1), ptr(out), stream()), "flair_conv_chain")
+        call.flair_conv_chain(ctypes.byref(p), arr, wA, _dense(bA), wB, _dense(bB), res0, res1, out)
     launch()
     if e0 is not None:
         cin = sum(x.shape[3] for x in xs)
@@ -332,9 +284,7 @@ def group_norm(x, gamma, beta, *, x1=None, groups=32, eps=1e-5, act=ACT_NONE, fi
     e0 = _prof_begin()
 
     def launch():
-        check(lib().flair_groupnorm_nhwc(ctypes.byref(p), ptr(x), ptr(x1), ptr(_f32(gamma)), ptr(_f32(beta)),
-                                         ptr(film), ptr(out), ptr(raw), ptr(ws), stream()),
-              "flair_groupnorm_nhwc")
+        call.flair_groupnorm_nhwc(ctypes.byref(p), x, x1, _dense(gamma), _dense(beta), film, out, raw, ws)
     launch()
     if e0 is not None:   # two-pass GroupNorm: the input is read twice, the output written once
         numel_in, numel_out = T * H * W * C, T * Ho * Wo * C
@@ -345,9 +295,7 @@ def group_norm(x, gamma, beta, *, x1=None, groups=32, eps=1e-5, act=ACT_NONE, fi
 
 
 def lib_ws_bytes(p):
-    f = lib().flair_groupnorm_workspace_bytes
-    f.restype = ctypes.c_size_t
-    return f(ctypes.byref(p))
+    return lib().flair_groupnorm_workspace_bytes(ctypes.byref(p))
 
 
 # ------------------------------------------------------------------ edge / small ops
@@ -355,8 +303,7 @@ def nchw_to_clip(src, dst, coff=0):
     """(N,C,H,W) f32 -> channels [coff, coff+C) of clip tensor dst (N,H,W,Cd)."""
     N, C, H, W = src.shape
     assert src.dtype == torch.float32 and src.is_contiguous()
-    check(lib().flair_nchw_f32_to_nhwc(ptr(src), N, C, H, W, ptr(dst), dtype_code(dst), _ld(dst), coff,
-                                       stream()), "flair_nchw_f32_to_nhwc")
+    call.flair_nchw_f32_to_nhwc(src, N, C, H, W, dst, dtype_code(dst), _ld(dst), coff)
     return dst
 
 
@@ -364,8 +311,7 @@ def clip_to_nchw(src, C, coff=0, out=None):
     N, H, W, _ = src.shape
     if out is None:
         out = torch.empty((N, C, H, W), dtype=torch.float32, device=src.device)
-    check(lib().flair_nhwc_to_nchw_f32(ptr(src), dtype_code(src), _ld(src), coff, N, C, H, W, ptr(out),
-                                       stream()), "flair_nhwc_to_nchw_f32")
+    call.flair_nhwc_to_nchw_f32(src, dtype_code(src), _ld(src), coff, N, C, H, W, out)
     return out
 
 
@@ -375,8 +321,7 @@ def timestep_embedding(t, dim, max_period=10000.0, out=None, sin_first=False):
     N = t.shape[0]
     if out is None:
         out = torch.empty((N, dim), dtype=torch.float32, device=t.device)
-    check(lib().flair_timestep_embedding(ptr(t), N, dim, ctypes.c_float(max_period), int(sin_first), ptr(out),
-                                         stream()), "flair_timestep_embedding")
+    call.flair_timestep_embedding(t, N, dim, max_period, sin_first, out)
     return out
 
 
@@ -387,8 +332,7 @@ def linear(x, w, b, *, act_in=ACT_NONE, act_out=ACT_NONE, out=None):
     assert x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_contiguous() and w.is_contiguous()
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    check(lib().flair_linear_f32(ptr(x), M, K, ptr(w), ptr(b), N, act_in, act_out, ptr(out), out.stride(0),
-                                 stream()), "flair_linear_f32")
+    call.flair_linear_f32(x, M, K, w, b, N, act_in, act_out, out, out.stride(0))
     return out
 
 
@@ -412,7 +356,7 @@ def qkv_attention(qkv, heads, *, new_order=False, out=None):
     e0 = _prof_begin()
 
     def launch():
-        check(lib().flair_qkv_attention(ctypes.byref(p), ptr(qkv), ptr(out), stream()), "flair_qkv_attention")
+        call.flair_qkv_attention(ctypes.byref(p), qkv, out)
     launch()
     if e0 is not None:   # QK^T + AV: 4 * frames * heads * L^2 * d FLOPs; q, k, v read + out written
         L = H * W
@@ -433,12 +377,11 @@ def temporal_attention(qkv, kpos, window, *, round_fp16, head_dim=64, out=None):
     if out is None:
         out = torch.empty((T, H, W, C), dtype=qkv.dtype, device=qkv.device)
     p.out_ld = _ld(out)
-    p.round_fp16 = int(round_fp16)
+    p.round_fp16 = round_fp16
     p.head_dim = head_dim
     p.scale = 1.0 / (head_dim ** 0.5)
     assert kpos.shape == (window - 1, C)
-    check(lib().flair_temporal_attention(ctypes.byref(p), ptr(qkv), ptr(_f32(kpos)), ptr(out), stream()),
-          "flair_temporal_attention")
+    call.flair_temporal_attention(ctypes.byref(p), qkv, _dense(kpos), out)
     return out
 
 
@@ -448,8 +391,7 @@ def flow_warp(x, flow, *, border=False, out=None):
     assert flow.dtype == torch.float32 and flow.shape == (F_, H, W, 2)
     if out is None:
         out = torch.empty((F_, H, W, C), dtype=x.dtype, device=x.device)
-    check(lib().flair_flow_warp(ptr(x), dtype_code(x), _ld(x), ptr(flow), _ld(flow), F_, H, W, C, int(border),
-                                ptr(out), _ld(out), stream()), "flair_flow_warp")
+    call.flair_flow_warp(x, dtype_code(x), _ld(x), flow, _ld(flow), F_, H, W, C, border, out, _ld(out))
     return out
 
 
@@ -458,7 +400,7 @@ def flow_compose(f1, f2, out=None):
     assert f1.dtype == torch.float32 and f1.is_contiguous() and f2.is_contiguous()
     if out is None:
         out = torch.empty_like(f1)
-    check(lib().flair_flow_compose(ptr(f1), ptr(f2), F_, H, W, ptr(out), stream()), "flair_flow_compose")
+    call.flair_flow_compose(f1, f2, F_, H, W, out)
     return out
 
 
@@ -471,9 +413,7 @@ def resize(x, size, mode, *, channels=None, out=None, scale_c0=1.0, scale_c1=1.0
     Ho, Wo = size
     if out is None:
         out = torch.zeros((F_, Ho, Wo, Cx), dtype=x.dtype, device=x.device)
-    check(lib().flair_resize_nhwc(ptr(x), dtype_code(x), _ld(x), F_, Hi, Wi, C, mode, Ho, Wo, ptr(out), _ld(out),
-                                  ctypes.c_float(scale_c0), ctypes.c_float(scale_c1), stream()),
-          "flair_resize_nhwc")
+    call.flair_resize_nhwc(x, dtype_code(x), _ld(x), F_, Hi, Wi, C, mode, Ho, Wo, out, _ld(out), scale_c0, scale_c1)
     return out
 
 
@@ -509,12 +449,11 @@ def dcn_align(x0, x1, raw, flow1, flow2, weight, bias, cout, *, groups=16, max_m
         out = torch.empty((F_, H, W, cout), dtype=x0.dtype, device=x0.device)
     p.y_ld = _ld(out)
     p.max_residue_magnitude = max_mag
-    p.raw_activated = int(raw_activated)
+    p.raw_activated = raw_activated
     e0 = _prof_begin()
 
     def launch():
-        check(lib().flair_dcn_align(ctypes.byref(p), ptr(x0), ptr(x1), ptr(raw), ptr(flow1), ptr(flow2), ptr(weight),
-                                    ptr(_f32(bias)), ptr(out), stream()), "flair_dcn_align")
+        call.flair_dcn_align(ctypes.byref(p), x0, x1, raw, flow1, flow2, weight, _dense(bias), out)
     launch()
     if e0 is not None:   # bytes = esz*(2c + 27G + c)*H*W; FLOPs = 2*9*2c*c*H*W + 9*2c*H*W*8
         px = F_ * H * W
@@ -536,8 +475,7 @@ def dcn_pack(x, raw, weight, bias, cout, *, groups, out=None):
 
 def scale_pixels(x, wmap):
     T, H, W, C = x.shape
-    check(lib().flair_scale_pixels(ptr(x), dtype_code(x), _ld(x), C, ctypes.c_long(T * H * W), ptr(_f32(wmap)),
-                                   stream()), "flair_scale_pixels")
+    call.flair_scale_pixels(x, dtype_code(x), _ld(x), C, T * H * W, _dense(wmap))
     return x
 
 
@@ -548,9 +486,7 @@ def predict_xstart(x, model_out, c_recip, c_recipm1, clip, out=None):
     assert x.dtype == torch.float32 and x.is_contiguous() and model_out.is_contiguous()
     if out is None:
         out = torch.empty_like(x)
-    check(lib().flair_predict_xstart(ptr(x), ptr(model_out), N, C, Cm, H, W, ctypes.c_float(c_recip),
-                                     ctypes.c_float(c_recipm1), int(clip), ptr(out), stream()),
-          "flair_predict_xstart")
+    call.flair_predict_xstart(x, model_out, N, C, Cm, H, W, c_recip, c_recipm1, clip, out)
     return out
 
 
@@ -559,9 +495,7 @@ def sampler_update(coefs, x, x0, restored, aux, z, prev_recon, out=None):
         out = torch.empty_like(x)
     for t in (x, x0, restored, aux, z, prev_recon):
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
-    check(lib().flair_sampler_update(ctypes.byref(coefs), ptr(x), ptr(x0), ptr(restored), ptr(aux), ptr(z),
-                                     ptr(prev_recon), ctypes.c_long(x.numel()), ptr(out), stream()),
-          "flair_sampler_update")
+    call.flair_sampler_update(ctypes.byref(coefs), x, x0, restored, aux, z, prev_recon, x.numel(), out)
     return out
 
 
@@ -569,17 +503,14 @@ def affine_channels(x, C, a, b, lo, hi, sub, mul, out):
     """f32 clip tensors: out = (clamp(x*a+b, lo, hi) - sub[c]) * mul[c] on the first C channels."""
     T, H, W, _ = x.shape
     assert x.dtype == torch.float32 and out.dtype == torch.float32
-    check(lib().flair_affine_channels_f32(ptr(x), _ld(x), C, ctypes.c_long(T * H * W), ctypes.c_float(a),
-                                          ctypes.c_float(b), ctypes.c_float(lo), ctypes.c_float(hi), ptr(sub),
-                                          ptr(mul), ptr(out), _ld(out), stream()), "flair_affine_channels_f32")
+    call.flair_affine_channels_f32(x, _ld(x), C, T * H * W, a, b, lo, hi, sub, mul, out, _ld(out))
     return out
 
 
 def add_frame_bias(x, bias):
     T, H, W, C = x.shape
     assert bias.dtype == torch.float32 and bias.stride(1) == 1
-    check(lib().flair_add_frame_bias(ptr(x), dtype_code(x), _ld(x), C, T, ctypes.c_long(H * W), ptr(bias),
-                                     bias.stride(0), stream()), "flair_add_frame_bias")
+    call.flair_add_frame_bias(x, dtype_code(x), _ld(x), C, T, H * W, bias, bias.stride(0))
     return x
 
 
@@ -587,8 +518,7 @@ def cast_channels(src, dst, coff=0):
     """src: (T,H,W,C) f32 -> channels [coff, coff+C) of clip tensor dst."""
     T, H, W, C = src.shape
     assert src.dtype == torch.float32
-    check(lib().flair_cast_channels(ptr(src), _ld(src), C, ctypes.c_long(T * H * W), ptr(dst), dtype_code(dst),
-                                    _ld(dst), coff, stream()), "flair_cast_channels")
+    call.flair_cast_channels(src, _ld(src), C, T * H * W, dst, dtype_code(dst), _ld(dst), coff)
     return dst
 
 
@@ -597,9 +527,7 @@ def axpby(x, y, a, b, out=None, lo=float("-inf"), hi=float("inf")):
     assert x.dtype == torch.float32 and x.is_contiguous() and (y is None or y.is_contiguous())
     if out is None:
         out = torch.empty_like(x)
-    check(lib().flair_axpby_f32(ptr(x), ptr(y), ctypes.c_float(a), ctypes.c_float(b), ctypes.c_float(lo),
-                                ctypes.c_float(hi), ctypes.c_long(x.numel()), ptr(out), stream()),
-          "flair_axpby_f32")
+    call.flair_axpby_f32(x, y, a, b, lo, hi, x.numel(), out)
     return out
 
 
@@ -612,9 +540,7 @@ def learned_range_variance(model_out, C, min_log, max_log, out=None):
     else:
         var, logvar = out
         assert all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == (N, C, H, W) for t in out)
-    check(lib().flair_learned_range_variance(ptr(model_out), N, C, H, W, ctypes.c_float(min_log),
-                                             ctypes.c_float(max_log), ptr(var), ptr(logvar), stream()),
-          "flair_learned_range_variance")
+    call.flair_learned_range_variance(model_out, N, C, H, W, min_log, max_log, var, logvar)
     return var, logvar
 
 
@@ -628,10 +554,8 @@ def depthwise_filter(x, filt, *, pad, out_stride=1, out_offset=0, stuff=1, stuff
     if out is None:
         out = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (N, C, Ho, Wo)
-    check(lib().flair_depthwise_filter(ptr(x), N * C, H, W, ptr(filt), filt.shape[0], filt.shape[1], pad,
-                                       out_stride, out_offset, stuff, stuff_offset, Ho, Wo, int(reflect), ptr(out),
-                                       stream()),
-          "flair_depthwise_filter")
+    call.flair_depthwise_filter(x, N * C, H, W, filt, filt.shape[0], filt.shape[1], pad, out_stride, out_offset, stuff,
+         stuff_offset, Ho, Wo, reflect, out)
     return out
 
 
@@ -656,11 +580,9 @@ def jpeg_roundtrip(x, q_luma, q_chroma, dct8, want_levels=False, entry="hw"):
         if H != W:
             raise ValueError(f"jpeg_roundtrip: the square entry cannot take {H}x{W}")
         ws = torch.empty_like(x)
-        check(lib().flair_jpeg_roundtrip(ptr(x), N, H, *tables, ptr(ws), ptr(out), ptr(luma), ptr(chroma), stream()),
-              "flair_jpeg_roundtrip")
+        call.flair_jpeg_roundtrip(x, N, H, *tables, ws, out, luma, chroma)
     else:
-        check(lib().flair_jpeg_roundtrip_hw(ptr(x), N, H, W, *tables, ptr(out), ptr(luma), ptr(chroma), stream()),
-              "flair_jpeg_roundtrip_hw")
+        call.flair_jpeg_roundtrip_hw(x, N, H, W, *tables, out, luma, chroma)
     return (out, [luma, chroma]) if want_levels else out
 
 
@@ -674,9 +596,7 @@ def matmul(a, b, out=None):
     if out is None:
         out = torch.empty((batch, M, N), dtype=torch.float32, device=a.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (batch, M, N)
-    check(lib().flair_matmul_f32(ptr(a), ctypes.c_long(M * K if a.dim() == 3 else 0), ptr(b),
-                                 ctypes.c_long(K * N if b.dim() == 3 else 0), ptr(out), batch, M, N, K, stream()),
-          "flair_matmul_f32")
+    call.flair_matmul_f32(a, M * K if a.dim() == 3 else 0, b, K * N if b.dim() == 3 else 0, out, batch, M, N, K)
     return out
 
 
@@ -688,8 +608,7 @@ def gather_mac(x, outer, lin, inner, fov, w, out=None):
     if out is None:
         out = torch.empty((outer, lout, inner), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (outer, lout, inner)
-    check(lib().flair_gather_mac_f32(ptr(x), ctypes.c_long(outer), lin, ctypes.c_long(inner), ptr(fov.contiguous()),
-                                     ptr(w.contiguous()), taps, lout, ptr(out), stream()), "flair_gather_mac_f32")
+    call.flair_gather_mac_f32(x, outer, lin, inner, fov.contiguous(), w.contiguous(), taps, lout, out)
     return out
 
 
@@ -701,11 +620,9 @@ def vsrpp_prep(prop, feat2, flow1, flow_prev, cond1, cond2, flow2_out, flowpad):
     e0 = _prof_begin()
 
     def launch():
-        check(lib().flair_vsrpp_prep(ptr(prop), _ld(prop), ptr(feat2 if second else None),
-                                     _ld(feat2) if second else 0, ptr(_f32(flow1)), ptr(_f32(flow_prev)),
-                                     dtype_code(prop), H, W, C, ptr(cond1), _ld(cond1), ptr(cond2 if second else None),
-                                     _ld(cond2) if second else 0, ptr(flow2_out if second else None), ptr(flowpad),
-                                     _ld(flowpad), stream()), "flair_vsrpp_prep")
+        call.flair_vsrpp_prep(prop, _ld(prop), feat2 if second else None, _ld(feat2) if second else 0, _dense(flow1),
+             _dense(flow_prev), dtype_code(prop), H, W, C, cond1, _ld(cond1), cond2 if second else None,
+             _ld(cond2) if second else 0, flow2_out if second else None, flowpad, _ld(flowpad))
     launch()
     if e0 is not None:   # reads 1-2 features, writes 1-2 warped features + the 4-channel flow pad
         n = 2 if second else 1
@@ -720,10 +637,9 @@ def vsrpp_warp2(prop, feat2, flow1, flow2, cond1, cond2):
     e0 = _prof_begin()
 
     def launch():
-        check(lib().flair_vsrpp_warp2(ptr(prop), _ld(prop), ptr(feat2 if second else None), _ld(feat2) if second else 0,
-                                      ptr(_f32(flow1)), ptr(_f32(flow2) if second else None), dtype_code(prop), H, W, C,
-                                      ptr(cond1), _ld(cond1), ptr(cond2 if second else None), _ld(cond2) if second else 0,
-                                      stream()), "flair_vsrpp_warp2")
+        call.flair_vsrpp_warp2(prop, _ld(prop), feat2 if second else None, _ld(feat2) if second else 0, _dense(flow1),
+             _dense(flow2) if second else None, dtype_code(prop), H, W, C, cond1, _ld(cond1), cond2 if second else None,
+             _ld(cond2) if second else 0)
     launch()
     if e0 is not None:
         n = 2 if second else 1
@@ -736,8 +652,8 @@ def add_act(x0, x1=None, act=ACT_NONE, out=None):
     T, H, W, C = x0.shape
     if out is None:
         out = torch.empty((T, H, W, C), dtype=x0.dtype, device=x0.device)
-    check(lib().flair_add_act_nhwc(ptr(x0), _ld(x0), ptr(x1), _ld(x1) if x1 is not None else 0, dtype_code(x0), C,
-                                   ctypes.c_long(T * H * W), act, ptr(out), _ld(out), stream()), "flair_add_act_nhwc")
+    call.flair_add_act_nhwc(x0, _ld(x0), x1, _ld(x1) if x1 is not None else 0, dtype_code(x0), C, T * H * W, act, out,
+         _ld(out))
     return out
 
 
@@ -754,8 +670,8 @@ def dwconv(x, w_dw, b_dw, *, stride, pw=None, act=ACT_LRELU01, out=None):
     if out is None:
         out = torch.empty((T, Ho, Wo, cout), dtype=torch.float32, device=x.device)
     assert tuple(out.shape[:3]) == (T, Ho, Wo) and out.shape[3] >= cout and out.dtype == torch.float32
-    check(lib().flair_dwconv_nhwc(ptr(x), _ld(x), T, H, W, C, stride, ptr(_f32(w_dw)), ptr(_f32(b_dw)), ptr(_f32(w_pw)),
-                                  ptr(_f32(b_pw)), cout, act, ptr(out), _ld(out), stream()), "flair_dwconv_nhwc")
+    call.flair_dwconv_nhwc(x, _ld(x), T, H, W, C, stride, _dense(w_dw), _dense(b_dw), _dense(w_pw), _dense(b_pw), cout, act, out,
+         _ld(out))
     return out
 
 
@@ -767,8 +683,7 @@ def dwconv7(x, w, b, *, out=None):
     if out is None:
         out = torch.empty((T, H, W, C), dtype=x.dtype, device=x.device)
     assert tuple(out.shape[:3]) == (T, H, W) and out.shape[3] >= C and out.dtype == x.dtype
-    check(lib().flair_dwconv7_nhwc(ptr(x), _ld(x), dtype_code(x), T, H, W, C, ptr(_f32(w)), ptr(_f32(b)), ptr(out),
-                                   _ld(out), stream()), "flair_dwconv7_nhwc")
+    call.flair_dwconv7_nhwc(x, _ld(x), dtype_code(x), T, H, W, C, _dense(w), _dense(b), out, _ld(out))
     return out
 
 
@@ -777,8 +692,7 @@ def maxpool3x3s2(x, out=None):
     T, H, W, C = x.shape
     if out is None:
         out = torch.empty((T, (H + 1) // 2, (W + 1) // 2, C), dtype=x.dtype, device=x.device)
-    check(lib().flair_maxpool3x3s2_nhwc(ptr(x), _ld(x), dtype_code(x), T, H, W, C, ptr(out), _ld(out), stream()),
-          "flair_maxpool3x3s2_nhwc")
+    call.flair_maxpool3x3s2_nhwc(x, _ld(x), dtype_code(x), T, H, W, C, out, _ld(out))
     return out
 
 
@@ -789,8 +703,7 @@ def probe_matrix_rate(iters, workgroups_per_cu=1, sink=None):
     if sink is None:
         sink = torch.zeros(4, dtype=torch.float32, device="cuda")
     flop = ctypes.c_double(0.0)
-    check(lib().flair_probe_matrix_rate(int(iters), int(workgroups_per_cu), ptr(sink), ctypes.byref(flop), stream()),
-          "flair_probe_matrix_rate")
+    call.flair_probe_matrix_rate(int(iters), int(workgroups_per_cu), sink, ctypes.byref(flop))
     return flop.value
 
 
@@ -799,8 +712,7 @@ def probe_stream_rate(src, dst, mode):
     n = dst.numel() * dst.element_size()
     if mode != 1:
         assert src.numel() * src.element_size() == n
-    check(lib().flair_probe_stream_rate(ptr(src) if mode != 1 else ctypes.c_void_p(0), ptr(dst), ctypes.c_size_t(n), int(mode), stream()),
-          "flair_probe_stream_rate")
+    call.flair_probe_stream_rate(src if mode != 1 else None, dst, n, int(mode))
     return n * (2 if mode == 2 else 1)
 
 
@@ -810,8 +722,7 @@ def gated_blend(x, m, gate, out=None):
     assert gate.dtype == torch.float32 and gate.stride(1) == 1 and gate.shape[0] == T
     if out is None:
         out = torch.empty_like(x)
-    check(lib().flair_gated_blend(ptr(x), _ld(x), ptr(m), _ld(m), ptr(gate), gate.stride(0), dtype_code(x), C, T,
-                                  ctypes.c_long(H * W), ptr(out), _ld(out), stream()), "flair_gated_blend")
+    call.flair_gated_blend(x, _ld(x), m, _ld(m), gate, gate.stride(0), dtype_code(x), C, T, H * W, out, _ld(out))
     return out
 
 
@@ -826,10 +737,8 @@ def layer_norm(x, gamma, beta, *, eps=1e-5, pos=None, out=None, out_pos=None):
         out_pos = torch.empty((F_, H, W, C), dtype=x.dtype, device=x.device)
     if pos is not None:
         assert pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape == (H * W, C)
-    check(lib().flair_layernorm_nhwc(ptr(x), dtype_code(x), _ld(x), ctypes.c_long(F_ * H * W), C, ptr(_f32(gamma)),
-                                     ptr(_f32(beta)), ctypes.c_float(eps), ptr(out), _ld(out), ptr(pos),
-                                     H * W if pos is not None else 0, ptr(out_pos), _ld(out_pos) if pos is not None else 0,
-                                     stream()), "flair_layernorm_nhwc")
+    call.flair_layernorm_nhwc(x, dtype_code(x), _ld(x), F_ * H * W, C, _dense(gamma), _dense(beta), eps, out, _ld(out), pos,
+         H * W if pos is not None else 0, out_pos, _ld(out_pos) if pos is not None else 0)
     return out if pos is None else (out, out_pos)
 
 
@@ -845,7 +754,7 @@ def attention_wide(qkv, heads, head_dim, *, q_off, k_off, v_off, head_stride, ou
     p.out_ld = _ld(out)
     p.q_off, p.k_off, p.v_off, p.head_stride = q_off, k_off, v_off, head_stride
     p.scale = 1.0 / (head_dim ** 0.5)
-    check(lib().flair_attention_wide(ctypes.byref(p), ptr(qkv), ptr(out), stream()), "flair_attention_wide")
+    call.flair_attention_wide(ctypes.byref(p), qkv, out)
     return out
 
 
@@ -859,9 +768,8 @@ def argmax_codebook(logits, n_codes, codebook, *, forced_idx=None, out=None):
     idx = torch.empty((F_ * H * W,), dtype=torch.int32, device=logits.device)
     if forced_idx is not None:
         assert forced_idx.dtype == torch.int32 and forced_idx.is_contiguous() and forced_idx.numel() == idx.numel()
-    check(lib().flair_argmax_codebook(ptr(logits), dtype_code(logits), _ld(logits), ctypes.c_long(F_ * H * W), n_codes,
-                                      ptr(codebook), D, ptr(forced_idx), ptr(idx), ptr(out), _ld(out), stream()),
-          "flair_argmax_codebook")
+    call.flair_argmax_codebook(logits, dtype_code(logits), _ld(logits), F_ * H * W, n_codes, codebook, D, forced_idx, idx,
+         out, _ld(out))
     return out, idx
 
 
@@ -877,8 +785,7 @@ def vq_nearest(z, codebook, *, forced_idx=None, out=None):
     idx = torch.empty((F_ * H * W,), dtype=torch.int32, device=z.device)
     if forced_idx is not None:
         assert forced_idx.dtype == torch.int32 and forced_idx.is_contiguous() and forced_idx.numel() == idx.numel()
-    check(lib().flair_vq_nearest_nhwc(ptr(z), dtype_code(z), _ld(z), ctypes.c_long(F_ * H * W), D, ptr(codebook), N,
-                                      ptr(forced_idx), ptr(idx), ptr(out), _ld(out), stream()), "flair_vq_nearest_nhwc")
+    call.flair_vq_nearest_nhwc(z, dtype_code(z), _ld(z), F_ * H * W, D, codebook, N, forced_idx, idx, out, _ld(out))
     return out, idx
 
 
@@ -887,8 +794,7 @@ def adain(content, style, *, eps=1e-5, out=None):
     assert style.shape == content.shape and style.dtype == content.dtype
     if out is None:
         out = torch.empty((F_, H, W, C), dtype=content.dtype, device=content.device)
-    check(lib().flair_adain_nhwc(ptr(content), _ld(content), ptr(style), _ld(style), dtype_code(content), F_, H * W, C,
-                                 ctypes.c_float(eps), ptr(out), _ld(out), stream()), "flair_adain_nhwc")
+    call.flair_adain_nhwc(content, _ld(content), style, _ld(style), dtype_code(content), F_, H * W, C, eps, out, _ld(out))
     return out
 
 
@@ -898,8 +804,7 @@ def sft_fuse(dec, scale, shift, w, out=None):
     assert dec.shape == scale.shape == shift.shape and dec.dtype == scale.dtype == shift.dtype
     if out is None:
         out = torch.empty_like(dec)
-    check(lib().flair_sft_fuse(ptr(dec), ptr(scale), ptr(shift), ctypes.c_float(w), dtype_code(dec),
-                               ctypes.c_long(dec.numel()), ptr(out), stream()), "flair_sft_fuse")
+    call.flair_sft_fuse(dec, scale, shift, w, dtype_code(dec), dec.numel(), out)
     return out
 
 
@@ -924,8 +829,7 @@ def warp_affine_cubic(src, minv, out_hw, *, border=(0.0, 0.0, 0.0), pre=False, p
     Hd, Wd = out_hw
     out = torch.empty((N, C, Hd, Wd), dtype=torch.float32, device=src.device)
     b = (ctypes.c_float * 4)(*([float(v) for v in border] + [0.0] * 4)[:4])
-    check(lib().flair_warp_affine_cubic(ptr(src), int(src.dtype == torch.float64), N, C, Hs, Ws, ptr(minv), Hd, Wd, b,
-                                        int(pre), int(post), ptr(out), stream()), "flair_warp_affine_cubic")
+    call.flair_warp_affine_cubic(src, src.dtype == torch.float64, N, C, Hs, Ws, minv, Hd, Wd, b, pre, post, out)
     return out
 
 
@@ -942,13 +846,11 @@ def _warp_affine_cubic_indexed(src, minv, out_hw, border, pre, post, src_index, 
     _refuse(src_index_host is not None and len(src_index_host) == K,
             f"{what}: src_index_host (the {K} indices on the host) is needed for the range check")
     _refuse(all(0 <= int(i) < Nsrc for i in src_index_host), f"{what}: src_index outside [0, {Nsrc})")
-    for t in (src, minv, src_index):
-        ptr(t)                                              # CPU tensors are refused (FlairHipError)
     Hd, Wd = out_hw
     out = torch.empty((K, C, Hd, Wd), dtype=torch.float32, device=src.device)
     b = (ctypes.c_float * 4)(*([float(v) for v in border] + [0.0] * 4)[:4])
-    check(lib().flair_warp_affine_cubic_indexed(ptr(src), int(src.dtype == torch.float64), Nsrc, ptr(src_index), K, C, Hs, Ws,
-                                                ptr(minv), Hd, Wd, b, int(pre), int(post), ptr(out), stream()), what)
+    call.flair_warp_affine_cubic_indexed(src, src.dtype == torch.float64, Nsrc, src_index, K, C, Hs, Ws, minv, Hd, Wd, b,
+         pre, post, out)
     return out
 
 
@@ -979,13 +881,10 @@ def face_paste(x0, faces, masks, minv, frame_start, frame_start_host, out=None):
     fs = [int(v) for v in frame_start_host]
     _refuse(len(fs) == T + 1 and fs[0] == 0 and fs[-1] == K and all(a <= b for a, b in zip(fs, fs[1:])),
             f"{what}: frame_start must be non-decreasing, start at 0 and end at K = {K} (got {fs})")
-    for t in (x0, faces, masks, minv, frame_start):
-        ptr(t)                                              # CPU tensors are refused (FlairHipError)
     if out is None:
         out = torch.empty_like(x0)
     _refuse(out.dtype == torch.float32 and out.is_contiguous() and out.shape == x0.shape, f"{what}: out must match x0")
-    check(lib().flair_face_paste(ptr(x0), T, C, H, W, ptr(faces), ptr(masks), ptr(minv), K, h, w, ptr(frame_start), ptr(out),
-                                 stream()), what)
+    call.flair_face_paste(x0, T, C, H, W, faces, masks, minv, K, h, w, frame_start, out)
     return out
 
 
@@ -996,8 +895,7 @@ def face_mask_blur(parse_idx, N, H, W, lut, kern, *, repeats=2, edge=10, div=255
     assert lut.dtype == torch.float64 and kern.dtype == torch.float64 and lut.is_cuda and kern.is_cuda
     tmp = torch.empty((N, 1, H, W), dtype=torch.float64, device=parse_idx.device)
     mask = torch.empty_like(tmp)
-    check(lib().flair_face_mask_blur(ptr(parse_idx), N, H, W, ptr(lut), lut.numel(), ptr(kern), kern.numel(), repeats, edge,
-                                     ctypes.c_double(div), ptr(tmp), ptr(mask), stream()), "flair_face_mask_blur")
+    call.flair_face_mask_blur(parse_idx, N, H, W, lut, lut.numel(), kern, kern.numel(), repeats, edge, div, tmp, mask)
     return mask
 
 
@@ -1007,7 +905,7 @@ def face_blend(x0, face, mask):
     assert x0.dtype == face.dtype == mask.dtype == torch.float32 and x0.is_contiguous() and face.is_contiguous()
     assert mask.is_contiguous() and tuple(mask.shape) == (N, 1, H, W) and face.shape == x0.shape
     out = torch.empty_like(x0)
-    check(lib().flair_face_blend(ptr(x0), ptr(face), ptr(mask), N, C, H, W, ptr(out), stream()), "flair_face_blend")
+    call.flair_face_blend(x0, face, mask, N, C, H, W, out)
     return out
 
 
@@ -1018,8 +916,7 @@ def global_avgpool(x, out=None):
     if out is None:
         out = torch.empty((F_, C), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.shape[0] == F_ and out.shape[1] >= C and out.stride(1) == 1
-    check(lib().flair_global_avgpool_nhwc(ptr(x), dtype_code(x), _ld(x), F_, H, W, C, ptr(out), out.stride(0), stream()),
-          "flair_global_avgpool_nhwc")
+    call.flair_global_avgpool_nhwc(x, dtype_code(x), _ld(x), F_, H, W, C, out, out.stride(0))
     return out
 
 
@@ -1033,10 +930,8 @@ def channel_gate(x, gate, *, logit=False, add_x=False, bias=None, add=None, out=
         assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == (F_, C) and t.stride(1) == 1)
     assert add is None or (add.dtype == x.dtype and add.shape == x.shape)
     assert out.dtype == x.dtype and tuple(out.shape[:3]) == (F_, H, W) and out.shape[3] >= C
-    check(lib().flair_channel_gate_nhwc(ptr(x), _ld(x), dtype_code(x), F_, ctypes.c_long(H * W), C, ptr(gate), gate.stride(0),
-                                        int(logit), int(add_x), ptr(bias), bias.stride(0) if bias is not None else 0,
-                                        ptr(add), _ld(add) if add is not None else 0, ptr(out), _ld(out), stream()),
-          "flair_channel_gate_nhwc")
+    call.flair_channel_gate_nhwc(x, _ld(x), dtype_code(x), F_, H * W, C, gate, gate.stride(0), logit, add_x, bias,
+         bias.stride(0) if bias is not None else 0, add, _ld(add) if add is not None else 0, out, _ld(out))
     return out
 
 
@@ -1052,8 +947,7 @@ def upsample_argmax(logits, n_classes, size, table=None):
         assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[0] == n_classes
         D = table.shape[1]
         y = torch.empty((F_, H, W, D), dtype=torch.float32, device=logits.device)
-    check(lib().flair_upsample_argmax_nhwc(ptr(logits), dtype_code(logits), _ld(logits), F_, h, w, n_classes, H, W, ptr(table), D,
-                                           ptr(idx), ptr(y), D, stream()), "flair_upsample_argmax_nhwc")
+    call.flair_upsample_argmax_nhwc(logits, dtype_code(logits), _ld(logits), F_, h, w, n_classes, H, W, table, D, idx, y, D)
     return idx, y
 
 
@@ -1065,8 +959,7 @@ def maxpool2x2s2(x, out=None):
     if out is None:
         out = torch.empty((T, (H + 1) // 2, (W + 1) // 2, C), dtype=x.dtype, device=x.device)
     assert tuple(out.shape) == (T, (H + 1) // 2, (W + 1) // 2, C) and out.dtype == x.dtype
-    check(lib().flair_maxpool2x2s2_nhwc(ptr(x), _ld(x), dtype_code(x), T, H, W, C, ptr(out), _ld(out), stream()),
-          "flair_maxpool2x2s2_nhwc")
+    call.flair_maxpool2x2s2_nhwc(x, _ld(x), dtype_code(x), T, H, W, C, out, _ld(out))
     return out
 
 
@@ -1075,8 +968,7 @@ def spp_maxpool(buf, C, ks):
     tensor ``buf`` and writes MaxPool2d(ks[j], 1, ks[j] // 2) of them into channels [(j + 1) C, (j + 2) C), j = 0, 1, 2."""
     T, H, W, cb = buf.shape
     assert cb >= 4 * C and len(ks) == 3
-    check(lib().flair_spp_maxpool_nhwc(ptr(buf), _ld(buf), dtype_code(buf), T, H, W, C, int(ks[0]), int(ks[1]), int(ks[2]),
-                                       stream()), "flair_spp_maxpool_nhwc")
+    call.flair_spp_maxpool_nhwc(buf, _ld(buf), dtype_code(buf), T, H, W, C, int(ks[0]), int(ks[1]), int(ks[2]))
     return buf
 
 
@@ -1088,8 +980,7 @@ def channel_interleave(a, b, out=None):
     if out is None:
         out = torch.empty((T, H, W, 2 * C), dtype=a.dtype, device=a.device)
     assert tuple(out.shape) == (T, H, W, 2 * C) and out.dtype == a.dtype
-    check(lib().flair_channel_interleave_nhwc(ptr(a), _ld(a), ptr(b), _ld(b), dtype_code(a), C, ctypes.c_long(T * H * W),
-                                              ptr(out), _ld(out), stream()), "flair_channel_interleave_nhwc")
+    call.flair_channel_interleave_nhwc(a, _ld(a), b, _ld(b), dtype_code(a), C, T * H * W, out, _ld(out))
     return out
 
 
@@ -1102,8 +993,7 @@ def yolo_face_decode(x, na, stride, anchor_grid, z, row0, no=16):
     flat = [float(v) for pair in anchor_grid for v in pair]
     assert len(flat) == 2 * na
     arr = (ctypes.c_float * len(flat))(*flat)
-    check(lib().flair_yolo_face_decode(ptr(x), _ld(x), B, ny, nx, int(na), int(no), ctypes.c_float(stride), arr, ptr(z),
-                                       ctypes.c_long(z.shape[1]), ctypes.c_long(row0), stream()), "flair_yolo_face_decode")
+    call.flair_yolo_face_decode(x, _ld(x), B, ny, nx, int(na), int(no), stride, arr, z, z.shape[1], row0)
     return z
 
 
@@ -1119,10 +1009,8 @@ def letterbox(src, new_hw, top_left, out_hw, *, pre=(1.0, 0.0, float("-inf"), fl
         out = torch.empty((B, Ho, Wo, 16), dtype=torch.float32, device=src.device)
     assert tuple(out.shape) == (B, Ho, Wo, 16) and out.dtype == torch.float32
     a, b, lo, hi = pre
-    check(lib().flair_letterbox_nhwc(ptr(src), B, H, W, int(new_hw[0]), int(new_hw[1]), int(top_left[0]), int(top_left[1]), Ho, Wo,
-                                     ctypes.c_float(a), ctypes.c_float(b), ctypes.c_float(lo), ctypes.c_float(hi),
-                                     ctypes.c_float(scale), ctypes.c_float(pad_value), ptr(out), _ld(out), stream()),
-          "flair_letterbox_nhwc")
+    call.flair_letterbox_nhwc(src, B, H, W, int(new_hw[0]), int(new_hw[1]), int(top_left[0]), int(top_left[1]), Ho, Wo,
+         a, b, lo, hi, scale, pad_value, out, _ld(out))
     return out
 
 
@@ -1140,9 +1028,9 @@ def image_metrics(a, b, out=None):
     if out is None:
         out = torch.empty((N, 4), dtype=torch.float64, device=a.device)
     _refuse(out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (N, 4), "image_metrics: out is a dense (N, 4) float64 tensor")
-    nbytes = _lib.image_metrics_workspace(N, H, W)
+    nbytes = lib().flair_image_metrics_workspace(N, H, W)
     ws = _workspace(max(nbytes, 8), a.device, tag="metrics")
-    check(_lib.image_metrics(ptr(a), ptr(b), N, H, W, ptr(out), ptr(ws), nbytes), "flair_image_metrics")
+    call.flair_image_metrics(a, b, N, H, W, out, ws, nbytes)
     return out
 
 
@@ -1159,7 +1047,7 @@ def block_luma_sums(u8, out=None):
         out = torch.empty((N, 64), dtype=torch.int64, device=u8.device)
     _refuse(out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (N, 64),
             "block_luma_sums: out is a dense (N, 64) int64 tensor")
-    check(lib().flair_block_luma_sums(ptr(u8), N, H, W, ptr(out), stream()), "flair_block_luma_sums")
+    call.flair_block_luma_sums(u8, N, H, W, out)
     return out
 
 
@@ -1184,9 +1072,7 @@ def slomo_warp_pack(pair, flow, coef, out=None):
     if out is None:
         out = torch.empty((B, H, W, oc), dtype=pair.dtype, device=pair.device)
     assert tuple(out.shape) == (B, H, W, oc) and out.dtype == pair.dtype
-    c = [ctypes.c_float(v) for v in coef]
-    check(lib().flair_slomo_warp_pack(ptr(pair), _ld(pair), ptr(flow), _ld(flow), dtype_code(pair), B, H, W, *c, ptr(out),
-                                      _ld(out), oc, stream()), "flair_slomo_warp_pack")
+    call.flair_slomo_warp_pack(pair, _ld(pair), flow, _ld(flow), dtype_code(pair), B, H, W, *coef, out, _ld(out), oc)
     return out
 
 
@@ -1197,11 +1083,9 @@ def slomo_blend(pair, flow, io, coef, t, out, mean=SLOMO_MEAN):
     assert flow.dtype == pair.dtype and io.dtype == pair.dtype
     assert tuple(flow.shape[:3]) == (B, H, W) and tuple(io.shape[:3]) == (B, H, W)
     assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, H, W) and out[0].is_contiguous()
-    c = [ctypes.c_float(v) for v in coef]
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    check(lib().flair_slomo_blend(ptr(pair), _ld(pair), ptr(flow), _ld(flow), ptr(io), _ld(io), dtype_code(pair), B, H, W, *c,
-                                  ctypes.c_double(t), m, ptr(out), ctypes.c_long(out.stride(0) if B > 1 else 3 * H * W),
-                                  stream()), "flair_slomo_blend")
+    call.flair_slomo_blend(pair, _ld(pair), flow, _ld(flow), io, _ld(io), dtype_code(pair), B, H, W, *coef, t, m, out,
+         out.stride(0) if B > 1 else 3 * H * W)
     return out
 
 
@@ -1217,7 +1101,7 @@ def corr_volume(fa, fb_nchw, out=None):
     assert tuple(fb_nchw.shape) == (B, D, h, w)
     vol = matmul(fa.reshape(B, h * w, D), fb_nchw.reshape(B, D, h * w), out=None if out is None else out.view(B, h * w, h * w))
     div = float(torch.sqrt(torch.tensor(D).float()))
-    check(lib().flair_corr_scale(ptr(vol), ctypes.c_long(vol.numel()), ctypes.c_float(div), stream()), "flair_corr_scale")
+    call.flair_corr_scale(vol, vol.numel(), div)
     return vol.view(B * h * w, h, w)
 
 
@@ -1230,7 +1114,7 @@ def corr_pool(vol, out=None):
     if out is None:
         out = torch.empty((P, h // 2, w // 2), dtype=torch.float32, device=vol.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (P, h // 2, w // 2)
-    check(lib().flair_corr_pool(ptr(vol), ctypes.c_long(P), h, w, ptr(out), stream()), "flair_corr_pool")
+    call.flair_corr_pool(vol, P, h, w, out)
     return out
 
 
@@ -1253,8 +1137,7 @@ def corr_lookup(pyramid, pyramid_t, flow, scale_corr, scale_corr_t, out):
     e0 = _prof_begin()
 
     def launch(_keep=(pyramid, pyramid_t)):
-        check(lib().flair_corr_lookup(pa, pb, lh, lw, n, ptr(flow), _ld(flow), B, h, w, ctypes.c_float(scale_corr),
-                                      ctypes.c_float(scale_corr_t), ptr(out), _ld(out), stream()), "flair_corr_lookup")
+        call.flair_corr_lookup(pa, pb, lh, lw, n, flow, _ld(flow), B, h, w, scale_corr, scale_corr_t, out, _ld(out))
     launch()
     if e0 is not None:      # algorithmic bytes: an 8 x 8 patch per level and direction read, 98 floats per level written
         _prof_end(e0, ("corr_lookup",), torch.float32, 2.0 * 7 * B * h * w * 2 * n * CORR_TAPS,
@@ -1270,8 +1153,7 @@ def prelu(x0, slope, x1=None, out=None):
     if out is None:
         out = torch.empty((T, H, W, C), dtype=torch.float32, device=x0.device)
     assert out.dtype == torch.float32 and out.shape == x0.shape
-    check(lib().flair_prelu_nhwc(ptr(x0), _ld(x0), ptr(x1), _ld(x1) if x1 is not None else 0, ptr(slope), C,
-                                 ctypes.c_long(T * H * W), ptr(out), _ld(out), stream()), "flair_prelu_nhwc")
+    call.flair_prelu_nhwc(x0, _ld(x0), x1, _ld(x1) if x1 is not None else 0, slope, C, T * H * W, out, _ld(out))
     return out
 
 
@@ -1282,8 +1164,7 @@ def depth_to_space2(x, C, out=None):
     if out is None:
         out = torch.empty((F_, 2 * H, 2 * W, C), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and tuple(out.shape[:3]) == (F_, 2 * H, 2 * W) and out.shape[3] >= C
-    check(lib().flair_depth_to_space2_nhwc(ptr(x), _ld(x), F_, H, W, C, ptr(out), _ld(out), stream()),
-          "flair_depth_to_space2_nhwc")
+    call.flair_depth_to_space2_nhwc(x, _ld(x), F_, H, W, C, out, _ld(out))
     return out
 
 
@@ -1316,8 +1197,7 @@ def axpby_nhwc(x0, a, x1=None, b=0.0, out=None):
     if out is None:
         out = torch.empty((T, H, W, C), dtype=torch.float32, device=x0.device)
     assert out.dtype == torch.float32 and out.shape == x0.shape
-    check(lib().flair_axpby_nhwc(ptr(x0), _ld(x0), ctypes.c_float(a), ptr(x1), _ld(x1) if x1 is not None else 0,
-                                 ctypes.c_float(b), C, ctypes.c_long(T * H * W), ptr(out), _ld(out), stream()), "flair_axpby_nhwc")
+    call.flair_axpby_nhwc(x0, _ld(x0), a, x1, _ld(x1) if x1 is not None else 0, b, C, T * H * W, out, _ld(out))
     return out
 
 
@@ -1328,8 +1208,7 @@ def amt_multiflow_prepare(dec, up, out=None):
     assert dec.dtype == torch.float32 and up.dtype == torch.float32 and tuple(up.shape[:3]) == (B, H, W)
     if out is None:
         out = torch.empty((B, H, W, 40), dtype=torch.float32, device=dec.device)
-    check(lib().flair_amt_multiflow_prepare(ptr(dec), _ld(dec), ptr(up), _ld(up), ctypes.c_long(B * H * W), ptr(out), _ld(out),
-                                            stream()), "flair_amt_multiflow_prepare")
+    call.flair_amt_multiflow_prepare(dec, _ld(dec), up, _ld(up), B * H * W, out, _ld(out))
     return out
 
 
@@ -1343,8 +1222,8 @@ def amt_multiflow_combine(pair, prep, neg_mean, x=None, avg=None):
         x = torch.empty((B, H, W, 16), dtype=torch.float32, device=pair.device)
     if avg is None:
         avg = torch.empty((B, H, W, 4), dtype=torch.float32, device=pair.device)
-    check(lib().flair_amt_multiflow_combine(ptr(pair), _ld(pair), ptr(prep), _ld(prep), ptr(neg_mean), neg_mean.stride(0), B, H, W,
-                                            ptr(x), _ld(x), ptr(avg), _ld(avg), stream()), "flair_amt_multiflow_combine")
+    call.flair_amt_multiflow_combine(pair, _ld(pair), prep, _ld(prep), neg_mean, neg_mean.stride(0), B, H, W, x, _ld(x),
+         avg, _ld(avg))
     return x, avg
 
 
@@ -1355,10 +1234,7 @@ def instance_norm(x, act=ACT_NONE, eps=1e-5, out=None):
     if out is None:
         out = torch.empty((F_, H, W, C), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.shape == x.shape
-    f = lib().flair_instnorm_workspace_bytes
-    f.restype = ctypes.c_size_t
-    nbytes = int(f(F_, H, W, C))
+    nbytes = lib().flair_instnorm_workspace_bytes(F_, H, W, C)
     ws = _workspace(nbytes, x.device, "instnorm")
-    check(lib().flair_instnorm_nhwc(ptr(x), _ld(x), F_, H, W, C, ctypes.c_double(eps), act, ptr(out), _ld(out), ptr(ws),
-                                    ctypes.c_size_t(nbytes), stream()), "flair_instnorm_nhwc")
+    call.flair_instnorm_nhwc(x, _ld(x), F_, H, W, C, eps, act, out, _ld(out), ws, nbytes)
     return out

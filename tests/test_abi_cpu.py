@@ -68,13 +68,13 @@ HOST_ONLY = {"k_align", "chain_supported", "slomo_coefficients"}
 
 
 def test_every_ops_wrapper_is_called_by_a_gpu_test():
-    """Every public function of flair_amd/ops.py (each ends in a lib().flair_* call or prepares one) is called, as
+    """Every public function of flair_amd/ops.py (each ends in a call.flair_*(...) launch or prepares one) is called, as
     `ops.<name>(` or `<name>(`, in at least one test file that carries the gpu marker; a private one that calls the library
     is reached through a public one.  A new entry without a test of its own fails here."""
     import glob
     src = open(os.path.join(ROOT, "flair_amd", "ops.py")).read()
     bodies = dict(zip(re.findall(r"(?m)^def (\w+)\(", src), re.split(r"(?m)^def \w+\(", src)[1:]))
-    launches = {n for n, b in bodies.items() if re.search(r"\blib\(\)\.flair_\w+", b)}
+    launches = {n for n, b in bodies.items() if re.search(r"\b(?:lib\(\)|call)\.flair_\w+", b)}
     assert len(launches) > 60 and {"axpby_nhwc", "amt_multiflow_prepare", "amt_multiflow_combine"} <= launches
     assert HOST_ONLY <= set(bodies) and not HOST_ONLY & launches
     tests = [open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "tests", "test_*.py")))]
