@@ -1,7 +1,8 @@
 """Command line: ``python -m flair_amd restore TASK VIDEO_DIR OUTPUT_DIR [options]`` and the four demo presets, plus the two
 ends of the loop around it: ``degrade TASK CLEAN_DIR OUT_DIR`` makes a task's degraded frames from clean ones with the exact
 operator the restoration assumes (flair_amd.degrade), and ``evaluate RESTORED_DIR TRUTH_DIR`` scores written frames with PSNR
-and SSIM (flair_amd.metrics); ``restore --ground-truth DIR`` scores every video as soon as it is written.
+and SSIM (flair_amd.metrics) and, with ``--lpips {vgg,alex} --weights DIR``, LPIPS (flair_amd.lpips); ``restore --ground-truth
+DIR`` scores every video as soon as it is written.
 ``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo or AMT-G (flair_amd.interpolate).
 ``scenes SRC_DIR --json PATH`` finds the hard cuts of a video (flair_amd.scenes); ``restore`` / ``interpolate --scene-cuts
 auto|PATH`` then treat every shot on its own.
@@ -69,6 +70,39 @@ def _add_cut_options(p, what):
     _add_cut_rule(p)
 
 
+def _add_lpips(p, what, where):
+    p.add_argument("--lpips", choices=("vgg", "alex"), default=None,
+                   help=f"{what} LPIPS on a VGG-16 trunk (vgg16.pth + lpips_vgg.pth; what BasicSR-style evaluation reports) or "
+                        f"an AlexNet trunk (alexnet.pth + lpips_alex.pth; the lpips package's default){where}")
+
+
+def lpips_of(args, command):
+    """(net, weights directory) of a parsed command line's --lpips, or None without it; refusals before any GPU work."""
+    net = getattr(args, "lpips", None)
+    if net is None:
+        return None
+    if command != "evaluate" and not args.ground_truth:
+        raise SystemExit(f"{command}: --lpips scores the written frames against --ground-truth DIR; give one")
+    if not args.weights:
+        raise SystemExit(f"{command}: --lpips {net} reads its trunk and linear layers from --weights DIR; give one")
+    from . import lpips as flp
+    missing = [p for p in flp.weight_files(net, args.weights) if not os.path.isfile(p)]
+    if missing:
+        raise SystemExit(f"{command}: --lpips {net} needs {' and '.join(missing)}")
+    return net, args.weights
+
+
+def load_lpips_of(spec, device, command):
+    """The LPIPS model of lpips_of's result on ``device`` (None for None)."""
+    if spec is None:
+        return None
+    from . import lpips as flp
+    try:
+        return flp.load_lpips(spec[0], spec[1], device)
+    except (ValueError, FileNotFoundError) as exc:
+        raise SystemExit(f"{command}: {exc}")
+
+
 def _add_hparams(p, d):
     p.add_argument("--t-start", type=int, default=d["t_start"])
     p.add_argument("--jpeg-qf", type=int, default=d["jpeg_qf"])
@@ -96,6 +130,7 @@ def make_parser():
     r.add_argument("--ground-truth", default=None, metavar="DIR",
                    help="clean frames of the video (with --output-root: a root holding one directory per video name): "
                         "after a video is written, log its mean PSNR / SSIM and write metrics.json next to the frames")
+    _add_lpips(r, "with --ground-truth: also score", "; the files are read from --weights")
     _add_hparams(r, pl.MAIN_DEFAULTS)
     _add_common(r)
     for name, demo in pl.DEMOS.items():
@@ -118,6 +153,8 @@ def make_parser():
     e.add_argument("truth_dir", metavar="TRUTH_DIR", help="frames are paired with RESTORED_DIR's in natural order")
     e.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the means as JSON")
     e.add_argument("--device", default=None, help="default: cuda")
+    _add_lpips(e, "also score", "")
+    e.add_argument("--weights", default=None, metavar="DIR", help="with --lpips: the directory that holds those files")
     i = sub.add_parser("interpolate", help="factor - 1 new frames between every two frames of a video (SuperSloMo or AMT-G)")
     i.add_argument("src_dir", metavar="SRC_DIR", help="frames of one size")
     i.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png, factor * (T - 1) + 1 of them")
@@ -131,6 +168,7 @@ def make_parser():
     i.add_argument("--ground-truth", default=None, metavar="DIR",
                    help="frames at the new rate: score the written frames against them (PSNR / SSIM)")
     i.add_argument("--json", default=None, metavar="PATH", help="with --ground-truth: also write the values as JSON")
+    _add_lpips(i, "with --ground-truth: also score", "; the files are read from --weights")
     _add_cut_options(i, "synthesise nothing between the two frames of a cut: the in-betweens there are copies of the nearer "
                         "frame (--min-shot keeps its default of 4 here too)")
     s = sub.add_parser("scenes", help="find the hard cuts of a video (block-luma distances; heuristic defaults, not validated "
@@ -215,6 +253,7 @@ def interpolate_of(args):
         raise SystemExit("interpolate: --json writes the scores of --ground-truth DIR")
     if args.ground_truth and not os.path.isdir(args.ground_truth):
         raise SystemExit(f"interpolate: ground truth {args.ground_truth} is not a directory")
+    lpips_of(args, "interpolate")
     return paths
 
 
@@ -237,8 +276,9 @@ def _interpolate(args):
     print(f"wrote {n} frames to {args.out_dir} ({args.factor}x the rate of {args.src_dir})")
     if args.ground_truth:
         from . import metrics as fm
+        model = load_lpips_of(lpips_of(args, "interpolate"), device, "interpolate")
         try:
-            result = fm.evaluate_dirs(args.out_dir, args.ground_truth, device)
+            result = fm.evaluate_dirs(args.out_dir, args.ground_truth, device, **({} if model is None else dict(lpips=model)))
         except ValueError as exc:
             raise SystemExit(str(exc))
         for line in fm.format_report(result):
@@ -298,11 +338,13 @@ def write_json(path, result):
 
 
 def _evaluate(args):
+    spec = lpips_of(args, "evaluate")
     import torch
     from . import metrics as fm
     torch.set_grad_enabled(False)
+    model = load_lpips_of(spec, args.device or "cuda", "evaluate")
     try:
-        result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda")
+        result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda", **({} if model is None else dict(lpips=model)))
     except ValueError as exc:
         raise SystemExit(str(exc))
     for line in fm.format_report(result):
@@ -378,6 +420,7 @@ def main(argv=None):
         return _scenes(args)
     task, jobs = jobs_of(args)
     truth = truth_of(args, jobs)
+    lpips_spec = lpips_of(args, "restore")
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
@@ -405,14 +448,16 @@ def main(argv=None):
                   rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
         hp.update(faces)
         hp.update(how)
+        lpips_model = load_lpips_of(lpips_spec, device, "restore")
+        lpips_kw = {} if lpips_model is None else dict(lpips=lpips_model)      # without the option, the call of before
 
         def restore_one(v, o):
             n = p.restore_video_files(v, o, **hp)
             if truth is not None:
                 from . import metrics as fm
-                result = fm.evaluate_dirs(o, truth[o], device)
+                result = fm.evaluate_dirs(o, truth[o], device, **lpips_kw)
                 print(f"{o}: mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  "
-                      f"ssim {result['mean']['ssim']:.4f}")
+                      f"ssim {result['mean']['ssim']:.4f}" + (f"  lpips {result['mean']['lpips']:.4f}" if lpips_model is not None else ""))
                 write_json(os.path.join(o, "metrics.json"), result)
             return n
         pl.restore_many(jobs, restore_one)

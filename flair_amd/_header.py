@@ -1,7 +1,8 @@
 """include/flair_hip.h read into ctypes: the parameter structs and every entry's prototype.
 
 The header is the contract with libflair_hip.so; nothing of it is restated in Python.  ``STRUCTS`` maps a C struct name to
-a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``.  Only the constructs the header uses
+a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``; ``EVAL_PROTOS`` is the same table
+of include/flair_eval.h, the evaluation-only entries of the same library.  Only the constructs the header uses
 are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
 """
 import collections
@@ -94,3 +95,11 @@ def parse(text):
 
 with open(HEADER_PATH) as _f:
     STRUCTS, PROTOS = parse(_f.read())
+
+# The evaluation-only ABI (include/flair_eval.h: LPIPS), same dialect and same library, in a table of its own: PROTOS stays
+# exactly flair_hip.h.  It declares no struct and may not redeclare an entry of flair_hip.h.
+EVAL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "flair_eval.h")
+with open(EVAL_HEADER_PATH) as _f:
+    _eval_structs, EVAL_PROTOS = parse(_f.read())
+if _eval_structs or set(EVAL_PROTOS) & set(PROTOS):
+    raise HeaderError(f"flair_eval.h declares a struct or an entry of flair_hip.h: {sorted(_eval_structs) + sorted(set(EVAL_PROTOS) & set(PROTOS))}")

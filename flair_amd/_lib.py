@@ -1,4 +1,5 @@
-"""ctypes binding of libflair_hip.so, derived from the C ABI's own header (include/flair_hip.h, read by _header.py).
+"""ctypes binding of libflair_hip.so, derived from the C ABI's own headers (include/flair_hip.h and the evaluation-only
+include/flair_eval.h, read by _header.py).
 
 The library is the product path: there is no CPU or PyTorch fallback.  Loading fails
 loudly (``FlairHipUnavailable``) when the shared object has not been built.  ``lib()`` is the
@@ -11,7 +12,10 @@ import os
 
 import torch  # noqa: F401  (must be imported first: the library binds to torch's HIP runtime)
 
-from ._header import PROTOS, STRUCTS
+from ._header import EVAL_PROTOS, PROTOS, STRUCTS
+
+# every declared entry of the library: the sampling path's (flair_hip.h) and the evaluation-only ones (flair_eval.h)
+ALL_PROTOS = {**PROTOS, **EVAL_PROTOS}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libflair_hip.so")
@@ -46,7 +50,7 @@ def lib():
                 f"g.build()'` (or `make -C flair_amd/csrc`). The HIP library is required; "
                 f"there is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (restype, params) in PROTOS.items():
+        for name, (restype, params) in ALL_PROTOS.items():
             f = getattr(l, name)
             f.restype, f.argtypes = restype, [p.ctype for p in params]
         _lib = l
@@ -89,7 +93,7 @@ _ELEM_DTYPE = {"float": torch.float32, "double": torch.float64, "int": torch.int
                "long long": torch.int64}
 _LAUNCHES = {name: [(i, p.name, _ELEM_DTYPE.get(p.elem)) for i, p in enumerate(params[:-1])
                     if p.elem is not None and p.ctype is ctypes.c_void_p]
-             for name, (restype, params) in PROTOS.items()
+             for name, (restype, params) in ALL_PROTOS.items()
              if restype is ctypes.c_int and params and params[-1].name == "stream"}
 
 
@@ -117,7 +121,7 @@ class _Entries:
 
     def __getattr__(self, name):
         if name not in _LAUNCHES:
-            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream")
+            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream, nor one of flair_eval.h")
         return functools.partial(_launch, name)
 
 

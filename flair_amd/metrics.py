@@ -1,4 +1,5 @@
-"""PSNR and SSIM of written frames against ground truth, on the GPU (``flair_image_metrics``, csrc/metrics.hip).
+"""PSNR, SSIM and (on request) LPIPS of written frames against ground truth, on the GPU (``flair_image_metrics``,
+csrc/metrics.hip; ``flair_amd.lpips``, csrc/lpips.hip).
 
 The reference ships no scoring tool; this is the restoration literature's usual pair, on the bytes that get written
 (float images go through ``io.to_bytes`` first, so a metric always describes the files):
@@ -8,7 +9,10 @@ The reference ships no scoring tool; this is the restoration literature's usual 
     ((H - 10) x (W - 10), no padding), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, the mean over the map and the three
     channels.
 
-Not measured: the Y-channel and border-cropped variants, perceptual (LPIPS), identity and temporal metrics.
+  * ``lpips``, only with a model from ``flair_amd.lpips.load_lpips``: the ``lpips`` package's 0.1 metric on a VGG-16 or AlexNet
+    trunk, as restated in include/flair_eval.h.
+
+Not measured: the Y-channel and border-cropped variants, identity and temporal metrics.
 """
 import math
 import os
@@ -67,25 +71,39 @@ def _groups(sizes, batch):
     return groups
 
 
-def evaluate_dirs(restored_dir, truth_dir, device, batch=8):
+def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None):
     """Score the frames of ``restored_dir`` against those of ``truth_dir``, paired in ``io.list_frames`` order:
     ``dict(frames=[{name, psnr, ssim}], mean={psnr, ssim}, count)``; the means are those of the per-frame values.
     ValueError when a directory is empty, the counts differ, a pair differs in size or is smaller than 11 pixels a side
     (checked on the file headers, before anything is decoded).  The next batch is decoded and uploaded while the current
-    one is measured (io.iter_frame_batches)."""
+    one is measured (io.iter_frame_batches).  ``lpips``: a ``flair_amd.lpips.LPIPS`` model; every frame dict and ``mean``
+    then gain ``lpips``, and frames below the trunk's minimum are refused with the others (without one the result is what
+    it was before the option existed)."""
     ra, rb, sizes = _pairs(restored_dir, truth_dir)
+    if lpips is not None:
+        from . import lpips as flp
+        for pa, pb, (h, w) in zip(ra, rb, sizes):
+            flp.check_size(lpips.net, h, w, what=f"evaluate: {pa} and {pb}")
     frames = []
     for first, (a, b) in fio.iter_frame_batches([ra, rb], _groups(sizes, max(1, int(batch))), device):
         got = psnr_ssim(a, b)
         for i, (p, s) in enumerate(zip(got["psnr"], got["ssim"])):
             frames.append(dict(name=os.path.basename(ra[first + i]), psnr=p, ssim=s))
+        if lpips is not None:
+            for i, d in enumerate(lpips(a, b)):
+                frames[first + i]["lpips"] = d
     n = len(frames)
     mean = dict(psnr=sum(f["psnr"] for f in frames) / n, ssim=sum(f["ssim"] for f in frames) / n)
+    if lpips is not None:
+        mean["lpips"] = sum(f["lpips"] for f in frames) / n
     return dict(frames=frames, mean=mean, count=n)
 
 
 def format_report(result):
-    """One line per frame and the means, four decimals each."""
-    lines = [f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" for f in result["frames"]]
-    lines.append(f"mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  ssim {result['mean']['ssim']:.4f}")
+    """One line per frame and the means, four decimals each (``lpips`` last, where the result holds it)."""
+    def tail(d):
+        return f"  lpips {d['lpips']:.4f}" if "lpips" in d else ""
+    lines = [f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" + tail(f) for f in result["frames"]]
+    lines.append(f"mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  ssim {result['mean']['ssim']:.4f}"
+                 + tail(result["mean"]))
     return lines

@@ -1034,6 +1034,67 @@ def image_metrics(a, b, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- LPIPS (lpips.hip, include/flair_eval.h)
+LPIPS_TAP_PARTS = 1024                      # FLAIR_LPIPS_TAP_PARTS: partials per frame, the tap kernel's workspace in closed form
+LPIPS_TAP_WIDTHS = (64, 128, 192, 256, 384, 512)
+
+
+def lpips_prepare(a, b, out=None):
+    """Both (N, H, W, 3) uint8 frame sets -> one (2 N, H, W, 16) f32 clip tensor (flair_lpips_prepare): frames 0 .. N-1 are
+    a's, the rest b's; channels 0 .. 2 = ((2 byte / 255 - 1) - shift) / scale, channels 3 .. 15 = 0.  a, b: dense, on the GPU,
+    at any byte alignment; out: optional (2 N, H, W, >= 16) view."""
+    _refuse(a.dim() == 4 and a.shape[3] == 3 and tuple(a.shape) == tuple(b.shape),
+            f"lpips_prepare: two (N, H, W, 3) frame sets of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    _refuse(a.dtype == torch.uint8 and b.dtype == torch.uint8, f"lpips_prepare: uint8 frames, got {a.dtype} and {b.dtype}")
+    _refuse(a.is_contiguous() and b.is_contiguous(), "lpips_prepare: dense (contiguous) frames")
+    N, H, W, _ = a.shape
+    if out is None:
+        out = torch.empty((2 * N, H, W, 16), dtype=torch.float32, device=a.device)
+    _refuse(tuple(out.shape[:3]) == (2 * N, H, W), f"lpips_prepare: out holds {tuple(out.shape[:3])} pixels, not {(2 * N, H, W)}")
+    call.flair_lpips_prepare(a, b, N, H, W, out, _ld(out))
+    return out
+
+
+def lpips_tap(fa, fb, w, acc):
+    """acc[f] += mean over the pixels of sum_c w_c (fa^ - fb^)^2, the features normalised per pixel over the channels
+    (flair_lpips_tap).  fa, fb: (F, H, W, C) f32 clip views of one shape (any pixel stride), C one of LPIPS_TAP_WIDTHS; w: (C,)
+    f32; acc: (F,) float64, accumulated over a trunk's five taps.  The same bits in every run and for every F."""
+    _refuse(fa.dim() == 4 and tuple(fa.shape) == tuple(fb.shape), f"lpips_tap: two clip tensors of one shape, got {tuple(fa.shape)} and {tuple(fb.shape)}")
+    F_, H, W, C = fa.shape
+    _refuse(w.dim() == 1 and w.shape[0] == C and w.is_contiguous(), f"lpips_tap: w holds the {C} weights of the tap, got {tuple(w.shape)}")
+    _refuse(acc.dim() == 1 and acc.shape[0] == F_ and acc.is_contiguous(), f"lpips_tap: acc is a dense ({F_},) float64 tensor")
+    nbytes = F_ * LPIPS_TAP_PARTS * 8
+    ws = _workspace(nbytes, fa.device, tag="lpips")
+    call.flair_lpips_tap(fa, _ld(fa), fb, _ld(fb), F_, H * W, C, w, acc, ws, nbytes)
+    return acc
+
+
+def maxpool_valid(x, k, out=None):
+    """nn.MaxPool2d(k, 2), no padding, floor mode, k = 2 or 3, on an f32 clip tensor (flair_maxpool_valid_s2_nhwc):
+    (F, H, W, C) -> (F, (H - k) // 2 + 1, (W - k) // 2 + 1, C); out: optional view of that shape."""
+    F_, H, W, C = x.shape
+    Ho, Wo = (H - k) // 2 + 1, (W - k) // 2 + 1
+    if out is None:
+        out = torch.empty((F_, max(Ho, 0), max(Wo, 0), C), dtype=torch.float32, device=x.device)
+    _refuse(tuple(out.shape) == (F_, max(Ho, 0), max(Wo, 0), C), f"maxpool_valid: out is {tuple(out.shape)}, not {(F_, Ho, Wo, C)}")
+    call.flair_maxpool_valid_s2_nhwc(x, _ld(x), F_, H, W, C, int(k), out, _ld(out))
+    return out
+
+
+def alexnet_stem(x, w, bias, out=None):
+    """relu(Conv2d(3, 64, 11, stride 4, padding 2)) of AlexNet on prepared frames (flair_alexnet_stem): x (F, H, W, >= 3) f32
+    clip tensor, w (363, 64) f32 with row (ky * 11 + kx) * 3 + c, bias (64,) -> (F, (H - 7) // 4 + 1, (W - 7) // 4 + 1, 64)."""
+    F_, H, W, _ = x.shape
+    _refuse(tuple(w.shape) == (363, 64) and w.is_contiguous() and tuple(bias.shape) == (64,),
+            f"alexnet_stem: w is (363, 64) and bias (64,), got {tuple(w.shape)} and {tuple(bias.shape)}")
+    Ho, Wo = max((H - 7) // 4 + 1, 0), max((W - 7) // 4 + 1, 0)
+    if out is None:
+        out = torch.empty((F_, Ho, Wo, 64), dtype=torch.float32, device=x.device)
+    _refuse(tuple(out.shape[:3]) == (F_, Ho, Wo) and out.shape[3] >= 64, f"alexnet_stem: out is {tuple(out.shape)}, not {(F_, Ho, Wo, 64)}")
+    call.flair_alexnet_stem(x, _ld(x), F_, H, W, w, bias, out, _ld(out))
+    return out
+
+
 # --------------------------------------------------------------------------- scene cuts (scenes.hip)
 def block_luma_sums(u8, out=None):
     """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB
