@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -44,30 +45,6 @@ struct ChainArgs {
     int T, H, W;
 };
 
-template <typename E> struct MmaC;
-template <> struct MmaC<bf16_t> {
-    static constexpr int BKE = 32;
-    static __device__ __forceinline__ int chunk(int i, int half) { return 2 * i + half; }
-    static __device__ __forceinline__ void run(const uint4 (&a)[2], const uint4 (&b)[2], f32x16& acc) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]),
-                                                      __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]),
-                                                      __builtin_bit_cast(bf16x8, b[1]), acc, 0, 0, 0);
-    }
-    static constexpr int MFMA_PER_STEP = 2;
-};
-template <> struct MmaC<float> {
-    static constexpr int BKE = 16;
-    static __device__ __forceinline__ int chunk(int i, int half) { return 2 * half + i; }
-    static __device__ __forceinline__ void run(const uint4 (&a)[2], const uint4 (&b)[2], f32x16& acc) {
-        const float* af = reinterpret_cast<const float*>(a);
-        const float* bf = reinterpret_cast<const float*>(b);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], bf[s], acc, 0, 0, 0);
-    }
-    static constexpr int MFMA_PER_STEP = 8;
-};
-
 // activation of N values with ONE (wave-uniform) branch on the runtime code, not one per element
 template <int N>
 __device__ __forceinline__ void act_vec(float (&v)[N], int act) {
@@ -75,6 +52,7 @@ __device__ __forceinline__ void act_vec(float (&v)[N], int act) {
 #pragma unroll
         for (int e = 0; e < N; ++e) v[e] = silu_f(v[e]);
     } else if (act != FLAIR_ACT_NONE) {
+        // (not leaky_slope / leaky_act: the rule in mfma_tile.h -- its fourth value grows conv_chain_kernel by ~100 instructions)
         const float slope = act == FLAIR_ACT_RELU ? 0.f : 0.1f;      // max(v, slope * v) for slope in [0, 1)
 #pragma unroll
         for (int e = 0; e < N; ++e) v[e] = fmaxf(v[e], v[e] * slope);
@@ -87,7 +65,7 @@ template <typename E, int C, int TH, int TW, bool HASA>
 __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
     prefetch_kernargs<sizeof(ChainArgs)>();
     constexpr int NT = 512, NW = 8;
-    constexpr int BKE = MmaC<E>::BKE;
+    constexpr int BKE = Mma<E>::BKE;
     constexpr int VEC = ET<E>::VEC;
     constexpr unsigned ESZ = sizeof(E);
     constexpr int PITCH = 80;
@@ -194,13 +172,13 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
         uint4 fa0[2][2], fa1[2][2], fb[2][2];
         auto load_tap = [&](int set, int tap9) {
             const int kh = tap9 / 3, kw = tap9 % 3;
-            fa0[set][0] = *reinterpret_cast<const uint4*>(wb0 + tap9 * PITCH + 16 * MmaC<E>::chunk(0, lh));
-            fa0[set][1] = *reinterpret_cast<const uint4*>(wb0 + tap9 * PITCH + 16 * MmaC<E>::chunk(1, lh));
-            fa1[set][0] = *reinterpret_cast<const uint4*>(wb1 + tap9 * PITCH + 16 * MmaC<E>::chunk(0, lh));
-            fa1[set][1] = *reinterpret_cast<const uint4*>(wb1 + tap9 * PITCH + 16 * MmaC<E>::chunk(1, lh));
+            fa0[set][0] = *reinterpret_cast<const uint4*>(wb0 + tap9 * PITCH + 16 * Mma<E>::chunk(0, lh));
+            fa0[set][1] = *reinterpret_cast<const uint4*>(wb0 + tap9 * PITCH + 16 * Mma<E>::chunk(1, lh));
+            fa1[set][0] = *reinterpret_cast<const uint4*>(wb1 + tap9 * PITCH + 16 * Mma<E>::chunk(0, lh));
+            fa1[set][1] = *reinterpret_cast<const uint4*>(wb1 + tap9 * PITCH + 16 * Mma<E>::chunk(1, lh));
             const char* hp = pb + (kh * inW + kw) * PITCH;
-            fb[set][0] = *reinterpret_cast<const uint4*>(hp + 16 * MmaC<E>::chunk(0, lh));
-            fb[set][1] = *reinterpret_cast<const uint4*>(hp + 16 * MmaC<E>::chunk(1, lh));
+            fb[set][0] = *reinterpret_cast<const uint4*>(hp + 16 * Mma<E>::chunk(0, lh));
+            fb[set][1] = *reinterpret_cast<const uint4*>(hp + 16 * Mma<E>::chunk(1, lh));
         };
         load_tap(0, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
@@ -208,10 +186,10 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
         for (int tap9 = 0; tap9 < 9; ++tap9) {
             const int set = tap9 & 1;
             if (tap9 < 8) load_tap(set ^ 1, tap9 + 1);
-            MmaC<E>::run(fa0[set], fb[set], acc[0]);
-            MmaC<E>::run(fa1[set], fb[set], acc[1]);
+            Mma<E>::run(fa0[set], fb[set], acc[0]);
+            Mma<E>::run(fa1[set], fb[set], acc[1]);
             if (tap9 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-            __builtin_amdgcn_sched_group_barrier(0x8, 2 * MmaC<E>::MFMA_PER_STEP, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 2 * Mma<E>::MFMA_PER_STEP, 0);
         }
     };
 
@@ -358,11 +336,8 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
                 __syncthreads();
             }
         }
-        // ---- epilogue of this batch, straight from the accumulators (no LDS round trip, no barrier).  A lane of
-        // the 32x32 MFMA result holds 4 consecutive couts of its pixel per register quad (quad g: couts 8g + 4*lh ..);
-        // v_permlane32_swap between the two half-waves turns quads 2j, 2j+1 into 8 consecutive couts per lane
-        // (lower half: 16j .. 16j+7, upper half: 16j+8 .. 16j+15), i.e. one 16-byte bf16 store (f32: the quad is
-        // already 16 bytes) and residual loads of the same shape.
+        // ---- epilogue of this batch, straight from the accumulators (no LDS round trip, no barrier): one 16-byte piece per
+        // lane and store -- bf16 the octet of acc_octet, f32 the register quad as it is (layout: mfma_tile.h).
 #pragma unroll
         for (int ii = 0; ii < MAXIB; ++ii) {
             const int it = wave + ii * NW;
@@ -384,20 +359,10 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
                         else
                             act_vec<4>(v, a.actB);
                         if (co < a.CoutB && hh < a.H) {
-                            if (a.res0) {
-                                float r[4];
-                                Vec16<E>::load(reinterpret_cast<const E*>(a.res0) + p * a.res0Ld + co, r);
+                            if (a.res0) add_piece<E>(v, reinterpret_cast<const E*>(a.res0) + p * a.res0Ld + co);
+                            if (a.res1) add_piece<E>(v, reinterpret_cast<const E*>(a.res1) + p * a.res1Ld + co);
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] += r[e];
-                            }
-                            if (a.res1) {
-                                float r[4];
-                                Vec16<E>::load(reinterpret_cast<const E*>(a.res1) + p * a.res1Ld + co, r);
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] += r[e];
-                            }
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] *= a.outScale;
+                            for (int e = 0; e < VEC; ++e) v[e] *= a.outScale;
                             Vec16<E>::store(reinterpret_cast<E*>(a.y) + p * a.yLd + co, v);
                         }
                     }
@@ -406,32 +371,16 @@ __global__ __launch_bounds__(512, 2) void conv_chain_kernel(ChainArgs a) {
                     for (int j = 0; j < 2; ++j) {
                         const int co = cofrag + 16 * j + 8 * lh;    // after the swap
                         float v[8];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const auto sw2 = __builtin_amdgcn_permlane32_swap(
-                                __float_as_uint(acc[ii][i][8 * j + e]), __float_as_uint(acc[ii][i][8 * j + 4 + e]), false, false);
-                            v[e] = __uint_as_float(sw2[0]);
-                            v[4 + e] = __uint_as_float(sw2[1]);
-                        }
+                        acc_octet(acc[ii][i], j, v);
                         if (a.actB == FLAIR_ACT_DCN_OFFSETS)
                             dcn_offset_act<8>(v, co, a.actParam, a.actPeriod);
                         else
                             act_vec<8>(v, a.actB);
                         if (co < a.CoutB && hh < a.H) {
-                            if (a.res0) {
-                                float r[8];
-                                Vec16<E>::load(reinterpret_cast<const E*>(a.res0) + p * a.res0Ld + co, r);
+                            if (a.res0) add_piece<E>(v, reinterpret_cast<const E*>(a.res0) + p * a.res0Ld + co);
+                            if (a.res1) add_piece<E>(v, reinterpret_cast<const E*>(a.res1) + p * a.res1Ld + co);
 #pragma unroll
-                                for (int e = 0; e < 8; ++e) v[e] += r[e];
-                            }
-                            if (a.res1) {
-                                float r[8];
-                                Vec16<E>::load(reinterpret_cast<const E*>(a.res1) + p * a.res1Ld + co, r);
-#pragma unroll
-                                for (int e = 0; e < 8; ++e) v[e] += r[e];
-                            }
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] *= a.outScale;
+                            for (int e = 0; e < VEC; ++e) v[e] *= a.outScale;
                             Vec16<E>::store(reinterpret_cast<E*>(a.y) + p * a.yLd + co, v);
                         }
                     }
@@ -552,18 +501,15 @@ __global__ __launch_bounds__(512, 2) void conv_resident_kernel(ResArgs a) {
 
     // ---- fragment read offsets (per lane, fixed): A = weight row tap9 * 64 + cf * 32 + lr, B = halo row (RPW wave + h) * 34 + kw + lr
     unsigned aoff[2], boff[3][2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        aoff[ks] = (unsigned)(lr * 64 + (((2 * ks + lh) ^ ((lr >> 2) & 3)) << 4));
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
-            boff[kw][ks] = (unsigned)((RPW * wave * HWP + kw + lr) * 64 + (((2 * ks + lh) ^ (((kw + lr) >> 2) & 3)) << 4));
-    }
+    dma_frag_offsets(lr, lh, RPW * wave * HWP, aoff, boff);
 
     // ---- epilogue of one 64-cout block, one (row, 16-cout group) piece at a time (all lanes take part in the swaps).  The
     // accumulators start at the bias.  DCN offsets / masks: out = A * rcp(1 + 2^(k v)) + B with per-lane constants
     // (residues: mag * tanh(v) = mag - 2 mag / (1 + e^{2v}); masks: 1 / (1 + e^{-v})), three vector and two transcendental
     // instructions per value.
+    // This kernel's epilogue pieces stand between the taps' MFMAs, and each of leaky_slope, acc_octet, dcn_offset_act_fast and
+    // pack_piece / store_piece moved hipcc's schedule and its waits here: under the rule in mfma_tile.h those four stay spelled
+    // out (dma_frag_offsets and dma_tap_loop did not, and are used).  The three-valued slope is enough: flair_conv_chain refuses LRELU02.
     const float slope = a.act == FLAIR_ACT_NONE ? 1.f : a.act == FLAIR_ACT_RELU ? 0.f : 0.1f;
     const unsigned yLdB = (unsigned)a.yLd * 2u;
     const long prow = ((long)t * a.H + h0 + RPW * wave) * a.W + w0;        // first pixel of the wave's first row
@@ -595,58 +541,19 @@ __global__ __launch_bounds__(512, 2) void conv_resident_kernel(ResArgs a) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] *= scale * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v[e]));
         }
+        // (plain stores: write-through `sc1` / `sc0 sc1` stores measured 176-177 us against 178.6 us on the conv_offset[6] ->
+        // alignment pair, non-temporal ones 188 us: profiles/README.md, round 4)
         alignas(16) E out[8];
         Vec16<E>::store(out, v);
         const uint4 ov = *reinterpret_cast<const uint4*>(out);
         const unsigned yo = co + 8 * lh < a.Cout ? yLane + (unsigned)(j * a.W) * yLdB + 2u * (unsigned)co : FLAIR_OOB;
-        // (plain stores: write-through `sc1` / `sc0 sc1` stores measured 176-177 us against 178.6 us on the conv_offset[6] ->
-        // alignment pair, non-temporal ones 188 us: profiles/README.md, round 4)
         __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{ov.x, ov.y, ov.z, ov.w}, yd, (int)yo, 0, 0);
     };
 
-    // ---- one stage = 3 column taps x 3 row taps x (RPW rows x 2 cout fragments x 2 k-steps) MFMAs.  The fragments of step n + 1
-    // (A: 4 reads; B: 2 (RPW + 2) more when the column tap changes) are requested before the MFMAs of step n;
-    // `hook(step)` runs after the MFMAs of a step have been issued (pieces of the previous block's epilogue).
+    // ---- one stage = dma_tap_loop (mfma_tile.h) on ring slot `slot` and halo chunk image `ch`; `hook(step)` runs after the MFMAs
+    // of a step have been issued (pieces of the previous block's epilogue, DMA instructions of stage s_ + 2).  One row per wave.
     auto compute = [&](int slot, int ch, f32x16 (&acc)[RPW][2], auto&& hook) {
-        const char* wb = smem + RING + slot * SLOT;
-        const char* xb = smem + ch * HBYTES;
-        uint4 fb[2][RPW + 2][2];   // [set][halo row RPW wave + h][k-step]
-        uint4 fa[2][2][2];         // [set][cout fragment][k-step]
-        auto load_b = [&](int set, int kw) {
-#pragma unroll
-            for (int h = 0; h < RPW + 2; ++h)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-                    fb[set][h][ks] = *reinterpret_cast<const uint4*>(xb + h * (HWP * 64) + boff[kw][ks]);
-        };
-        auto load_a = [&](int set, int kh, int kw) {
-#pragma unroll
-            for (int cf = 0; cf < 2; ++cf)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-                    fa[set][cf][ks] = *reinterpret_cast<const uint4*>(wb + (kh * 3 + kw) * 4096 + cf * 2048 + aoff[ks]);
-        };
-        load_b(0, 0);
-        load_a(0, 0, 0);
-#pragma unroll
-        for (int step = 0; step < 9; ++step) {
-            const int kq = step / 3, kh = step % 3;
-            const int nkq = (step + 1) / 3, nkh = (step + 1) % 3;
-            if (step < 8) {
-                if (nkh == 0) load_b(nkq & 1, nkq);
-                load_a((step + 1) & 1, nkh, nkq);
-            }
-#pragma unroll
-            for (int j = 0; j < RPW; ++j)
-#pragma unroll
-                for (int cf = 0; cf < 2; ++cf) {
-                    acc[j][cf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[step & 1][cf][0]),
-                                                                         __builtin_bit_cast(bf16x8, fb[kq & 1][j + kh][0]), acc[j][cf], 0, 0, 0);
-                    acc[j][cf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[step & 1][cf][1]),
-                                                                         __builtin_bit_cast(bf16x8, fb[kq & 1][j + kh][1]), acc[j][cf], 0, 0, 0);
-                }
-            hook(step);
-        }
+        dma_tap_loop(smem + RING + slot * SLOT, smem + ch * HBYTES, aoff, boff, acc[0], hook);
     };
     // accumulators of a block start at its biases (register r of a fragment <-> cout 8 (r / 4) + 4 lh + r % 4)
     auto init_acc = [&](f32x16 (&acc)[RPW][2], int blk) {
@@ -909,6 +816,8 @@ __global__ __launch_bounds__(512, 2) void conv_pair_kernel(PairArgs a) {
 
     // ---- intermediate -> LDS over the halo: activation, zero outside the image, bf16; lane = pixel q, 8 consecutive channels per piece
     {
+        // (three-valued, not leaky_slope: the rule in mfma_tile.h -- the fourth value costs this kernel 5 VGPRs; the entry sends
+        // only none / ReLU / LeakyReLU(0.1) here)
         const float slopeA = a.actA == FLAIR_ACT_NONE ? 1.f : a.actA == FLAIR_ACT_RELU ? 0.f : 0.1f;
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii) {
@@ -922,12 +831,7 @@ __global__ __launch_bounds__(512, 2) void conv_pair_kernel(PairArgs a) {
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
                     float v[8];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(accA[ii][cf][8 * jj + e]), __float_as_uint(accA[ii][cf][8 * jj + 4 + e]), false, false);
-                        v[e] = __uint_as_float(sw2[0]);
-                        v[4 + e] = __uint_as_float(sw2[1]);
-                    }
+                    acc_octet(accA[ii][cf], jj, v);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = inimg ? fmaxf(v[e], v[e] * slopeA) : 0.f;
                     alignas(16) E out[8];
@@ -959,46 +863,10 @@ __global__ __launch_bounds__(512, 2) void conv_pair_kernel(PairArgs a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) r1v[g] = buf_load16(r1d, (unsigned)lr * r1LdB + (unsigned)(32 * g + 16 * lh));
     }
-    unsigned boffB[3][2];
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-            boffB[kw][ks] = (unsigned)((wave * WMID + kw + lr) * 64 + (((2 * ks + lh) ^ (((kw + lr) >> 2) & 3)) << 4));
+    unsigned aoffB[2], boffB[3][2];                   // (aoffB == aoff)
+    dma_frag_offsets(lr, lh, wave * WMID, aoffB, boffB);
     f32x16 accB[2];
-    auto compute_B = [&](int slot, int ch) {
-        const char* wb = smem + RING + slot * SLOT;
-        const char* xb = smem + ch * MID_IMG;
-        uint4 fb[2][3][2], fa[2][2][2];
-        auto load_b = [&](int set, int kw) {
-#pragma unroll
-            for (int h = 0; h < 3; ++h)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fb[set][h][ks] = *reinterpret_cast<const uint4*>(xb + h * (WMID * 64) + boffB[kw][ks]);
-        };
-        auto load_a = [&](int set, int kh, int kw) {
-#pragma unroll
-            for (int cf = 0; cf < 2; ++cf)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fa[set][cf][ks] = *reinterpret_cast<const uint4*>(wb + (kh * 3 + kw) * 4096 + cf * 2048 + aoff[ks]);
-        };
-        load_b(0, 0);
-        load_a(0, 0, 0);
-#pragma unroll
-        for (int step = 0; step < 9; ++step) {
-            const int kq = step / 3, kh = step % 3;
-            const int nkq = (step + 1) / 3, nkh = (step + 1) % 3;
-            if (step < 8) {
-                if (nkh == 0) load_b(nkq & 1, nkq);
-                load_a((step + 1) & 1, nkh, nkq);
-            }
-#pragma unroll
-            for (int cf = 0; cf < 2; ++cf)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-                    accB[cf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[step & 1][cf][ks]), __builtin_bit_cast(bf16x8, fb[kq & 1][kh][ks]), accB[cf], 0, 0, 0);
-        }
-    };
+    auto compute_B = [&](int slot, int ch) { dma_tap_loop(smem + RING + slot * SLOT, smem + ch * MID_IMG, aoffB, boffB, accB, dma_no_hook{}); };
     // stage 2 (B, chunk 0): weights B0 landed (younger: weights B1 and the residual loads), the intermediate is written
     if (nres == 0) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NWS) : "memory");
     else if (nres == 4) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NWS + 4) : "memory");
@@ -1014,7 +882,7 @@ __global__ __launch_bounds__(512, 2) void conv_pair_kernel(PairArgs a) {
     compute_B(1, 1);
 
     // ---- epilogue from the accumulators: activation, + res0 + res1, scale, 16-byte stores
-    const float slopeB = a.actB == FLAIR_ACT_NONE ? 1.f : a.actB == FLAIR_ACT_RELU ? 0.f : 0.1f;
+    const float slopeB = a.actB == FLAIR_ACT_NONE ? 1.f : a.actB == FLAIR_ACT_RELU ? 0.f : 0.1f;     // (as slopeA)
     const float scale = a.outScale;
 #pragma unroll
     for (int cf = 0; cf < 2; ++cf)
@@ -1022,25 +890,13 @@ __global__ __launch_bounds__(512, 2) void conv_pair_kernel(PairArgs a) {
         for (int jj = 0; jj < 2; ++jj) {
             const int g = 2 * cf + jj;                   // couts 16 g + 8 lh .. + 7
             float v[8];
+            acc_octet(accB[cf], jj, v);
+            leaky_act(v, slopeB);
+            add_piece<E>(v, r0v[g]);
+            add_piece<E>(v, r1v[g]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(accB[cf][8 * jj + e]), __float_as_uint(accB[cf][8 * jj + 4 + e]), false, false);
-                v[e] = __uint_as_float(sw2[0]);
-                v[4 + e] = __uint_as_float(sw2[1]);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], v[e] * slopeB);
-            float r[8];
-            Vec16<E>::load(reinterpret_cast<const E*>(&r0v[g]), r);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += r[e];
-            Vec16<E>::load(reinterpret_cast<const E*>(&r1v[g]), r);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (v[e] + r[e]) * scale;
-            alignas(16) E out[8];
-            Vec16<E>::store(out, v);
-            const uint4 ov = *reinterpret_cast<const uint4*>(out);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{ov.x, ov.y, ov.z, ov.w}, yd, (int)((unsigned)lr * yLdB + (unsigned)(32 * g + 16 * lh)), 0, 0);
+            for (int e = 0; e < 8; ++e) v[e] *= scale;
+            store_piece(yd, pack_piece<E>(v), (unsigned)lr * yLdB + (unsigned)(32 * g + 16 * lh));
         }
 }
 
@@ -1062,7 +918,7 @@ int launch_pair(const ChainArgs& c, hipStream_t s) {
 
 template <typename E, int C, int TH, int TW, bool HASA>
 int launch_chain(const ChainArgs& a, hipStream_t s) {
-    constexpr int BKE = MmaC<E>::BKE;
+    constexpr int BKE = Mma<E>::BKE;
     constexpr size_t lds = (size_t)(C / BKE) * (TH + 2) * (TW + 2) * 80 + (size_t)C * 9 * 80 +
                            (HASA ? (size_t)(TH + 4) * (TW + 4) * 80 : 0) + (size_t)(C + CHAIN_MAX_COUTB) * 4;
     static_assert(lds <= 160 * 1024, "LDS budget");

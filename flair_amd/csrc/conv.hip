@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -59,49 +60,6 @@ struct ConvArgs {
     int actPeriod;         // FLAIR_ACT_DCN_OFFSETS: 3 * deform groups
     int Hin, Win;          // input frame size (== H, W when stride == 1); H, W, P describe the OUTPUT
     int esz;               // element size in bytes (2: bf16, 4: f32)
-};
-
-template <typename E> struct Mma;
-
-// bf16: one K-step = 32 channels = two 32x32x16 MFMAs per (co-tile, pixel-tile) pair.
-template <> struct Mma<bf16_t> {
-    static constexpr int BKE = 32;
-    // fr[0], fr[1]: the two 16-byte chunks this lane needs from its 64-byte row.
-    static __device__ __forceinline__ int chunk(int i, int half) { return 2 * i + half; }
-    static __device__ __forceinline__ void run(const uint4 (&a)[2], const uint4 (&b)[2], f32x16& acc) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]),
-                                                      __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]),
-                                                      __builtin_bit_cast(bf16x8, b[1]), acc, 0, 0, 0);
-    }
-    // one half of the K-step (16 channels)
-    static __device__ __forceinline__ void run1(const uint4& a, const uint4& b, f32x16& acc) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                      acc, 0, 0, 0);
-    }
-    static constexpr int MFMA_PER_HALF = 1;
-};
-
-// f32: one K-step = 16 channels = eight 32x32x2 MFMAs.  Lane half h consumes channels
-// 8h..8h+7 of the step (the same permutation on both operands, so the sum is complete).
-template <> struct Mma<float> {
-    static constexpr int BKE = 16;
-    static __device__ __forceinline__ int chunk(int i, int half) { return 2 * half + i; }
-    static __device__ __forceinline__ void run(const uint4 (&a)[2], const uint4 (&b)[2], f32x16& acc) {
-        const float* af = reinterpret_cast<const float*>(a);
-        const float* bf = reinterpret_cast<const float*>(b);
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], bf[s], acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void run1(const uint4& a, const uint4& b, f32x16& acc) {
-        const float* af = reinterpret_cast<const float*>(&a);
-        const float* bf = reinterpret_cast<const float*>(&b);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], bf[s], acc, 0, 0, 0);
-    }
-    static constexpr int MFMA_PER_HALF = 4;
 };
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {
@@ -168,13 +126,12 @@ __device__ __forceinline__ void store_quad(const ConvArgs& a, long p, int co, fl
 // two CUs share).  Branch-free memory access: buffer descriptors based at the wave's first pixel / first cout, an out-of-range
 // offset on lanes past P or Cout; per fragment, the bias, frame-bias and residual pieces of both halves are requested in one batch.  With the loads and stores under `if (pvalid && co < Cout)` hipcc put `s_waitcnt vmcnt(0)` behind every
 // one: each 16-cout half was a bias round trip that also waited for the previous half's store -- on the 1x1 128 -> 64 convolution
-// of 16 x 256^2 the epilogue was 60 us of 110 (profiles/r03_dma_switches.txt, r3k).  All lanes must call this (the swaps cross
-// the half-waves).
+// of 16 x 256^2 the epilogue was 60 us of 110 (profiles/r03_dma_switches.txt, r3k).  All lanes must call this (acc_octet).
 template <typename E, int ACT, int FC, int FP>
 __device__ __forceinline__ void igemm_epilogue(const ConvArgs& a, const f32x16 (&acc)[FC][FP], long pbase, int cobase, int lr, int lh) {
     constexpr unsigned ESZ = sizeof(E);
     constexpr int VEC = ET<E>::VEC, NV = 8 / VEC;               // 16-byte pieces per 8 couts: 1 (bf16) or 2 (f32)
-    const float slope = a.act == FLAIR_ACT_NONE ? 1.f : a.act == FLAIR_ACT_RELU ? 0.f : a.act == FLAIR_ACT_LRELU01 ? 0.1f : 0.2f;
+    const float slope = leaky_slope(a.act);
     const unsigned yLdB = (unsigned)a.yLd * ESZ, r0LdB = (unsigned)a.res0Ld * ESZ, r1LdB = (unsigned)a.res1Ld * ESZ;
     constexpr unsigned SPAN = FP * 32;                           // pixels the wave's offsets stay below
     const __amdgpu_buffer_rsrc_t yd = make_rsrc(reinterpret_cast<char*>(a.y) + ((size_t)pbase * a.yLd + cobase) * ESZ, SPAN * yLdB);
@@ -219,14 +176,8 @@ __device__ __forceinline__ void igemm_epilogue(const ConvArgs& a, const f32x16 (
             }
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const f32x16& c = acc[i][j];
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(c[8 * jj + e]), __float_as_uint(c[8 * jj + 4 + e]), false, false);
-                    v[e] = __uint_as_float(sw2[0]);
-                    v[4 + e] = __uint_as_float(sw2[1]);
-                }
+                acc_octet(acc[i][j], jj, v);
                 const int cw = i * 32 + 16 * jj + 8 * lh;
                 const bool ok = pvalid && cw < coLeft;
                 {
@@ -237,8 +188,7 @@ __device__ __forceinline__ void igemm_epilogue(const ConvArgs& a, const f32x16 (
                     v[6] += __uint_as_float(b1.z) + __uint_as_float(f1.z); v[7] += __uint_as_float(b1.w) + __uint_as_float(f1.w);
                 }
                 if constexpr (ACT == 0) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], v[e] * slope);
+                    leaky_act(v, slope);
                 } else if constexpr (ACT == 1) {
                     dcn_offset_act<8>(v, cobase + cw, a.actParam, a.actPeriod);
                 } else if constexpr (ACT == 2) {
@@ -248,26 +198,17 @@ __device__ __forceinline__ void igemm_epilogue(const ConvArgs& a, const f32x16 (
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = 0.5f * v[e] * (1.f + erff(v[e] * 0.70710678118654752f));
                 }
-#pragma unroll
-                for (int q = 0; q < NV; ++q) {
-                    float t[VEC];
-                    Vec16<E>::load(reinterpret_cast<const E*>(&r0v[jj][q]), t);
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) v[q * VEC + e] += t[e];
-                    Vec16<E>::load(reinterpret_cast<const E*>(&r1v[jj][q]), t);
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) v[q * VEC + e] += t[e];
+                add_piece<E>(v, r0v[jj][0]);
+                add_piece<E>(v, r1v[jj][0]);
+                if constexpr (NV == 2) {                         // f32: the octet's second piece
+                    add_piece<E, VEC>(v, r0v[jj][1]);
+                    add_piece<E, VEC>(v, r1v[jj][1]);
                 }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] *= a.outScale;
 #pragma unroll
-                for (int q = 0; q < NV; ++q) {
-                    alignas(16) E out[VEC];
-                    Vec16<E>::store(out, v + q * VEC);
-                    const uint4 ov = *reinterpret_cast<const uint4*>(out);
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{ov.x, ov.y, ov.z, ov.w}, yd,
-                                                           (int)(ok ? pl * yLdB + (unsigned)(cw + q * VEC) * ESZ : FLAIR_OOB), 0, 0);
-                }
+                for (int q = 0; q < NV; ++q)
+                    store_piece(yd, pack_piece<E>(v + q * VEC), ok ? pl * yLdB + (unsigned)(cw + q * VEC) * ESZ : FLAIR_OOB);
             }
         }
     }
@@ -289,7 +230,9 @@ template <typename E, int TH>
 __global__ __launch_bounds__(64 * TH, (2 * 64 * TH + 255) / 256)  // two workgroups per CU
 void conv3x3_halo_kernel(ConvArgs a) {
     prefetch_kernargs<sizeof(ConvArgs)>();
-    constexpr int RPW = 1, PF = 1;                 // image rows per wavefront; register sets = prefetch depth in chunks
+    // RPW image rows per wavefront, PF register sets = prefetch depth in chunks.  Both have one value; the loops and array
+    // extents over them stay because hipcc compiles this kernel to different code without them (the rule in mfma_tile.h).
+    constexpr int RPW = 1, PF = 1;
     constexpr int BKE = Mma<E>::BKE;
     constexpr int VEC = ET<E>::VEC;
     constexpr int NT = 64 * TH / RPW;              // one wavefront per RPW image rows
@@ -578,24 +521,23 @@ int launch_halo(const ConvArgs& a0, hipStream_t s) {
 // ---------------------------------------------------------------------------------------
 // K-split halo kernel for launches of at most one workgroup per CU (the per-frame convolutions of
 // the BasicVSR++ recurrence): same TH x 32 px x 64 cout tile and staging as above, but a wavefront
-// owns RPW image rows x 64 couts x ONE 16-channel half of the K step (wave = row group + k-half *
-// TH/RPW), so the tile is spread over twice the wavefronts per row group and the serial MFMA chain
+// owns one image row x 64 couts x ONE 16-channel half of the K step (wave = row + k-half * TH), so the tile
+// is spread over twice the wavefronts per row and the serial MFMA chain
 // of a chunk halves: with one workgroup per CU nothing else hides the staging phases, and more
 // resident waves do (measured: -10..-20 % per launch; the register tile shape itself does not
 // matter, tools/probes/lds_mfma_probe.hip).  The two k-halves of a tile are summed through the
 // LDS staging tile of the epilogue.  Two LDS stages (one barrier per chunk), one workgroup per CU (up to 146 KB of LDS,
-// 256 VGPRs).  Needs Cout % 8 == 0.
+// 256 VGPRs).  Needs Cout % 8 == 0.  Its own: biasv at entry, the residual pieces requested ahead of the reduction
+// barriers, the two-stage ring and the k-half sum.
 template <typename E, int TH>
 __global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_kernel(ConvArgs a) {
-    constexpr int RPW = 1, CF = 2;                 // one image row and both 32-cout fragments per wave
     prefetch_kernargs<sizeof(ConvArgs)>();
-    constexpr int NRG = TH / RPW;                  // row groups
-    constexpr int NCG = 2 / CF;                    // cout-fragment groups (CF fragments of 32 couts per wave)
-    constexpr int NW = 2 * NRG * NCG, NT = 64 * NW;
+    constexpr int NW = 2 * TH;                     // wave = image row + k-half * TH
+    constexpr int NT = 64 * NW;
     constexpr int BKE = Mma<E>::BKE;
     constexpr int VEC = ET<E>::VEC;
     constexpr unsigned ESZ = sizeof(E);
-    constexpr int HW_ = 34, PITCH = 80;
+    constexpr int HW_ = 34, PITCH = 80;                        // halo width (32 + 2); bytes per staged pixel / weight row
     constexpr int HALO_ROWS = (TH + 2) * HW_;
     constexpr int HALO_PIECES = (HALO_ROWS + 7) / 8 * 8 * 4;   // whole groups of 8 rows (see staged_row)
     constexpr int W_PIECES = 64 * 9 * 4;
@@ -603,11 +545,13 @@ __global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_ke
     constexpr int WI = (W_PIECES + NT - 1) / NT;
     constexpr int HALO_BYTES = (TH + 2) * HW_ * PITCH;
     constexpr int STAGE_BYTES = HALO_BYTES + 64 * 9 * PITCH;
+    constexpr int FPITCH = 64 * 4 + 16;                        // f32 staging pitch of the epilogue (both dtypes)
+    constexpr int CHUNKS = 64 / VEC;                           // 16-byte output pieces per pixel
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 31, lh = lane >> 5;
-    const int rp = wave % NRG, kh2 = (wave / NRG) & 1, cg = wave / (2 * NRG);   // row group, k-half, cout group
+    const int rp = wave % TH, kh2 = (wave / TH) & 1;           // image row, k-half
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int coTile = bid % a.nCoTiles;
     int rest = bid / a.nCoTiles;
@@ -696,42 +640,36 @@ __global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_ke
     for (int d = -pt; d <= pt; ++d) nValidDt += dt_valid(d) ? 1 : 0;
     const int nch = nValidDt * (a.CinTot / BKE);
 
-    f32x16 acc[RPW][CF];   // [row of the group][cout fragment]
+    f32x16 acc[2];                                   // [cout fragment]
 #pragma unroll
-    for (int j = 0; j < RPW; ++j)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < CF; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 
     const int ck = 16 * Mma<E>::chunk(kh2, lh);      // this wave's 16-byte piece of every staged row
     auto compute = [&](int stage) {
         const char* sh = smem + stage * STAGE_BYTES;
-        const char* hb = sh + ((RPW * rp * HW_) + lr) * PITCH + ck;
-        const char* wb0 = sh + HALO_BYTES + ((cg * CF * 32 + lr) * 9) * PITCH + ck;
-        uint4 fa[2][CF], fb[2][RPW];
+        const char* hb = sh + ((rp * HW_) + lr) * PITCH + ck;
+        const char* wb0 = sh + HALO_BYTES + (lr * 9) * PITCH + ck;
+        uint4 fa[2][2], fb[2];
         auto load_tap = [&](int set, int tap9) {
             const int kh = tap9 / 3, kw = tap9 % 3;
 #pragma unroll
-            for (int i = 0; i < CF; ++i)
+            for (int i = 0; i < 2; ++i)
                 fa[set][i] = *reinterpret_cast<const uint4*>(wb0 + (i * 32 * 9 + tap9) * PITCH);
-#pragma unroll
-            for (int j = 0; j < RPW; ++j)
-                fb[set][j] = *reinterpret_cast<const uint4*>(hb + ((kh + j) * HW_ + kw) * PITCH);
+            fb[set] = *reinterpret_cast<const uint4*>(hb + (kh * HW_ + kw) * PITCH);
         };
         load_tap(0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, CF + RPW, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
 #pragma unroll
         for (int tap9 = 0; tap9 < 9; ++tap9) {
             const int set = tap9 & 1;
             if (tap9 < 8) load_tap(set ^ 1, tap9 + 1);
 #pragma unroll
-            for (int j = 0; j < RPW; ++j)
-#pragma unroll
-                for (int i = 0; i < CF; ++i) Mma<E>::run1(fa[set][i], fb[set][j], acc[j][i]);
+            for (int i = 0; i < 2; ++i) Mma<E>::run1(fa[set][i], fb[set], acc[i]);
             // pin the interleave: next tap's LDS reads are issued ahead of this tap's MFMAs
-            if (tap9 < 8) __builtin_amdgcn_sched_group_barrier(0x100, CF + RPW, 0);
-            __builtin_amdgcn_sched_group_barrier(0x8, CF * RPW * Mma<E>::MFMA_PER_HALF, 0);
+            if (tap9 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x8, 2 * Mma<E>::MFMA_PER_HALF, 0);
         }
     };
 
@@ -755,8 +693,6 @@ __global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_ke
     // bias values were requested at kernel entry (biasv) and the residual pieces are requested here, ahead of the three
     // barriers of the k-half reduction: a per-frame launch has nothing else to hide those round trips behind (they were
     // issued after the staging tile was read: ~1 us of exposed latency per launch, 1 264 launches per step).
-    constexpr int FPITCH = 64 * 4 + 16;
-    constexpr int CHUNKS = 64 / VEC;                         // 16-byte output pieces per pixel
     constexpr int PARTS = NW / TH;                           // wavefronts sharing one output row
     constexpr int NIT = 32 * CHUNKS / 64 / PARTS;            // passes per wave
     const int orow = wave % TH, part = wave / TH;
@@ -778,28 +714,24 @@ __global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_ke
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         if (kh2 == pass) {
+            char* tile = smem + rp * 32 * FPITCH + lr * FPITCH;
 #pragma unroll
-            for (int j = 0; j < RPW; ++j) {
-                char* tile = smem + (RPW * rp + j) * 32 * FPITCH + lr * FPITCH;
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int i = 0; i < CF; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        float4* dst = reinterpret_cast<float4*>(tile + ((cg * CF + i) * 32 + 8 * g + 4 * lh) * 4);
-                        float4 v = make_float4(acc[j][i][4 * g], acc[j][i][4 * g + 1], acc[j][i][4 * g + 2],
-                                               acc[j][i][4 * g + 3]);
-                        if (pass == 1) {
-                            const float4 o = *dst;
-                            v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-                        }
-                        *dst = v;
+                for (int g = 0; g < 4; ++g) {
+                    float4* dst = reinterpret_cast<float4*>(tile + (i * 32 + 8 * g + 4 * lh) * 4);
+                    float4 v = make_float4(acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]);
+                    if (pass == 1) {
+                        const float4 o = *dst;
+                        v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
                     }
-            }
+                    *dst = v;
+                }
         }
         __syncthreads();
     }
     if (!eok) return;
-    const float slope = a.act == FLAIR_ACT_NONE ? 1.f : a.act == FLAIR_ACT_RELU ? 0.f : a.act == FLAIR_ACT_LRELU01 ? 0.1f : 0.2f;
+    const float slope = leaky_slope(a.act);
     const bool leaky = a.act == FLAIR_ACT_NONE || a.act == FLAIR_ACT_RELU || a.act == FLAIR_ACT_LRELU01 || a.act == FLAIR_ACT_LRELU02;
     const char* tile = smem + orow * 32 * FPITCH;
 #pragma unroll
@@ -821,8 +753,7 @@ __global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_ke
             for (int e = 0; e < VEC; ++e) v[e] += fb[e];
         }
         if (leaky) {                       // none / ReLU / LeakyReLU: max(v, slope v); one class per branch keeps the code short
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = fmaxf(v[e], v[e] * slope);
+            leaky_act(v, slope);
         } else if (a.act == FLAIR_ACT_DCN_OFFSETS) {
             dcn_offset_act<VEC>(v, eco, a.actParam, a.actPeriod);
         } else if (a.act == FLAIR_ACT_SILU) {
@@ -832,18 +763,8 @@ __global__ __launch_bounds__(128 * TH, (128 * TH) / 256) void conv3x3_halo_ks_ke
 #pragma unroll
             for (int e = 0; e < VEC; ++e) v[e] = apply_act(v[e], a.act);
         }
-        if (a.res0) {
-            float r[VEC];
-            Vec16<E>::load(reinterpret_cast<const E*>(&r0v[k]), r);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] += r[e];
-        }
-        if (a.res1) {
-            float r[VEC];
-            Vec16<E>::load(reinterpret_cast<const E*>(&r1v[k]), r);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] += r[e];
-        }
+        if (a.res0) add_piece<E>(v, r0v[k]);
+        if (a.res1) add_piece<E>(v, r1v[k]);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) v[e] *= a.outScale;
         Vec16<E>::store(reinterpret_cast<E*>(a.y) + p * a.yLd + eco, v);
@@ -1038,7 +959,9 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     };
 
     // ---- fragment read offsets (per lane, fixed).  A: weight row tap9 * 64 + cf * 32 + lr, chunk 2 s + lh;
-    // B: halo row (2 wave + j + kh) * 34 + kw + lr, same chunk; XOR terms as written by the DMA.
+    // B: halo row (2 wave + j + kh) * 34 + kw + lr, same chunk; XOR terms as written by the DMA.  (dma_frag_offsets of
+    // mfma_tile.h with the stage's weight base folded into aoff and RPW rows per wave; the tap loop below is not
+    // dma_tap_loop either: RPW rows, and its interleave is pinned by the sched_group_barrier lines.)
     unsigned aoff[KSTEPS], boff[3][KSTEPS];
 #pragma unroll
     for (int s_ = 0; s_ < KSTEPS; ++s_) {
@@ -1107,7 +1030,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     auto epilogue_as = [&](const DmaTile& tl, int biasSlot, auto actTag, auto resTag) {
         constexpr int ACT = decltype(actTag)::value;       // 0: max(v, slope v)   1: DCN offsets / masks   2: SiLU
         constexpr bool HASRES = decltype(resTag)::value;   // a residual input exists (its own copy of the code: see below)
-        const float slope = a.act == FLAIR_ACT_NONE ? 1.f : a.act == FLAIR_ACT_RELU ? 0.f : a.act == FLAIR_ACT_LRELU01 ? 0.1f : 0.2f;
+        const float slope = leaky_slope(a.act);
         // Branch-free: every access is a buffer instruction on a wave-uniform descriptor (the wave's first pixel, this tile's
         // first cout); lanes whose couts are padding use an out-of-range offset (loads deliver 0, stores are dropped).  With
         // EXEC-masked branches around the loads / stores, hipcc merged its counters at every join into `s_waitcnt vmcnt(0)`:
@@ -1161,6 +1084,8 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                 }
 #pragma unroll
                 for (int j = 0; j < RPW; ++j) {
+                    // acc_octet + bias, leaky_act, add_piece and pack_piece / store_piece spelled out: the rule in mfma_tile.h
+                    // (with the helpers hipcc schedules this epilogue differently)
                     float v[8];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -1210,7 +1135,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
     // residual is rare on this path (the recurrence's residual blocks are fused chains).
     auto epilogue_plain_as = [&](const DmaTile& tl, int biasSlot, auto actTag) {
         constexpr int ACT = decltype(actTag)::value;       // 0: max(v, slope v)   1: DCN offsets / masks   2: SiLU
-        const float slope = a.act == FLAIR_ACT_NONE ? 1.f : a.act == FLAIR_ACT_RELU ? 0.f : a.act == FLAIR_ACT_LRELU01 ? 0.1f : 0.2f;
+        const float slope = leaky_slope(a.act);
         const long p0 = ((long)tl.t * H + tl.h0 + RPW * wave) * W + tl.w0 + lr;          // this lane's pixel in row j = 0
         const int cl = 8 * lh;                                                           // this lane's cout offset inside a 16-cout half
         E* yb = reinterpret_cast<E*>(a.y) + p0 * a.yLd + tl.co0 + cl;
@@ -1236,6 +1161,7 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                 }
 #pragma unroll
                 for (int j = 0; j < RPW; ++j) {
+                    // acc_octet + bias and leaky_act spelled out: the rule in mfma_tile.h
                     float v[8];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -1254,18 +1180,8 @@ __device__ __forceinline__ void conv3x3_dma_body(const ConvArgs& a, int nTiles, 
                         for (int e = 0; e < 8; ++e) v[e] = silu_f(v[e]);
                     }
                     const long ro = (long)j * W;                                         // row j of the wave's pair
-                    if (r0b && lane_ok) {
-                        float r[8];
-                        Vec16<E>::load(r0b + ro * a.res0Ld + cofs, r);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += r[e];
-                    }
-                    if (r1b && lane_ok) {
-                        float r[8];
-                        Vec16<E>::load(r1b + ro * a.res1Ld + cofs, r);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += r[e];
-                    }
+                    if (r0b && lane_ok) add_piece<E>(v, r0b + ro * a.res0Ld + cofs);
+                    if (r1b && lane_ok) add_piece<E>(v, r1b + ro * a.res1Ld + cofs);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= scale;
                     if (!lane_ok) continue;
@@ -1437,18 +1353,10 @@ __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {      /
     const u32x4_t wdesc = make_desc(a.w, a.wBytes);
     const u32x4_t bdesc = make_desc(a.bias, a.bias ? (unsigned)a.Cout * 4u : 0u);
     dma16(bdesc, (unsigned)(lane * 16), (unsigned)BIAS);
-    // halo pixel of each of this wave's halo instructions (frame-relative pixel index, or "outside") and its swizzled 16-byte piece
+    // halo pixel of each of this wave's halo instructions and its swizzled 16-byte piece (dma_halo_coords, mfma_tile.h)
     unsigned hpix[NH], hpiece[NH];
 #pragma unroll
-    for (int i = 0; i < NH; ++i) {
-        const int k = (wave * NH + i) % HINSTR;
-        const int R = k * 16 + lrow;
-        const int hr = R / HWP, c = R - hr * HWP;
-        const int hh = h0 - 1 + hr, ww = w0 - 1 + c;
-        const bool ok = R < 10 * HWP && (unsigned)hh < (unsigned)a.H && (unsigned)ww < (unsigned)a.W;
-        hpix[i] = ok ? (unsigned)(hh * a.W + ww) : 0xffffffffu;
-        hpiece[i] = (unsigned)((lchunk ^ ((c >> 2) & 3)) << 4);
-    }
+    for (int i = 0; i < NH; ++i) dma_halo_coords((wave * NH + i) % HINSTR, lrow, lchunk, 10, h0, w0, a.H, a.W, hpix[i], hpiece[i]);
     unsigned wlane[NWS];
 #pragma unroll
     for (int i = 0; i < NWS; ++i) {
@@ -1488,47 +1396,9 @@ __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {      /
     if (nS > 2) issue_halo(2);
 
     unsigned aoff[2], boff[3][2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        aoff[ks] = (unsigned)(lr * 64 + (((2 * ks + lh) ^ ((lr >> 2) & 3)) << 4));
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
-            boff[kw][ks] = (unsigned)((wave * HWP + kw + lr) * 64 + (((2 * ks + lh) ^ (((kw + lr) >> 2) & 3)) << 4));
-    }
+    dma_frag_offsets(lr, lh, wave * HWP, aoff, boff);
     f32x16 acc[2];
-    auto compute = [&](int wslot, int hslot) {
-        const char* wb = smem + RING + wslot * SLOT;
-        const char* xb = smem + hslot * HIMG;
-        uint4 fb[2][3][2], fa[2][2][2];
-        auto load_b = [&](int set, int kw) {
-#pragma unroll
-            for (int h = 0; h < 3; ++h)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fb[set][h][ks] = *reinterpret_cast<const uint4*>(xb + h * (HWP * 64) + boff[kw][ks]);
-        };
-        auto load_a = [&](int set, int kh, int kw) {
-#pragma unroll
-            for (int cf = 0; cf < 2; ++cf)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fa[set][cf][ks] = *reinterpret_cast<const uint4*>(wb + (kh * 3 + kw) * 4096 + cf * 2048 + aoff[ks]);
-        };
-        load_b(0, 0);
-        load_a(0, 0, 0);
-#pragma unroll
-        for (int step = 0; step < 9; ++step) {
-            const int kq = step / 3, kh = step % 3;
-            const int nkq = (step + 1) / 3, nkh = (step + 1) % 3;
-            if (step < 8) {
-                if (nkh == 0) load_b(nkq & 1, nkq);
-                load_a((step + 1) & 1, nkh, nkq);
-            }
-#pragma unroll
-            for (int cf = 0; cf < 2; ++cf)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-                    acc[cf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[step & 1][cf][ks]), __builtin_bit_cast(bf16x8, fb[kq & 1][kh][ks]), acc[cf], 0, 0, 0);
-        }
-    };
+    auto compute = [&](int wslot, int hslot) { dma_tap_loop(smem + RING + wslot * SLOT, smem + hslot * HIMG, aoff, boff, acc, dma_no_hook{}); };
 
     const long prow = ((long)t * a.H + h0 + wave) * a.W + w0;
     const unsigned yLdB = (unsigned)a.yLd * 2u, r0LdB = (unsigned)a.res0Ld * 2u, r1LdB = (unsigned)a.res1Ld * 2u;
@@ -1572,7 +1442,7 @@ __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {      /
         compute(s_ % WR, s_ % HR);
     }
 
-    const float slope = a.act == FLAIR_ACT_NONE ? 1.f : a.act == FLAIR_ACT_RELU ? 0.f : a.act == FLAIR_ACT_LRELU01 ? 0.1f : 0.2f;
+    const float slope = leaky_slope(a.act);
     const float scale = a.outScale;
 #pragma unroll
     for (int cf = 0; cf < 2; ++cf)
@@ -1580,26 +1450,13 @@ __global__ __launch_bounds__(512, 2) void conv_frame_kernel(ConvArgs a) {      /
         for (int jj = 0; jj < 2; ++jj) {
             const int g = 2 * cf + jj;                   // couts 16 g + 8 lh .. + 7
             float v[8];
+            acc_octet(acc[cf], jj, v);
+            leaky_act(v, slope);
+            add_piece<E>(v, r0v[g]);
+            add_piece<E>(v, r1v[g]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[cf][8 * jj + e]), __float_as_uint(acc[cf][8 * jj + 4 + e]), false, false);
-                v[e] = __uint_as_float(sw2[0]);
-                v[4 + e] = __uint_as_float(sw2[1]);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], v[e] * slope);
-            float r[8];
-            Vec16<E>::load(reinterpret_cast<const E*>(&r0v[g]), r);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += r[e];
-            Vec16<E>::load(reinterpret_cast<const E*>(&r1v[g]), r);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (v[e] + r[e]) * scale;
-            alignas(16) E out[8];
-            Vec16<E>::store(out, v);
-            const uint4 ov = *reinterpret_cast<const uint4*>(out);
-            const unsigned yo = 16 * g + 8 * lh < a.Cout ? (unsigned)lr * yLdB + (unsigned)(32 * g + 16 * lh) : FLAIR_OOB;
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{ov.x, ov.y, ov.z, ov.w}, yd, (int)yo, 0, 0);
+            for (int e = 0; e < 8; ++e) v[e] *= scale;
+            store_piece(yd, pack_piece<E>(v), 16 * g + 8 * lh < a.Cout ? (unsigned)lr * yLdB + (unsigned)(32 * g + 16 * lh) : FLAIR_OOB);
         }
 }
 

@@ -28,6 +28,7 @@
 
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -46,26 +47,6 @@ struct DcnArgs {
     int activated;       // 1: raw holds finished residues / masks (FLAIR_ACT_DCN_OFFSETS upstream); 2: raw offsets
     long P;
     unsigned xBytes[2], rawBytes, wBytes;
-};
-
-template <typename E> struct MmaD;
-template <> struct MmaD<bf16_t> {
-    static __device__ __forceinline__ int chunk(int i, int half) { return 2 * i + half; }
-    static __device__ __forceinline__ void run(const uint4 (&a)[2], const uint4 (&b)[2], f32x16& acc) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]),
-                                                      __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]),
-                                                      __builtin_bit_cast(bf16x8, b[1]), acc, 0, 0, 0);
-    }
-};
-template <> struct MmaD<float> {
-    static __device__ __forceinline__ int chunk(int i, int half) { return 2 * half + i; }
-    static __device__ __forceinline__ void run(const uint4 (&a)[2], const uint4 (&b)[2], f32x16& acc) {
-        const float* af = reinterpret_cast<const float*>(a);
-        const float* bf = reinterpret_cast<const float*>(b);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], bf[s], acc, 0, 0, 0);
-    }
 };
 
 // LDS tile rows hold one K step (CPR 16-byte chunks) of one cout / pixel; the chunk index is
@@ -430,11 +411,11 @@ void dcn_kernel(DcnArgs a) {
                 uint4 af[2], bf[2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const int ch = ks * 4 + MmaD<E>::chunk(h, lh);
+                    const int ch = ks * 4 + Mma<E>::chunk(h, lh);
                     bf[h] = *reinterpret_cast<const uint4*>(xb + tile_off<CPR>(pfrag * 32 + lr, ch));
                     af[h] = *reinterpret_cast<const uint4*>(wb + tile_off<CPR>(cf * 32 + lr, ch));
                 }
-                MmaD<E>::run(af, bf, acc[i]);
+                Mma<E>::run(af, bf, acc[i]);
             }
         }
     };
@@ -506,24 +487,14 @@ void dcn_kernel(DcnArgs a) {
                 for (int j = 0; j < 2; ++j) {
                     const int co = cf * 32 + 16 * j + 8 * lh;
                     float v[8];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[i][8 * j + e]),
-                                                                          __float_as_uint(acc[i][8 * j + 4 + e]), false, false);
-                        v[e] = __uint_as_float(sw2[0]);
-                        v[4 + e] = __uint_as_float(sw2[1]);
-                    }
+                    acc_octet(acc[i], j, v);                       // (layout: mfma_tile.h)
                     v[0] += __uint_as_float(bq[j][0].x); v[1] += __uint_as_float(bq[j][0].y);
                     v[2] += __uint_as_float(bq[j][0].z); v[3] += __uint_as_float(bq[j][0].w);
                     v[4] += __uint_as_float(bq[j][1].x); v[5] += __uint_as_float(bq[j][1].y);
                     v[6] += __uint_as_float(bq[j][1].z); v[7] += __uint_as_float(bq[j][1].w);
-                    alignas(16) E out[8];
-                    Vec16<E>::store(out, v);
-                    const uint4 ov = *reinterpret_cast<const uint4*>(out);
                     // (a buffer store with an out-of-range offset for tail pixels / padding couts: under an EXEC-masked branch
                     // hipcc waits for the previous store's acknowledgement at the join)
-                    const unsigned yo = po < a.P && co < a.Cout ? ((unsigned)po * a.yLd + co) * 2u : FLAIR_OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{ov.x, ov.y, ov.z, ov.w}, yd, (int)yo, 0, 0);
+                    store_piece(yd, pack_piece<E>(v), po < a.P && co < a.Cout ? ((unsigned)po * a.yLd + co) * 2u : FLAIR_OOB);
                 }
             }
             return;

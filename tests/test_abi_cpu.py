@@ -98,9 +98,9 @@ def test_dispatch_reads_no_environment():
     reads os.environ (FLAIR_HIP_LIB, which picks the library file in flair_amd/_lib.py, is not a dispatch switch)."""
     import glob
     csrc = os.path.join(ROOT, "flair_amd", "csrc")
-    hip = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "common.h")]
+    hip = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + sorted(glob.glob(os.path.join(csrc, "*.h")))
     py = sorted(glob.glob(os.path.join(ROOT, "flair_amd", "guided_diffusion", "*.py")))
-    assert len(hip) > 1 and py
+    assert len(hip) > 1 and os.path.join(csrc, "common.h") in hip and py
     bad = [os.path.relpath(f, ROOT) for f in hip if re.search(r"\bgetenv\b", open(f).read())]
     bad += [os.path.relpath(f, ROOT) for f in py if re.search(r"\benviron\b", open(f).read())]
     assert not bad, bad
