@@ -73,6 +73,25 @@ def pk_int(name):
     return property(lambda self: self._pk[name], fset)
 
 
+class LinearStack:
+    """A network's embedding linears batched into one matrix (one launch per step evaluates them all)."""
+
+    def __init__(self):
+        self.linears, self.width = [], 0
+
+    def add(self, lin):
+        """-> the row at which ``lin`` starts in the batched matrix."""
+        off = self.width
+        self.linears.append(lin)
+        self.width += lin.out_features
+        return off
+
+    def cat(self, device):
+        """-> (W, b): the f32 weights and biases of every added linear, concatenated along the output rows."""
+        return (torch.cat([dev_f32(lin.weight, device) for lin in self.linears]).contiguous(),
+                torch.cat([dev_f32(lin.bias, device) for lin in self.linears]).contiguous())
+
+
 def invalidate_packed(model):
     """``model.invalidate_packed()``; a foreign container that merely carries a ``_packed_key`` has it cleared."""
     if isinstance(model, PackedModel):

@@ -21,8 +21,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .clip_model import ClipModel
 from .nn_new import linear, zero_module
-from .packing import PackedModel, dev_f32, pack_w, packed_conv, pk_int, run_conv
+from .packing import LinearStack, dev_f32, pack_w, packed_conv, pk_int, run_conv
 from .unet_new import A, BasicVSRPP, Ctx, PlaceHolder, SPyNet, TemporalAttention, normalization
 
 LazyReshaper2D = LazyReshaper3D = PlaceHolder
@@ -291,11 +292,12 @@ class Upsample(nn.Module):
         return run_conv(up, self._pk, self.conv)
 
 
-class UNet(PackedModel, nn.Module):
+class UNet(ClipModel, nn.Module):
     """sr3.py:317-525.  ``timesteps`` is the continuous noise level sqrt(acp_prev)[t+1] that
     respace._WrappedModel supplies (attribute ``takes_noise_level``)."""
 
     takes_noise_level = True
+    _name = "flair_amd.sr3.UNet"
 
     def __init__(self, in_channel=6, out_channel=3, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 4, 8, 8), attn_res=(8,), vsrpp_res=(64,), spatial_attn=False,
@@ -353,42 +355,17 @@ class UNet(PackedModel, nn.Module):
                 res *= 2
         self.ups = nn.ModuleList(ups)
         self.final_conv = Block(pre, out_channel if out_channel is not None else in_channel, groups=norm_groups)
-        self._flow_cache = {}
-        self._graphs = {}
-        self.use_hip_graph = False
-
-    def enable_hip_graph(self, flag=True):
-        """Replay one captured hipGraph per (clip shape, dtype, weight-map kind) instead of ~2000 launches per
-        forward (the eager step spends ~8 % of its time in launch gaps).  Inputs are copied into static buffers; the
-        returned tensor is overwritten by the next call (the sampler consumes it immediately)."""
-        self.use_hip_graph = bool(flag)
-        self._graphs = {}
-        return self
-
-    # ---- dtype management --------------------------------------------------------------
-    convert_to_fp16 = PackedModel.convert_to_bf16        # the reference's name; bfloat16 is the reduced precision here
-
-    def invalidate_packed(self):
-        super().invalidate_packed()
-        self._graphs, self._flow_cache = {}, {}      # captured launches and cached flows were made with the old copies
 
     # ---- packing -----------------------------------------------------------------------
     def _pack_all(self, dt, device):
         stem = self.downs[0].wrapped_module
         stem._pk = packed_conv(stem, None, dt, device)
-        plain_w, plain_b, silu_w, silu_b = [], [], [], []
-        po = so = 0
+        plain, silu = LinearStack(), LinearStack()
         for m in self.modules():
             if isinstance(m, ResnetBlock):
-                m.pack(dt, device, self._skip_split.get(id(m)), plain_off=po)
-                lin = m.noise_func.noise_func[0]
-                plain_w.append(dev_f32(lin.weight, device)); plain_b.append(dev_f32(lin.bias, device))
-                po += lin.out_features
+                m.pack(dt, device, self._skip_split.get(id(m)), plain_off=plain.add(m.noise_func.noise_func[0]))
             elif isinstance(m, (ResBlock, TemporalWrapper2)):
-                m.pack(dt, device, silu_off=so)
-                lin = m.emb_layers[1]
-                silu_w.append(dev_f32(lin.weight, device)); silu_b.append(dev_f32(lin.bias, device))
-                so += lin.out_features
+                m.pack(dt, device, silu_off=silu.add(m.emb_layers[1]))
             elif isinstance(m, (TemporalAttention, BasicVSRPP, Downsample, Upsample)):
                 m.pack(dt, device)
         if self._shared_spynet[0] is not None:
@@ -396,108 +373,37 @@ class UNet(PackedModel, nn.Module):
             self._shared_spynet[0].pack(dt, device)
         mlp, fc = self.noise_level_mlp, self.final_conv.block
         self._pk = dict(
-            plain=(torch.cat(plain_w).contiguous(), torch.cat(plain_b).contiguous()),
-            silu=(torch.cat(silu_w).contiguous(), torch.cat(silu_b).contiguous()),
+            plain=plain.cat(device), silu=silu.cat(device),
             mlp=[dev_f32(p, device) for p in (mlp[1].weight, mlp[1].bias, mlp[3].weight, mlp[3].bias)],
             fin_g=dev_f32(fc[0].wrapped_module.weight, device), fin_b=dev_f32(fc[0].wrapped_module.bias, device),
             fin=packed_conv(fc[3].wrapped_module, None, dt, device))
         self._flow_cache = {}
 
-    def reset_flow_cache(self):
-        """Forget cached SPyNet flows (called by the sampler at the start of every chain)."""
-        self._flow_cache = {}
-        self._flow_gen = getattr(self, "_flow_gen", 0) + 1
-
     # ---- flows: once per (clip, resolution) ----------------------------------------------
-    def _flows_for(self, rnn_clip, resolutions):
-        key = (rnn_clip.data_ptr(), rnn_clip._version, tuple(rnn_clip.shape), tuple(resolutions))
-        hit = self._flow_cache.get(key)
-        if hit is None:
-            sp = self._shared_spynet[0]
-            flows = {}
-            for rh, r in resolutions:                         # (height, width) of a level, stored under its width
-                src = rnn_clip if tuple(rnn_clip.shape[-2:]) == (rh, r) else aa_resize(rnn_clip, (rh, r))
-                T = src.shape[0]
-                raw = torch.zeros((T, rh, r, 4), dtype=torch.float32, device=src.device)
-                ops.nchw_to_clip(src.contiguous(), raw, 0)
-                norm = torch.zeros_like(raw)
-                ops.affine_channels(raw, 3, 0.5, 0.5, 0.0, 1.0, sp._pk["mean"], sp._pk["istd"], norm)
-                a, b = norm[:-1], norm[1:]
-                flows[r] = (sp.run(b, a), sp.run(a, b))       # (forward, backward)
-            flows["_prop"] = {}              # per-clip store of composed second-order flows (BasicVSRPP._propagate)
-            if len(self._flow_cache) >= 16:
-                self._flow_cache.clear()
-            hit = (flows, rnn_clip)
-            self._flow_cache[key] = hit
-        return hit[0]
+    def _flow_spec(self, H, W, enable_cross_frames):
+        return tuple(self._flow_resolutions(H, W)) if enable_cross_frames else ()
 
-    # ---- forward -------------------------------------------------------------------------
+    def _compute_flows(self, rnn_clip, resolutions):
+        flows = {}
+        for rh, r in resolutions:                         # (height, width) of a level, stored under its width
+            src = rnn_clip if tuple(rnn_clip.shape[-2:]) == (rh, r) else aa_resize(rnn_clip, (rh, r))
+            raw = torch.zeros((src.shape[0], rh, r, 4), dtype=torch.float32, device=src.device)
+            ops.nchw_to_clip(src.contiguous(), raw, 0)
+            flows[r] = self._shared_spynet[0].pair_flows(raw)
+        return flows
+
+    # ---- forward (clip_model.ClipModel: per-clip slicing, graph capture / replay, the flow cache) ------------------
     def forward(self, x, timesteps, low_res_input=None, rnn_input=None, num_frames=None,
                 enable_cross_frames=True, vsrpp_weights=None, **kwargs):
-        if not x.is_cuda:
-            raise RuntimeError("flair_amd.sr3.UNet runs on the MI355X only (tensors must be on 'cuda'); "
-                               "there is no CPU path")
-        self._ensure_packed(x.device)
-        T = int(num_frames)
-        B = x.shape[0] // T
-        if rnn_input is None:
-            rnn_input = low_res_input
-        outs = []
-        for b in range(B):
-            vw = vsrpp_weights[b] if isinstance(vsrpp_weights, torch.Tensor) else vsrpp_weights
-            fn = self._forward_clip_graphed if (self.use_hip_graph and getattr(self, "_trace", None) is None) \
-                else self._forward_clip
-            outs.append(fn(x[b * T:(b + 1) * T].float().contiguous(), timesteps[b * T:(b + 1) * T].float().contiguous(),
-                           low_res_input[b].float().contiguous(), rnn_input[b].float(), enable_cross_frames, vw,
-                           **({"clip": b} if fn == self._forward_clip_graphed else {})))
-        return outs[0] if B == 1 else torch.cat(outs, dim=0)
+        return self._run_clips(x, timesteps, low_res_input, rnn_input, num_frames, enable_cross_frames, vsrpp_weights)
 
-    def _forward_clip_graphed(self, x, level, low_res, rnn, enable_cross_frames, vsrpp_weights, clip=0):
-        """One hipGraph per (clip shape, dtype, weight-map kind); re-captured when the conditioning (low-res clip, flow
-        source, per-pixel weight map) or the sampler's chain counter changes -- same scheme as unet_new.UNetModel."""
-        vw_t = vsrpp_weights if isinstance(vsrpp_weights, torch.Tensor) else None
-        key = (tuple(x.shape), self.dtype, bool(enable_cross_frames),
-               tuple(vw_t.shape) if vw_t is not None else vsrpp_weights, x.device, clip)
-        src = (rnn.data_ptr(), rnn._version, low_res.data_ptr(), low_res._version, getattr(self, "_flow_gen", 0),
-               (vw_t.data_ptr(), vw_t._version) if vw_t is not None else None)
-        ent = self._graphs.get(key)
-        if ent is not None and ent["src"] != src:
-            del self._graphs[key]
-            ent = None
-        if ent is None:
-            st = dict(x=x.clone(), level=level.clone(), lr=low_res.clone(), rnn=rnn.clone(),
-                      vw=vw_t.clone() if vw_t is not None else vsrpp_weights)
-            res_needed = self._flow_resolutions(*x.shape[2:]) if enable_cross_frames else []
-            flows = self._flows_for(st["rnn"], res_needed) if res_needed else {}      # SPyNet runs eagerly, before capture
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):                                              # warm-up (allocator, workspaces)
-                self._forward_clip(st["x"], st["level"], st["lr"], st["rnn"], enable_cross_frames, st["vw"], flows=flows)
-            cur.wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):   # see unet_new.UNetModel
-                out = self._forward_clip(st["x"], st["level"], st["lr"], st["rnn"], enable_cross_frames, st["vw"],
-                                         flows=flows)
-            ent = dict(graph=graph, st=st, out=out, src=src, flows=flows)
-            self._graphs[key] = ent
-        ent["st"]["x"].copy_(x)
-        ent["st"]["level"].copy_(level)
-        ent["graph"].replay()
-        return ent["out"]
-
-    def _forward_clip(self, x, level, low_res, rnn, enable_cross_frames, vsrpp_weights, flows=None):
+    def _forward_clip(self, x, level, low_res, flows, enable_cross_frames, vsrpp_weights):
         T, _, H, W = x.shape
         dev, dt = x.device, self.dtype
         ctx = Ctx(dt, dev, T)
         ctx.enable_cross_frames = enable_cross_frames
         ctx.vsrpp_weights = vsrpp_weights
-        res_needed = self._flow_resolutions(H, W) if enable_cross_frames else []
-        if flows is not None:
-            ctx.flows = flows
-        else:
-            ctx.flows = self._flows_for(rnn, res_needed) if res_needed else {}
+        ctx.flows = flows
         pe = ops.timestep_embedding(level, self.inner_channel, sin_first=True)
         pk = self._pk
         e = ops.linear(pe, pk["mlp"][0], pk["mlp"][1], act_out=A.ACT_SILU)

@@ -25,8 +25,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .clip_model import ClipModel
 from .nn_new import conv_nd, linear, normalization, zero_module
-from .packing import PackedModel, dev_f32, pack_w, packed_conv, pk_int, run_conv
+from .packing import LinearStack, dev_f32, pack_w, packed_conv, pk_int, run_conv
 
 A = ops  # activation codes live there
 
@@ -516,6 +517,18 @@ class SPyNet(nn.Module):
         istd = (1.0 / dev_f32(self.std.reshape(-1), device)).contiguous()
         self._pk = dict(levels=levels, mean=mean, istd=istd)
 
+    def pair_flows(self, raw):
+        """raw: (T,h,w,4) f32 clip in [-1,1] (channel 3 zero) -> (flows_forward, flows_backward) between neighbouring
+        frames, each (T-1,h,w,2) f32."""
+        if raw.shape[0] < 2:      # a single frame has no neighbour: empty flow stacks, nothing to propagate
+            empty = torch.zeros((0, raw.shape[1], raw.shape[2], 2), dtype=torch.float32, device=raw.device)
+            return empty, empty
+        norm = torch.zeros_like(raw)
+        ops.affine_channels(raw, 3, 0.5, 0.5, 0.0, 1.0, self._pk["mean"], self._pk["istd"], norm)
+        a, b = norm[:-1], norm[1:]
+        flows_backward = self.run(a, b)
+        return self.run(b, a), flows_backward
+
     def run(self, ref, supp):
         """ref, supp: (F,h,w,4) f32 normalised frames (channel 3 zero) -> (F,h,w,2) flow."""
         F_, h0, w0, _ = ref.shape
@@ -577,8 +590,10 @@ class TimestepEmbedSequential(nn.Sequential):
         return h
 
 
-class UNetModel(PackedModel, nn.Module):
+class UNetModel(ClipModel, nn.Module):
     """unet_new.py:901-1362 (same arguments; ``use_fp16`` / ``convert_to_fp16`` select bf16)."""
+
+    _name = "flair_amd.UNetModel"
 
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks,
                  attention_resolutions, rnn_resolutions, dropout=0, channel_mult=(1, 2, 4, 8),
@@ -661,32 +676,6 @@ class UNetModel(PackedModel, nn.Module):
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(LazyReshaper3D(normalization(ch)), nn.SiLU(),
                                  zero_module(LazyReshaper2D(conv_nd(dims, input_ch, out_channels, 3, padding=1))))
-        self._flow_cache = {}
-        self._graphs = {}
-        self.use_hip_graph = False
-
-    def enable_hip_graph(self, flag=True):
-        """Replay one captured hipGraph per (clip shape, dtype) instead of ~7000 launches per
-        forward.  Inputs are copied into static buffers; the returned tensor is overwritten by
-        the next call (the sampler consumes it immediately)."""
-        self.use_hip_graph = bool(flag)
-        self._graphs = {}
-        return self
-
-    # ---- dtype management (reference names) ------------------------------------------
-    # Reference: fp16 torso (unet_new.py:1224-1238).  Here: bfloat16 kernels (f32 accumulate; GroupNorm statistics,
-    # embeddings, flows and SPyNet stay f32).
-    convert_to_fp16 = PackedModel.convert_to_bf16
-
-    def invalidate_packed(self):
-        super().invalidate_packed()
-        self._graphs, self._flow_cache = {}, {}      # captured launches and cached flows were made with the old copies
-
-    def reset_flow_cache(self):
-        """Forget cached SPyNet flows (the sampler calls this at the start of every chain: flows are a
-        function of the conditioning clip, which only changes between chains)."""
-        self._flow_cache = {}
-        self._flow_gen = getattr(self, "_flow_gen", 0) + 1
 
     # ---- weight packing ---------------------------------------------------------------
     def _pack_all(self, dt, device):
@@ -694,22 +683,20 @@ class UNetModel(PackedModel, nn.Module):
         stem._pk = packed_conv(stem, None, dt, device)
         # first ResBlock of every output stage reads (h | skip) as two segments
         first_out = {id(st[0]): split for st, split in zip(self.output_blocks, self._skip_split)}
-        ws, bs, off = [], [], 0
+        film = LinearStack()
         for m in self.modules():
-            film = isinstance(m, ResBlock) or (isinstance(m, AttentionBlock) and m.bottleneck)
+            # a block with emb_layers reads its slice of film_all
+            has_film = isinstance(m, ResBlock) or (isinstance(m, AttentionBlock) and m.bottleneck)
+            off = film.add(m.emb_layers[1]) if has_film else 0
             if isinstance(m, ResBlock):
                 m.pack(dt, device, list(first_out[id(m)]) if id(m) in first_out else None, film_off=off)
             elif isinstance(m, AttentionBlock):
-                m.pack(dt, device, film_off=off if film else 0)
+                m.pack(dt, device, film_off=off)
             elif isinstance(m, (TemporalAttention, BasicVSRPP, SPyNet)):
                 m.pack(dt, device)
-            if film:                                  # has emb_layers: a slice of film_all
-                lin = m.emb_layers[1]
-                ws.append(dev_f32(lin.weight, device))
-                bs.append(dev_f32(lin.bias, device))
-                off += lin.out_features
+        emb_w, emb_b = film.cat(device)
         self._pk = dict(
-            emb_w=torch.cat(ws).contiguous(), emb_b=torch.cat(bs).contiguous(),
+            emb_w=emb_w, emb_b=emb_b,
             te=[dev_f32(p, device) for p in (self.time_embed[0].weight, self.time_embed[0].bias,
                                             self.time_embed[2].weight, self.time_embed[2].bias)],
             head_g=dev_f32(self.out[0].wrapped_module.weight, device), head_b=dev_f32(self.out[0].wrapped_module.bias, device),
@@ -723,122 +710,46 @@ class UNetModel(PackedModel, nn.Module):
         T, _, h, w = lqs.shape
         raw = torch.zeros((T, h, w, 4), dtype=torch.float32, device=lqs.device)
         ops.nchw_to_clip(lqs.contiguous(), raw, 0)
-        return self._flows_from_clip(raw)
+        return self.spynet.pair_flows(raw)
 
-    def _flows_from_clip(self, raw):
-        if raw.shape[0] < 2:      # a single frame has no neighbour: empty flow stacks, nothing to propagate
-            empty = torch.zeros((0, raw.shape[1], raw.shape[2], 2), dtype=torch.float32, device=raw.device)
-            return empty, empty
-        pk = self.spynet._pk
-        norm = torch.zeros_like(raw)
-        ops.affine_channels(raw, 3, 0.5, 0.5, 0.0, 1.0, pk["mean"], pk["istd"], norm)
-        a, b = norm[:-1], norm[1:]
-        flows_backward = self.spynet.run(a, b)
-        flows_forward = self.spynet.run(b, a)
-        return flows_forward, flows_backward
+    def _flow_spec(self, H, W, enable_cross_frames):
+        return (H, W)              # the (H, W) of the clip the network denoises; computed with cross-frames off too
 
-    def _flows_for(self, rnn_clip, hw=None):
-        """rnn_clip: (T,3,h,w) f32 device tensor; hw: the (H, W) of the clip the network denoises (default: the
-        conditioning clip's own).  The level at down-sampling s gets the flows of the conditioning clip resized
-        bicubically to (H/s, W/s), stored under W/s -- the key BasicVSRPP.run looks up.  For a square clip of side
-        image_size these are the reference's (res, res) of need_flows_res.  Flows are a pure function of the clip, so
-        they are cached across the denoising steps (keyed on storage + version)."""
+    def _compute_flows(self, rnn_clip, hw):
+        """The level at down-sampling s gets the flows of the conditioning clip resized bicubically to (H/s, W/s),
+        stored under W/s -- the key BasicVSRPP.run looks up.  For a square clip of side image_size these are the
+        reference's (res, res) of need_flows_res."""
         T, _, h, w = rnn_clip.shape
-        H, W = (h, w) if hw is None else hw
-        key = (rnn_clip.data_ptr(), rnn_clip._version, tuple(rnn_clip.shape), (H, W))
-        hit = self._flow_cache.get(key)
-        if hit is None:
-            raw = torch.zeros((T, h, w, 4), dtype=torch.float32, device=rnn_clip.device)
-            ops.nchw_to_clip(rnn_clip.contiguous(), raw, 0)
-            flows = {}
-            for s in self.rnn_resolutions:
-                if H % s or W % s:
-                    raise ValueError(f"flair_amd.UNetModel: a {H}x{W} clip has no level at down-sampling {s}")
-                rh, rw = H // s, W // s
-                src = raw
-                if (h, w) != (rh, rw):
-                    src = ops.resize(raw, (rh, rw), ops.RESIZE_BICUBIC, channels=3)
-                flows[rw] = self._flows_from_clip(src)
-            flows["_prop"] = {}              # per-clip store of composed second-order flows (BasicVSRPP._propagate)
-            if len(self._flow_cache) >= 16:
-                self._flow_cache.clear()
-            hit = (flows, rnn_clip)          # keep the keyed storage alive
-            self._flow_cache[key] = hit
-        return hit[0]
+        H, W = hw
+        raw = torch.zeros((T, h, w, 4), dtype=torch.float32, device=rnn_clip.device)
+        ops.nchw_to_clip(rnn_clip.contiguous(), raw, 0)
+        flows = {}
+        for s in self.rnn_resolutions:
+            if H % s or W % s:
+                raise ValueError(f"{self._name}: a {H}x{W} clip has no level at down-sampling {s}")
+            rh, rw = H // s, W // s
+            src = raw if (h, w) == (rh, rw) else ops.resize(raw, (rh, rw), ops.RESIZE_BICUBIC, channels=3)
+            flows[rw] = self.spynet.pair_flows(src)
+        return flows
 
-    # ---- forward ----------------------------------------------------------------------
+    # ---- forward (clip_model.ClipModel: per-clip slicing, graph capture / replay, the flow cache) ------------------
     def forward(self, x, timesteps, low_res_input=None, num_frames=None, rnn_input=None,
                 enable_cross_frames=True, vsrpp_weights=None, **kwargs):
         """Same contract as unet_new.py:1311-1362.  x: (B*T, C, H, W) f32 on the GPU;
         low_res_input / rnn_input: (B, T, 3, H, W); returns (B*T, out_channels, H, W) f32.
         Extra sampler kwargs (old_ts, sqrt_recip_alphas_cumprod, ...) are ignored."""
-        if not x.is_cuda:
-            raise RuntimeError("flair_amd.UNetModel runs on the MI355X only (tensors must be on "
-                               "'cuda'); there is no CPU path")
-        self._ensure_packed(x.device)
-        T = int(num_frames)
-        B = x.shape[0] // T
-        if rnn_input is None:
-            rnn_input = low_res_input
-        outs = []
-        for b in range(B):
-            vw = vsrpp_weights
-            if isinstance(vw, torch.Tensor):
-                vw = vw[b]
-            fn = self._forward_clip_graphed if (self.use_hip_graph and not isinstance(vw, torch.Tensor)
-                                                and getattr(self, "_trace", None) is None) else self._forward_clip
-            outs.append(fn(x[b * T:(b + 1) * T].float().contiguous(), timesteps[b * T:(b + 1) * T],
-                           low_res_input[b].float(), rnn_input[b].float(), enable_cross_frames, vw,
-                           **({"clip": b} if fn == self._forward_clip_graphed else {})))
-        return outs[0] if B == 1 else torch.cat(outs, dim=0)
+        return self._run_clips(x, timesteps, low_res_input, rnn_input, num_frames, enable_cross_frames, vsrpp_weights)
 
-    def _forward_clip_graphed(self, x, t, low_res, rnn, enable_cross_frames, vsrpp_weights, clip=0):
-        # one graph per clip of the batch: clips differ in their conditioning (rnn / low_res storage), so sharing one
-        # entry would evict and re-capture it on every forward of every sampler step
-        key = (tuple(x.shape), self.dtype, bool(enable_cross_frames), vsrpp_weights, x.device, clip)
-        ent = self._graphs.get(key)
-        # conditioning identity: storage + torch version + the sampler's chain counter (kernels launched
-        # through ctypes do not bump _version, so every new chain refreshes conditioning and flows once)
-        src = (rnn.data_ptr(), rnn._version, low_res.data_ptr(), low_res._version, getattr(self, "_flow_gen", 0))
-        if ent is not None and ent["src"] != src:
-            # a new clip / chain: the captured launches read this clip's flows AND the second-order flows composed
-            # from them (BasicVSRPP._propagate's per-clip store): re-capture (one eager forward, once per chain)
-            del self._graphs[key]
-            ent = None
-        if ent is None:
-            st = dict(x=x.clone(), t=t.clone(), lr=low_res.clone(), rnn=rnn.clone())
-            flows = self._flows_for(st["rnn"], tuple(x.shape[-2:]))   # SPyNet runs eagerly, before capture
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):                    # warm-up (allocator, workspaces)
-                self._forward_clip(st["x"], st["t"], st["lr"], st["rnn"], enable_cross_frames, vsrpp_weights,
-                                   flows=flows)
-            cur.wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            # thread_local: HIP calls of OTHER host threads (flair_amd.io's reader pins memory / uploads the next
-            # window, its writer waits on events) must not invalidate this thread's capture
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                out = self._forward_clip(st["x"], st["t"], st["lr"], st["rnn"], enable_cross_frames,
-                                         vsrpp_weights, flows=flows)
-            ent = dict(graph=graph, st=st, out=out, src=src, flows=flows)
-            self._graphs[key] = ent
-        st = ent["st"]
-        st["x"].copy_(x)
-        st["t"].copy_(t)
-        ent["graph"].replay()
-        return ent["out"]
-
-    def _forward_clip(self, x, t, low_res, rnn, enable_cross_frames, vsrpp_weights, flows=None):
+    def _forward_clip(self, x, t, low_res, flows, enable_cross_frames, vsrpp_weights):
+        """t: (T,) f32 timesteps (integers up to the schedule length are exact in f32)."""
         T, _, H, W = x.shape
         dev, dt = x.device, self.dtype
         ctx = Ctx(dt, dev, T)
         ctx.enable_cross_frames = enable_cross_frames
         ctx.vsrpp_weights = vsrpp_weights
-        ctx.flows = flows if flows is not None else self._flows_for(rnn, (H, W))
+        ctx.flows = flows
         # timestep embedding MLP and every emb_layers linear of the network (f32)
-        temb = ops.timestep_embedding(t.float().contiguous(), self.model_channels)
+        temb = ops.timestep_embedding(t, self.model_channels)
         pk = self._pk
         e = ops.linear(temb, pk["te"][0], pk["te"][1], act_out=A.ACT_SILU)
         ctx.emb = ops.linear(e, pk["te"][2], pk["te"][3])
@@ -849,7 +760,7 @@ class UNetModel(PackedModel, nn.Module):
         ops.nchw_to_clip(x, h, 0)
         ops.nchw_to_clip(low_res.contiguous(), h, x.shape[1])
         hs = []
-        trace = getattr(self, "_trace", None)   # tests: per-stage activations
+        trace = self._trace                     # tests: per-stage activations
         for i, blk in enumerate(self.input_blocks):
             h = blk.run(ctx, h)
             hs.append(h)

@@ -112,32 +112,59 @@ def test_unet_flows_vs_oracle(dev):
 
 
 @pytest.mark.gpu
-def test_hip_graph_replay_matches_eager(dev):
+def test_spynet_pair_flows(dev):
+    """SPyNet.pair_flows: a single frame has no neighbour (two empty stacks); on three frames it is what
+    compute_flow returns, bit for bit."""
+    _, m = build_pair(SMALL)
+    m = m.to(dev)
+    m._ensure_packed(dev)
+    S = 32
+    for T in (1, 3):
+        lr = _inputs(T, S, seed=8)[1][0].to(dev)
+        raw = torch.zeros((T, S, S, 4), dtype=torch.float32, device=dev)
+        raw[..., :3] = lr.permute(0, 2, 3, 1)
+        got = m.spynet.pair_flows(raw)
+        want = m.compute_flow(lr)
+        torch.cuda.synchronize()
+        for g, w in zip(got, want):
+            assert g.shape == (T - 1, S, S, 2) and g.dtype == torch.float32
+            assert torch.equal(g, w)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tensor_weights", [False, True])
+def test_hip_graph_replay_matches_eager(dev, tensor_weights):
     """enable_hip_graph(): the captured forward replays bit-identically to eager launches, for new
-    latents / timesteps and after the conditioning clip changes (flows recomputed into the same buffers)."""
+    latents / timesteps, after the conditioning clip changes (flows recomputed into the same buffers), and with a
+    per-pixel propagation-weight map (a static input of the graph: a new map tensor re-captures)."""
     _, m = build_pair(SMALL)
     m = m.to(dev)
     m.convert_to_fp16()
     T, S = 4, 32
+    g = torch.Generator().manual_seed(2)
+    wmap = (0.9 + 0.1 * torch.rand(1, T, 1, S, S, generator=g)).to(dev) if tensor_weights else 1.0
+    wmap2 = (0.9 + 0.1 * torch.rand(1, T, 1, S, S, generator=g)).to(dev) if tensor_weights else 1.0
     cases, clips = [], {}
-    for seed, tval in [(3, 371), (3, 12), (3, 655), (8, 940)]:   # the same clip three times, then a new clip
+    for seed, tval, w in [(3, 371, wmap), (3, 12, wmap), (3, 655, wmap), (8, 940, wmap), (8, 207, wmap2)]:
+        # the same clip three times, then a new clip, then a new weight map of the same shape
         x, lr, t = _inputs(T, S, seed=seed)
         x = x + 0.01 * tval                                    # a different latent every time
         if seed not in clips:
             clips[seed] = lr.to(dev)                           # ONE device tensor per clip: later calls are pure replays
-        cases.append((x.to(dev), clips[seed], torch.full((T,), tval, dtype=torch.long, device=dev)))
-    eager = [m(x, t, low_res_input=lr, num_frames=T, vsrpp_weights=1.0).clone() for x, lr, t in cases]
+        cases.append((x.to(dev), clips[seed], torch.full((T,), tval, dtype=torch.long, device=dev), w))
+    eager = [m(x, t, low_res_input=lr, num_frames=T, vsrpp_weights=w).clone() for x, lr, t, w in cases]
     m.enable_hip_graph()
     graphs = []
-    for (x, lr, t), ref in zip(cases, eager):
-        y = m(x, t, low_res_input=lr, num_frames=T, vsrpp_weights=1.0)
+    for (x, lr, t, w), ref in zip(cases, eager):
+        y = m(x, t, low_res_input=lr, num_frames=T, vsrpp_weights=w)
         torch.cuda.synchronize()
         assert torch.equal(y, ref)
         assert len(m._graphs) == 1
         graphs.append(next(iter(m._graphs.values()))["graph"])
     # calls 2 and 3 replayed the graph captured by call 1 with new x / t (nothing baked in at capture time);
-    # the new clip re-captured
+    # the new clip re-captured; a new map tensor re-captures, the same number replays
     assert graphs[0] is graphs[1] is graphs[2] and graphs[3] is not graphs[0]
+    assert (graphs[4] is not graphs[3]) if tensor_weights else (graphs[4] is graphs[3])
     m.enable_hip_graph(False)
 
 
