@@ -133,8 +133,9 @@ def _prof_end(e0, family, dtype, flops, nbytes, replay=None, sig=None):
     PROFILE.append((family, str(dtype), float(flops), float(nbytes), e0, e1, replay, sig))
 
 
-def conv_variant(T, H, W, cins, cout, kernel, dtype=torch.bfloat16, stride=1):
-    """Kernel variant flair_conv_nhwc dispatches this geometry to (flair_conv_variant); host-only."""
+def conv_variant(T, H, W, cins, cout, kernel, dtype=torch.bfloat16, stride=1, act=ACT_NONE):
+    """Kernel variant flair_conv_nhwc dispatches this geometry to (flair_conv_variant); host-only.  The activation is part
+    of the choice: GELU stays off the LDS-DMA kernels."""
     p = ConvParams()
     p.dtype = 1 if dtype == torch.bfloat16 else 0      # FLAIR_BF16 / FLAIR_F32
     p.T, p.H, p.W = T, H, W
@@ -146,6 +147,7 @@ def conv_variant(T, H, W, cins, cout, kernel, dtype=torch.bfloat16, stride=1):
         p.seg_ld[i] = c
     p.stride = stride
     p.y_ld = cout
+    p.act = act
     return lib().flair_conv_variant(ctypes.byref(p))
 
 

@@ -181,15 +181,21 @@ def assert_bits_equal(got, ref, what="", tile=None):
     msg = (f"{what}: {n} of {ne.numel()} element(s) differ in bits; first at {list(first)}: got {got[first].item()!r}, "
            f"expected {ref[first].item()!r}; largest |difference| {d[ne].max().item():.6g}")
     if tile is not None and got.dim() == 4:
-        rows, cols, couts = tile
-        key = (idx[:, 1] % rows) * (cols * couts) + (idx[:, 2] % cols) * couts + idx[:, 3] % couts
-        cnt = torch.bincount(key, minlength=rows * cols * couts).view(rows, cols, couts)
-        msg += (f"\n  by h % {rows}: {cnt.sum((1, 2)).tolist()}\n  by w % {cols}: {cnt.sum((0, 2)).tolist()}"
-                f"\n  by c % {couts}: {cnt.sum((0, 1)).tolist()}")
-        top = cnt.flatten().argsort(descending=True)[:8].tolist()
-        msg += "\n  most hit (h % rows, w % cols, c % couts): " + ", ".join(
-            f"({k // (cols * couts)}, {k // couts % cols}, {k % couts}): {int(cnt.flatten()[k])}" for k in top if cnt.flatten()[k] > 0)
+        msg += tile_histogram(idx, tile)
     raise AssertionError(msg)
+
+
+def tile_histogram(idx, tile):
+    """idx: (n, 4) positions in a (T, H, W, C) clip tensor, tile = (rows, cols, couts) -> the lines that count them by
+    (h % rows, w % cols, c % couts)."""
+    rows, cols, couts = tile
+    key = (idx[:, 1] % rows) * (cols * couts) + (idx[:, 2] % cols) * couts + idx[:, 3] % couts
+    cnt = torch.bincount(key, minlength=rows * cols * couts).view(rows, cols, couts)
+    msg = (f"\n  by h % {rows}: {cnt.sum((1, 2)).tolist()}\n  by w % {cols}: {cnt.sum((0, 2)).tolist()}"
+           f"\n  by c % {couts}: {cnt.sum((0, 1)).tolist()}")
+    top = cnt.flatten().argsort(descending=True)[:8].tolist()
+    return msg + "\n  most hit (h % rows, w % cols, c % couts): " + ", ".join(
+        f"({k // (cols * couts)}, {k // couts % cols}, {k % couts}): {int(cnt.flatten()[k])}" for k in top if cnt.flatten()[k] > 0)
 
 
 # Attention with a known softmax (tests/test_gpu_attn_exact.py, tests/test_attn_exact_cpu.py).  q, k, v are float32 CPU
@@ -669,3 +675,57 @@ def gn_fold_f32(x, mean64, var64, gamma, beta, eps, film=None):
         A = A * m
         B = (B.double() * m.double() + film[:, None, None, C:2 * C].double()).float()
     return (x.double() * A.double() + B.double()).float()
+
+
+# Activation epilogues on an exact pre-activation (tests/test_gpu_act_exact.py, tests/test_act_exact_cpu.py).  v is a float64
+# tensor whose last axis is the output channel; co is the channel index along that axis.
+ACT_DCN_OFFSETS = 4
+ACT_FLOOR = 2.0 ** -120     # a few f32 denormal steps: what an underflowing tail may leave
+
+
+def dcn_is_residue(co, period):
+    """The class map of FLAIR_ACT_DCN_OFFSETS in the tap-major channel order: of every `period` = 3 G channels the first
+    2 G are residues (mag * tanh), the last G masks (sigmoid)."""
+    return 3 * (co % period) < 2 * period
+
+
+def dcn_act64(v, co, mag, period):
+    assert v.dtype == torch.float64 and v.shape[-1] == co.numel()
+    return torch.where(dcn_is_residue(co, period), mag * torch.tanh(v), torch.sigmoid(v))
+
+
+def act_sens64(v, act, co=None, mag=10.0, period=48):
+    """S of |got - act(v)| <= k 2^-24 S: the magnitude that the f32 roundings of the formula act on, in float64.
+    |a| + |v a'(v)| (the value, and what a relative error of the exponential's argument does to it), plus the cancellation
+    term of the formula where it has one: GELU = 0.5 v (1 + erf) carries 0.5 |v| (1 + |erf|) in place of |a|, and
+    mag tanh = mag (1 - 2 r) carries mag (1 - tanh) beside mag |tanh|."""
+    assert v.dtype == torch.float64
+    if act == ACT_SILU:
+        s = torch.sigmoid(v)
+        return (v * s).abs() + (v * (s + v * s * (1 - s))).abs()
+    if act == ACT_GELU:
+        erf = torch.erf(v * 0.7071067811865476)
+        da = 0.5 * (1 + erf) + v * torch.exp(-0.5 * v * v) * 0.3989422804014327
+        return 0.5 * v.abs() * (1 + erf.abs()) + (v * da).abs()
+    if act == ACT_DCN_OFFSETS:
+        t, s = torch.tanh(v), torch.sigmoid(v)
+        return torch.where(dcn_is_residue(co, period), mag * (t.abs() + (1 - t) + (v * (1 - t * t)).abs()),
+                           s + (v * s * (1 - s)).abs())
+    raise ValueError(act)
+
+
+def assert_act_close(got, ref64, S, k, dtype, what="", tile=None, extra=None):
+    """|got - ref64| <= k 2^-24 S + out_rounding(ref64, dtype) + ACT_FLOOR (+ extra, the roundings of what follows the
+    activation) for every element; NaN and Inf fail.  On failure the message counts the failing elements by tile position
+    like assert_bits_equal.  -> the largest (err - those terms) / (2^-24 S)."""
+    ab = out_rounding(ref64, dtype) + ACT_FLOOR
+    if extra is not None:
+        ab = ab + extra
+    try:
+        return k * assert_elem_close(got, ref64, S, k * U24, what, ab=ab)
+    except AssertionError as e:
+        if tile is None or ref64.dim() != 4:
+            raise
+        err = (got.detach().cpu().double() - ref64).abs()
+        bad = ~(err - ab <= k * U24 * S)
+        raise AssertionError(str(e) + tile_histogram(bad.nonzero(), tile)) from None
