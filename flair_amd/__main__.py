@@ -2,7 +2,8 @@
 ends of the loop around it: ``degrade TASK CLEAN_DIR OUT_DIR`` makes a task's degraded frames from clean ones with the exact
 operator the restoration assumes (flair_amd.degrade), and ``evaluate RESTORED_DIR TRUTH_DIR`` scores written frames with PSNR
 and SSIM (flair_amd.metrics) and, with ``--lpips {vgg,alex} --weights DIR``, LPIPS (flair_amd.lpips); ``restore --ground-truth
-DIR`` scores every video as soon as it is written.
+DIR`` scores every video as soon as it is written.  ``niqe FRAMES_DIR --params FILE`` scores frames that have no ground truth
+(flair_amd.niqe); ``--niqe FILE`` adds that score to evaluate, restore and interpolate, the last two with or without ground truth.
 ``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo or AMT-G (flair_amd.interpolate).
 ``scenes SRC_DIR --json PATH`` finds the hard cuts of a video (flair_amd.scenes); ``restore`` / ``interpolate --scene-cuts
 auto|PATH`` then treat every shot on its own.
@@ -76,6 +77,35 @@ def _add_lpips(p, what, where):
                         f"an AlexNet trunk (alexnet.pth + lpips_alex.pth; the lpips package's default){where}")
 
 
+def _add_niqe(p, what):
+    p.add_argument("--niqe", default=None, metavar="FILE",
+                   help=f"{what} the no-reference NIQE of the written frames (lower is better); FILE is BasicSR's "
+                        "niqe_pris_params.npz (mu_pris_param, cov_pris_param, gaussian_window).  Needs no ground truth; frames "
+                        "must hold at least two 96x96 blocks")
+
+
+def niqe_of(args, command, option="--niqe"):
+    """The parameter file of a parsed command line's --niqe (--params of the niqe command), or None without it; refused
+    before any GPU work where it is not a file."""
+    path = getattr(args, "niqe" if option == "--niqe" else "params", None)
+    if path is None:
+        return None
+    if not os.path.isfile(path):
+        raise SystemExit(f"{command}: {option} {path} is not a file (BasicSR's niqe_pris_params.npz)")
+    return path
+
+
+def load_niqe_of(path, device, command):
+    """The NIQE model of niqe_of's result on ``device`` (None for None)."""
+    if path is None:
+        return None
+    from . import niqe as fnq
+    try:
+        return fnq.load_niqe(path, device)
+    except (ValueError, FileNotFoundError) as exc:
+        raise SystemExit(f"{command}: {exc}")
+
+
 def lpips_of(args, command):
     """(net, weights directory) of a parsed command line's --lpips, or None without it; refusals before any GPU work."""
     net = getattr(args, "lpips", None)
@@ -131,6 +161,7 @@ def make_parser():
                    help="clean frames of the video (with --output-root: a root holding one directory per video name): "
                         "after a video is written, log its mean PSNR / SSIM and write metrics.json next to the frames")
     _add_lpips(r, "with --ground-truth: also score", "; the files are read from --weights")
+    _add_niqe(r, "after a video is written, log its mean and write into metrics.json")
     _add_hparams(r, pl.MAIN_DEFAULTS)
     _add_common(r)
     for name, demo in pl.DEMOS.items():
@@ -155,6 +186,12 @@ def make_parser():
     e.add_argument("--device", default=None, help="default: cuda")
     _add_lpips(e, "also score", "")
     e.add_argument("--weights", default=None, metavar="DIR", help="with --lpips: the directory that holds those files")
+    _add_niqe(e, "also report")
+    q = sub.add_parser("niqe", help="no-reference NIQE of written frames: one line per frame and the mean")
+    q.add_argument("frames_dir", metavar="FRAMES_DIR", help="frames of at least two 96x96 blocks each")
+    q.add_argument("--params", default=None, metavar="FILE", help="BasicSR's niqe_pris_params.npz (required)")
+    q.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the mean as JSON")
+    q.add_argument("--device", default=None, help="default: cuda")
     i = sub.add_parser("interpolate", help="factor - 1 new frames between every two frames of a video (SuperSloMo or AMT-G)")
     i.add_argument("src_dir", metavar="SRC_DIR", help="frames of one size")
     i.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png, factor * (T - 1) + 1 of them")
@@ -167,8 +204,9 @@ def make_parser():
     i.add_argument("--device", default=None, help="default: cuda")
     i.add_argument("--ground-truth", default=None, metavar="DIR",
                    help="frames at the new rate: score the written frames against them (PSNR / SSIM)")
-    i.add_argument("--json", default=None, metavar="PATH", help="with --ground-truth: also write the values as JSON")
+    i.add_argument("--json", default=None, metavar="PATH", help="with --ground-truth or --niqe: also write the values as JSON")
     _add_lpips(i, "with --ground-truth: also score", "; the files are read from --weights")
+    _add_niqe(i, "also report")
     _add_cut_options(i, "synthesise nothing between the two frames of a cut: the in-betweens there are copies of the nearer "
                         "frame (--min-shot keeps its default of 4 here too)")
     s = sub.add_parser("scenes", help="find the hard cuts of a video (block-luma distances; heuristic defaults, not validated "
@@ -249,11 +287,12 @@ def interpolate_of(args):
         fi.check_interpolator(args.interpolator, args.dtype, size)
     except ValueError as exc:
         raise SystemExit(f"interpolate: {exc}")
-    if args.json and not args.ground_truth:
+    if args.json and not args.ground_truth and not args.niqe:
         raise SystemExit("interpolate: --json writes the scores of --ground-truth DIR")
     if args.ground_truth and not os.path.isdir(args.ground_truth):
         raise SystemExit(f"interpolate: ground truth {args.ground_truth} is not a directory")
     lpips_of(args, "interpolate")
+    niqe_of(args, "interpolate")
     return paths
 
 
@@ -274,17 +313,48 @@ def _interpolate(args):
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"interpolate: {exc}")
     print(f"wrote {n} frames to {args.out_dir} ({args.factor}x the rate of {args.src_dir})")
+    niqe = load_niqe_of(niqe_of(args, "interpolate"), device, "interpolate")
+    niqe_kw = {} if niqe is None else dict(niqe=niqe)
     if args.ground_truth:
         from . import metrics as fm
         model = load_lpips_of(lpips_of(args, "interpolate"), device, "interpolate")
         try:
-            result = fm.evaluate_dirs(args.out_dir, args.ground_truth, device, **({} if model is None else dict(lpips=model)))
+            result = fm.evaluate_dirs(args.out_dir, args.ground_truth, device, **({} if model is None else dict(lpips=model)), **niqe_kw)
         except ValueError as exc:
             raise SystemExit(str(exc))
         for line in fm.format_report(result):
             print(line)
         if args.json:
             write_json(args.json, result)
+    elif niqe is not None:
+        _report_niqe(args.out_dir, device, niqe, args.json, "interpolate")
+    return 0
+
+
+def _report_niqe(frames_dir, device, model, json_path, command):
+    """Score a directory without ground truth: one line per frame, the mean, and the JSON file where one is asked for."""
+    from . import niqe as fnq
+    try:
+        result = fnq.niqe_dir(frames_dir, device, model)
+    except ValueError as exc:                               # the messages name niqe themselves
+        raise SystemExit(str(exc) if command == "niqe" else f"{command}: {exc}")
+    for line in fnq.format_report(result):
+        print(line)
+    if json_path:
+        write_json(json_path, result)
+    return result
+
+
+def _niqe(args):
+    if args.params is None:
+        raise SystemExit("niqe: --params FILE is required (BasicSR's niqe_pris_params.npz); nothing is shipped or downloaded")
+    path = niqe_of(args, "niqe", option="--params")
+    if not os.path.isdir(args.frames_dir):
+        raise SystemExit(f"niqe: {args.frames_dir} is not a directory")
+    import torch
+    torch.set_grad_enabled(False)
+    device = args.device or "cuda"
+    _report_niqe(args.frames_dir, device, load_niqe_of(path, device, "niqe"), args.json, "niqe")
     return 0
 
 
@@ -339,12 +409,15 @@ def write_json(path, result):
 
 def _evaluate(args):
     spec = lpips_of(args, "evaluate")
+    niqe_path = niqe_of(args, "evaluate")
     import torch
     from . import metrics as fm
     torch.set_grad_enabled(False)
     model = load_lpips_of(spec, args.device or "cuda", "evaluate")
+    niqe = load_niqe_of(niqe_path, args.device or "cuda", "evaluate")
     try:
-        result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda", **({} if model is None else dict(lpips=model)))
+        result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda", **({} if model is None else dict(lpips=model)),
+                                  **({} if niqe is None else dict(niqe=niqe)))
     except ValueError as exc:
         raise SystemExit(str(exc))
     for line in fm.format_report(result):
@@ -352,6 +425,14 @@ def _evaluate(args):
     if args.json:
         write_json(args.json, result)
     return 0
+
+
+def niqe_tail(result):
+    """``  niqe X`` of a result's mean where it holds one ('' without --niqe)."""
+    if "niqe" not in result["mean"]:
+        return ""
+    from .niqe import format_value
+    return format_value(result["mean"]["niqe"])
 
 
 def jobs_of(args):
@@ -418,9 +499,12 @@ def main(argv=None):
         return _interpolate(args)
     if args.command == "scenes":
         return _scenes(args)
+    if args.command == "niqe":
+        return _niqe(args)
     task, jobs = jobs_of(args)
     truth = truth_of(args, jobs)
     lpips_spec = lpips_of(args, "restore")
+    niqe_path = niqe_of(args, "restore")
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
@@ -449,15 +533,28 @@ def main(argv=None):
         hp.update(faces)
         hp.update(how)
         lpips_model = load_lpips_of(lpips_spec, device, "restore")
-        lpips_kw = {} if lpips_model is None else dict(lpips=lpips_model)      # without the option, the call of before
+        score_kw = {} if lpips_model is None else dict(lpips=lpips_model)      # without the option, the call of before
+        niqe_model = load_niqe_of(niqe_path, device, "restore")
+        if niqe_model is not None:
+            score_kw["niqe"] = niqe_model
 
         def restore_one(v, o):
             n = p.restore_video_files(v, o, **hp)
             if truth is not None:
                 from . import metrics as fm
-                result = fm.evaluate_dirs(o, truth[o], device, **lpips_kw)
+                result = fm.evaluate_dirs(o, truth[o], device, **score_kw)
                 print(f"{o}: mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  "
-                      f"ssim {result['mean']['ssim']:.4f}" + (f"  lpips {result['mean']['lpips']:.4f}" if lpips_model is not None else ""))
+                      f"ssim {result['mean']['ssim']:.4f}" + (f"  lpips {result['mean']['lpips']:.4f}" if lpips_model is not None else "")
+                      + niqe_tail(result))
+                write_json(os.path.join(o, "metrics.json"), result)
+            elif niqe_model is not None:                # footage without a clean original: the no-reference score alone
+                from . import niqe as fnq
+                try:
+                    result = fnq.niqe_dir(o, device, niqe_model)
+                except ValueError as exc:               # frames under two blocks: the video is written, only the score is not
+                    print(f"{o}: no score: {exc}")
+                    return n
+                print(f"{o}: mean of {result['mean']['niqe_frames']} of {result['count']} frames" + niqe_tail(result))
                 write_json(os.path.join(o, "metrics.json"), result)
             return n
         pl.restore_many(jobs, restore_one)

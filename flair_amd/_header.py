@@ -2,7 +2,8 @@
 
 The header is the contract with libflair_hip.so; nothing of it is restated in Python.  ``STRUCTS`` maps a C struct name to
 a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``; ``EVAL_PROTOS`` is the same table
-of include/flair_eval.h, the evaluation-only entries of the same library.  Only the constructs the header uses
+of include/flair_eval.h, the evaluation-only entries of the same library, and ``NOREF_PROTOS`` that of include/flair_noref.h,
+the no-reference scores.  Only the constructs the header uses
 are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
 """
 import collections
@@ -103,3 +104,11 @@ with open(EVAL_HEADER_PATH) as _f:
     _eval_structs, EVAL_PROTOS = parse(_f.read())
 if _eval_structs or set(EVAL_PROTOS) & set(PROTOS):
     raise HeaderError(f"flair_eval.h declares a struct or an entry of flair_hip.h: {sorted(_eval_structs) + sorted(set(EVAL_PROTOS) & set(PROTOS))}")
+
+# The no-reference ABI (include/flair_noref.h: NIQE), on the same terms: a table of its own, no struct, no entry declared twice.
+NOREF_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "flair_noref.h")
+with open(NOREF_HEADER_PATH) as _f:
+    _noref_structs, NOREF_PROTOS = parse(_f.read())
+if _noref_structs or set(NOREF_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS)):
+    raise HeaderError("flair_noref.h declares a struct or an entry of another header: "
+                      f"{sorted(_noref_structs) + sorted(set(NOREF_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS)))}")

@@ -1,5 +1,5 @@
-"""ctypes binding of libflair_hip.so, derived from the C ABI's own headers (include/flair_hip.h and the evaluation-only
-include/flair_eval.h, read by _header.py).
+"""ctypes binding of libflair_hip.so, derived from the C ABI's own headers (include/flair_hip.h, the evaluation-only
+include/flair_eval.h and the no-reference include/flair_noref.h, read by _header.py).
 
 The library is the product path: there is no CPU or PyTorch fallback.  Loading fails
 loudly (``FlairHipUnavailable``) when the shared object has not been built.  ``lib()`` is the
@@ -12,10 +12,11 @@ import os
 
 import torch  # noqa: F401  (must be imported first: the library binds to torch's HIP runtime)
 
-from ._header import EVAL_PROTOS, PROTOS, STRUCTS
+from ._header import EVAL_PROTOS, NOREF_PROTOS, PROTOS, STRUCTS
 
-# every declared entry of the library: the sampling path's (flair_hip.h) and the evaluation-only ones (flair_eval.h)
-ALL_PROTOS = {**PROTOS, **EVAL_PROTOS}
+# every declared entry of the library: the sampling path's (flair_hip.h), the evaluation-only ones (flair_eval.h) and the
+# no-reference scores (flair_noref.h)
+ALL_PROTOS = {**PROTOS, **EVAL_PROTOS, **NOREF_PROTOS}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libflair_hip.so")
@@ -121,7 +122,7 @@ class _Entries:
 
     def __getattr__(self, name):
         if name not in _LAUNCHES:
-            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream, nor one of flair_eval.h")
+            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream, nor one of flair_eval.h or flair_noref.h")
         return functools.partial(_launch, name)
 
 

@@ -1,5 +1,5 @@
-"""PSNR, SSIM and (on request) LPIPS of written frames against ground truth, on the GPU (``flair_image_metrics``,
-csrc/metrics.hip; ``flair_amd.lpips``, csrc/lpips.hip).
+"""PSNR, SSIM and (on request) LPIPS of written frames against ground truth, and (on request) their no-reference NIQE, on
+the GPU (``flair_image_metrics``, csrc/metrics.hip; ``flair_amd.lpips``, csrc/lpips.hip; ``flair_amd.niqe``, csrc/niqe.hip).
 
 The reference ships no scoring tool; this is the restoration literature's usual pair, on the bytes that get written
 (float images go through ``io.to_bytes`` first, so a metric always describes the files):
@@ -12,7 +12,11 @@ The reference ships no scoring tool; this is the restoration literature's usual 
   * ``lpips``, only with a model from ``flair_amd.lpips.load_lpips``: the ``lpips`` package's 0.1 metric on a VGG-16 or AlexNet
     trunk, as restated in include/flair_eval.h.
 
-Not measured: the Y-channel and border-cropped variants, identity and temporal metrics.
+  * ``niqe``, only with a model from ``flair_amd.niqe.load_niqe``: the no-reference NIQE of the RESTORED frames (the truth is
+    not scored), as restated in include/flair_noref.h; ``flair_amd.niqe.niqe_dir`` scores a directory without any truth.
+
+Not measured: the Y-channel and border-cropped variants of PSNR / SSIM, NIQE's colour and border-cropped variants, other
+no-reference scores (BRISQUE, PI), identity and temporal metrics.
 """
 import math
 import os
@@ -71,15 +75,21 @@ def _groups(sizes, batch):
     return groups
 
 
-def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None):
+def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=None):
     """Score the frames of ``restored_dir`` against those of ``truth_dir``, paired in ``io.list_frames`` order:
     ``dict(frames=[{name, psnr, ssim}], mean={psnr, ssim}, count)``; the means are those of the per-frame values.
     ValueError when a directory is empty, the counts differ, a pair differs in size or is smaller than 11 pixels a side
     (checked on the file headers, before anything is decoded).  The next batch is decoded and uploaded while the current
     one is measured (io.iter_frame_batches).  ``lpips``: a ``flair_amd.lpips.LPIPS`` model; every frame dict and ``mean``
     then gain ``lpips``, and frames below the trunk's minimum are refused with the others (without one the result is what
-    it was before the option existed)."""
+    it was before the option existed).  ``niqe``: a ``flair_amd.niqe.NIQE`` model; every frame dict then gains ``niqe`` of the
+    restored frame (None where it has no score) and ``mean`` gains ``niqe``, over the ``niqe_frames`` frames that have one;
+    frames with fewer than two 96 x 96 blocks are refused with the others."""
     ra, rb, sizes = _pairs(restored_dir, truth_dir)
+    if niqe is not None:
+        from . import niqe as fnq
+        for pa, (h, w) in zip(ra, sizes):
+            fnq.check_size(h, w, what=f"evaluate: {pa}")
     if lpips is not None:
         from . import lpips as flp
         for pa, pb, (h, w) in zip(ra, rb, sizes):
@@ -92,17 +102,27 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None):
         if lpips is not None:
             for i, d in enumerate(lpips(a, b)):
                 frames[first + i]["lpips"] = d
+        if niqe is not None:
+            for i, v in enumerate(niqe(a)):
+                frames[first + i]["niqe"] = None if math.isnan(v) else v
     n = len(frames)
     mean = dict(psnr=sum(f["psnr"] for f in frames) / n, ssim=sum(f["ssim"] for f in frames) / n)
     if lpips is not None:
         mean["lpips"] = sum(f["lpips"] for f in frames) / n
+    if niqe is not None:
+        mean.update(fnq.mean_of([f["niqe"] for f in frames]))
     return dict(frames=frames, mean=mean, count=n)
 
 
 def format_report(result):
-    """One line per frame and the means, four decimals each (``lpips`` last, where the result holds it)."""
+    """One line per frame and the means, four decimals each (``lpips``, then ``niqe``, where the result holds them; ``niqe
+    n/a`` for a frame without a score, which the mean leaves out)."""
     def tail(d):
-        return f"  lpips {d['lpips']:.4f}" if "lpips" in d else ""
+        text = f"  lpips {d['lpips']:.4f}" if "lpips" in d else ""
+        if "niqe" in d:
+            from .niqe import format_value
+            text += format_value(d["niqe"])
+        return text
     lines = [f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" + tail(f) for f in result["frames"]]
     lines.append(f"mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  ssim {result['mean']['ssim']:.4f}"
                  + tail(result["mean"]))

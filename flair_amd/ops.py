@@ -1097,6 +1097,54 @@ def alexnet_stem(x, w, bias, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- NIQE (niqe.hip, include/flair_noref.h)
+NIQE_BLOCK = 96                             # FLAIR_NIQE_BLOCK: block side at scale 1, half of it at scale 2
+NIQE_HALF_UNIT = 2.0 ** -16                 # a value of the half-scale plane is y2 * NIQE_HALF_UNIT
+
+
+def niqe_luma(u8, y1=None, y2=None):
+    """Exact BT.601 luma of the top-left (96 nh, 96 nw) crop and 65536 x its MATLAB-bicubic half scale (flair_niqe_luma):
+    u8 (N, H, W, 3) uint8 dense RGB on the GPU at any byte alignment, H, W >= 96 -> (y1 (N, 96 nh, 96 nw), y2 (N, 48 nh,
+    48 nw)), both int32 and bit-exact; y1, y2: optional dense tensors of those shapes."""
+    _refuse(u8.dim() == 4 and u8.shape[3] == 3, f"niqe_luma: (N, H, W, 3) frames, got {tuple(u8.shape)}")
+    _refuse(u8.dtype == torch.uint8, f"niqe_luma: uint8 frames, got {u8.dtype}")
+    _refuse(u8.is_contiguous(), "niqe_luma: dense (contiguous) frames")
+    N, H, W, _ = u8.shape
+    _refuse(min(H, W) >= NIQE_BLOCK, f"niqe_luma: frames of {H}x{W} hold no {NIQE_BLOCK}x{NIQE_BLOCK} block")
+    Hc, Wc = H // NIQE_BLOCK * NIQE_BLOCK, W // NIQE_BLOCK * NIQE_BLOCK
+    if y1 is None:
+        y1 = torch.empty((N, Hc, Wc), dtype=torch.int32, device=u8.device)
+    if y2 is None:
+        y2 = torch.empty((N, Hc // 2, Wc // 2), dtype=torch.int32, device=u8.device)
+    for name, t, shape in (("y1", y1, (N, Hc, Wc)), ("y2", y2, (N, Hc // 2, Wc // 2))):
+        _refuse(t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape,
+                f"niqe_luma: {name} is a dense {shape} int32 tensor, got {tuple(t.shape)} {t.dtype}")
+    call.flair_niqe_luma(u8, N, H, W, y1, y2)
+    return y1, y2
+
+
+def niqe_moments(y, block, inv_scale, window, out=None, mscn=None):
+    """The MSCN map of one scale and the 25 moments of each of its blocks (flair_niqe_moments): y (N, Hc, Wc) int32 dense, a
+    pixel's value being y * inv_scale (1, or NIQE_HALF_UNIT for niqe_luma's y2); block 96 or 48, dividing Hc and Wc; window
+    (7, 7) float64 on the GPU -> (N, (Hc / block) (Wc / block), 5, 5) float64: block j nh + i, maps M, M roll(M, (0,1)),
+    (1,0), (1,1), (1,-1), moments c-, c+, s-, s+, a.  mscn: optional dense (N, Hc, Wc) float64 tensor that receives M.
+    The same bits in every run, for every N and every position in the batch."""
+    _refuse(y.dim() == 3 and y.dtype == torch.int32 and y.is_contiguous(), f"niqe_moments: y is a dense (N, Hc, Wc) int32 tensor, got {tuple(y.shape)} {y.dtype}")
+    N, Hc, Wc = y.shape
+    _refuse(block in (NIQE_BLOCK, NIQE_BLOCK // 2), f"niqe_moments: block = {block}, one of {NIQE_BLOCK} and {NIQE_BLOCK // 2}")
+    _refuse(Hc % block == 0 and Wc % block == 0 and Hc and Wc, f"niqe_moments: the plane of {Hc}x{Wc} is not made of {block}x{block} blocks")
+    _refuse(window.dtype == torch.float64 and window.is_contiguous() and tuple(window.shape) == (7, 7),
+            f"niqe_moments: window is a dense (7, 7) float64 tensor, got {tuple(window.shape)} {window.dtype}")
+    shape = (N, (Hc // block) * (Wc // block), 5, 5)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=y.device)
+    _refuse(out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == shape, f"niqe_moments: out is a dense {shape} float64 tensor")
+    _refuse(mscn is None or (mscn.dtype == torch.float64 and mscn.is_contiguous() and tuple(mscn.shape) == (N, Hc, Wc)),
+            f"niqe_moments: mscn is a dense {(N, Hc, Wc)} float64 tensor")
+    call.flair_niqe_moments(y, N, Hc, Wc, int(block), float(inv_scale), window, out, mscn)
+    return out
+
+
 # --------------------------------------------------------------------------- scene cuts (scenes.hip)
 def block_luma_sums(u8, out=None):
     """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB
