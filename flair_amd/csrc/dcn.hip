@@ -98,9 +98,11 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // DOT2 (bf16, round 4): the four-corner blend on v_dot2c_f32_bf16 -- corner pairs of one channel packed by v_perm_b32 against the
 // pair of bilinear weights rounded to bf16 (f32 accumulation): 38 vector instructions per 8 channels instead of 52 (32 bf16 -> f32
 // unpacks + 16 v_pk_fma_f32, which issue at 1.4x the cost of a plain instruction: tools/probes/valu_rate_probe.hip).  The weights lose
-// 16 mantissa bits: |error| <= 2^-9 * sum_k |w_k v_k| <= 2^-9 max|v| per blended value, the size of the bf16 rounding the value gets
-// anyway when it is staged for the MFMA.  Used by the bf16 per-frame activated forms (ACTIVATED && ONEFRAME); the other bf16 forms
-// and f32 tensors keep the exact path.
+// 16 mantissa bits: |error| <= 2^-8 * sum_k |w_k v_k| <= 2^-8 max|v| per blended value (round to nearest moves a weight by half a unit
+// in the last place: 2^-8 of it at the bottom of a binade, 2^-9 only at the top), the size of the bf16 rounding the value gets anyway when
+// it is staged for the MFMA; weights on a grid of 1/32 (quarter-pixel positions, masks 0, 0.5, 1) are exact.  Both statements are tested:
+// tests/test_gpu_dcn_frac.py.  Used by the bf16 per-frame activated forms (ACTIVATED && ONEFRAME); the other bf16 forms and f32 tensors
+// keep the exact path.
 // PFD = gather register sets in flight (2: the loads of step k+1 fly while step k is blended; 3: also step k+2 --
 // for the c = 128 tiles, where only 8 wavefronts per CU exist to hide the gather round trip; 1 (round 4, the c = 64 per-frame form): the
 // loads of a step are waited for in the same step, at 64 VGPRs, and a SECOND workgroup on the CU hides them).
