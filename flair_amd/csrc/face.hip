@@ -14,16 +14,29 @@
 // coordinates with 10 + 5 fractional bits, 32 x 32 table of a = -0.75 cubic weights held in float, the
 // BORDER_CONSTANT edge rule; filter.simd.hpp: RowFilter / SymmColumnFilter summation order, BORDER_REFLECT_101);
 // cv2 is not installable here and the reference holds no fixture for it: PARITY UNPINNED (oracle/facewarp.py is the
-// same restatement in numpy).  Floating-point contraction is off in this file so that sums round like the scalar C code.
+// same restatement in numpy).  Sums must round like the scalar C code: no product may contract into the sum that follows.
+// The pragma below is not enough for that -- the library is compiled with -ffp-contract=fast, and under that flag the
+// backend fuses a multiply into an add whatever the front end marked -- so every product that feeds a sum or a
+// difference goes through unfused() (tests/test_gpu_face_exact.py compares with numpy, which never contracts).
 #include "common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+// The value itself, behind an empty asm statement that the instruction selector cannot look through: the product
+// is rounded on its own and the add that consumes it stays an add.  No instruction is emitted for it.
+template <typename T>
+__device__ __forceinline__ T unfused(T v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
 constexpr int INTER_BITS = 5, INTER_TAB = 1 << INTER_BITS, AB_BITS = 10;
 
-// imgwarp.cpp interpolateCubic (A = -0.75), evaluated in float like initInterTab1D does
+// imgwarp.cpp interpolateCubic (A = -0.75), evaluated in float like initInterTab1D does.  x is a multiple of 1/32, so
+// every intermediate below is a dyadic rational of a few bits that f32 holds exactly: contraction cannot change a weight
+// (tests/face_ref.py cubic_table asserts it step by step), and the products here need no unfused()
 __device__ __forceinline__ void cubic_coeffs(float x, float (&c)[4]) {
 #pragma clang fp contract(off)
     const float A = -0.75f;
@@ -41,8 +54,8 @@ __device__ __forceinline__ void affine_taps(const double* M, int x, int y, int& 
     const int round_delta = (1 << AB_BITS) / INTER_TAB / 2;
     // cvRound = round-half-to-even, as rint in the default rounding mode
     const int adelta = (int)rint(M[0] * x * ABS), bdelta = (int)rint(M[3] * x * ABS);
-    const int X0 = (int)rint((M[1] * y + M[2]) * ABS) + round_delta;
-    const int Y0 = (int)rint((M[4] * y + M[5]) * ABS) + round_delta;
+    const int X0 = (int)rint((unfused(M[1] * y) + M[2]) * ABS) + round_delta;
+    const int Y0 = (int)rint((unfused(M[4] * y) + M[5]) * ABS) + round_delta;
     const int X = (X0 + adelta) >> (AB_BITS - INTER_BITS), Y = (Y0 + bdelta) >> (AB_BITS - INTER_BITS);
     sx = X >> INTER_BITS;
     sy = Y >> INTER_BITS;
@@ -73,7 +86,7 @@ __device__ __forceinline__ T cubic_sample(const T* P, int Hs, int Ws, int sx, in
         T v = P[off];
         if (pre) {                                               // VF.normalize(x, [-1]*3, [2]*3).clamp(0, 1) * 255
             float f = ((float)v + 1.f) / 2.f;
-            f = fminf(fmaxf(f, 0.f), 1.f) * 255.f;
+            f = unfused(fminf(fmaxf(f, 0.f), 1.f) * 255.f);      // the caller subtracts the border value from it
             v = (T)f;
         }
         return v;
@@ -87,9 +100,9 @@ __device__ __forceinline__ T cubic_sample(const T* P, int Hs, int Ws, int sx, in
         sum = 0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            T row = fetch((long)(sy + r) * Ws + sx) * (T)(cy[r] * cx[0]);
+            T row = unfused(fetch((long)(sy + r) * Ws + sx) * (T)(cy[r] * cx[0]));
 #pragma unroll
-            for (int c = 1; c < 4; ++c) row = row + fetch((long)(sy + r) * Ws + sx + c) * (T)(cy[r] * cx[c]);
+            for (int c = 1; c < 4; ++c) row = row + unfused(fetch((long)(sy + r) * Ws + sx + c) * (T)(cy[r] * cx[c]));
             sum = r == 0 ? row : sum + row;
         }
     } else {
@@ -101,7 +114,7 @@ __device__ __forceinline__ T cubic_sample(const T* P, int Hs, int Ws, int sx, in
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int xi = sx + c;
-                if ((unsigned)xi < (unsigned)Ws) sum += (fetch((long)yi * Ws + xi) - cv) * (T)(cy[r] * cx[c]);
+                if ((unsigned)xi < (unsigned)Ws) sum += unfused((fetch((long)yi * Ws + xi) - cv) * (T)(cy[r] * cx[c]));
             }
         }
     }
@@ -177,7 +190,7 @@ __global__ __launch_bounds__(256) void face_paste_kernel(const float* x0, int C,
         for (int k = 0; k < 4; ++k) {
             if (k < C) {
                 const float s = cubic_sample<float>(faces + ((long)f * C + k) * fp, h, w, sx, sy, cx, cy, 0.f, 1, inner, false);
-                v[k] = v[k] * (1.f - m) + warp_post(s, 1) * m;
+                v[k] = unfused(v[k] * (1.f - m)) + unfused(warp_post(s, 1) * m);
             }
         }
     }
@@ -213,7 +226,7 @@ __global__ __launch_bounds__(256) void blur_row_kernel(const double* in, const i
         } else {
             v = in[row * W + xi];
         }
-        const double t = kern[k] * v;
+        const double t = unfused(kern[k] * v);
         s = k == 0 ? t : s + t;
     }
     out[i] = s;
@@ -230,11 +243,11 @@ __global__ __launch_bounds__(256) void blur_col_kernel(const double* in, const d
     const int y = (int)((i / W) % H);
     const long base = (i / ((long)W * H)) * (long)W * H;
     const int r = ksize / 2;
-    double s = kern[r] * in[base + (long)y * W + x];
+    double s = unfused(kern[r] * in[base + (long)y * W + x]);
     for (int k = 1; k <= r; ++k) {
         const double a = in[base + (long)reflect101(y + k, H) * W + x];
         const double b = in[base + (long)reflect101(y - k, H) * W + x];
-        s += kern[r + k] * (a + b);
+        s += unfused(kern[r + k] * (a + b));
     }
     if (edge >= 0) {
         if (y < edge || y >= H - edge || x < edge || x >= W - edge) s = 0;
@@ -249,7 +262,7 @@ __global__ __launch_bounds__(256) void face_blend_kernel(const float* x0, const 
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long n = i / (C * plane), p = i % plane;
         const float m = mask[n * plane + p];
-        out[i] = x0[i] * (1.f - m) + face[i] * m;
+        out[i] = unfused(x0[i] * (1.f - m)) + unfused(face[i] * m);
     }
 }
 

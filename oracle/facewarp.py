@@ -16,8 +16,10 @@ restates OpenCV's published algorithms in numpy, function by function:
     X = (cvRound((M01 y + M02) 2^10) + 16 + cvRound(M00 x 2^10)) >> 5 (5 fractional bits; cvRound = round half to even),
     integer part -1 is the first of 4 taps, the fractional part indexes a 32-entry table of cubic weights (a = -0.75)
     evaluated in float; the 16 2-D weights are float products cy[r] * cx[c]; float images accumulate in float, double
-    images in double, tap by tap in row-major order; BORDER_CONSTANT: a window completely outside gives the border
-    value, a partial window starts from the border value and adds (S - border) * w for the taps inside;
+    images in double; a window completely inside the image sums the four taps of a row first (left to right) and then
+    adds the row sum to the running sum (remapBicubic), which rounds differently from 16 sequential adds;
+    BORDER_CONSTANT: a window completely outside gives the border value, a partial window starts from the border value
+    and adds (S - border) * w for the taps inside, tap by tap in row-major order;
   * ``cv2.getGaussianKernel(101, 26)`` (exp(-x^2 / (2 sigma^2)) normalised in double) and ``cv2.GaussianBlur`` as a
     separable float64 filter with BORDER_REFLECT_101: rows sum_k k[k] S[i + k] in ascending k, columns
     k[c] S[c] + sum_{j >= 1} k[c + j] (S[c + j] + S[c - j]) (filter.simd.hpp RowFilter / SymmColumnFilter).
