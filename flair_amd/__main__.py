@@ -4,6 +4,7 @@ operator the restoration assumes (flair_amd.degrade), and ``evaluate RESTORED_DI
 and SSIM (flair_amd.metrics) and, with ``--lpips {vgg,alex} --weights DIR``, LPIPS (flair_amd.lpips); ``restore --ground-truth
 DIR`` scores every video as soon as it is written.  ``niqe FRAMES_DIR --params FILE`` scores frames that have no ground truth
 (flair_amd.niqe); ``--niqe FILE`` adds that score to evaluate, restore and interpolate, the last two with or without ground truth.
+``--identity FILE`` adds the ArcFace identity similarity and drift (flair_amd.identity) wherever there is ground truth.
 ``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo or AMT-G (flair_amd.interpolate).
 ``scenes SRC_DIR --json PATH`` finds the hard cuts of a video (flair_amd.scenes); ``restore`` / ``interpolate --scene-cuts
 auto|PATH`` then treat every shot on its own.
@@ -84,6 +85,46 @@ def _add_niqe(p, what):
                         "must hold at least two 96x96 blocks")
 
 
+def _add_identity(p, what):
+    p.add_argument("--identity", default=None, metavar="FILE",
+                   help=f"{what} the ArcFace identity similarity of every frame with its truth (ids, a cosine: higher is closer) "
+                        "and the identity drift from frame to frame of both sets; FILE is GFPGAN's / VQFR's arcface_resnet18.pth.  "
+                        "Frames are taken as aligned face crops and must be square: faces are not detected.  Scene cuts are not "
+                        "consulted: a cut shows up as drift")
+
+
+def identity_of(args, command):
+    """The checkpoint of a parsed command line's --identity, or None without it; refused before any GPU work where there is no
+    ground truth to compare with or it is not a file."""
+    path = getattr(args, "identity", None)
+    if path is None:
+        return None
+    if command != "evaluate" and not args.ground_truth:
+        raise SystemExit(f"{command}: --identity compares the written frames with --ground-truth DIR; give one")
+    if not os.path.isfile(path):
+        raise SystemExit(f"{command}: --identity {path} is not a file (GFPGAN's / VQFR's arcface_resnet18.pth)")
+    return path
+
+
+def load_identity_of(path, device, command):
+    """The ArcFace model of identity_of's result on ``device`` (None for None)."""
+    if path is None:
+        return None
+    from . import identity as fid
+    try:
+        return fid.load_identity(path, device)
+    except (ValueError, FileNotFoundError) as exc:
+        raise SystemExit(f"{command}: {exc}")
+
+
+def identity_tail(result):
+    """``  ids X  id-drift Y (truth Z)`` of a result's mean where it holds them ('' without --identity)."""
+    if "ids" not in result["mean"]:
+        return ""
+    from .identity import format_mean
+    return format_mean(result["mean"])
+
+
 def niqe_of(args, command, option="--niqe"):
     """The parameter file of a parsed command line's --niqe (--params of the niqe command), or None without it; refused
     before any GPU work where it is not a file."""
@@ -162,6 +203,7 @@ def make_parser():
                         "after a video is written, log its mean PSNR / SSIM and write metrics.json next to the frames")
     _add_lpips(r, "with --ground-truth: also score", "; the files are read from --weights")
     _add_niqe(r, "after a video is written, log its mean and write into metrics.json")
+    _add_identity(r, "with --ground-truth: also score")
     _add_hparams(r, pl.MAIN_DEFAULTS)
     _add_common(r)
     for name, demo in pl.DEMOS.items():
@@ -187,6 +229,7 @@ def make_parser():
     _add_lpips(e, "also score", "")
     e.add_argument("--weights", default=None, metavar="DIR", help="with --lpips: the directory that holds those files")
     _add_niqe(e, "also report")
+    _add_identity(e, "also report")
     q = sub.add_parser("niqe", help="no-reference NIQE of written frames: one line per frame and the mean")
     q.add_argument("frames_dir", metavar="FRAMES_DIR", help="frames of at least two 96x96 blocks each")
     q.add_argument("--params", default=None, metavar="FILE", help="BasicSR's niqe_pris_params.npz (required)")
@@ -207,6 +250,7 @@ def make_parser():
     i.add_argument("--json", default=None, metavar="PATH", help="with --ground-truth or --niqe: also write the values as JSON")
     _add_lpips(i, "with --ground-truth: also score", "; the files are read from --weights")
     _add_niqe(i, "also report")
+    _add_identity(i, "with --ground-truth: also report")
     _add_cut_options(i, "synthesise nothing between the two frames of a cut: the in-betweens there are copies of the nearer "
                         "frame (--min-shot keeps its default of 4 here too)")
     s = sub.add_parser("scenes", help="find the hard cuts of a video (block-luma distances; heuristic defaults, not validated "
@@ -293,6 +337,7 @@ def interpolate_of(args):
         raise SystemExit(f"interpolate: ground truth {args.ground_truth} is not a directory")
     lpips_of(args, "interpolate")
     niqe_of(args, "interpolate")
+    identity_of(args, "interpolate")
     return paths
 
 
@@ -318,8 +363,10 @@ def _interpolate(args):
     if args.ground_truth:
         from . import metrics as fm
         model = load_lpips_of(lpips_of(args, "interpolate"), device, "interpolate")
+        ident = load_identity_of(identity_of(args, "interpolate"), device, "interpolate")
         try:
-            result = fm.evaluate_dirs(args.out_dir, args.ground_truth, device, **({} if model is None else dict(lpips=model)), **niqe_kw)
+            result = fm.evaluate_dirs(args.out_dir, args.ground_truth, device, **({} if model is None else dict(lpips=model)), **niqe_kw,
+                                      **({} if ident is None else dict(identity=ident)))
         except ValueError as exc:
             raise SystemExit(str(exc))
         for line in fm.format_report(result):
@@ -410,14 +457,16 @@ def write_json(path, result):
 def _evaluate(args):
     spec = lpips_of(args, "evaluate")
     niqe_path = niqe_of(args, "evaluate")
+    ident_path = identity_of(args, "evaluate")
     import torch
     from . import metrics as fm
     torch.set_grad_enabled(False)
     model = load_lpips_of(spec, args.device or "cuda", "evaluate")
     niqe = load_niqe_of(niqe_path, args.device or "cuda", "evaluate")
+    ident = load_identity_of(ident_path, args.device or "cuda", "evaluate")
     try:
         result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda", **({} if model is None else dict(lpips=model)),
-                                  **({} if niqe is None else dict(niqe=niqe)))
+                                  **({} if niqe is None else dict(niqe=niqe)), **({} if ident is None else dict(identity=ident)))
     except ValueError as exc:
         raise SystemExit(str(exc))
     for line in fm.format_report(result):
@@ -505,6 +554,7 @@ def main(argv=None):
     truth = truth_of(args, jobs)
     lpips_spec = lpips_of(args, "restore")
     niqe_path = niqe_of(args, "restore")
+    ident_path = identity_of(args, "restore")
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
@@ -537,6 +587,9 @@ def main(argv=None):
         niqe_model = load_niqe_of(niqe_path, device, "restore")
         if niqe_model is not None:
             score_kw["niqe"] = niqe_model
+        ident_model = load_identity_of(ident_path, device, "restore")
+        if ident_model is not None:
+            score_kw["identity"] = ident_model
 
         def restore_one(v, o):
             n = p.restore_video_files(v, o, **hp)
@@ -545,7 +598,7 @@ def main(argv=None):
                 result = fm.evaluate_dirs(o, truth[o], device, **score_kw)
                 print(f"{o}: mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  "
                       f"ssim {result['mean']['ssim']:.4f}" + (f"  lpips {result['mean']['lpips']:.4f}" if lpips_model is not None else "")
-                      + niqe_tail(result))
+                      + niqe_tail(result) + identity_tail(result))
                 write_json(os.path.join(o, "metrics.json"), result)
             elif niqe_model is not None:                # footage without a clean original: the no-reference score alone
                 from . import niqe as fnq

@@ -2,8 +2,8 @@
 
 The header is the contract with libflair_hip.so; nothing of it is restated in Python.  ``STRUCTS`` maps a C struct name to
 a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``; ``EVAL_PROTOS`` is the same table
-of include/flair_eval.h, the evaluation-only entries of the same library, and ``NOREF_PROTOS`` that of include/flair_noref.h,
-the no-reference scores.  Only the constructs the header uses
+of include/flair_eval.h, the evaluation-only entries of the same library, ``NOREF_PROTOS`` that of include/flair_noref.h,
+the no-reference scores, and ``IDENT_PROTOS`` that of include/flair_ident.h, the identity score.  Only the constructs the header uses
 are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
 """
 import collections
@@ -112,3 +112,11 @@ with open(NOREF_HEADER_PATH) as _f:
 if _noref_structs or set(NOREF_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS)):
     raise HeaderError("flair_noref.h declares a struct or an entry of another header: "
                       f"{sorted(_noref_structs) + sorted(set(NOREF_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS)))}")
+
+# The identity ABI (include/flair_ident.h: ArcFace similarity), on the same terms once more.
+IDENT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "flair_ident.h")
+with open(IDENT_HEADER_PATH) as _f:
+    _ident_structs, IDENT_PROTOS = parse(_f.read())
+if _ident_structs or set(IDENT_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS) | set(NOREF_PROTOS)):
+    raise HeaderError("flair_ident.h declares a struct or an entry of another header: "
+                      f"{sorted(_ident_structs) + sorted(set(IDENT_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS) | set(NOREF_PROTOS)))}")

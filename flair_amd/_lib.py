@@ -1,5 +1,5 @@
 """ctypes binding of libflair_hip.so, derived from the C ABI's own headers (include/flair_hip.h, the evaluation-only
-include/flair_eval.h and the no-reference include/flair_noref.h, read by _header.py).
+include/flair_eval.h, the no-reference include/flair_noref.h and the identity score's include/flair_ident.h, read by _header.py).
 
 The library is the product path: there is no CPU or PyTorch fallback.  Loading fails
 loudly (``FlairHipUnavailable``) when the shared object has not been built.  ``lib()`` is the
@@ -12,11 +12,13 @@ import os
 
 import torch  # noqa: F401  (must be imported first: the library binds to torch's HIP runtime)
 
-from ._header import EVAL_PROTOS, NOREF_PROTOS, PROTOS, STRUCTS
+from ._header import EVAL_PROTOS, IDENT_PROTOS, NOREF_PROTOS, PROTOS, STRUCTS
 
 # every declared entry of the library: the sampling path's (flair_hip.h), the evaluation-only ones (flair_eval.h) and the
 # no-reference scores (flair_noref.h)
 ALL_PROTOS = {**PROTOS, **EVAL_PROTOS, **NOREF_PROTOS}
+# ... and the identity score's (flair_ident.h), typed and launched like the others from a table of its own
+_TYPED_PROTOS = {**ALL_PROTOS, **IDENT_PROTOS}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libflair_hip.so")
@@ -51,7 +53,7 @@ def lib():
                 f"g.build()'` (or `make -C flair_amd/csrc`). The HIP library is required; "
                 f"there is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (restype, params) in ALL_PROTOS.items():
+        for name, (restype, params) in _TYPED_PROTOS.items():
             f = getattr(l, name)
             f.restype, f.argtypes = restype, [p.ctype for p in params]
         _lib = l
@@ -94,7 +96,7 @@ _ELEM_DTYPE = {"float": torch.float32, "double": torch.float64, "int": torch.int
                "long long": torch.int64}
 _LAUNCHES = {name: [(i, p.name, _ELEM_DTYPE.get(p.elem)) for i, p in enumerate(params[:-1])
                     if p.elem is not None and p.ctype is ctypes.c_void_p]
-             for name, (restype, params) in ALL_PROTOS.items()
+             for name, (restype, params) in _TYPED_PROTOS.items()
              if restype is ctypes.c_int and params and params[-1].name == "stream"}
 
 
@@ -122,7 +124,7 @@ class _Entries:
 
     def __getattr__(self, name):
         if name not in _LAUNCHES:
-            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream, nor one of flair_eval.h or flair_noref.h")
+            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream, nor one of flair_eval.h, flair_noref.h or flair_ident.h")
         return functools.partial(_launch, name)
 
 

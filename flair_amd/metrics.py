@@ -1,5 +1,6 @@
-"""PSNR, SSIM and (on request) LPIPS of written frames against ground truth, and (on request) their no-reference NIQE, on
-the GPU (``flair_image_metrics``, csrc/metrics.hip; ``flair_amd.lpips``, csrc/lpips.hip; ``flair_amd.niqe``, csrc/niqe.hip).
+"""PSNR, SSIM and (on request) LPIPS of written frames against ground truth, and (on request) their no-reference NIQE and
+their ArcFace identity similarity, on the GPU (``flair_image_metrics``, csrc/metrics.hip; ``flair_amd.lpips``, csrc/lpips.hip;
+``flair_amd.niqe``, csrc/niqe.hip; ``flair_amd.identity``, csrc/ident.hip).
 
 The reference ships no scoring tool; this is the restoration literature's usual pair, on the bytes that get written
 (float images go through ``io.to_bytes`` first, so a metric always describes the files):
@@ -15,8 +16,11 @@ The reference ships no scoring tool; this is the restoration literature's usual 
   * ``niqe``, only with a model from ``flair_amd.niqe.load_niqe``: the no-reference NIQE of the RESTORED frames (the truth is
     not scored), as restated in include/flair_noref.h; ``flair_amd.niqe.niqe_dir`` scores a directory without any truth.
 
+  * ``ids``, only with a model from ``flair_amd.identity.load_identity``: the cosine of the ArcFace embeddings of a restored
+    frame and its truth, as restated in include/flair_ident.h, with the identity drift from frame to frame of both sets.
+
 Not measured: the Y-channel and border-cropped variants of PSNR / SSIM, NIQE's colour and border-cropped variants, other
-no-reference scores (BRISQUE, PI), identity and temporal metrics.
+no-reference scores (BRISQUE, PI), temporal metrics other than the identity drift.
 """
 import math
 import os
@@ -75,7 +79,7 @@ def _groups(sizes, batch):
     return groups
 
 
-def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=None):
+def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=None, identity=None):
     """Score the frames of ``restored_dir`` against those of ``truth_dir``, paired in ``io.list_frames`` order:
     ``dict(frames=[{name, psnr, ssim}], mean={psnr, ssim}, count)``; the means are those of the per-frame values.
     ValueError when a directory is empty, the counts differ, a pair differs in size or is smaller than 11 pixels a side
@@ -84,7 +88,9 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
     then gain ``lpips``, and frames below the trunk's minimum are refused with the others (without one the result is what
     it was before the option existed).  ``niqe``: a ``flair_amd.niqe.NIQE`` model; every frame dict then gains ``niqe`` of the
     restored frame (None where it has no score) and ``mean`` gains ``niqe``, over the ``niqe_frames`` frames that have one;
-    frames with fewer than two 96 x 96 blocks are refused with the others."""
+    frames with fewer than two 96 x 96 blocks are refused with the others.  ``identity``: a ``flair_amd.identity.ArcFace``
+    model; every frame dict then gains ``ids`` (None where an embedding is zero) and ``mean`` gains ``ids``, ``id_drift`` and
+    ``id_drift_truth``; every frame goes through the network once, and frames that are not square are refused with the others."""
     ra, rb, sizes = _pairs(restored_dir, truth_dir)
     if niqe is not None:
         from . import niqe as fnq
@@ -94,7 +100,11 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
         from . import lpips as flp
         for pa, pb, (h, w) in zip(ra, rb, sizes):
             flp.check_size(lpips.net, h, w, what=f"evaluate: {pa} and {pb}")
-    frames = []
+    if identity is not None:
+        from . import identity as fid
+        for pa, (h, w) in zip(ra, sizes):
+            fid.check_size(h, w, what=f"evaluate: {pa}")
+    frames, emb_a, emb_b = [], [], []
     for first, (a, b) in fio.iter_frame_batches([ra, rb], _groups(sizes, max(1, int(batch))), device):
         got = psnr_ssim(a, b)
         for i, (p, s) in enumerate(zip(got["psnr"], got["ssim"])):
@@ -105,23 +115,36 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
         if niqe is not None:
             for i, v in enumerate(niqe(a)):
                 frames[first + i]["niqe"] = None if math.isnan(v) else v
+        if identity is not None:
+            e = identity.embed(a, b)
+            emb_a += list(e[:a.shape[0]])
+            emb_b += list(e[a.shape[0]:])
     n = len(frames)
     mean = dict(psnr=sum(f["psnr"] for f in frames) / n, ssim=sum(f["ssim"] for f in frames) / n)
     if lpips is not None:
         mean["lpips"] = sum(f["lpips"] for f in frames) / n
     if niqe is not None:
         mean.update(fnq.mean_of([f["niqe"] for f in frames]))
+    if identity is not None:
+        ids, id_mean = fid.scores(emb_a, emb_b)
+        for f, v in zip(frames, ids):
+            f["ids"] = v
+        mean.update(id_mean)
     return dict(frames=frames, mean=mean, count=n)
 
 
 def format_report(result):
-    """One line per frame and the means, four decimals each (``lpips``, then ``niqe``, where the result holds them; ``niqe
-    n/a`` for a frame without a score, which the mean leaves out)."""
+    """One line per frame and the means, four decimals each (``lpips``, then ``niqe``, then ``ids``, where the result holds
+    them; ``niqe n/a`` / ``ids n/a`` for a frame without a score, which the mean leaves out; the means' line ends with the
+    identity drift of the restored frames and, in brackets, of the truth)."""
     def tail(d):
         text = f"  lpips {d['lpips']:.4f}" if "lpips" in d else ""
         if "niqe" in d:
             from .niqe import format_value
             text += format_value(d["niqe"])
+        if "ids" in d:
+            from . import identity as fid
+            text += fid.format_mean(d) if "id_drift" in d else fid.format_value(d["ids"])
         return text
     lines = [f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" + tail(f) for f in result["frames"]]
     lines.append(f"mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  ssim {result['mean']['ssim']:.4f}"

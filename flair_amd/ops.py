@@ -1145,6 +1145,48 @@ def niqe_moments(y, block, inv_scale, window, out=None, mscn=None):
     return out
 
 
+# --------------------------------------------------------------------------- ArcFace identity (ident.hip, include/flair_ident.h)
+IDENT_SIDE = 128                            # FLAIR_IDENT_SIDE: the network's input is 1 x 128 x 128
+IDENT_EMBED_KCHUNK = 1024                   # FLAIR_IDENT_EMBED_KCHUNK: inputs per workgroup, the embed kernel's workspace in closed form
+
+
+def ident_prepare(a, b=None, out=None):
+    """One or two (N, H, W, 3) uint8 frame sets -> one (F, 128, 128, 16) f32 clip tensor (flair_ident_prepare), F = N without b
+    and 2 N with it (a's frames first): channel 0 = the bilinear 128 x 128 resize of 0.2989 R + 0.5870 G + 0.1140 B on
+    2 byte / 255 - 1, in double and rounded once; channels 1 .. 15 = 0.  a, b: dense, on the GPU, at any byte alignment; out:
+    optional (F, 128, 128, >= 16) view."""
+    _refuse(a.dim() == 4 and a.shape[3] == 3 and (b is None or tuple(a.shape) == tuple(b.shape)),
+            f"ident_prepare: (N, H, W, 3) frame sets of one shape, got {tuple(a.shape)}" + ("" if b is None else f" and {tuple(b.shape)}"))
+    _refuse(a.dtype == torch.uint8 and (b is None or b.dtype == torch.uint8), "ident_prepare: uint8 frames")
+    _refuse(a.is_contiguous() and (b is None or b.is_contiguous()), "ident_prepare: dense (contiguous) frames")
+    N, H, W, _ = a.shape
+    F_ = N if b is None else 2 * N
+    if out is None:
+        out = torch.empty((F_, IDENT_SIDE, IDENT_SIDE, 16), dtype=torch.float32, device=a.device)
+    _refuse(tuple(out.shape[:3]) == (F_, IDENT_SIDE, IDENT_SIDE), f"ident_prepare: out holds {tuple(out.shape[:3])} pixels, not {(F_, IDENT_SIDE, IDENT_SIDE)}")
+    call.flair_ident_prepare(a, b, N, H, W, out, _ld(out))
+    return out
+
+
+def ident_embed(x, w, bias, out=None):
+    """out[f][o] = bias[o] + sum_k w[o][k] x[f][k] with float64 products and sums, rounded to f32 once (flair_ident_embed).
+    x: (F, K) f32 rows (any row stride), K a multiple of 4; w: (O, K) f32 dense; bias: (O,) f32; out: optional (F, O) f32 rows.
+    The same bits in every run, for every F and every position in the batch."""
+    _refuse(x.dim() == 2 and x.stride(1) == 1, f"ident_embed: x is (F, K) rows of floats, got {tuple(x.shape)}")
+    F_, K = x.shape
+    _refuse(w.dim() == 2 and w.shape[1] == K and w.is_contiguous(), f"ident_embed: w is a dense (O, {K}) tensor, got {tuple(w.shape)}")
+    O = w.shape[0]
+    _refuse(bias.dim() == 1 and bias.shape[0] == O and bias.is_contiguous(), f"ident_embed: bias holds {O} values, got {tuple(bias.shape)}")
+    if out is None:
+        out = torch.empty((F_, O), dtype=torch.float32, device=x.device)
+    _refuse(out.dim() == 2 and tuple(out.shape) == (F_, O) and out.stride(1) == 1, f"ident_embed: out is ({F_}, {O}) rows of floats, got {tuple(out.shape)}")
+    nbytes = -(-K // IDENT_EMBED_KCHUNK) * F_ * O * 8
+    ws = _workspace(nbytes, x.device, tag="ident")
+    call.flair_ident_embed(x, x.stride(0) if F_ > 1 else max(x.stride(0), K), F_, K, w, bias, O, out,
+                           out.stride(0) if F_ > 1 else max(out.stride(0), O), ws, nbytes)
+    return out
+
+
 # --------------------------------------------------------------------------- scene cuts (scenes.hip)
 def block_luma_sums(u8, out=None):
     """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB
