@@ -5,6 +5,8 @@ and SSIM (flair_amd.metrics) and, with ``--lpips {vgg,alex} --weights DIR``, LPI
 DIR`` scores every video as soon as it is written.  ``niqe FRAMES_DIR --params FILE`` scores frames that have no ground truth
 (flair_amd.niqe); ``--niqe FILE`` adds that score to evaluate, restore and interpolate, the last two with or without ground truth.
 ``--identity FILE`` adds the ArcFace identity similarity and drift (flair_amd.identity) wherever there is ground truth.
+``--warp-error FILE`` adds the flow-warping error, the temporal consistency of the written frames (flair_amd.temporal), to
+evaluate, restore and interpolate, and ``warp-error FRAMES_DIR --flow-weights FILE`` scores footage that has no ground truth.
 ``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo or AMT-G (flair_amd.interpolate).
 ``scenes SRC_DIR --json PATH`` finds the hard cuts of a video (flair_amd.scenes); ``restore`` / ``interpolate --scene-cuts
 auto|PATH`` then treat every shot on its own.
@@ -91,6 +93,59 @@ def _add_identity(p, what):
                         "and the identity drift from frame to frame of both sets; FILE is GFPGAN's / VQFR's arcface_resnet18.pth.  "
                         "Frames are taken as aligned face crops and must be square: faces are not detected.  Scene cuts are not "
                         "consulted: a cut shows up as drift")
+
+
+WARP_FILE = "a bare mmedit SPyNet state dict or any FLAIR task checkpoint (flair_<task>.pt), which holds one"
+
+
+def _add_warp_error(p, what):
+    p.add_argument("--warp-error", default=None, metavar="FILE",
+                   help=f"{what} the flow-warping error of every two consecutive written frames (warp-err, printed x 10^3: lower "
+                        "is steadier; Lai et al. 2018 with the occlusion mask of Ruder et al. 2016, on SPyNet flows) and the "
+                        f"masked-out share; FILE is {WARP_FILE}.  With ground truth the flows and the mask come from the truth "
+                        "and the truth's own value is printed in brackets; without it they come from the written frames.  "
+                        "Frames must be at least 32 pixels a side; pairs across a scene cut are left out")
+
+
+def warp_of(args, command, option="--warp-error"):
+    """The flow weights of a parsed command line's --warp-error (--flow-weights of the warp-error command), or None without
+    it; refused before any GPU work where it is not a file."""
+    path = getattr(args, "warp_error" if option == "--warp-error" else "flow_weights", None)
+    if path is None:
+        return None
+    if not os.path.isfile(path):
+        raise SystemExit(f"{command}: {option} {path} is not a file ({WARP_FILE})")
+    return path
+
+
+def load_warp_of(path, device, command):
+    """The WarpError model of warp_of's result on ``device`` (None for None)."""
+    if path is None:
+        return None
+    from . import temporal as ftm
+    try:
+        return ftm.WarpError(ftm.load_flow(path, device))
+    except (ValueError, FileNotFoundError) as exc:
+        raise SystemExit(f"{command}: {exc}")
+
+
+def warp_tail(result):
+    """``  warp-err X (truth Y)  masked Z`` of a result's mean where it holds them ('' without --warp-error)."""
+    if "warp_err" not in result["mean"]:
+        return ""
+    from .temporal import format_mean
+    return format_mean(result["mean"])
+
+
+def warp_skip_of(scene_cuts, cut_rule, paths, device, command, factor=1):
+    """The ``warp_skip`` argument of evaluate_dirs: the later frames of the pairs that straddle a cut of ``paths`` (``factor``:
+    the frames scored are interpolate's output at that multiple of ``paths``' rate)."""
+    from . import temporal as ftm
+    try:
+        cuts, _ = scenes.resolve(scene_cuts, paths, device, **cut_rule)
+    except (ValueError, OSError) as exc:
+        raise SystemExit(f"{command}: {exc}")
+    return ftm.straddling(cuts, factor)
 
 
 def identity_of(args, command):
@@ -204,6 +259,7 @@ def make_parser():
     _add_lpips(r, "with --ground-truth: also score", "; the files are read from --weights")
     _add_niqe(r, "after a video is written, log its mean and write into metrics.json")
     _add_identity(r, "with --ground-truth: also score")
+    _add_warp_error(r, "after a video is written, log and write into metrics.json")
     _add_hparams(r, pl.MAIN_DEFAULTS)
     _add_common(r)
     for name, demo in pl.DEMOS.items():
@@ -230,6 +286,15 @@ def make_parser():
     e.add_argument("--weights", default=None, metavar="DIR", help="with --lpips: the directory that holds those files")
     _add_niqe(e, "also report")
     _add_identity(e, "also report")
+    _add_warp_error(e, "also report")
+    _add_cut_options(e, "with --warp-error: leave out the frame pairs that straddle a cut of TRUTH_DIR")
+    w = sub.add_parser("warp-error", help="flow-warping error (temporal consistency) of written frames without ground truth: one "
+                                          "line per frame and the means")
+    w.add_argument("frames_dir", metavar="FRAMES_DIR", help="frames of at least 32 pixels a side")
+    w.add_argument("--flow-weights", default=None, metavar="FILE", help=f"{WARP_FILE} (required)")
+    w.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the means as JSON")
+    w.add_argument("--device", default=None, help="default: cuda")
+    _add_cut_options(w, "leave out the frame pairs that straddle a cut")
     q = sub.add_parser("niqe", help="no-reference NIQE of written frames: one line per frame and the mean")
     q.add_argument("frames_dir", metavar="FRAMES_DIR", help="frames of at least two 96x96 blocks each")
     q.add_argument("--params", default=None, metavar="FILE", help="BasicSR's niqe_pris_params.npz (required)")
@@ -247,10 +312,11 @@ def make_parser():
     i.add_argument("--device", default=None, help="default: cuda")
     i.add_argument("--ground-truth", default=None, metavar="DIR",
                    help="frames at the new rate: score the written frames against them (PSNR / SSIM)")
-    i.add_argument("--json", default=None, metavar="PATH", help="with --ground-truth or --niqe: also write the values as JSON")
+    i.add_argument("--json", default=None, metavar="PATH", help="with --ground-truth, --niqe or --warp-error: also write the values as JSON")
     _add_lpips(i, "with --ground-truth: also score", "; the files are read from --weights")
     _add_niqe(i, "also report")
     _add_identity(i, "with --ground-truth: also report")
+    _add_warp_error(i, "also report")
     _add_cut_options(i, "synthesise nothing between the two frames of a cut: the in-betweens there are copies of the nearer "
                         "frame (--min-shot keeps its default of 4 here too)")
     s = sub.add_parser("scenes", help="find the hard cuts of a video (block-luma distances; heuristic defaults, not validated "
@@ -331,13 +397,14 @@ def interpolate_of(args):
         fi.check_interpolator(args.interpolator, args.dtype, size)
     except ValueError as exc:
         raise SystemExit(f"interpolate: {exc}")
-    if args.json and not args.ground_truth and not args.niqe:
+    if args.json and not args.ground_truth and not args.niqe and not args.warp_error:
         raise SystemExit("interpolate: --json writes the scores of --ground-truth DIR")
     if args.ground_truth and not os.path.isdir(args.ground_truth):
         raise SystemExit(f"interpolate: ground truth {args.ground_truth} is not a directory")
     lpips_of(args, "interpolate")
     niqe_of(args, "interpolate")
     identity_of(args, "interpolate")
+    warp_of(args, "interpolate")
     return paths
 
 
@@ -360,21 +427,84 @@ def _interpolate(args):
     print(f"wrote {n} frames to {args.out_dir} ({args.factor}x the rate of {args.src_dir})")
     niqe = load_niqe_of(niqe_of(args, "interpolate"), device, "interpolate")
     niqe_kw = {} if niqe is None else dict(niqe=niqe)
+    warp = load_warp_of(warp_of(args, "interpolate"), device, "interpolate")
     if args.ground_truth:
         from . import metrics as fm
+        from . import temporal as ftm
         model = load_lpips_of(lpips_of(args, "interpolate"), device, "interpolate")
         ident = load_identity_of(identity_of(args, "interpolate"), device, "interpolate")
+        warp_kw = {} if warp is None else dict(warp_error=warp, warp_skip=ftm.straddling(cuts, args.factor))
         try:
             result = fm.evaluate_dirs(args.out_dir, args.ground_truth, device, **({} if model is None else dict(lpips=model)), **niqe_kw,
-                                      **({} if ident is None else dict(identity=ident)))
+                                      **({} if ident is None else dict(identity=ident)), **warp_kw)
         except ValueError as exc:
             raise SystemExit(str(exc))
         for line in fm.format_report(result):
             print(line)
         if args.json:
             write_json(args.json, result)
-    elif niqe is not None:
-        _report_niqe(args.out_dir, device, niqe, args.json, "interpolate")
+    elif niqe is not None or warp is not None:
+        result = None
+        if niqe is not None:
+            result = _report_niqe(args.out_dir, device, niqe, None, "interpolate")
+        if warp is not None:
+            from . import temporal as ftm
+            got = _report_warp(args.out_dir, device, warp, ftm.straddling(cuts, args.factor), None, "interpolate")
+            result = got if result is None else merge_results(result, got)
+        if args.json:
+            write_json(args.json, result)
+    return 0
+
+
+def merge_results(first, second):
+    """Two results of one directory (frames in the same order) as one: every frame dict and the means hold both's keys."""
+    return dict(frames=[dict(a, **b) for a, b in zip(first["frames"], second["frames"])], mean=dict(first["mean"], **second["mean"]),
+                count=first["count"])
+
+
+def _report_warp(frames_dir, device, model, skip, json_path, command):
+    """Score a directory by its own flows: one line per frame, the means, and the JSON file where one is asked for.  ``skip``:
+    the later frames of the pairs to leave out."""
+    from . import temporal as ftm
+    try:
+        result = ftm.warp_error_dir(frames_dir, device, model, skip=skip)
+    except ValueError as exc:                               # the messages name warp-error themselves
+        raise SystemExit(str(exc) if command == "warp-error" else f"{command}: {exc}")
+    for line in ftm.format_report(result):
+        print(line)
+    if json_path:
+        write_json(json_path, result)
+    return result
+
+
+def warp_error_of(args):
+    """The refusals of a parsed ``warp-error`` command line, before any GPU work -> (flow weights path, frame paths)."""
+    if args.flow_weights is None:
+        raise SystemExit(f"warp-error: --flow-weights FILE is required ({WARP_FILE}); nothing is shipped or downloaded")
+    path = warp_of(args, "warp-error", option="--flow-weights")
+    if not os.path.isdir(args.frames_dir):
+        raise SystemExit(f"warp-error: {args.frames_dir} is not a directory")
+    from . import io as fio
+    from . import temporal as ftm
+    paths = fio.list_frames(args.frames_dir)
+    if not paths:
+        raise SystemExit(f"warp-error: no frame files in {args.frames_dir}")
+    try:
+        for p in paths:
+            ftm.check_size(*fio.frame_size(p), what=p)
+    except ValueError as exc:
+        raise SystemExit(str(exc))
+    return path, paths
+
+
+def _warp_error(args):
+    path, paths = warp_error_of(args)
+    how = cuts_of(args, "warp-error", [args.frames_dir])
+    import torch
+    torch.set_grad_enabled(False)
+    device = args.device or "cuda"
+    skip = warp_skip_of(how["scene_cuts"], how["cut_rule"], paths, device, "warp-error")
+    _report_warp(args.frames_dir, device, load_warp_of(path, device, "warp-error"), skip, args.json, "warp-error")
     return 0
 
 
@@ -458,15 +588,24 @@ def _evaluate(args):
     spec = lpips_of(args, "evaluate")
     niqe_path = niqe_of(args, "evaluate")
     ident_path = identity_of(args, "evaluate")
+    warp_path = warp_of(args, "evaluate")
+    if warp_path is None and args.scene_cuts != "off":
+        raise SystemExit("evaluate: --scene-cuts only tells --warp-error FILE which frame pairs to leave out; give one")
+    how = cuts_of(args, "evaluate", [args.truth_dir]) if warp_path is not None else None
     import torch
     from . import metrics as fm
     torch.set_grad_enabled(False)
     model = load_lpips_of(spec, args.device or "cuda", "evaluate")
     niqe = load_niqe_of(niqe_path, args.device or "cuda", "evaluate")
     ident = load_identity_of(ident_path, args.device or "cuda", "evaluate")
+    warp_kw = {}
+    if warp_path is not None:
+        from . import io as fio
+        skip = warp_skip_of(how["scene_cuts"], how["cut_rule"], fio.list_frames(args.truth_dir), args.device or "cuda", "evaluate")
+        warp_kw = dict(warp_error=load_warp_of(warp_path, args.device or "cuda", "evaluate"), warp_skip=skip)
     try:
         result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda", **({} if model is None else dict(lpips=model)),
-                                  **({} if niqe is None else dict(niqe=niqe)), **({} if ident is None else dict(identity=ident)))
+                                  **({} if niqe is None else dict(niqe=niqe)), **({} if ident is None else dict(identity=ident)), **warp_kw)
     except ValueError as exc:
         raise SystemExit(str(exc))
     for line in fm.format_report(result):
@@ -550,11 +689,14 @@ def main(argv=None):
         return _scenes(args)
     if args.command == "niqe":
         return _niqe(args)
+    if args.command == "warp-error":
+        return _warp_error(args)
     task, jobs = jobs_of(args)
     truth = truth_of(args, jobs)
     lpips_spec = lpips_of(args, "restore")
     niqe_path = niqe_of(args, "restore")
     ident_path = identity_of(args, "restore")
+    warp_path = warp_of(args, "restore")
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
@@ -590,24 +732,37 @@ def main(argv=None):
         ident_model = load_identity_of(ident_path, device, "restore")
         if ident_model is not None:
             score_kw["identity"] = ident_model
+        warp_model = load_warp_of(warp_path, device, "restore")
+
+        def warp_skip(v):
+            """The pairs across the cuts restore_video_files worked with: the same rule on the same degraded frames."""
+            from . import io as fio
+            return warp_skip_of(how["scene_cuts"], how["cut_rule"], fio.list_frames(v), device, "restore")
 
         def restore_one(v, o):
             n = p.restore_video_files(v, o, **hp)
             if truth is not None:
                 from . import metrics as fm
-                result = fm.evaluate_dirs(o, truth[o], device, **score_kw)
+                warp_kw = {} if warp_model is None else dict(warp_error=warp_model, warp_skip=warp_skip(v))
+                result = fm.evaluate_dirs(o, truth[o], device, **score_kw, **warp_kw)
                 print(f"{o}: mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  "
                       f"ssim {result['mean']['ssim']:.4f}" + (f"  lpips {result['mean']['lpips']:.4f}" if lpips_model is not None else "")
-                      + niqe_tail(result) + identity_tail(result))
+                      + niqe_tail(result) + identity_tail(result) + warp_tail(result))
                 write_json(os.path.join(o, "metrics.json"), result)
-            elif niqe_model is not None:                # footage without a clean original: the no-reference score alone
+            elif niqe_model is not None or warp_model is not None:      # footage without a clean original: the no-reference scores alone
                 from . import niqe as fnq
+                from . import temporal as ftm
                 try:
-                    result = fnq.niqe_dir(o, device, niqe_model)
-                except ValueError as exc:               # frames under two blocks: the video is written, only the score is not
+                    result = fnq.niqe_dir(o, device, niqe_model) if niqe_model is not None else None
+                    if warp_model is not None:
+                        got = ftm.warp_error_dir(o, device, warp_model, skip=warp_skip(v))
+                        result = got if result is None else merge_results(result, got)
+                except ValueError as exc:               # frames too small for a score: the video is written, only the score is not
                     print(f"{o}: no score: {exc}")
                     return n
-                print(f"{o}: mean of {result['mean']['niqe_frames']} of {result['count']} frames" + niqe_tail(result))
+                head = (f"{o}: mean of {result['mean']['niqe_frames']} of {result['count']} frames" if niqe_model is not None
+                        else f"{o}: mean of {result['mean']['warp_err_pairs']} pairs of {result['count']} frames")
+                print(head + niqe_tail(result) + warp_tail(result))
                 write_json(os.path.join(o, "metrics.json"), result)
             return n
         pl.restore_many(jobs, restore_one)

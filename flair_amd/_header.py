@@ -3,7 +3,8 @@
 The header is the contract with libflair_hip.so; nothing of it is restated in Python.  ``STRUCTS`` maps a C struct name to
 a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``; ``EVAL_PROTOS`` is the same table
 of include/flair_eval.h, the evaluation-only entries of the same library, ``NOREF_PROTOS`` that of include/flair_noref.h,
-the no-reference scores, and ``IDENT_PROTOS`` that of include/flair_ident.h, the identity score.  Only the constructs the header uses
+the no-reference scores, ``IDENT_PROTOS`` that of include/flair_ident.h, the identity score, and ``TEMPORAL_PROTOS`` that of
+include/flair_temporal.h, the flow-warping error.  Only the constructs the header uses
 are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
 """
 import collections
@@ -120,3 +121,12 @@ with open(IDENT_HEADER_PATH) as _f:
 if _ident_structs or set(IDENT_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS) | set(NOREF_PROTOS)):
     raise HeaderError("flair_ident.h declares a struct or an entry of another header: "
                       f"{sorted(_ident_structs) + sorted(set(IDENT_PROTOS) & (set(PROTOS) | set(EVAL_PROTOS) | set(NOREF_PROTOS)))}")
+
+# The temporal ABI (include/flair_temporal.h: the flow-warping error), on the same terms.
+TEMPORAL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "flair_temporal.h")
+with open(TEMPORAL_HEADER_PATH) as _f:
+    _temporal_structs, TEMPORAL_PROTOS = parse(_f.read())
+_older = set(PROTOS) | set(EVAL_PROTOS) | set(NOREF_PROTOS) | set(IDENT_PROTOS)
+if _temporal_structs or set(TEMPORAL_PROTOS) & _older:
+    raise HeaderError("flair_temporal.h declares a struct or an entry of another header: "
+                      f"{sorted(_temporal_structs) + sorted(set(TEMPORAL_PROTOS) & _older)}")

@@ -1,6 +1,7 @@
-"""PSNR, SSIM and (on request) LPIPS of written frames against ground truth, and (on request) their no-reference NIQE and
-their ArcFace identity similarity, on the GPU (``flair_image_metrics``, csrc/metrics.hip; ``flair_amd.lpips``, csrc/lpips.hip;
-``flair_amd.niqe``, csrc/niqe.hip; ``flair_amd.identity``, csrc/ident.hip).
+"""PSNR, SSIM and (on request) LPIPS of written frames against ground truth, and (on request) their no-reference NIQE, their
+ArcFace identity similarity and their flow-warping error, on the GPU (``flair_image_metrics``, csrc/metrics.hip;
+``flair_amd.lpips``, csrc/lpips.hip; ``flair_amd.niqe``, csrc/niqe.hip; ``flair_amd.identity``, csrc/ident.hip;
+``flair_amd.temporal``, csrc/temporal.hip).
 
 The reference ships no scoring tool; this is the restoration literature's usual pair, on the bytes that get written
 (float images go through ``io.to_bytes`` first, so a metric always describes the files):
@@ -19,8 +20,12 @@ The reference ships no scoring tool; this is the restoration literature's usual 
   * ``ids``, only with a model from ``flair_amd.identity.load_identity``: the cosine of the ArcFace embeddings of a restored
     frame and its truth, as restated in include/flair_ident.h, with the identity drift from frame to frame of both sets.
 
+  * ``warp_err``, only with a model from ``flair_amd.temporal``: the flow-warping error of every consecutive frame pair, as
+    restated in include/flair_temporal.h, of the restored frames and of the truth under the truth's flows and mask.
+
 Not measured: the Y-channel and border-cropped variants of PSNR / SSIM, NIQE's colour and border-cropped variants, other
-no-reference scores (BRISQUE, PI), temporal metrics other than the identity drift.
+no-reference scores (BRISQUE, PI), temporal metrics other than the identity drift and the flow-warping error (tOF, tLP,
+warping errors over longer ranges than one frame).
 """
 import math
 import os
@@ -79,7 +84,7 @@ def _groups(sizes, batch):
     return groups
 
 
-def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=None, identity=None):
+def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=None, identity=None, warp_error=None, warp_skip=()):
     """Score the frames of ``restored_dir`` against those of ``truth_dir``, paired in ``io.list_frames`` order:
     ``dict(frames=[{name, psnr, ssim}], mean={psnr, ssim}, count)``; the means are those of the per-frame values.
     ValueError when a directory is empty, the counts differ, a pair differs in size or is smaller than 11 pixels a side
@@ -90,7 +95,12 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
     restored frame (None where it has no score) and ``mean`` gains ``niqe``, over the ``niqe_frames`` frames that have one;
     frames with fewer than two 96 x 96 blocks are refused with the others.  ``identity``: a ``flair_amd.identity.ArcFace``
     model; every frame dict then gains ``ids`` (None where an embedding is zero) and ``mean`` gains ``ids``, ``id_drift`` and
-    ``id_drift_truth``; every frame goes through the network once, and frames that are not square are refused with the others."""
+    ``id_drift_truth``; every frame goes through the network once, and frames that are not square are refused with the others.
+    ``warp_error``: a ``flair_amd.temporal.WarpError`` model; every frame dict then gains ``warp_err``, the flow-warping error of
+    the restored frame and the one before it under the TRUTH's flows and mask (None for the first frame, after a change of
+    size, for a pair with an empty mask and for the later-frame indices in ``warp_skip``: ``temporal.straddling`` of the scene
+    cuts), and ``mean`` gains ``warp_err``, ``warp_err_truth``, ``warp_err_pairs`` and ``masked``; frames under 32 pixels a
+    side are refused with the others."""
     ra, rb, sizes = _pairs(restored_dir, truth_dir)
     if niqe is not None:
         from . import niqe as fnq
@@ -104,6 +114,11 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
         from . import identity as fid
         for pa, (h, w) in zip(ra, sizes):
             fid.check_size(h, w, what=f"evaluate: {pa}")
+    if warp_error is not None:
+        from . import temporal as ftm
+        for pa, (h, w) in zip(ra, sizes):
+            ftm.check_size(h, w, what=f"evaluate: {pa}")
+        pair_stream = ftm.PairStream(warp_error)
     frames, emb_a, emb_b = [], [], []
     for first, (a, b) in fio.iter_frame_batches([ra, rb], _groups(sizes, max(1, int(batch))), device):
         got = psnr_ssim(a, b)
@@ -119,6 +134,8 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
             e = identity.embed(a, b)
             emb_a += list(e[:a.shape[0]])
             emb_b += list(e[a.shape[0]:])
+        if warp_error is not None:
+            pair_stream.push(a, b)
     n = len(frames)
     mean = dict(psnr=sum(f["psnr"] for f in frames) / n, ssim=sum(f["ssim"] for f in frames) / n)
     if lpips is not None:
@@ -130,13 +147,19 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
         for f, v in zip(frames, ids):
             f["ids"] = v
         mean.update(id_mean)
+    if warp_error is not None:
+        values, warp_mean = ftm.scores(pair_stream.rows, pair_stream.pixels, set(warp_skip))
+        for f, v in zip(frames, values):
+            f["warp_err"] = v
+        mean.update(warp_mean)
     return dict(frames=frames, mean=mean, count=n)
 
 
 def format_report(result):
-    """One line per frame and the means, four decimals each (``lpips``, then ``niqe``, then ``ids``, where the result holds
-    them; ``niqe n/a`` / ``ids n/a`` for a frame without a score, which the mean leaves out; the means' line ends with the
-    identity drift of the restored frames and, in brackets, of the truth)."""
+    """One line per frame and the means, four decimals each (``lpips``, then ``niqe``, then ``ids``, then ``warp-err``, where the
+    result holds them; ``niqe n/a`` / ``ids n/a`` / ``warp-err n/a`` for a frame without a score, which the mean leaves out; the
+    means' line carries the identity drift of the restored frames and, in brackets, of the truth, and ends with the
+    flow-warping error (x 10^3), the truth's in brackets, and the masked-out share)."""
     def tail(d):
         text = f"  lpips {d['lpips']:.4f}" if "lpips" in d else ""
         if "niqe" in d:
@@ -145,6 +168,9 @@ def format_report(result):
         if "ids" in d:
             from . import identity as fid
             text += fid.format_mean(d) if "id_drift" in d else fid.format_value(d["ids"])
+        if "warp_err" in d:
+            from . import temporal as ftm
+            text += ftm.format_mean(d) if "masked" in d else ftm.format_value(d["warp_err"])
         return text
     lines = [f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" + tail(f) for f in result["frames"]]
     lines.append(f"mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  ssim {result['mean']['ssim']:.4f}"

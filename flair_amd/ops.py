@@ -1187,6 +1187,56 @@ def ident_embed(x, w, bias, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- flow-warping error (temporal.hip, include/flair_temporal.h)
+WARP_TILE_H, WARP_TILE_W = 32, 64           # FLAIR_WARP_TILE_H / _W: the tile of one workgroup, the workspace in closed form
+
+
+def _flow_pair(name, f, what):
+    _refuse(f.dim() == 4 and f.shape[3] == 2 and f.dtype == torch.float32 and f.is_contiguous() and f.shape[0] >= 1,
+            f"{name}: {what} is a dense (P, H, W, 2) float32 tensor with P >= 1, got {tuple(f.shape)} {f.dtype}")
+
+
+def flow_occlusion(f, g, out=None):
+    """The mask of include/flair_temporal.h, steps 1 to 5 (flair_flow_occlusion): f (the flow frame t -> t + 1) and g (the flow
+    t + 1 -> t), dense (P, H, W, 2) f32 of (dx, dy) -> (P, H, W) uint8, 1 where a pixel is inside, not occluded and not on a
+    motion boundary.  Float64 inside; out: an optional dense tensor of that shape."""
+    _flow_pair("flow_occlusion", f, "f")
+    _refuse(tuple(g.shape) == tuple(f.shape) and g.dtype == torch.float32 and g.is_contiguous(),
+            f"flow_occlusion: g is a dense {tuple(f.shape)} float32 tensor like f, got {tuple(g.shape)} {g.dtype}")
+    P, H, W, _ = f.shape
+    if out is None:
+        out = torch.empty((P, H, W), dtype=torch.uint8, device=f.device)
+    _refuse(out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (P, H, W),
+            f"flow_occlusion: out is a dense {(P, H, W)} uint8 tensor, got {tuple(out.shape)} {out.dtype}")
+    call.flair_flow_occlusion(f, g, P, H, W, out)
+    return out
+
+
+def warp_error(a, f, mask, a2=None, out=None):
+    """(S, N) of include/flair_temporal.h, steps 6 and 7, per frame pair (flair_warp_error): a (P + 1, H, W, 3) uint8 dense RGB on
+    the GPU at any byte alignment, pair i being frames i and i + 1; f (P, H, W, 2) f32, the flow frame i -> i + 1; mask
+    (P, H, W) uint8; a2: a second frame set like a, judged by the same f and mask -> (sets, P, 2) float64, sets = 1 or 2.
+    The same bits in every run, for every P and every position in the batch."""
+    _flow_pair("warp_error", f, "f")
+    P, H, W, _ = f.shape
+    for name, t in (("a", a), ("a2", a2)):
+        _refuse(t is None or (t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (P + 1, H, W, 3)),
+                f"warp_error: {name} is a dense {(P + 1, H, W, 3)} uint8 tensor, one frame more than f has pairs" +
+                ("" if t is None else f", got {tuple(t.shape)} {t.dtype}"))
+    _refuse(a is not None, "warp_error: a is missing")
+    _refuse(mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (P, H, W),
+            f"warp_error: mask is a dense {(P, H, W)} uint8 tensor, got {tuple(mask.shape)} {mask.dtype}")
+    sets = 1 if a2 is None else 2
+    if out is None:
+        out = torch.empty((sets, P, 2), dtype=torch.float64, device=f.device)
+    _refuse(out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (sets, P, 2),
+            f"warp_error: out is a dense {(sets, P, 2)} float64 tensor, got {tuple(out.shape)} {out.dtype}")
+    nbytes = sets * P * -(-H // WARP_TILE_H) * -(-W // WARP_TILE_W) * 16
+    ws = _workspace(nbytes, f.device, tag="temporal")
+    call.flair_warp_error(a, a2, f, mask, P, H, W, out, ws, nbytes)
+    return out
+
+
 # --------------------------------------------------------------------------- scene cuts (scenes.hip)
 def block_luma_sums(u8, out=None):
     """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB
