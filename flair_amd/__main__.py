@@ -7,6 +7,8 @@ DIR`` scores every video as soon as it is written.  ``niqe FRAMES_DIR --params F
 ``--identity FILE`` adds the ArcFace identity similarity and drift (flair_amd.identity) wherever there is ground truth.
 ``--warp-error FILE`` adds the flow-warping error, the temporal consistency of the written frames (flair_amd.temporal), to
 evaluate, restore and interpolate, and ``warp-error FRAMES_DIR --flow-weights FILE`` scores footage that has no ground truth.
+``--score-faces largest|all`` adds the same scores over the face regions of unaligned frames (flair_amd.facescore) to evaluate and
+restore --ground-truth.
 ``interpolate SRC_DIR OUT_DIR --factor N`` changes the frame rate of written frames with SuperSloMo or AMT-G (flair_amd.interpolate).
 ``scenes SRC_DIR --json PATH`` finds the hard cuts of a video (flair_amd.scenes); ``restore`` / ``interpolate --scene-cuts
 auto|PATH`` then treat every shot on its own.
@@ -148,6 +150,57 @@ def warp_skip_of(scene_cuts, cut_rule, paths, device, command, factor=1):
     return ftm.straddling(cuts, factor)
 
 
+def _add_score_faces(p, what, own_detector):
+    p.add_argument("--score-faces", choices=("largest", "all"), default=None,
+                   help=f"{what} PSNR / SSIM (and --lpips, --identity) of the face regions: the faces are found on the ground-truth "
+                        "frames and one alignment cuts both frame sets; largest: at most one face per frame, with the identity "
+                        "drift; all: every face, at most --max-faces per frame.  --identity then scores the face crops only")
+    p.add_argument("--face-size", type=int, default=512, metavar="S", help="with --score-faces: the side of the aligned face crops")
+    if own_detector:
+        p.add_argument("--max-faces", type=int, default=4, metavar="N", help="with --score-faces all: at most N faces per frame, largest first")
+        p.add_argument("--det-model", choices=tuple(pl.DETECTOR_FILES), default="retinaface_resnet50",
+                       help="with --score-faces: the face detector, read from --weights DIR")
+
+
+def face_scorer_of(args, command):
+    """dict(mode, max_faces, face_size, det_model, weights) of a parsed command line's --score-faces, or None without it;
+    refused before any GPU work where there is no ground truth, a number is out of range or (evaluate, which builds the
+    detector itself) the detector's file is missing."""
+    mode = getattr(args, "score_faces", None)
+    if mode is None:
+        return None
+    if command != "evaluate" and not args.ground_truth:
+        raise SystemExit(f"{command}: --score-faces compares the written frames with --ground-truth DIR; give one")
+    if args.max_faces < 1:
+        raise SystemExit(f"{command}: --max-faces must be at least 1")
+    from .metrics import SSIM_WINDOW
+    if args.face_size < SSIM_WINDOW:
+        raise SystemExit(f"{command}: --face-size must be at least {SSIM_WINDOW} (SSIM's window)")
+    if command == "evaluate":
+        if not args.weights:
+            raise SystemExit(f"{command}: --score-faces reads the {args.det_model} detector from --weights DIR; give one")
+        path = os.path.join(args.weights, pl.DETECTOR_FILES[args.det_model][1])
+        if not os.path.isfile(path):
+            raise SystemExit(f"{command}: --score-faces with --det-model {args.det_model} needs {path}")
+    return dict(mode=mode, max_faces=args.max_faces, face_size=args.face_size, det_model=args.det_model, weights=args.weights)
+
+
+def load_face_scorer_of(spec, device, command, face_det=None):
+    """The FaceScorer of face_scorer_of's result on ``device`` (None for None); ``face_det``: a loaded detector to reuse
+    (restore's) instead of reading one from the weights directory."""
+    if spec is None:
+        return None
+    from . import facescore as ffs
+    try:
+        if face_det is None:
+            return ffs.load_face_scorer(spec["det_model"], spec["weights"], device, spec["mode"], spec["max_faces"], spec["face_size"])
+        from .guided_diffusion.face_restoration_helper import FaceRestoreHelper
+        helper = FaceRestoreHelper(face_size=spec["face_size"], det_model=spec["det_model"], device=device, face_det=face_det)
+        return ffs.FaceScorer(helper, spec["mode"], max_faces=spec["max_faces"])
+    except (ValueError, FileNotFoundError) as exc:
+        raise SystemExit(f"{command}: {exc}")
+
+
 def identity_of(args, command):
     """The checkpoint of a parsed command line's --identity, or None without it; refused before any GPU work where there is no
     ground truth to compare with or it is not a file."""
@@ -260,6 +313,7 @@ def make_parser():
     _add_niqe(r, "after a video is written, log its mean and write into metrics.json")
     _add_identity(r, "with --ground-truth: also score")
     _add_warp_error(r, "after a video is written, log and write into metrics.json")
+    _add_score_faces(r, "with --ground-truth: also score", own_detector=False)
     _add_hparams(r, pl.MAIN_DEFAULTS)
     _add_common(r)
     for name, demo in pl.DEMOS.items():
@@ -283,11 +337,12 @@ def make_parser():
     e.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the means as JSON")
     e.add_argument("--device", default=None, help="default: cuda")
     _add_lpips(e, "also score", "")
-    e.add_argument("--weights", default=None, metavar="DIR", help="with --lpips: the directory that holds those files")
+    e.add_argument("--weights", default=None, metavar="DIR", help="with --lpips or --score-faces: the directory that holds those files")
     _add_niqe(e, "also report")
     _add_identity(e, "also report")
     _add_warp_error(e, "also report")
     _add_cut_options(e, "with --warp-error: leave out the frame pairs that straddle a cut of TRUTH_DIR")
+    _add_score_faces(e, "also report", own_detector=True)
     w = sub.add_parser("warp-error", help="flow-warping error (temporal consistency) of written frames without ground truth: one "
                                           "line per frame and the means")
     w.add_argument("frames_dir", metavar="FRAMES_DIR", help="frames of at least 32 pixels a side")
@@ -589,6 +644,7 @@ def _evaluate(args):
     niqe_path = niqe_of(args, "evaluate")
     ident_path = identity_of(args, "evaluate")
     warp_path = warp_of(args, "evaluate")
+    face_spec = face_scorer_of(args, "evaluate")
     if warp_path is None and args.scene_cuts != "off":
         raise SystemExit("evaluate: --scene-cuts only tells --warp-error FILE which frame pairs to leave out; give one")
     how = cuts_of(args, "evaluate", [args.truth_dir]) if warp_path is not None else None
@@ -598,6 +654,7 @@ def _evaluate(args):
     model = load_lpips_of(spec, args.device or "cuda", "evaluate")
     niqe = load_niqe_of(niqe_path, args.device or "cuda", "evaluate")
     ident = load_identity_of(ident_path, args.device or "cuda", "evaluate")
+    scorer = load_face_scorer_of(face_spec, args.device or "cuda", "evaluate")
     warp_kw = {}
     if warp_path is not None:
         from . import io as fio
@@ -605,7 +662,8 @@ def _evaluate(args):
         warp_kw = dict(warp_error=load_warp_of(warp_path, args.device or "cuda", "evaluate"), warp_skip=skip)
     try:
         result = fm.evaluate_dirs(args.restored_dir, args.truth_dir, args.device or "cuda", **({} if model is None else dict(lpips=model)),
-                                  **({} if niqe is None else dict(niqe=niqe)), **({} if ident is None else dict(identity=ident)), **warp_kw)
+                                  **({} if niqe is None else dict(niqe=niqe)), **({} if ident is None else dict(identity=ident)), **warp_kw,
+                                  **({} if scorer is None else dict(faces=scorer)))
     except ValueError as exc:
         raise SystemExit(str(exc))
     for line in fm.format_report(result):
@@ -613,6 +671,14 @@ def _evaluate(args):
     if args.json:
         write_json(args.json, result)
     return 0
+
+
+def face_tail(result):
+    """The face scores of a result's mean for restore's one-line log ('' without --score-faces)."""
+    if "face_count" not in result["mean"]:
+        return ""
+    from .facescore import face_tail as tail
+    return tail(result)
 
 
 def niqe_tail(result):
@@ -697,6 +763,7 @@ def main(argv=None):
     niqe_path = niqe_of(args, "restore")
     ident_path = identity_of(args, "restore")
     warp_path = warp_of(args, "restore")
+    face_spec = face_scorer_of(args, "restore")
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
@@ -733,6 +800,8 @@ def main(argv=None):
         if ident_model is not None:
             score_kw["identity"] = ident_model
         warp_model = load_warp_of(warp_path, device, "restore")
+        if face_spec is not None:                       # the detector restore built is the one that scores
+            score_kw["faces"] = load_face_scorer_of(face_spec, device, "restore", face_det=p.face_helper.face_det)
 
         def warp_skip(v):
             """The pairs across the cuts restore_video_files worked with: the same rule on the same degraded frames."""
@@ -747,7 +816,7 @@ def main(argv=None):
                 result = fm.evaluate_dirs(o, truth[o], device, **score_kw, **warp_kw)
                 print(f"{o}: mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  "
                       f"ssim {result['mean']['ssim']:.4f}" + (f"  lpips {result['mean']['lpips']:.4f}" if lpips_model is not None else "")
-                      + niqe_tail(result) + identity_tail(result) + warp_tail(result))
+                      + niqe_tail(result) + identity_tail(result) + warp_tail(result) + face_tail(result))
                 write_json(os.path.join(o, "metrics.json"), result)
             elif niqe_model is not None or warp_model is not None:      # footage without a clean original: the no-reference scores alone
                 from . import niqe as fnq

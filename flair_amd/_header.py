@@ -3,8 +3,9 @@
 The header is the contract with libflair_hip.so; nothing of it is restated in Python.  ``STRUCTS`` maps a C struct name to
 a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``; ``EVAL_PROTOS`` is the same table
 of include/flair_eval.h, the evaluation-only entries of the same library, ``NOREF_PROTOS`` that of include/flair_noref.h,
-the no-reference scores, ``IDENT_PROTOS`` that of include/flair_ident.h, the identity score, and ``TEMPORAL_PROTOS`` that of
-include/flair_temporal.h, the flow-warping error.  Only the constructs the header uses
+the no-reference scores, ``IDENT_PROTOS`` that of include/flair_ident.h, the identity score, ``TEMPORAL_PROTOS`` that of
+include/flair_temporal.h, the flow-warping error, and ``FACESCORE_PROTOS`` that of include/flair_facescore.h, the face score's
+crop.  Only the constructs the header uses
 are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
 """
 import collections
@@ -130,3 +131,12 @@ _older = set(PROTOS) | set(EVAL_PROTOS) | set(NOREF_PROTOS) | set(IDENT_PROTOS)
 if _temporal_structs or set(TEMPORAL_PROTOS) & _older:
     raise HeaderError("flair_temporal.h declares a struct or an entry of another header: "
                       f"{sorted(_temporal_structs) + sorted(set(TEMPORAL_PROTOS) & _older)}")
+
+# The face-score ABI (include/flair_facescore.h: the byte crop of the face-region scores), on the same terms.
+FACESCORE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "flair_facescore.h")
+with open(FACESCORE_HEADER_PATH) as _f:
+    _facescore_structs, FACESCORE_PROTOS = parse(_f.read())
+_older = _older | set(TEMPORAL_PROTOS)
+if _facescore_structs or set(FACESCORE_PROTOS) & _older:
+    raise HeaderError("flair_facescore.h declares a struct or an entry of another header: "
+                      f"{sorted(_facescore_structs) + sorted(set(FACESCORE_PROTOS) & _older)}")

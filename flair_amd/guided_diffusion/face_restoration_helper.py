@@ -137,12 +137,11 @@ class FaceRestoreHelper(object):
         cropped = self.get_crop_face_from_affine_matrices(x[find_face_idx].contiguous(), affine_matrices)
         return cropped, affine_matrices, find_face_idx
 
-    def get_crop_faces_all(self, bathed_imgs, eye_dist_threshold=None, max_faces=None, face_template_resize=None,
-                           face_template_x_offset=None, face_template_y_offset=None):
-        """Every face of every frame (extension; the reference keeps one per frame): (B, 3, H, W) frames in [-1, 1] ->
-        (cropped faces (K, 3, face_h, face_w) in [-1, 1] or None, K affine matrices, face_frames: the frame of every face,
-        non-decreasing).  A frame may have no face or several (retinaface_utils.select_faces: largest first, at most
-        ``max_faces`` per frame); K = 0 gives (None, [], [])."""
+    def get_face_matrices(self, bathed_imgs, eye_dist_threshold=None, max_faces=None, face_template_resize=None,
+                          face_template_x_offset=None, face_template_y_offset=None):
+        """The detection and alignment of get_crop_faces_all without its crop: (B, 3, H, W) frames in [-1, 1] -> (K affine
+        matrices, face_frames: the frame of every face, non-decreasing); K = 0 gives ([], []).  For callers that cut
+        something other than these f32 frames with the matrices (flair_amd.facescore cuts the written bytes)."""
         if self.detector is not None:
             raise NotImplementedError("flair_amd: get_crop_faces_all needs the package's own detector (face_det): an external "
                                       "detector= object returns faces without their frames")
@@ -157,8 +156,18 @@ class FaceRestoreHelper(object):
             raise RuntimeError(f"batched_detect_faces(keep_empty=True) returned {len(dets)} entries for {B} frames")
         template = np.stack([self.face_template[:, 0] + face_template_x_offset,
                              self.face_template[:, 1] + face_template_y_offset], axis=1) * face_template_resize
-        affine_matrices, face_frames = select_faces(dets, H, W, template, template_3points=self.template_3points,
-                                                    eye_dist_threshold=eye_dist_threshold, max_faces=max_faces)
+        return select_faces(dets, H, W, template, template_3points=self.template_3points,
+                            eye_dist_threshold=eye_dist_threshold, max_faces=max_faces)
+
+    def get_crop_faces_all(self, bathed_imgs, eye_dist_threshold=None, max_faces=None, face_template_resize=None,
+                           face_template_x_offset=None, face_template_y_offset=None):
+        """Every face of every frame (extension; the reference keeps one per frame): (B, 3, H, W) frames in [-1, 1] ->
+        (cropped faces (K, 3, face_h, face_w) in [-1, 1] or None, K affine matrices, face_frames: the frame of every face,
+        non-decreasing).  A frame may have no face or several (retinaface_utils.select_faces: largest first, at most
+        ``max_faces`` per frame); K = 0 gives (None, [], [])."""
+        x = bathed_imgs.float().contiguous().to(self.device)
+        affine_matrices, face_frames = self.get_face_matrices(x, eye_dist_threshold, max_faces, face_template_resize,
+                                                              face_template_x_offset, face_template_y_offset)
         if len(affine_matrices) == 0:
             return None, [], []
         return self.get_crop_face_from_affine_matrices(x, affine_matrices, face_frames), affine_matrices, face_frames

@@ -15,7 +15,8 @@ The cosines and their means are numpy float64 here.
   * ``id_drift`` = the mean over t >= 1 of 1 - cos(e_t, e_{t-1}) on the restored frames, ``id_drift_truth`` the same on the
     truth frames for comparison.  Scene cuts are not consulted: a cut shows up as drift.
 
-Frames are taken as aligned face crops (the package's ``aligned`` mode) and must be square; faces are not detected here.
+Frames are taken as aligned face crops (the package's ``aligned`` mode) and must be square; faces are not detected here
+(``flair_amd.facescore`` cuts the faces out of unaligned frames and hands the crops to ``embed``).
 
 The weights are the user's: GFPGAN's / VQFR's ``arcface_resnet18.pth``, ``ResNetArcFace(block='IRBlock', layers=(2, 2, 2, 2),
 use_se=False)`` stored with a ``module.`` prefix.  Nothing is downloaded or shipped.  The key names below were restated from

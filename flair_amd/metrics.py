@@ -1,7 +1,7 @@
 """PSNR, SSIM and (on request) LPIPS of written frames against ground truth, and (on request) their no-reference NIQE, their
-ArcFace identity similarity and their flow-warping error, on the GPU (``flair_image_metrics``, csrc/metrics.hip;
-``flair_amd.lpips``, csrc/lpips.hip; ``flair_amd.niqe``, csrc/niqe.hip; ``flair_amd.identity``, csrc/ident.hip;
-``flair_amd.temporal``, csrc/temporal.hip).
+ArcFace identity similarity, their flow-warping error and the same scores over their face regions, on the GPU
+(``flair_image_metrics``, csrc/metrics.hip; ``flair_amd.lpips``, csrc/lpips.hip; ``flair_amd.niqe``, csrc/niqe.hip;
+``flair_amd.identity``, csrc/ident.hip; ``flair_amd.temporal``, csrc/temporal.hip; ``flair_amd.facescore``, csrc/facecrop.hip).
 
 The reference ships no scoring tool; this is the restoration literature's usual pair, on the bytes that get written
 (float images go through ``io.to_bytes`` first, so a metric always describes the files):
@@ -22,6 +22,9 @@ The reference ships no scoring tool; this is the restoration literature's usual 
 
   * ``warp_err``, only with a model from ``flair_amd.temporal``: the flow-warping error of every consecutive frame pair, as
     restated in include/flair_temporal.h, of the restored frames and of the truth under the truth's flows and mask.
+
+  * ``faces``, only with a ``flair_amd.facescore.FaceScorer``: PSNR, SSIM and, where those models are given, LPIPS and the
+    identity similarity of every face of unaligned frames, on aligned byte crops of both sets (include/flair_facescore.h).
 
 Not measured: the Y-channel and border-cropped variants of PSNR / SSIM, NIQE's colour and border-cropped variants, other
 no-reference scores (BRISQUE, PI), temporal metrics other than the identity drift and the flow-warping error (tOF, tLP,
@@ -84,7 +87,8 @@ def _groups(sizes, batch):
     return groups
 
 
-def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=None, identity=None, warp_error=None, warp_skip=()):
+def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=None, identity=None, warp_error=None, warp_skip=(),
+                  faces=None):
     """Score the frames of ``restored_dir`` against those of ``truth_dir``, paired in ``io.list_frames`` order:
     ``dict(frames=[{name, psnr, ssim}], mean={psnr, ssim}, count)``; the means are those of the per-frame values.
     ValueError when a directory is empty, the counts differ, a pair differs in size or is smaller than 11 pixels a side
@@ -100,8 +104,17 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
     the restored frame and the one before it under the TRUTH's flows and mask (None for the first frame, after a change of
     size, for a pair with an empty mask and for the later-frame indices in ``warp_skip``: ``temporal.straddling`` of the scene
     cuts), and ``mean`` gains ``warp_err``, ``warp_err_truth``, ``warp_err_pairs`` and ``masked``; frames under 32 pixels a
-    side are refused with the others."""
+    side are refused with the others.  ``faces``: a ``flair_amd.facescore.FaceScorer``; every frame dict then gains ``faces``, a
+    list of ``{psnr, ssim, [lpips], [ids], clipped, matrix}`` per face found on the TRUTH frame and cut from both sets by one
+    matrix, and ``mean`` gains ``face_psnr``, ``face_ssim``, ``[face_lpips]``, ``[face_ids]`` (means over faces; absent without a
+    face), ``face_count`` and ``frames_with_faces`` and, in mode "largest" with ``identity``, ``face_id_drift`` and
+    ``face_id_drift_truth``.  ``identity`` then applies to the crops only: the whole-frame ``ids`` and its squareness check
+    are skipped; every other whole-frame value stays what it is without the scorer."""
     ra, rb, sizes = _pairs(restored_dir, truth_dir)
+    face_identity = None
+    if faces is not None:
+        faces.check_models(lpips=lpips, identity=identity)
+        face_identity, identity = identity, None
     if niqe is not None:
         from . import niqe as fnq
         for pa, (h, w) in zip(ra, sizes):
@@ -119,7 +132,7 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
         for pa, (h, w) in zip(ra, sizes):
             ftm.check_size(h, w, what=f"evaluate: {pa}")
         pair_stream = ftm.PairStream(warp_error)
-    frames, emb_a, emb_b = [], [], []
+    frames, emb_a, emb_b, face_emb = [], [], [], []
     for first, (a, b) in fio.iter_frame_batches([ra, rb], _groups(sizes, max(1, int(batch))), device):
         got = psnr_ssim(a, b)
         for i, (p, s) in enumerate(zip(got["psnr"], got["ssim"])):
@@ -136,6 +149,11 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
             emb_b += list(e[a.shape[0]:])
         if warp_error is not None:
             pair_stream.push(a, b)
+        if faces is not None:
+            per_frame, emb = faces.score(a, b, lpips=lpips, identity=face_identity)
+            for i, found in enumerate(per_frame):
+                frames[first + i]["faces"] = found
+            face_emb += emb
     n = len(frames)
     mean = dict(psnr=sum(f["psnr"] for f in frames) / n, ssim=sum(f["ssim"] for f in frames) / n)
     if lpips is not None:
@@ -152,6 +170,9 @@ def evaluate_dirs(restored_dir, truth_dir, device, batch=8, lpips=None, niqe=Non
         for f, v in zip(frames, values):
             f["warp_err"] = v
         mean.update(warp_mean)
+    if faces is not None:
+        from . import facescore as ffs
+        mean.update(ffs.means(frames, faces.mode, face_emb if face_identity is not None else None))
     return dict(frames=frames, mean=mean, count=n)
 
 
@@ -159,7 +180,9 @@ def format_report(result):
     """One line per frame and the means, four decimals each (``lpips``, then ``niqe``, then ``ids``, then ``warp-err``, where the
     result holds them; ``niqe n/a`` / ``ids n/a`` / ``warp-err n/a`` for a frame without a score, which the mean leaves out; the
     means' line carries the identity drift of the restored frames and, in brackets, of the truth, and ends with the
-    flow-warping error (x 10^3), the truth's in brackets, and the masked-out share)."""
+    flow-warping error (x 10^3), the truth's in brackets, and the masked-out share).  Where the frames hold ``faces``, one
+    indented line per face follows a frame's line (``  faces 0`` for a frame without one) and the faces' means follow the
+    means' line (``flair_amd.facescore.format_faces`` / ``format_mean``)."""
     def tail(d):
         text = f"  lpips {d['lpips']:.4f}" if "lpips" in d else ""
         if "niqe" in d:
@@ -172,7 +195,15 @@ def format_report(result):
             from . import temporal as ftm
             text += ftm.format_mean(d) if "masked" in d else ftm.format_value(d["warp_err"])
         return text
-    lines = [f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" + tail(f) for f in result["frames"]]
+    lines = []
+    for f in result["frames"]:
+        lines.append(f"{f['name']}  psnr {f['psnr']:.4f}  ssim {f['ssim']:.4f}" + tail(f))
+        if "faces" in f:
+            from . import facescore as ffs
+            lines += ffs.format_faces(f["faces"])
     lines.append(f"mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  ssim {result['mean']['ssim']:.4f}"
                  + tail(result["mean"]))
+    if "face_count" in result["mean"]:
+        from . import facescore as ffs
+        lines.append(ffs.format_mean(result["mean"], result["count"]))
     return lines

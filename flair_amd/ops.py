@@ -1237,6 +1237,53 @@ def warp_error(a, f, mask, a2=None, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- face-score crop (facecrop.hip, include/flair_facescore.h)
+FACE_CROP_REACH = 32000                     # source pixels: beyond it lies the 16-bit saturation of the fixed-point form, left out
+
+
+def face_crop_u8(a, minv, minv_host, src_index, src_index_host, out_hw, *, b=None, border=(135, 133, 132), out_a=None, out_b=None):
+    """Aligned byte crops of the faces of one or two frame sets (flair_face_crop_u8): a (Nsrc, Hs, Ws, 3) uint8 dense RGB on the
+    GPU at any byte alignment; b: a second frame set like a, cut with the same geometry; minv (K, 6) float64 DEVICE tensor, the
+    dst -> src matrices, and ``minv_host`` the same numbers on the host; src_index (K,) int32 DEVICE tensor and
+    ``src_index_host`` the same numbers on the host.  The host copies are what gets checked: an index outside [0, Nsrc) and a
+    matrix that maps a corner of the crop beyond +-32 000 source pixels are refused before the launch.  -> out_a (K, Hd, Wd, 3)
+    uint8 without b, (out_a, out_b) with it: the exact a = -0.75 cubic of include/flair_facescore.h with ``border`` (three
+    bytes) outside the frame, rounded once.  The same bits in every run, for every K and every position in the batch."""
+    import numpy as np
+    what = "face_crop_u8"
+    for name, t in (("a", a), ("b", b)):
+        _refuse(t is None or (t.dim() == 4 and t.shape[3] == 3 and t.dtype == torch.uint8 and t.is_contiguous() and t.shape[0] >= 1),
+                f"{what}: {name} is a dense (Nsrc, Hs, Ws, 3) uint8 tensor with Nsrc >= 1" + ("" if t is None else f", got {tuple(t.shape)} {t.dtype}"))
+    _refuse(a is not None, f"{what}: a is missing")
+    _refuse(b is None or tuple(b.shape) == tuple(a.shape), f"{what}: b is a frame set of a's shape {tuple(a.shape)}" + ("" if b is None else f", got {tuple(b.shape)}"))
+    Nsrc, Hs, Ws, _ = a.shape
+    _refuse(src_index.dim() == 1 and src_index.dtype == torch.int32 and src_index.is_contiguous(), f"{what}: src_index must be a contiguous (K,) int32 tensor")
+    K = src_index.shape[0]
+    _refuse(minv.dtype == torch.float64 and minv.is_contiguous() and tuple(minv.shape) == (K, 6), f"{what}: minv must be a contiguous ({K}, 6) float64 tensor")
+    _refuse(src_index_host is not None and len(src_index_host) == K, f"{what}: src_index_host (the {K} indices on the host) is needed for the range check")
+    _refuse(all(0 <= int(i) < Nsrc for i in src_index_host), f"{what}: src_index outside [0, {Nsrc})")
+    Hd, Wd = (int(v) for v in out_hw)
+    _refuse(Hd >= 1 and Wd >= 1, f"{what}: a crop of {Hd}x{Wd} pixels")
+    m = np.asarray(minv_host, dtype=np.float64).reshape(-1, 6) if minv_host is not None and K else np.zeros((0, 6))
+    _refuse(minv_host is not None and m.shape[0] == K, f"{what}: minv_host (the {K} matrices on the host) is needed for the range check")
+    for k in range(K):
+        corners = [(m[k, 0] * x + m[k, 1] * y + m[k, 2], m[k, 3] * x + m[k, 4] * y + m[k, 5]) for x in (0, Wd - 1) for y in (0, Hd - 1)]
+        _refuse(all(abs(v) <= FACE_CROP_REACH for p in corners for v in p),                 # a not-a-number fails the comparison too
+                f"{what}: matrix {k} maps a corner of the crop beyond +-{FACE_CROP_REACH} source pixels")
+    _refuse(len(border) == 3 and all(int(v) == v and 0 <= int(v) <= 255 for v in border), f"{what}: border is three bytes, got {tuple(border)}")
+    for name, t in (("out_a", out_a), ("out_b", out_b)):
+        _refuse(t is None or (t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (K, Hd, Wd, 3)),
+                f"{what}: {name} is a dense {(K, Hd, Wd, 3)} uint8 tensor" + ("" if t is None else f", got {tuple(t.shape)} {t.dtype}"))
+    _refuse(b is not None or out_b is None, f"{what}: out_b without b")
+    if out_a is None:
+        out_a = torch.empty((K, Hd, Wd, 3), dtype=torch.uint8, device=a.device)
+    if b is not None and out_b is None:
+        out_b = torch.empty((K, Hd, Wd, 3), dtype=torch.uint8, device=a.device)
+    if K:
+        call.flair_face_crop_u8(a, b, Nsrc, Hs, Ws, minv, src_index, K, Hd, Wd, (ctypes.c_uint8 * 3)(*(int(v) for v in border)), out_a, out_b)
+    return out_a if b is None else (out_a, out_b)
+
+
 # --------------------------------------------------------------------------- scene cuts (scenes.hip)
 def block_luma_sums(u8, out=None):
     """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB
