@@ -344,6 +344,14 @@ extern "C" int flair_depthwise_filter(const float* x, int planes, int Hin, int W
                 "flair_depthwise_filter: bad argument");
     FLAIR_CHECK(out_stride >= 1 && stuff >= 1 && stuff_offset >= 0 && stuff_offset < stuff && Hout > 0 && Wout > 0,
                 "flair_depthwise_filter: bad sampling parameters");
+    if (reflect) {   // one reflection only: beyond it pad_index would clamp, where F.pad(mode="reflect") raises
+        const long lo = (long)out_offset - pad, Hv = (long)Hin * stuff, Wv = (long)Win * stuff;
+        const long hiH = (long)(Hout - 1) * out_stride + out_offset + kh - 1 - pad;
+        const long hiW = (long)(Wout - 1) * out_stride + out_offset + kw - 1 - pad;
+        FLAIR_CHECK(lo >= -(Hv - 1) && lo >= -(Wv - 1) && hiH <= 2 * (Hv - 1) && hiW <= 2 * (Wv - 1),
+                    "flair_depthwise_filter: reflect padding reaches rows [%ld, %ld] and columns [%ld, %ld] of a %ld x %ld plane: "
+                    "more than one reflection (at most size - 1 beyond either border)", lo, hiH, lo, hiW, Hv, Wv);
+    }
     if (kh == 39 && kw == 39 && stuff == 1 && out_stride == 1 && Hout % 32 == 0 && Wout % 32 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
         hipLaunchKernelGGL(depthwise_filter_tiled_kernel<39>, dim3(planes * (Hout / 32) * (Wout / 32)), dim3(256), 0, stream, x, Hin, Win,
                            filt, pad, out_offset, Hout, Wout, reflect, y);
@@ -401,6 +409,9 @@ extern "C" int flair_jpeg_roundtrip_hw(const float* x, int N, int H, int W, cons
 extern "C" int flair_matmul_f32(const float* A, long a_batch_stride, const float* B, long b_batch_stride, float* C,
                                 int batch, int M, int N, int K, hipStream_t stream) {
     FLAIR_CHECK(A && B && C && batch > 0 && M > 0 && N > 0 && K > 0, "flair_matmul_f32: bad argument");
+    FLAIR_CHECK(batch <= 65535 && (M - 1) / 16 + 1 <= 65535,
+                "flair_matmul_f32: batch = %d and ceil(M / 16) = %d are the grid's z and y extents, at most 65535 each", batch,
+                (M - 1) / 16 + 1);
     hipLaunchKernelGGL(matmul_kernel, dim3((N + 15) / 16, (M + 15) / 16, batch), dim3(16, 16), 0, stream, A,
                        a_batch_stride, B, b_batch_stride, C, M, N, K);
     FLAIR_LAUNCH_CHECK();

@@ -561,12 +561,13 @@ def depthwise_filter(x, filt, *, pad, out_stride=1, out_offset=0, stuff=1, stuff
     return out
 
 
-def jpeg_roundtrip(x, q_luma, q_chroma, dct8, want_levels=False, entry="hw"):
+def jpeg_roundtrip(x, q_luma, q_chroma, dct8, want_levels=False, entry="hw", out=None, levels=None, workspace=None):
     """x: (N,3,H,W) f32 in [-1,1], H and W multiples of 16; tables: python sequences / numpy arrays of 64 floats (host).
     want_levels: also return the quantised integer levels [luma (N,1,H,W), chroma (N,2,H/2,W/2)] (f32).
     entry: "hw" = flair_jpeg_roundtrip_hw (one launch, any H x W); "square" = the three-launch flair_jpeg_roundtrip
     with its workspace (H == W only).  The two agree bit for bit on squares (tests/test_gpu_rect.py) and "hw" is the
-    faster one (43.6 against 76.0 us at 10 x 3 x 128 x 128), so it serves every shape."""
+    faster one (43.6 against 76.0 us at 10 x 3 x 128 x 128), so it serves every shape.
+    out, levels = (luma, chroma) and workspace (square entry): optional contiguous f32 tensors of those shapes to write to."""
     N, C, H, W = x.shape
     assert C == 3 and x.dtype == torch.float32 and x.is_contiguous()
     if H % 16 or W % 16:
@@ -575,13 +576,20 @@ def jpeg_roundtrip(x, q_luma, q_chroma, dct8, want_levels=False, entry="hw"):
         raise ValueError(f"jpeg_roundtrip: unknown entry {entry!r}")
     arr = ctypes.c_float * 64
     tables = [arr(*[float(v) for v in t]) for t in (q_luma, q_chroma, dct8)]
-    out = torch.empty_like(x)
-    luma = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device) if want_levels else None
-    chroma = torch.empty((N, 2, H // 2, W // 2), dtype=torch.float32, device=x.device) if want_levels else None
+    if out is None:
+        out = torch.empty_like(x)
+    if levels is not None:
+        want_levels = True
+        luma, chroma = levels
+    else:
+        luma = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device) if want_levels else None
+        chroma = torch.empty((N, 2, H // 2, W // 2), dtype=torch.float32, device=x.device) if want_levels else None
+    for t, shape in ((out, (N, 3, H, W)), (luma, (N, 1, H, W)), (chroma, (N, 2, H // 2, W // 2)), (workspace, (N, 3, H, W))):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == shape), (t.shape, shape)
     if entry == "square":
         if H != W:
             raise ValueError(f"jpeg_roundtrip: the square entry cannot take {H}x{W}")
-        ws = torch.empty_like(x)
+        ws = torch.empty_like(x) if workspace is None else workspace
         call.flair_jpeg_roundtrip(x, N, H, *tables, ws, out, luma, chroma)
     else:
         call.flair_jpeg_roundtrip_hw(x, N, H, W, *tables, out, luma, chroma)

@@ -418,7 +418,8 @@ int flair_dcn_align(const flair_dcn_params* p, const void* x0, const void* x1, c
  * except at coordinates == stuff_offset (mod stuff) (zero-stuffing up-sampler).
  *   Down  : pad 4, out_stride 4, out_offset pre_stride;  InvHtH: pad 19;  Up: stuff 4.
  * reflect != 0 uses F.pad(mode="reflect") instead of replication (imresize_efficient, the
- * forward operator A: imresize_pseudoSR.py:163-178). */
+ * forward operator A: imresize_pseudoSR.py:163-178): one reflection only, as there -- a call whose taps reach more
+ * than size - 1 beyond a border of the (virtual) plane is refused. */
 int flair_depthwise_filter(const float* x, int planes, int Hin, int Win, const float* filt, int kh,
                            int kw, int pad, int out_stride, int out_offset, int stuff,
                            int stuff_offset, int Hout, int Wout, int reflect, float* y,
@@ -441,7 +442,8 @@ int flair_jpeg_roundtrip(const float* x, int N, int S, const float* q_luma, cons
 int flair_jpeg_roundtrip_hw(const float* x, int N, int H, int W, const float* q_luma, const float* q_chroma,
                             const float* dct8, float* y, float* luma_q, float* chroma_q, hipStream_t stream);
 /* C[b] = A[b] (MxK) * B[b] (KxN), row-major f32; a stride of 0 shares the matrix across the
- * batch.  SRConv's separable U/V products (restore_util.py:102-227). */
+ * batch.  SRConv's separable U/V products (restore_util.py:102-227).  batch and ceil(M / 16) are grid extents:
+ * at most 65535 each, refused beyond. */
 int flair_matmul_f32(const float* A, long a_batch_stride, const float* B, long b_batch_stride,
                      float* C, int batch, int M, int N, int K, hipStream_t stream);
 /* Resizer (resizer.py:54-73) along one axis of a tensor viewed [outer][Lin][inner]:
