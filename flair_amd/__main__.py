@@ -15,7 +15,8 @@ auto|PATH`` then treat every shot on its own.
 
 The options of the reference's ``main()`` keep their names and defaults (``scripts/video_sample.py:249-263``); the
 presets are its ``x8_bicubic_demo`` ... ``jpeg_demo`` commands (:500-556).  Several videos go through one call with
-``--output-root DIR`` (each to ``DIR/<video dir name>``); ``--frame-size HxW`` (or ``auto``) restores rectangular frames; under ``torch.distributed.run`` the videos are split over the
+``--output-root DIR`` (each to ``DIR/<video dir name>``); a YUV4MPEG2 stream (a path ending ``.y4m``, flair_amd.y4m) stands
+wherever a directory of frames does, as input of every command and as output of restore, degrade and interpolate; ``--frame-size HxW`` (or ``auto``) restores rectangular frames; under ``torch.distributed.run`` the videos are split over the
 ranks (flair_amd.pipeline.restore_many) and rank 0 reads the checkpoints once and ships them to the others.
 """
 import argparse
@@ -27,7 +28,45 @@ from . import pipeline as pl
 from . import scenes
 
 
+def _add_yuv(p, writes=False):
+    """The options of .y4m streams: what a stream's header leaves open and, for the commands that write one, its format."""
+    p.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default=None,
+                   help="colour matrix of .y4m streams, read and written; their header cannot say (default: bt601)")
+    p.add_argument("--yuv-range", choices=("limited", "full"), default=None,
+                   help="range of .y4m streams whose header has no XCOLORRANGE tag, and of written ones that follow no input "
+                        "stream (default: limited)")
+    if writes:
+        p.add_argument("--y4m-chroma", choices=("420jpeg", "420mpeg2", "422", "444"), default=None,
+                       help="chroma format of a written .y4m stream (default: the input stream's, else 420jpeg)")
+        p.add_argument("--fps", default=None, metavar="N[:D]",
+                       help="frame rate in a written .y4m stream's header (default: the input stream's, else 25:1)")
+
+
+def apply_yuv(args):
+    """Make a parsed command line's stream options the process-wide ones of flair_amd.y4m (a command line is complete: what it
+    does not say is the default, not what an earlier one said)."""
+    from . import y4m
+    try:
+        y4m.set_defaults(args.yuv_matrix or "bt601", args.yuv_range or "limited")
+        y4m.set_output(getattr(args, "y4m_chroma", None), getattr(args, "fps", None))
+    except ValueError as exc:
+        raise SystemExit(f"{args.command}: {exc}")
+
+
+def frames_exist(path):
+    """A directory of frame files, or a .y4m file."""
+    from .y4m import is_y4m
+    return os.path.isfile(path) if is_y4m(path) else os.path.isdir(path)
+
+
+def metrics_path(output):
+    """Where restore writes a video's scores: metrics.json in a directory of frames, <output>.metrics.json next to a stream."""
+    from .y4m import is_y4m
+    return output + ".metrics.json" if is_y4m(output) else os.path.join(output, "metrics.json")
+
+
 def _add_common(p):
+    _add_yuv(p, writes=True)
     p.add_argument("--weights", default="./checkpoints", metavar="DIR",
                    help="directory with flair_<task>.pt, the prior's checkpoint (codeformer.pth, RestoreFormer.ckpt or VQFR_v2.pth), "
                         "the detector and the parser's parsing_parsenet.pth / parsing_bisenet.pth")
@@ -304,7 +343,7 @@ def make_parser():
     sub = ap.add_subparsers(dest="command", required=True)
     r = sub.add_parser("restore", help="restore one video (VIDEO_DIR OUTPUT_DIR) or several (VIDEO_DIR... --output-root)")
     r.add_argument("task", choices=pl.TASK_NAMES)
-    r.add_argument("paths", nargs="+", metavar="PATH", help="VIDEO_DIR OUTPUT_DIR, or VIDEO_DIR... with --output-root")
+    r.add_argument("paths", nargs="+", metavar="PATH", help="VIDEO_DIR OUTPUT_DIR, or VIDEO_DIR... with --output-root; either may be a .y4m stream")
     r.add_argument("--output-root", default=None, metavar="DIR", help="write every VIDEO_DIR to DIR/<its name>")
     r.add_argument("--ground-truth", default=None, metavar="DIR",
                    help="clean frames of the video (with --output-root: a root holding one directory per video name): "
@@ -322,8 +361,8 @@ def make_parser():
         _add_common(d)
     g = sub.add_parser("degrade", help="clean frames -> the task's degraded frames, with the operator restore assumes")
     g.add_argument("task", choices=pl.TASK_NAMES)
-    g.add_argument("clean_dir", metavar="CLEAN_DIR", help="clean frames of one size valid for the task (--frame-size's rule)")
-    g.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png at 1/f of the size")
+    g.add_argument("clean_dir", metavar="CLEAN_DIR", help="directory or .y4m stream of clean frames of one size valid for the task (--frame-size's rule)")
+    g.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png at 1/f of the size; a path ending .y4m receives a stream")
     g.add_argument("--kernels", default=pl.DEFAULT_KERNELS, metavar="PATH",
                    help="the blur kernels .mat file (MATLAB v5) of the gaussian and jpeg tasks")
     g.add_argument("--jpeg-qf", type=int, default=None, metavar="Q", help="jpeg only: the codec's quality factor (default 60)")
@@ -331,6 +370,7 @@ def make_parser():
                    help="add white Gaussian noise of standard deviation S on the 0..255 scale before quantisation")
     g.add_argument("--seed", type=int, default=None, help="seed of the noise")
     g.add_argument("--device", default=None, help="default: cuda")
+    _add_yuv(g, writes=True)
     e = sub.add_parser("evaluate", help="PSNR / SSIM of written frames against ground truth")
     e.add_argument("restored_dir", metavar="RESTORED_DIR")
     e.add_argument("truth_dir", metavar="TRUTH_DIR", help="frames are paired with RESTORED_DIR's in natural order")
@@ -343,6 +383,7 @@ def make_parser():
     _add_warp_error(e, "also report")
     _add_cut_options(e, "with --warp-error: leave out the frame pairs that straddle a cut of TRUTH_DIR")
     _add_score_faces(e, "also report", own_detector=True)
+    _add_yuv(e)
     w = sub.add_parser("warp-error", help="flow-warping error (temporal consistency) of written frames without ground truth: one "
                                           "line per frame and the means")
     w.add_argument("frames_dir", metavar="FRAMES_DIR", help="frames of at least 32 pixels a side")
@@ -350,14 +391,19 @@ def make_parser():
     w.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the means as JSON")
     w.add_argument("--device", default=None, help="default: cuda")
     _add_cut_options(w, "leave out the frame pairs that straddle a cut")
+    _add_yuv(w)
     q = sub.add_parser("niqe", help="no-reference NIQE of written frames: one line per frame and the mean")
     q.add_argument("frames_dir", metavar="FRAMES_DIR", help="frames of at least two 96x96 blocks each")
     q.add_argument("--params", default=None, metavar="FILE", help="BasicSR's niqe_pris_params.npz (required)")
     q.add_argument("--json", default=None, metavar="PATH", help="also write the per-frame values and the mean as JSON")
     q.add_argument("--device", default=None, help="default: cuda")
-    i = sub.add_parser("interpolate", help="factor - 1 new frames between every two frames of a video (SuperSloMo or AMT-G)")
+    _add_yuv(q)
+    i = sub.add_parser("interpolate", help="factor - 1 new frames between every two frames of a video (SuperSloMo or AMT-G)",
+                       description="With a .y4m output the header's frame rate is the input's (or --fps) times --factor.  With .y4m in "
+                                   "and out the original frames are re-encoded from their RGB bytes: payloads are not passed "
+                                   "through byte for byte.")
     i.add_argument("src_dir", metavar="SRC_DIR", help="frames of one size")
-    i.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png, factor * (T - 1) + 1 of them")
+    i.add_argument("out_dir", metavar="OUT_DIR", help="receives {i:04d}.png, factor * (T - 1) + 1 of them; a path ending .y4m receives a stream")
     i.add_argument("--factor", type=int, required=True, metavar="N", help="frame-rate multiplier, >= 2")
     i.add_argument("--interpolator", choices=("superslomo", "amt-g"), default="superslomo",
                    help="the network: SuperSloMo (default) or AMT-G (fp32 only; frames whose coarsest correlation level is "
@@ -374,6 +420,7 @@ def make_parser():
     _add_warp_error(i, "also report")
     _add_cut_options(i, "synthesise nothing between the two frames of a cut: the in-betweens there are copies of the nearer "
                         "frame (--min-shot keeps its default of 4 here too)")
+    _add_yuv(i, writes=True)
     s = sub.add_parser("scenes", help="find the hard cuts of a video (block-luma distances; heuristic defaults, not validated "
                                       "on real footage) and write the cuts file restore / interpolate --scene-cuts PATH read",
                        description="Print one line per shot and, with --json, write the cuts file that restore / interpolate "
@@ -384,6 +431,7 @@ def make_parser():
     s.add_argument("--json", default=None, metavar="PATH", help='write {"cuts": [...], "distances": [...], "frames": n}')
     _add_cut_rule(s)
     s.add_argument("--device", default=None, help="default: cuda")
+    _add_yuv(s)
     return ap
 
 
@@ -418,11 +466,11 @@ def cuts_of(args, command, video_dirs):
 def scenes_of(args):
     """The refusals of a parsed ``scenes`` command line, before any GPU work -> (frame paths, rule)."""
     rule = rule_of(args, "scenes")
-    if not os.path.isdir(args.src_dir):
+    if not frames_exist(args.src_dir):
         raise SystemExit(f"scenes: {args.src_dir} is not a directory")
     from . import io as fio
-    paths = fio.list_frames(args.src_dir)
     try:
+        paths = fio.list_frames(args.src_dir)
         scenes.check_frames(paths)
     except ValueError as exc:
         raise SystemExit(f"scenes: {args.src_dir}: {exc}")
@@ -454,7 +502,7 @@ def interpolate_of(args):
         raise SystemExit(f"interpolate: {exc}")
     if args.json and not args.ground_truth and not args.niqe and not args.warp_error:
         raise SystemExit("interpolate: --json writes the scores of --ground-truth DIR")
-    if args.ground_truth and not os.path.isdir(args.ground_truth):
+    if args.ground_truth and not frames_exist(args.ground_truth):
         raise SystemExit(f"interpolate: ground truth {args.ground_truth} is not a directory")
     lpips_of(args, "interpolate")
     niqe_of(args, "interpolate")
@@ -537,11 +585,14 @@ def warp_error_of(args):
     if args.flow_weights is None:
         raise SystemExit(f"warp-error: --flow-weights FILE is required ({WARP_FILE}); nothing is shipped or downloaded")
     path = warp_of(args, "warp-error", option="--flow-weights")
-    if not os.path.isdir(args.frames_dir):
+    if not frames_exist(args.frames_dir):
         raise SystemExit(f"warp-error: {args.frames_dir} is not a directory")
     from . import io as fio
     from . import temporal as ftm
-    paths = fio.list_frames(args.frames_dir)
+    try:
+        paths = fio.list_frames(args.frames_dir)
+    except ValueError as exc:
+        raise SystemExit(f"warp-error: {exc}")
     if not paths:
         raise SystemExit(f"warp-error: no frame files in {args.frames_dir}")
     try:
@@ -581,7 +632,7 @@ def _niqe(args):
     if args.params is None:
         raise SystemExit("niqe: --params FILE is required (BasicSR's niqe_pris_params.npz); nothing is shipped or downloaded")
     path = niqe_of(args, "niqe", option="--params")
-    if not os.path.isdir(args.frames_dir):
+    if not frames_exist(args.frames_dir):
         raise SystemExit(f"niqe: {args.frames_dir} is not a directory")
     import torch
     torch.set_grad_enabled(False)
@@ -598,7 +649,7 @@ def degrade_of(args):
         raise SystemExit("degrade: --jpeg-qf is a quality factor in 1..100")
     if not args.noise_sigma >= 0:
         raise SystemExit("degrade: --noise-sigma must not be negative")
-    if not os.path.isdir(args.clean_dir):
+    if not frames_exist(args.clean_dir):
         raise SystemExit(f"degrade: {args.clean_dir} is not a directory")
     return dict(jpeg_qf=args.jpeg_qf, noise_sigma=args.noise_sigma, seed=args.seed)
 
@@ -614,7 +665,7 @@ def truth_of(args, jobs):
     else:
         truth = [os.path.join(root, os.path.basename(os.path.normpath(v))) for v, _ in jobs]
     for t in truth:
-        if not os.path.isdir(t):
+        if not frames_exist(t):
             raise SystemExit(f"restore: ground truth {t} is not a directory")
     return {o: t for (_, o), t in zip(jobs, truth)}
 
@@ -701,8 +752,14 @@ def jobs_of(args):
     else:
         jobs = [(v, os.path.join(args.output_root, os.path.basename(os.path.normpath(v)))) for v in args.paths]
     for v, _ in jobs:
-        if not os.path.isdir(v):
+        if not frames_exist(v):
             raise SystemExit(f"restore: {v} is not a directory")
+        if os.path.isfile(v):                           # a stream: its header's refusals come before any GPU work
+            from . import io as fio
+            try:
+                fio.list_frames(v)
+            except ValueError as exc:
+                raise SystemExit(f"restore: {exc}")
     return args.task, jobs
 
 
@@ -745,6 +802,7 @@ def size_of(args, task, jobs):
 
 def main(argv=None):
     args = make_parser().parse_args(argv)
+    apply_yuv(args)
     if args.command == "degrade":
         return _degrade(args)
     if args.command == "evaluate":
@@ -817,7 +875,7 @@ def main(argv=None):
                 print(f"{o}: mean of {result['count']} frames  psnr {result['mean']['psnr']:.4f}  "
                       f"ssim {result['mean']['ssim']:.4f}" + (f"  lpips {result['mean']['lpips']:.4f}" if lpips_model is not None else "")
                       + niqe_tail(result) + identity_tail(result) + warp_tail(result) + face_tail(result))
-                write_json(os.path.join(o, "metrics.json"), result)
+                write_json(metrics_path(o), result)
             elif niqe_model is not None or warp_model is not None:      # footage without a clean original: the no-reference scores alone
                 from . import niqe as fnq
                 from . import temporal as ftm
@@ -832,7 +890,7 @@ def main(argv=None):
                 head = (f"{o}: mean of {result['mean']['niqe_frames']} of {result['count']} frames" if niqe_model is not None
                         else f"{o}: mean of {result['mean']['warp_err_pairs']} pairs of {result['count']} frames")
                 print(head + niqe_tail(result) + warp_tail(result))
-                write_json(os.path.join(o, "metrics.json"), result)
+                write_json(metrics_path(o), result)
             return n
         pl.restore_many(jobs, restore_one)
     finally:

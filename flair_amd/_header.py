@@ -4,8 +4,8 @@ The header is the contract with libflair_hip.so; nothing of it is restated in Py
 a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ...])``; ``EVAL_PROTOS`` is the same table
 of include/flair_eval.h, the evaluation-only entries of the same library, ``NOREF_PROTOS`` that of include/flair_noref.h,
 the no-reference scores, ``IDENT_PROTOS`` that of include/flair_ident.h, the identity score, ``TEMPORAL_PROTOS`` that of
-include/flair_temporal.h, the flow-warping error, and ``FACESCORE_PROTOS`` that of include/flair_facescore.h, the face score's
-crop.  Only the constructs the header uses
+include/flair_temporal.h, the flow-warping error, ``FACESCORE_PROTOS`` that of include/flair_facescore.h, the face score's
+crop, and ``YUV_PROTOS`` that of include/flair_yuv.h, the video streams' colour conversion.  Only the constructs the header uses
 are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
 """
 import collections
@@ -140,3 +140,12 @@ _older = _older | set(TEMPORAL_PROTOS)
 if _facescore_structs or set(FACESCORE_PROTOS) & _older:
     raise HeaderError("flair_facescore.h declares a struct or an entry of another header: "
                       f"{sorted(_facescore_structs) + sorted(set(FACESCORE_PROTOS) & _older)}")
+
+# The video-stream ABI (include/flair_yuv.h: the colour conversion and chroma resampling of .y4m input and output), on the same terms.
+YUV_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "flair_yuv.h")
+with open(YUV_HEADER_PATH) as _f:
+    _yuv_structs, YUV_PROTOS = parse(_f.read())
+_older = _older | set(FACESCORE_PROTOS)
+if _yuv_structs or set(YUV_PROTOS) & _older:
+    raise HeaderError("flair_yuv.h declares a struct or an entry of another header: "
+                      f"{sorted(_yuv_structs) + sorted(set(YUV_PROTOS) & _older)}")

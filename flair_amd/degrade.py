@@ -85,7 +85,7 @@ def degrade_video_files(task, clean_dir, out_dir, *, device, kernel=None, jpeg_q
         gen.manual_seed(0 if seed is None else int(seed))
     batch = max(1, int(batch))
     groups = [(i, min(batch, len(paths) - i)) for i in range(0, len(paths), batch)]
-    writer = fio._Writer(out_dir)
+    writer = fio._Writer(out_dir, y4m=fio.y4m.output_params(fio.y4m.stream_of(paths)))
     written = 0
     try:
         for first, (u8,) in fio.iter_frame_batches([paths], groups, deg.device):

@@ -188,7 +188,10 @@ def check_source(src_dir, factor):
     """The refusals of the command line, before any GPU work: ValueError -> the frame paths and their (h, w)."""
     if isinstance(factor, bool) or int(factor) != factor or factor < 2:
         raise ValueError(f"--factor {factor} makes no frame: an integer >= 2")
-    if not os.path.isdir(src_dir):
+    if fio.is_y4m(src_dir):
+        if not os.path.isfile(src_dir):
+            raise ValueError(f"{src_dir} is not a file")
+    elif not os.path.isdir(src_dir):
         raise ValueError(f"{src_dir} is not a directory")
     paths = fio.list_frames(src_dir)
     if len(paths) < 2:
@@ -214,7 +217,7 @@ def interpolate_video_files(src_dir, out_dir, factor, *, net, device, batch=4, c
     cutset = set(scenes.check_cuts(cuts or [], T))
     # group g holds frames first .. first + n - 1: its pairs and the frame that closes the last of them
     groups = [(p, min(batch, T - 1 - p) + 1) for p in range(0, T - 1, batch)]
-    writer = fio._Writer(out_dir)
+    writer = fio._Writer(out_dir, y4m=fio.y4m.output_params(fio.y4m.stream_of(paths), rate=factor))
     try:
         for first, (u8,) in fio.iter_frame_batches([paths], groups, device):
             frames01 = u8.permute(0, 3, 1, 2).float() / 255.0

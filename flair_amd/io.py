@@ -14,6 +14,10 @@ results on the host and writes them at the end; here the three stages overlap:
 Windows of one video stay sequential (``prev_recon`` couples them); independent videos are the
 clip-parallel unit (``flair_amd.parallel``).  Host-side glue only: no arithmetic of the hot path
 happens here.
+
+A path that ends in ``.y4m`` is a YUV4MPEG2 stream (flair_amd.y4m) wherever a directory of frame files stands: list_frames
+gives one ``Y4MFrame`` per frame, the readers upload the file's payload bytes and turn them into RGB with
+flair_yuv_to_rgb_u8 on the side stream, and the writer turns RGB bytes into payloads with flair_rgb_to_yuv_u8.
 """
 import os
 import queue
@@ -24,6 +28,8 @@ import numpy as np
 import torch
 
 from . import video
+from . import y4m
+from .y4m import Y4MFrame, is_y4m
 
 _FRAME_RE = re.compile(r".*\.[jJpP][pPnN][gG]$")          # the reference's glob: jpg / png / jng / pnG ...
 
@@ -35,13 +41,75 @@ def natural_key(name):
 
 
 def list_frames(video_path):
-    """Frame files of a directory in the reference's order (video_sample.py:334)."""
+    """Frame files of a directory in the reference's order (video_sample.py:334); for a ``.y4m`` path (any case) one
+    Y4MFrame per frame of the stream."""
+    if is_y4m(video_path):
+        return y4m.frames_of(video_path)
     names = [n for n in os.listdir(video_path) if _FRAME_RE.match(n)]
     return [os.path.join(str(video_path), n) for n in sorted(names, key=natural_key)]
 
 
+def _need_gpu(ref, device):
+    if torch.device(device).type != "cuda":
+        raise ValueError(f"{ref}: the frames of a .y4m stream become RGB in flair_yuv_to_rgb_u8 on the GPU; there is no CPU colour "
+                         f"path (device {device})")
+
+
+def _y4m_runs(refs):
+    """Split a frame list into runs of one kind: (first, n, stream or None), Y4MFrames of one stream or frame files."""
+    runs = []
+    for i, r in enumerate(refs):
+        s = r.stream if isinstance(r, Y4MFrame) else None
+        if runs and runs[-1][2] is s:
+            runs[-1][1] += 1
+        else:
+            runs.append([i, 1, s])
+    return runs
+
+
+def _y4m_payloads(refs):
+    """The payloads of Y4MFrames of one stream in one pinned (n, payload) uint8 host tensor, one readinto per frame."""
+    stream = refs[0].stream
+    host = torch.empty((len(refs), stream.payload_bytes), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    rows = host.numpy()
+    for k, r in enumerate(refs):
+        stream.read_into(r.index, rows[k])
+    return host
+
+
+def _y4m_decode(refs, device, planar):
+    """Y4MFrames of one stream -> (n, h, w, 3) or, planar, (n, 3, h, w) uint8 on ``device``, enqueued on the CURRENT stream:
+    the upload of the file's bytes and flair_yuv_to_rgb_u8.  -> (device tensor, the pinned host tensor to keep alive)."""
+    from . import ops
+    stream = refs[0].stream
+    host = _y4m_payloads(refs)
+    dev = host.to(device, non_blocking=True)
+    return ops.yuv_to_rgb_u8(dev, (stream.height, stream.width), stream.format, stream.matrix, stream.range, planar=planar), host
+
+
+def _upload_group(refs, device, planar):
+    """One group of a frame list on the current (side) stream -> (uint8 device tensor, [host tensors to keep alive])."""
+    parts, keep = [], []
+    for first, n, stream in _y4m_runs(refs):
+        run = refs[first:first + n]
+        if stream is not None:
+            dev, host = _y4m_decode(run, device, planar)
+        else:
+            host = torch.from_numpy(np.stack([(decode_frame if planar else decode_frame_hwc)(p) for p in run])).pin_memory()
+            dev = host.to(device, non_blocking=True)
+        parts.append(dev)
+        keep.append(host)
+    return (parts[0] if len(parts) == 1 else torch.cat(parts)), keep
+
+
 def decode_frame_hwc(path):
-    """One frame file -> dense (h, w, 3) uint8 RGB, the layout of the files and of to_bytes."""
+    """One frame file -> dense (h, w, 3) uint8 RGB, the layout of the files and of to_bytes.  A Y4MFrame goes through
+    flair_yuv_to_rgb_u8 on the current device and comes back as host bytes: there is no CPU colour path."""
+    if isinstance(path, Y4MFrame):
+        if not torch.cuda.is_available():
+            _need_gpu(path, "cpu")
+        dev, _host = _y4m_decode([path], torch.device("cuda", torch.cuda.current_device()), False)
+        return np.ascontiguousarray(dev[0].cpu().numpy())
     from PIL import Image
     with Image.open(path) as im:
         return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
@@ -72,14 +140,23 @@ def write_frame(path, hwc_u8):
 
 class _Writer(threading.Thread):
     """Encodes finished frames in the background (PNG compression is host work that would otherwise sit
-    between two windows)."""
+    between two windows).  An ``output_path`` ending in ``.y4m`` opens a stream instead of a directory: the frames become
+    payloads in flair_rgb_to_yuv_u8 and the thread writes ``FRAME\\n`` and the payload in submission order (``first`` is not
+    looked at).  ``y4m``: y4m.output_params(...) of the stream to write, None for those of no input stream."""
 
-    def __init__(self, output_path):
+    def __init__(self, output_path, y4m=None):
         super().__init__(daemon=True)
         self.q = queue.Queue()
         self.output_path = str(output_path)
         self.error = None
-        os.makedirs(self.output_path, exist_ok=True)
+        self.file = self.params = self.size = None
+        if is_y4m(self.output_path):
+            from . import y4m as _y4m
+            self.params = dict(_y4m.output_params() if y4m is None else y4m)
+            os.makedirs(os.path.dirname(os.path.abspath(self.output_path)), exist_ok=True)
+            self.file = open(self.output_path, "wb")
+        else:
+            os.makedirs(self.output_path, exist_ok=True)
         self.start()
 
     def run(self):
@@ -91,6 +168,14 @@ class _Writer(threading.Thread):
             try:
                 if event is not None:
                     event.synchronize()                    # the asynchronous D2H copy has landed
+                if self.file is not None:
+                    if first is None:                      # the stream's header line
+                        self.file.write(host)
+                    else:
+                        for payload in host.numpy():
+                            self.file.write(y4m.FRAME)
+                            self.file.write(payload.data)
+                    continue
                 for i, frame in enumerate(host.numpy()):
                     write_frame(os.path.join(self.output_path, f"{first + i:04d}.png"), frame)
             except Exception as exc:                       # surfaced by close()
@@ -102,6 +187,8 @@ class _Writer(threading.Thread):
 
     def submit_bytes(self, first, u8):
         """u8: (n, H, W, 3) uint8 on the GPU (or host), written as they are."""
+        if self.file is not None:
+            return self._submit_stream(u8)
         if u8.is_cuda:
             host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(u8, non_blocking=True)
@@ -111,9 +198,35 @@ class _Writer(threading.Thread):
         else:
             self.q.put((first, u8, None))
 
+    def _submit_stream(self, u8):
+        """The frames as payloads of the stream: flair_rgb_to_yuv_u8 on the current stream (a host tensor is uploaded first),
+        an asynchronous copy to pinned memory, and the bytes to the writer thread.  The header goes first, once."""
+        from . import ops
+        if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != torch.uint8:
+            raise ValueError(f"{self.output_path}: frames are (n, H, W, 3) uint8, got {tuple(u8.shape)} {u8.dtype}")
+        if not u8.is_cuda:
+            if not torch.cuda.is_available():
+                raise ValueError(f"{self.output_path}: the frames of a .y4m stream are made in flair_rgb_to_yuv_u8 on the GPU; there is "
+                                 "no CPU colour path")
+            u8 = u8.pin_memory().to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+        p, size = self.params, tuple(u8.shape[1:3])
+        if self.size is None:
+            self.size = size
+            self.q.put((None, y4m.header_line(size[1], size[0], p["fps"], p["format"], p["range"], p["aspect"], p["extra"]), None))
+        elif size != self.size:
+            raise ValueError(f"{self.output_path}: frames of {size[0]}x{size[1]} in a stream of {self.size[0]}x{self.size[1]}")
+        payload = ops.rgb_to_yuv_u8(u8.contiguous(), p["format"], p["matrix"], p["range"])
+        host = torch.empty(payload.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(payload, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.q.put((0, host, ev))
+
     def close(self):
         self.q.put(None)
         self.join()
+        if self.file is not None:
+            self.file.close()
         if self.error is not None:
             raise self.error
 
@@ -127,10 +240,20 @@ def iter_windows(paths, device, length=video.FRAME_SLICE_LEN, overlap=video.OVER
     cache, q = {}, queue.Queue(maxsize=2)
     on_gpu = torch.device(device).type == "cuda"
     side = torch.cuda.Stream(device=device) if on_gpu else None
+    streamed = any(isinstance(p, Y4MFrame) for p in paths)
+    if streamed:
+        _need_gpu(next(p for p in paths if isinstance(p, Y4MFrame)), device)
 
     def produce():
         try:
             for w, idx in enumerate(wins):
+                if streamed:                                   # the file's bytes go up as they are; a window re-reads its overlap
+                    with torch.cuda.stream(side):
+                        dev_u8, keep = _upload_group([paths[i] for i in idx], device, True)
+                        ev = torch.cuda.Event()
+                        ev.record(side)
+                    q.put((idx, dev_u8, ev, keep))
+                    continue
                 for i in idx:
                     if i not in cache:
                         cache[i] = decode_frame(paths[i])
@@ -174,10 +297,21 @@ def iter_frame_batches(path_lists, groups, device):
     q = queue.Queue(maxsize=2)
     on_gpu = torch.device(device).type == "cuda"
     side = torch.cuda.Stream(device=device) if on_gpu else None
+    streamed = [any(isinstance(p, Y4MFrame) for p in paths) for paths in path_lists]
+    for paths, has in zip(path_lists, streamed):
+        if has:
+            _need_gpu(next(p for p in paths if isinstance(p, Y4MFrame)), device)
 
     def produce():
         try:
             for first, n in groups:
+                if any(streamed):                              # lists one by one: a stream's payloads through the kernel, files through PIL
+                    with torch.cuda.stream(side):
+                        got = [_upload_group(paths[first:first + n], device, False) for paths in path_lists]
+                        ev = torch.cuda.Event()
+                        ev.record(side)
+                    q.put((first, [d for d, _ in got], ev, [k for _, k in got]))
+                    continue
                 hosts = [torch.from_numpy(np.stack([decode_frame_hwc(p) for p in paths[first:first + n]]))
                          for paths in path_lists]
                 if on_gpu:
@@ -210,7 +344,9 @@ def iter_frame_batches(path_lists, groups, device):
 
 
 def frame_size(path):
-    """(h, w) of a frame file; only its header is read."""
+    """(h, w) of a frame file; only its header is read.  A Y4MFrame answers from its stream's header."""
+    if isinstance(path, Y4MFrame):
+        return path.stream.height, path.stream.width
     from PIL import Image
     with Image.open(path) as im:
         w, h = im.size
@@ -227,7 +363,7 @@ def restore_video_files(task, video_path, output_path, model, diffusion, restore
     window gets no ``prev_recon`` (video.window_plan).  Returns the number of frames written."""
     paths = list_frames(video_path)
     plan = video.window_plan(len(paths), cuts, length, overlap)            # refuses bad cuts before anything is decoded
-    writer = _Writer(output_path)
+    writer = _Writer(output_path, y4m=y4m.output_params(y4m.stream_of(paths)))
     prev_recon, written = None, 0
     try:
         for wi, (idx, degraded01) in enumerate(iter_windows(paths, device, length, overlap, cuts=cuts)):

@@ -1292,6 +1292,59 @@ def face_crop_u8(a, minv, minv_host, src_index, src_index_host, out_hw, *, b=Non
     return out_a if b is None else (out_a, out_b)
 
 
+# --------------------------------------------------------------------------- video streams (yuv.hip, include/flair_yuv.h)
+YUV_FORMATS = {"420jpeg": 0, "420mpeg2": 1, "422": 2, "444": 3, "mono": 4}
+YUV_MATRICES = {"bt601": 0, "bt709": 1}
+YUV_RANGES = {"limited": 0, "full": 1}
+from .y4m import payload_bytes as _yuv_payload_bytes  # noqa: E402  (W H + 2 wc hc: the size of one frame's payload)
+
+
+def _yuv_ids(what, fmt, matrix, range_):
+    _refuse(fmt in YUV_FORMATS, f"{what}: format {fmt!r}, one of {', '.join(YUV_FORMATS)}")
+    _refuse(matrix in YUV_MATRICES, f"{what}: matrix {matrix!r}, one of {', '.join(YUV_MATRICES)}")
+    _refuse(range_ in YUV_RANGES, f"{what}: range {range_!r}, one of {', '.join(YUV_RANGES)}")
+    return YUV_FORMATS[fmt], YUV_MATRICES[matrix], YUV_RANGES[range_]
+
+
+def yuv_to_rgb_u8(payload, hw, fmt, matrix, range_, *, planar=False, out=None):
+    """The frames of a .y4m stream as RGB bytes (flair_yuv_to_rgb_u8): payload (N, P) uint8 on the GPU with dense rows, exactly
+    the file's bytes Y | U | V of N frames of hw = (H, W) luma samples, at any byte alignment -> (N, H, W, 3) uint8, or
+    (N, 3, H, W) with ``planar``.  fmt: 420jpeg, 420mpeg2, 422, 444 or mono; matrix: bt601 or bt709; range_: limited or full.
+    The integer definition of include/flair_yuv.h: the same bits in every run."""
+    what = "yuv_to_rgb_u8"
+    ids = _yuv_ids(what, fmt, matrix, range_)
+    H, W = (int(v) for v in hw)
+    _refuse(H >= 1 and W >= 1, f"{what}: frames of {H}x{W} pixels")
+    P = _yuv_payload_bytes(fmt, H, W)
+    _refuse(payload.dim() == 2 and payload.dtype == torch.uint8 and payload.shape[1] == P and payload.is_contiguous(),
+            f"{what}: payload is a dense (N, {P}) uint8 tensor for {fmt} frames of {H}x{W}, got {tuple(payload.shape)} {payload.dtype}")
+    N = payload.shape[0]
+    shape = (N, 3, H, W) if planar else (N, H, W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=payload.device)
+    _refuse(out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape, f"{what}: out is a dense {shape} uint8 tensor, got {tuple(out.shape)} {out.dtype}")
+    if N:
+        call.flair_yuv_to_rgb_u8(payload, N, H, W, *ids, int(bool(planar)), out)
+    return out
+
+
+def rgb_to_yuv_u8(rgb, fmt, matrix, range_, *, out=None):
+    """RGB bytes as the payloads of a .y4m stream (flair_rgb_to_yuv_u8): rgb (N, H, W, 3) uint8 dense on the GPU -> (N, P) uint8,
+    every row Y | U | V of one frame, the encode of include/flair_yuv.h (chroma footprints clamped to the frame, rounded once)."""
+    what = "rgb_to_yuv_u8"
+    ids = _yuv_ids(what, fmt, matrix, range_)
+    _refuse(rgb.dim() == 4 and rgb.shape[3] == 3 and rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.shape[1] >= 1 and rgb.shape[2] >= 1,
+            f"{what}: rgb is a dense (N, H, W, 3) uint8 tensor, got {tuple(rgb.shape)} {rgb.dtype}")
+    N, H, W, _ = rgb.shape
+    P = _yuv_payload_bytes(fmt, H, W)
+    if out is None:
+        out = torch.empty((N, P), dtype=torch.uint8, device=rgb.device)
+    _refuse(out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (N, P), f"{what}: out is a dense {(N, P)} uint8 tensor, got {tuple(out.shape)} {out.dtype}")
+    if N:
+        call.flair_rgb_to_yuv_u8(rgb, N, H, W, *ids, out)
+    return out
+
+
 # --------------------------------------------------------------------------- scene cuts (scenes.hip)
 def block_luma_sums(u8, out=None):
     """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB
