@@ -26,6 +26,7 @@ import sys
 
 from . import pipeline as pl
 from . import scenes
+from .tiling import DEFAULT_OVERLAP, DEFAULT_TILE
 
 
 def _add_yuv(p, writes=False):
@@ -78,6 +79,18 @@ def _add_common(p):
                    help="rectangular frames of height H and width W (multiples of the task's frame multiple); the degraded "
                         "frames must be exactly H/f x W/f and are not resized; auto: the first frame's size times the "
                         "task's factor f.  Excludes a non-default --size")
+    p.add_argument("--tile", default="off", metavar="off|auto|HxW",
+                   help="tiled denoising (needs --frame-size): at every step the network runs on overlapping tiles of H x W pixels, "
+                        "clipped per axis to the frame, and the tile outputs are blended with feathered weights; everything else "
+                        "of a step stays on whole frames.  off (default): whole frames, with today's size rules; HxW: always "
+                        "tile; auto: tile at 512x512 only where the frame is refused whole (not a multiple of the task's frame "
+                        "multiple, or beyond the kernels' 32-bit limits, e.g. 1080x1920).  The frame's H and W must still be "
+                        "multiples of the task's factor (of 64 for jpeg) and hold one tile; frames are not padded.  Tiling costs "
+                        "work (the overlaps are denoised twice), faces cut by a seam get per-tile propagation weights in the "
+                        "bicubic tasks, and 512 with overlap 64 is a heuristic that has NOT been validated on real footage")
+    p.add_argument("--tile-overlap", type=int, default=DEFAULT_OVERLAP, metavar="P",
+                   help="with --tile: neighbouring tiles share at least P pixels, over which the blend ramps from one to the "
+                        "other (a multiple of the task's factor; default 64, a heuristic)")
     p.add_argument("--steps", type=int, default=100, help="sampler steps (respacing of the diffusion)")
     p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
     p.add_argument("--det-model", choices=tuple(pl.DETECTOR_FILES), default="retinaface_resnet50")
@@ -795,7 +808,33 @@ def size_of(args, task, jobs):
         size = pl.parse_frame_size(args.frame_size)
         if size == "auto":
             size = pl.auto_frame_size(task, jobs[0][0])
+        if getattr(args, "tile", "off") != "off":               # tile_of holds the tiled frame's refusals
+            from .video import frame_hw
+            return frame_hw(size)
         return pl.check_frame_size(task, size)
+    except ValueError as exc:
+        raise SystemExit(f"restore: {exc}")
+
+
+def tile_of(args, task, size):
+    """build_pipeline's ``tile`` / ``tile_overlap`` keywords for a parsed command line ({} for --tile off, the default: the
+    call of before).  --tile HxW tiles; --tile auto tiles at 512x512 only where the frame is refused whole.  The refusals
+    of the tiled frame come here, before any GPU work."""
+    if getattr(args, "tile", "off") == "off":
+        return {}
+    try:
+        tile = pl.parse_tile(args.tile)
+        if tile is None:
+            return {}
+        if args.frame_size is None:
+            raise ValueError("--tile needs --frame-size HxW or auto (tiles are cut from rectangular frames that are not resized)")
+        if tile == "auto":
+            from .video import FRAME_SLICE_LEN
+            if not pl.needs_tiling(task, size, frames=FRAME_SLICE_LEN, parser=args.parser, dtype=args.dtype):
+                return {}
+            tile = DEFAULT_TILE
+        _, tile = pl.check_tiled_frame_size(task, size, tile, args.tile_overlap, parser=args.parser, dtype=args.dtype)
+        return dict(tile=tile, tile_overlap=args.tile_overlap)
     except ValueError as exc:
         raise SystemExit(f"restore: {exc}")
 
@@ -825,6 +864,7 @@ def main(argv=None):
     prior = prior_of(args)
     faces = faces_of(args)
     size = size_of(args, task, jobs)
+    tiling = tile_of(args, task, size)
     how = cuts_of(args, "restore", [v for v, _ in jobs])
     import torch
     import torch.distributed as dist
@@ -844,7 +884,7 @@ def main(argv=None):
                               model_kwargs=json.loads(args.model_kwargs) if args.model_kwargs else None,
                               graph=not args.no_graph,
                               prior_kwargs=json.loads(args.prior_kwargs) if args.prior_kwargs else None,
-                              parser=args.parser)
+                              parser=args.parser, **tiling)
         hp = dict(aligned=args.aligned, t_start=args.t_start, jpeg_qf=args.jpeg_qf, w=args.w, tau=args.tau,
                   rho=args.rho, noise_level=args.noise_level, zeta=args.zeta, seed=args.seed)
         hp.update(faces)

@@ -5,7 +5,8 @@ a ``ctypes.Structure`` class, ``PROTOS`` an entry name to ``(restype, [Param, ..
 of include/flair_eval.h, the evaluation-only entries of the same library, ``NOREF_PROTOS`` that of include/flair_noref.h,
 the no-reference scores, ``IDENT_PROTOS`` that of include/flair_ident.h, the identity score, ``TEMPORAL_PROTOS`` that of
 include/flair_temporal.h, the flow-warping error, ``FACESCORE_PROTOS`` that of include/flair_facescore.h, the face score's
-crop, and ``YUV_PROTOS`` that of include/flair_yuv.h, the video streams' colour conversion.  Only the constructs the header uses
+crop, ``YUV_PROTOS`` that of include/flair_yuv.h, the video streams' colour conversion, and ``TILE_PROTOS`` that of
+include/flair_tile.h, the gather and blend of tiled denoising.  Only the constructs the header uses
 are understood, and anything else raises ``HeaderError`` with the offending text: a declaration is never skipped.
 """
 import collections
@@ -149,3 +150,12 @@ _older = _older | set(FACESCORE_PROTOS)
 if _yuv_structs or set(YUV_PROTOS) & _older:
     raise HeaderError("flair_yuv.h declares a struct or an entry of another header: "
                       f"{sorted(_yuv_structs) + sorted(set(YUV_PROTOS) & _older)}")
+
+# The tiling ABI (include/flair_tile.h: the gather and the feathered blend of tiled denoising), on the same terms.
+TILE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "flair_tile.h")
+with open(TILE_HEADER_PATH) as _f:
+    _tile_structs, TILE_PROTOS = parse(_f.read())
+_older = _older | set(YUV_PROTOS)
+if _tile_structs or set(TILE_PROTOS) & _older:
+    raise HeaderError("flair_tile.h declares a struct or an entry of another header: "
+                      f"{sorted(_tile_structs) + sorted(set(TILE_PROTOS) & _older)}")

@@ -1,7 +1,7 @@
 """ctypes binding of libflair_hip.so, derived from the C ABI's own headers (include/flair_hip.h, the evaluation-only
 include/flair_eval.h, the no-reference include/flair_noref.h, the identity score's include/flair_ident.h, the flow-warping
-error's include/flair_temporal.h, the face score's include/flair_facescore.h and the video streams' include/flair_yuv.h, read by
-_header.py).
+error's include/flair_temporal.h, the face score's include/flair_facescore.h, the video streams' include/flair_yuv.h and tiled
+denoising's include/flair_tile.h, read by _header.py).
 
 The library is the product path: there is no CPU or PyTorch fallback.  Loading fails
 loudly (``FlairHipUnavailable``) when the shared object has not been built.  ``lib()`` is the
@@ -14,14 +14,16 @@ import os
 
 import torch  # noqa: F401  (must be imported first: the library binds to torch's HIP runtime)
 
-from ._header import EVAL_PROTOS, FACESCORE_PROTOS, IDENT_PROTOS, NOREF_PROTOS, PROTOS, STRUCTS, TEMPORAL_PROTOS, YUV_PROTOS
+from ._header import (EVAL_PROTOS, FACESCORE_PROTOS, IDENT_PROTOS, NOREF_PROTOS, PROTOS, STRUCTS, TEMPORAL_PROTOS, TILE_PROTOS,
+                      YUV_PROTOS)
 
 # every declared entry of the library: the sampling path's (flair_hip.h), the evaluation-only ones (flair_eval.h) and the
 # no-reference scores (flair_noref.h)
 ALL_PROTOS = {**PROTOS, **EVAL_PROTOS, **NOREF_PROTOS}
 # ... and the identity score's (flair_ident.h), the flow-warping error's (flair_temporal.h), the face score's
-# (flair_facescore.h) and the video streams' (flair_yuv.h), typed and launched like the others from tables of their own
-_TYPED_PROTOS = {**ALL_PROTOS, **IDENT_PROTOS, **TEMPORAL_PROTOS, **FACESCORE_PROTOS, **YUV_PROTOS}
+# (flair_facescore.h), the video streams' (flair_yuv.h) and tiled denoising's (flair_tile.h), typed and launched like the others
+# from tables of their own
+_TYPED_PROTOS = {**ALL_PROTOS, **IDENT_PROTOS, **TEMPORAL_PROTOS, **FACESCORE_PROTOS, **YUV_PROTOS, **TILE_PROTOS}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libflair_hip.so")
@@ -127,7 +129,7 @@ class _Entries:
 
     def __getattr__(self, name):
         if name not in _LAUNCHES:
-            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream, nor one of flair_eval.h, flair_noref.h, flair_ident.h, flair_temporal.h, flair_facescore.h or flair_yuv.h")
+            raise AttributeError(f"{name} is not an entry of flair_hip.h that launches on a stream, nor one of flair_eval.h, flair_noref.h, flair_ident.h, flair_temporal.h, flair_facescore.h, flair_yuv.h or flair_tile.h")
         return functools.partial(_launch, name)
 
 

@@ -19,7 +19,9 @@ class ClipModel(PackedModel):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._flow_cache = {}
+        self._flow_cache_limit = 16   # entries before the cache clears itself; flair_amd.tiling raises it to its tiles for the length of a call
         self._graphs = {}
+        self._graph_clip_limit = None   # clips of a batch replayed from graphs, the rest launched eagerly (None: all; flair_amd.tiling)
         self.use_hip_graph = False
         self._flow_gen = 0         # the sampler's chain counter (reset_flow_cache)
         self._trace = None         # tests: a list here receives per-stage activations (and turns graphs off)
@@ -55,7 +57,7 @@ class ClipModel(PackedModel):
         if hit is None:
             flows = self._compute_flows(rnn_clip, spec)
             flows["_prop"] = {}              # per-clip store of composed second-order flows (BasicVSRPP._propagate)
-            if len(self._flow_cache) >= 16:
+            if len(self._flow_cache) >= self._flow_cache_limit:
                 self._flow_cache.clear()
             hit = (flows, rnn_clip)          # keep the keyed storage alive
             self._flow_cache[key] = hit
@@ -83,7 +85,7 @@ class ClipModel(PackedModel):
             xb, tb = (v[b * T:(b + 1) * T].float().contiguous() for v in (x, timesteps))
             lr, rnn = (v[b].float().contiguous() for v in (low_res_input, rnn_input))
             vw = vsrpp_weights[b] if isinstance(vsrpp_weights, torch.Tensor) else vsrpp_weights
-            if graphed:
+            if graphed and (self._graph_clip_limit is None or b < self._graph_clip_limit):
                 outs.append(self._forward_clip_graphed(xb, tb, lr, rnn, enable_cross_frames, vw, b))
             else:
                 outs.append(self._forward_clip(xb, tb, lr, self._clip_flows(rnn, xb, enable_cross_frames),

@@ -357,7 +357,8 @@ def restore_video_files(task, video_path, output_path, model, diffusion, restore
                         length=video.FRAME_SLICE_LEN, overlap=video.OVERLAP, aligned=True, face_helper=None, cuts=None, **kw):
     """``scripts/video_sample.py:334-492`` end to end: frame files in, restored ``{i:04d}.png`` out, with
     decode / upload / sampling / download / encode overlapped.  ``kw`` goes to ``video.restore_window``
-    (aux_model, vsrpp_weights_fn, hp, tau, t_start, noise_fn, q_noise_fn, faces, max_faces).  ``aligned=False`` detects every window's
+    (aux_model, vsrpp_weights_fn, hp, tau, t_start, noise_fn, q_noise_fn, faces, max_faces, and tile / tile_overlap: tiled
+    denoising of frames the network cannot take whole, flair_amd.tiling).  ``aligned=False`` detects every window's
     faces on the main thread before its first step (video.window_faces) while the reader thread decodes the next
     window.  ``cuts`` (None = one shot): frames that start a new shot; every shot is windowed on its own and its first
     window gets no ``prev_recon`` (video.window_plan).  Returns the number of frames written."""

@@ -1345,6 +1345,75 @@ def rgb_to_yuv_u8(rgb, fmt, matrix, range_, *, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- tiled denoising (tile.hip, include/flair_tile.h)
+_tile_origin_arrays = {}
+
+
+def _tile_origins(what, name, origins, t, L, device, cover):
+    """A plan's origins along one axis as the int32 device array the kernels read, uploaded once per (device, origins).  The host
+    list is checked first: every tile inside the axis and, for the blend (``cover``), every pixel under a tile."""
+    key = tuple(int(o) for o in origins)
+    _refuse(len(key) >= 1 and all(0 <= o <= L - t for o in key),
+            f"{what}: {name} = {list(key)}: every tile of {t} pixels must lie inside the axis of {L}")
+    if cover:
+        reach = 0
+        for o in sorted(key):
+            _refuse(o <= reach, f"{what}: {name} = {list(key)} with tiles of {t} pixels leaves pixel {reach} of {L} uncovered")
+            reach = max(reach, o + t)
+        _refuse(reach >= L, f"{what}: {name} = {list(key)} with tiles of {t} pixels leaves pixel {reach} of {L} uncovered")
+    k = (str(device), key)
+    if k not in _tile_origin_arrays:
+        if len(_tile_origin_arrays) >= 64:
+            _tile_origin_arrays.clear()
+        _tile_origin_arrays[k] = torch.tensor(key, dtype=torch.int32, device=device)
+    return _tile_origin_arrays[k]
+
+
+def _dense_f32(t):
+    return t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
+
+
+def tile_gather(frame, oy, ox, tile_hw, out=None):
+    """Whole frames -> overlapping tiles (flair_tile_gather_f32), a plain copy: frame (N, C, H, W) f32 dense on the GPU (a dense view
+    at any offset will do); oy / ox: the tile rows' and columns' origins (host ints); tile_hw = (th, tw) -> (len(oy) len(ox) N, C, th,
+    tw), the tile index major and row-major over (oy, ox): out[(r len(ox) + c) N + n] = frame[n, :, oy[r]:oy[r] + th, ox[c]:ox[c] + tw]."""
+    what = "tile_gather"
+    _refuse(_dense_f32(frame), f"{what}: frame is a dense (N, C, H, W) float32 tensor, got {tuple(frame.shape)} {frame.dtype}")
+    N, C, H, W = frame.shape
+    th, tw = (int(v) for v in tile_hw)
+    _refuse(N >= 1 and C >= 1 and 1 <= th <= H and 1 <= tw <= W, f"{what}: tiles of {th}x{tw} of frames {tuple(frame.shape)}")
+    dy, dx = _tile_origins(what, "oy", oy, th, H, frame.device, False), _tile_origins(what, "ox", ox, tw, W, frame.device, False)
+    shape = (len(oy) * len(ox) * N, C, th, tw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=frame.device)
+    _refuse(_dense_f32(out) and tuple(out.shape) == shape, f"{what}: out is a dense {shape} float32 tensor, got {tuple(out.shape)} {out.dtype}")
+    call.flair_tile_gather_f32(frame, N, C, H, W, dy, len(oy), dx, len(ox), th, tw, out)
+    return out
+
+
+def tile_blend(tiles, oy, ox, frame_hw, ramp, out=None):
+    """Tiles -> whole frames with feathered weights (flair_tile_blend_f32; include/flair_tile.h holds the definition): tiles
+    (len(oy) len(ox) N, C, th, tw) f32 dense on the GPU in tile_gather's order -> (N, C, H, W) for frame_hw = (H, W).  ``ramp``: the
+    width in pixels over which a tile's weight rises from its inner edges (the plan's minimum overlap).  Any number of tiles may
+    cover a pixel; every pixel must be covered.  The same bits in every run; a pixel under one tile is that tile's value."""
+    what = "tile_blend"
+    _refuse(_dense_f32(tiles), f"{what}: tiles is a dense (K N, C, th, tw) float32 tensor, got {tuple(tiles.shape)} {tiles.dtype}")
+    KN, C, th, tw = tiles.shape
+    H, W = (int(v) for v in frame_hw)
+    K = len(oy) * len(ox)
+    _refuse(K >= 1 and KN >= K and KN % K == 0 and C >= 1, f"{what}: {KN} tile planes for a plan of {len(oy)}x{len(ox)} tiles")
+    _refuse(1 <= th <= H and 1 <= tw <= W, f"{what}: tiles of {th}x{tw} for frames of {H}x{W}")
+    _refuse(int(ramp) >= 1, f"{what}: ramp = {ramp} pixels, at least 1")
+    N = KN // K
+    dy, dx = _tile_origins(what, "oy", oy, th, H, tiles.device, True), _tile_origins(what, "ox", ox, tw, W, tiles.device, True)
+    shape = (N, C, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=tiles.device)
+    _refuse(_dense_f32(out) and tuple(out.shape) == shape, f"{what}: out is a dense {shape} float32 tensor, got {tuple(out.shape)} {out.dtype}")
+    call.flair_tile_blend_f32(tiles, N, C, H, W, dy, len(oy), dx, len(ox), th, tw, int(ramp), out)
+    return out
+
+
 # --------------------------------------------------------------------------- scene cuts (scenes.hip)
 def block_luma_sums(u8, out=None):
     """Exact integer luma sums over an 8 x 8 grid of blocks per frame (flair_block_luma_sums): u8 (N, H, W, 3) uint8 dense RGB

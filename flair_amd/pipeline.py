@@ -22,6 +22,7 @@ from . import io as fio
 from . import ops
 from . import parallel
 from . import scenes
+from . import tiling
 from . import video
 from . import workload as wl
 from .guided_diffusion import gaussian_diffusion as gd
@@ -178,6 +179,67 @@ def check_frame_size(task, size, frames=None, parser=None, dtype="bf16"):
     return H, W
 
 
+def tile_multiple(task, parser=None):
+    """What a tile's sides must be multiples of: frame_multiple(task) and, for the bicubic tasks, the parser's stride (the parser
+    reads every tile's init frames for the propagation weights)."""
+    import math
+    m = frame_multiple(task)
+    return math.lcm(m, PARSER_MULTIPLE[parser]) if parser is not None and "bicubic" in task else m
+
+
+def parse_tile(text):
+    """--tile: ``"off"`` -> None, ``"auto"`` -> ``"auto"``, ``"HxW"`` -> (H, W)."""
+    t = str(text).strip().lower()
+    if t == "off":
+        return None
+    if t == "auto":
+        return "auto"
+    try:
+        return parse_frame_size(t)
+    except ValueError:
+        raise ValueError(f"tile {text!r}: off, auto or HxW with positive integers (height first)") from None
+
+
+def check_tiled_frame_size(task, size, tile, tile_overlap=tiling.DEFAULT_OVERLAP, frames=None, parser=None, dtype="bf16"):
+    """Refuse a frame size tiled denoising cannot restore, and choose the tile: per axis min(requested, the largest multiple of
+    tile_multiple(task, parser) the axis holds).  The frame's H and W must be multiples of the task's factor (tile origins lie on
+    the low-resolution grid) and hold at least one tile of frame_minimum(task); the jpeg task keeps frame_multiple(task) for the
+    FRAME, because the codec's MCU grid is the frame's and not the tile's.  The tile itself then passes check_frame_size: its
+    multiples, the parser's stride and -- given ``frames`` -- the window's 32-bit limits hold for the tile, and
+    video.check_tiled_frame_elements for the frame.  Returns ((H, W), (th, tw))."""
+    _check_task(task)
+    H, W = video.frame_hw(size)
+    f = wl.TASKS[task]["factor"]
+    if H % f or W % f:
+        raise ValueError(f"{task}: tiled frames of {H}x{W}: H and W must be multiples of the factor {f} (the degraded frames are "
+                         f"{H // f}x{W // f} at best; frames are not padded or cropped for you)")
+    if task == "jpeg" and (H % frame_multiple(task) or W % frame_multiple(task)):
+        raise ValueError(f"jpeg: tiled frames of {H}x{W}: H and W must stay multiples of {frame_multiple(task)}, because the codec's "
+                         "16x16 MCU grid on the degraded frames is the frame's, not the tile's")
+    m, lo = tile_multiple(task, parser), frame_minimum(task)
+    req = video.frame_hw(tile)
+    th, tw = tiling.tile_side(H, req[0], m), tiling.tile_side(W, req[1], m)
+    if min(th, tw) < lo or min(th, tw) < m:
+        raise ValueError(f"{task}: frames of {H}x{W} with tiles of {req[0]}x{req[1]}: a tile's sides are multiples of {m} and at least "
+                         f"{lo}, and the frame must hold one; frames smaller than a tile are not padded")
+    check_frame_size(task, (th, tw), frames=frames, parser=parser, dtype=dtype)
+    p = int(tile_overlap)
+    if p < f or p % f or p >= min(th, tw):
+        raise ValueError(f"{task}: tile overlap {tile_overlap}: a positive multiple of the factor {f} below the tile's sides {th}x{tw}")
+    if frames is not None:
+        video.check_tiled_frame_elements(task, frames, H, W, tiling.make_plan((H, W), (th, tw), p, f))
+    return (H, W), (th, tw)
+
+
+def needs_tiling(task, size, frames=None, parser=None, dtype="bf16"):
+    """--tile auto: True when check_frame_size refuses the frame whole."""
+    try:
+        check_frame_size(task, size, frames=frames, parser=parser, dtype=dtype)
+    except ValueError:
+        return True
+    return False
+
+
 def model_config(task, size=512):
     """MODEL_CONFIG[task] for clips of ``size`` x ``size``: the attention / propagation resolutions scale with the size
     as in workload.sr3_config / script_util.blur_unet_config (at 512 this is the reference's table).  A pair (H, W)
@@ -256,10 +318,12 @@ class Pipeline:
     """One task's networks and operators on one device; ``restore_video_files`` runs the reference's window loop over a
     directory of frames (flair_amd.io.restore_video_files)."""
 
-    def __init__(self, task, model, diffusion, A_func, face_helper, aux_model, vsrpp_weights_fn, size, device, prior=None):
+    def __init__(self, task, model, diffusion, A_func, face_helper, aux_model, vsrpp_weights_fn, size, device, prior=None,
+                 tile=None, tile_overlap=tiling.DEFAULT_OVERLAP):
         self.task, self.model, self.diffusion, self.A_func = task, model, diffusion, A_func
         self.face_helper, self.aux_model, self.vsrpp_weights_fn = face_helper, aux_model, vsrpp_weights_fn
         self.size, self.device, self.prior = size, torch.device(device), prior
+        self.tile, self.tile_overlap = tile, tile_overlap          # tiled denoising (flair_amd.tiling): None = whole frames
 
     def check_aligned(self, aligned):
         """aligned=True hands whole frames to the prior, which restores 512 x 512 faces: with a size pair and a prior the
@@ -315,7 +379,7 @@ class Pipeline:
             self.task, video_path, output_path, self.model, self.diffusion, self.restore_fn_for(jpeg_qf), size=self.size,
             device=self.device, aligned=aligned, face_helper=self.face_helper, aux_model=self.aux_model,
             vsrpp_weights_fn=self.vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, faces=faces, max_faces=max_faces,
-            cuts=cuts)
+            cuts=cuts, **({} if self.tile is None else dict(tile=self.tile, tile_overlap=self.tile_overlap)))
 
 
 def build_operator(task, size, device, kernel=None):
@@ -338,7 +402,8 @@ def build_operator(task, size, device, kernel=None):
 
 
 def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=100, kernels_path=None, prior=True,
-                   det_model="retinaface_resnet50", model_kwargs=None, graph=True, prior_kwargs=None, parser="parsenet"):
+                   det_model="retinaface_resnet50", model_kwargs=None, graph=True, prior_kwargs=None, parser="parsenet",
+                   tile=None, tile_overlap=tiling.DEFAULT_OVERLAP):
     """Build ``task``'s Pipeline from the checkpoints in ``weights_dir``: ``flair_{task}.pt``, the prior's checkpoint,
     the detector's ``detection_Resnet50_Final.pth`` / ``detection_mobilenet0.25_Final.pth`` / ``yolov5l-face.pth`` /
     ``yolov5n-face.pth`` (``det_model``: the RetinaFace bodies or the YOLOv5-face detectors) and the parser's
@@ -347,7 +412,10 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     input is resized to S x S; a prior needs S = 512); a pair (H, W) restores rectangular frames: H and W multiples of
     frame_multiple(task), degraded frames of exactly (H/f, W/f), the network in its literal 512 layout, and the face
     helper at face size 512 whenever a prior is configured, whatever the frame size (check_frame_size holds the
-    refusals).  ``model_kwargs`` overrides entries of MODEL_CONFIG[task]
+    refusals).  ``tile`` = (th, tw) (needs a size pair; None, the default, restores whole frames exactly as before): the network
+    runs on overlapping tiles sharing at least ``tile_overlap`` pixels, clipped per axis to the frame, and the tile outputs are
+    blended at every step (flair_amd.tiling); check_tiled_frame_size holds the refusals, and check_frame_size then applies to
+    the tile.  ``model_kwargs`` overrides entries of MODEL_CONFIG[task]
     (checkpoints of other widths).  ``kernels_path``: the reference's ``miscs/kernels_12.mat`` (gaussian and jpeg tasks).
 
     ``prior``: ``"codeformer"`` (or True, the default) reads ``codeformer.pth`` (its ``params_ema``);
@@ -374,7 +442,11 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
         raise ValueError(f"dtype={dtype!r}: 'bf16' or 'fp32'")
     prior = prior_name(prior)
     pair = video.is_pair(size)
-    if pair:
+    if tile is not None:
+        if not pair:
+            raise ValueError(f"tile={tile!r} needs a size pair (H, W): size={size!r} resizes every frame to a square")
+        size, tile = check_tiled_frame_size(task, size, tile, tile_overlap, frames=video.FRAME_SLICE_LEN, parser=parser, dtype=dtype)
+    elif pair:
         size = check_frame_size(task, size, frames=video.FRAME_SLICE_LEN, parser=parser, dtype=dtype)
     if prior is not None and not pair and size != 512:
         raise ValueError(f"the {PRIOR_LABELS[prior]} prior restores 512 x 512 faces (its code grid is 16 x 16): size={size} needs "
@@ -455,7 +527,8 @@ def build_pipeline(task, weights_dir, *, device, size=512, dtype="bf16", steps=1
     elif prior == "vqfrv2":
         aux = wl.vqfr_aux(gan, fidelity_ratio)
     diffusion = create_diffusion(task, steps)
-    return Pipeline(task, model, diffusion, A_func, helper, aux, weights_fn, size, device, prior=prior)
+    return Pipeline(task, model, diffusion, A_func, helper, aux, weights_fn, size, device, prior=prior, tile=tile,
+                    tile_overlap=tile_overlap)
 
 
 def restore_many(jobs, restore_one, *, log=print):

@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from . import scenes
+from . import tiling
 from . import workload as wl
 
 FRAME_SLICE_LEN = 10   # scripts/video_sample.py:202
@@ -146,6 +147,60 @@ def check_clip_elements(T, H, W, dtype=torch.bfloat16, channels=OFFSET_CHANNELS)
                          f"addresses at most {max_clip_pixels()} (2 GiB): use shorter windows")
 
 
+# Tiled denoising (flair_amd.tiling; DESIGN section 7, "Tiled denoising").  With ``tile=`` the two limits above bound the TILE, and
+# the frame is bounded only by the whole-frame consumers of the sampler path.  All of them index with 64 bits; what is left:
+#   * ops.resize (init_frames, rnn_input), flair_warp_affine_cubic_indexed and paste_faces compute pixel coordinates in f32, where
+#     integers + 0.5 are exact below 2^23: a side of at most 2^23 - 1 pixels;
+#   * the blur tasks' operator: flair_depthwise_filter's inverse filter on the low-resolution grid counts its T * 3 * ceil(h / 32) *
+#     ceil(w / 32) workgroups in an int, the codec (flair_jpeg_roundtrip_hw) one workgroup per 10 MCUs of 16 x 16: below 2^31,
+#     which the blend's limit below implies (it launches 5 and 40 times as many workgroups on the same window);
+#   * the bicubic tasks' operator: flair_matmul_f32 puts ceil(H / 16) row blocks and the T * 3 planes on grid axes of at most 65535;
+#   * flair_tile_gather_f32 / flair_tile_blend_f32: one launch of at most 2^31 - 1 workgroups of 256 threads, 4 pixels a thread
+#     (the blend's counted per frame, the gather's per plane of a tile: check_tiled_frame_elements checks both);
+#   * nchw_to_clip / clip_to_nchw, affine_channels and the sampler's element-wise kernels are grid-stride loops over 64-bit
+#     counts: no limit of their own.
+MAX_TILED_SIDE = 2 ** 23 - 1
+MAX_WORKGROUPS = 2 ** 31 - 1
+MATMUL_GRID_AXIS = 65535
+
+
+def check_tiled_frame_elements(task, T, H, W, plan=None):
+    """Refuse, by the consumer's name, a window of ``T`` whole frames of H x W that a whole-frame kernel of the tiled sampler path
+    cannot index (the list above).  ``plan`` (a tiling.TilePlan): also the gather's launch, whose workgroups are counted per
+    plane of a tile (three channels: x, low_res_input, rnn_input).  Raised before the first launch."""
+    if plan is not None and plan.n_tiles * T * 3 * -(-plan.th * -(-plan.tw // 4) // 256) > MAX_WORKGROUPS:
+        raise ValueError(f"a window of {T} frames in {plan.n_tiles} tiles of {plan.th}x{plan.tw} exceeds one launch of "
+                         f"flair_tile_gather_f32 ({MAX_WORKGROUPS} workgroups): use shorter windows or larger tiles")
+    if max(H, W) > MAX_TILED_SIDE:
+        raise ValueError(f"frames of {H}x{W}: ops.resize and the face warps (flair_warp_affine_cubic_indexed, paste_faces) compute "
+                         f"pixel coordinates in f32, exact up to {MAX_TILED_SIDE} pixels a side")
+    if T * -(-H * -(-W // 4) // 256) > MAX_WORKGROUPS:
+        raise ValueError(f"a window of {T} frames of {H}x{W} exceeds one launch of flair_tile_blend_f32 ({MAX_WORKGROUPS} workgroups "
+                         "of 1024 pixels): use shorter windows")
+    if "bicubic" in task and (-(-H // 16) > MATMUL_GRID_AXIS or T * 3 > MATMUL_GRID_AXIS):
+        raise ValueError(f"a window of {T} frames of {H}x{W}: the bicubic operator's flair_matmul_f32 takes at most "
+                         f"{MATMUL_GRID_AXIS * 16} rows and {MATMUL_GRID_AXIS} planes")
+
+
+def tiled_model(task, model, size, tile, tile_overlap, frames, vsrpp_weights_fn=None):
+    """``model`` wrapped for tiled denoising of ``size`` = (H, W) frames with tiles of ``tile`` = (th, tw) sharing at least
+    ``tile_overlap`` pixels (flair_amd.tiling.TiledModel).  Origins are multiples of the task's factor, so H, W, th, tw and the
+    overlap must be.  The window limits of check_clip_elements hold for the tile, check_tiled_frame_elements for the frame; a
+    frame smaller than one tile is refused (frames are not padded)."""
+    if not is_pair(size):
+        raise ValueError(f"tile={tile!r} needs a size pair (H, W); size={size!r} resizes every frame to a square")
+    (H, W), (th, tw) = frame_hw(size), frame_hw(tile)
+    if th > H or tw > W:
+        raise ValueError(f"{task}: frames of {H}x{W} are smaller than one tile of {th}x{tw}; frames are not padded: use a smaller tile")
+    try:
+        plan = tiling.make_plan((H, W), (th, tw), tile_overlap, wl.TASKS[task]["factor"])
+    except ValueError as exc:
+        raise ValueError(f"{task}: tiles of {th}x{tw} with overlap {tile_overlap} on frames of {H}x{W}: {exc}") from exc
+    check_clip_elements(frames, th, tw, dtype=getattr(model, "dtype", torch.bfloat16), channels=offset_channels(model))
+    check_tiled_frame_elements(task, frames, H, W, plan)
+    return tiling.TiledModel(model, plan, vsrpp_weights_fn)
+
+
 def init_frames(task, degraded01, size):
     """INIT_FUNC (video_sample.py:158-163) followed by the (x - 0.5) / 0.5 of :372-373: bicubic for the
     bicubic tasks, ``area`` (= block replication when upscaling by an integer factor) for the blur tasks,
@@ -219,7 +274,7 @@ def window_faces(face_helper, init_n, window_index=0, frame_indices=None, faces=
 def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, prev_recon=None, overlap=OVERLAP,
                    window_index=0, aux_model=wl.identity_aux, vsrpp_weights_fn=None, hp=None, tau=5, t_start=-1,
                    noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, frame_indices=None, faces="largest",
-                   max_faces=None):
+                   max_faces=None, tile=None, tile_overlap=tiling.DEFAULT_OVERLAP):
     """One window of the loop (video_sample.py:371-485).  degraded01: (1, T, 3, h, w) in [0, 1] on the GPU;
     prev_recon: the previous window's last ``overlap`` results ((1, <=overlap, 3, S, S), [-1, 1] domain) or None.
     ``aligned=False`` (the reference's default, :275) detects the faces of the window's init frames with
@@ -229,6 +284,9 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
     ``size``: an int S (every frame is resized to S x S, as in the reference) or a pair (H, W): the degraded frames must
     be exactly (H/f, W/f), and aligned=False crops the faces to the helper's face size -- which is then independent of
     the frame size -- and pastes them back with paste_faces (faces="largest" passes face_frames = 0..T-1 itself).
+    ``tile`` = (th, tw) (ours; needs a size pair): the network runs on overlapping th x tw tiles sharing at least ``tile_overlap``
+    pixels and the tile outputs are blended into the whole-frame model output at every step (tiled_model); everything else of
+    the step stays on whole frames.  The window limits then hold for the tile, and ``vsrpp_weights_fn`` is applied per tile.
     Returns (frames01 of the frames this window contributes, (T', 3, H, W) in [0, 1]; next prev_recon)."""
     hp = hp or wl.TASKS[task]
     dev = degraded01.device
@@ -236,8 +294,11 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
     pair = is_pair(size)
     if pair:                                                                      # refusals come before the first launch
         check_degraded(task, degraded01.shape[-2:], size)
-        check_clip_elements(degraded01.shape[1], *frame_hw(size), dtype=getattr(model, "dtype", torch.bfloat16),
-                            channels=offset_channels(model))
+        if tile is None:
+            check_clip_elements(degraded01.shape[1], *frame_hw(size), dtype=getattr(model, "dtype", torch.bfloat16),
+                                channels=offset_channels(model))
+    if tile is not None:
+        model = tiled_model(task, model, size, tile, tile_overlap, degraded01.shape[1], vsrpp_weights_fn)
     deg = degraded01[0].float().contiguous()                                      # (T,3,h,w) in [0,1]
     T = deg.shape[0]
     init_n = init_frames(task, deg, size)[None]                                   # (1,T,3,S,S) in [-1,1]
@@ -260,8 +321,11 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
     tt = torch.full((T,), t0, device=dev, dtype=torch.long)
     qn = q_noise_fn(wi, init_n[0]) if q_noise_fn is not None else None
     noise = diffusion.q_sample(init_n[0].contiguous(), tt, noise=qn)
-    kwargs = dict(low_res_input=init_n, num_frames=T, enable_cross_frames=True,
-                  vsrpp_weights=vsrpp_weights_fn(init_n) if vsrpp_weights_fn is not None else 1.0)
+    if tile is not None:                          # the tiled model parses every tile's init frames itself
+        weights = None if vsrpp_weights_fn is not None else 1.0
+    else:
+        weights = vsrpp_weights_fn(init_n) if vsrpp_weights_fn is not None else 1.0
+    kwargs = dict(low_res_input=init_n, num_frames=T, enable_cross_frames=True, vsrpp_weights=weights)
     if "bicubic" not in task:
         kwargs["rnn_input"] = rnn_input(deg_n_clip, size)[None]
     sample = diffusion.sample(
@@ -279,7 +343,8 @@ def restore_window(task, degraded01, model, diffusion, restore_fn_for, *, size, 
 
 def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, aux_model=wl.identity_aux,
                   vsrpp_weights_fn=None, hp=None, tau=5, t_start=-1, length=FRAME_SLICE_LEN, overlap=OVERLAP,
-                  noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, faces="largest", max_faces=None, cuts=None):
+                  noise_fn=None, q_noise_fn=None, aligned=True, face_helper=None, faces="largest", max_faces=None, cuts=None,
+                  tile=None, tile_overlap=tiling.DEFAULT_OVERLAP):
     """degraded01: (1, N, 3, h, w) frames in [0, 1] on the GPU.  Returns (N, 3, H, W) in [0, 1] for ``size`` = an int
     S (H = W = S) or a pair (H, W) (see restore_window).
 
@@ -287,7 +352,7 @@ def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, a
     operator of the window (video_sample.py:455-459); vsrpp_weights_fn(init_norm (1,T,3,S,S)) supplies
     the per-pixel propagation weights of the bicubic tasks (face parsing, :427-444) and defaults to 1.0;
     noise_fn / q_noise_fn(window_index, like) let tests share one noise tape with the oracle; aligned / face_helper /
-    faces / max_faces: see restore_window.  ``cuts`` (ours; None = one shot, exactly the reference's loop): frames that start
+    faces / max_faces / tile / tile_overlap: see restore_window.  ``cuts`` (ours; None = one shot, exactly the reference's loop): frames that start
     a new shot (flair_amd.scenes).  Every shot is windowed on its own (window_plan): its first window gets no prev_recon and
     contributes all its frames, while window_index keeps counting over the whole video (noise_fn / q_noise_fn are keyed by it).
     (File-to-file form with decode / upload / encode overlapped: flair_amd.io.restore_video_files.)"""
@@ -303,7 +368,8 @@ def restore_video(task, degraded01, model, diffusion, restore_fn_for, *, size, a
             task, degraded01[:, idx[0]:idx[-1] + 1], model, diffusion, restore_fn_for, size=size,
             prev_recon=None if starts_shot else prev_recon, overlap=overlap, window_index=wi, aux_model=aux_model,
             vsrpp_weights_fn=vsrpp_weights_fn, hp=hp, tau=tau, t_start=t_start, noise_fn=noise_fn, q_noise_fn=q_noise_fn,
-            aligned=aligned, face_helper=face_helper, frame_indices=idx, faces=faces, max_faces=max_faces)
+            aligned=aligned, face_helper=face_helper, frame_indices=idx, faces=faces, max_faces=max_faces,
+            **({} if tile is None else dict(tile=tile, tile_overlap=tile_overlap)))
         out[filled:filled + frames01.shape[0]].copy_(frames01)
         filled += frames01.shape[0]
     return out[:filled]
